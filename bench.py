@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: tile-iterations/s of the tiled style-transfer hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W untimed and K timed steps and prints the line (metric, value, unit,
+ms_per_step, dtype, config and the roofline of the timed steps).  Everything else the line can
+carry -- the sub-records, checks and legs listed below (`bit_identical`, `farm`, `config4`, `weak`,
+`steady` with the clock reading, `roofline.per_kernel`, `fp32_kernels`, `wall_clock_s`,
+`cpu_baseline`) -- runs with --full only; the --no-* switches turn single legs of it off.
+--dump-outputs DIR writes what the last timed step handed back as DIR/<name>.npy (dump_outputs).
 
 One step = one optimizer iteration of the reference's step loop (style_transfer.py:771-806) at the
 top scale of the configuration BASELINE.json's metric is quoted on ("VGG-19 --size 2048 --tile-size
@@ -198,11 +205,12 @@ class FarmJob:
         self.run_ahead = optimizer == 'adam' and os.environ.get('STX_RUN_AHEAD', '1') != '0'
         self.in_flight = None
         self.last_loss = None
+        self.last_stats = None
 
     def _finish(self, item):
         loss, stats = item
         self.last_loss = float(loss)          # waits for that iteration's fences only
-        stats.values()
+        self.last_stats = stats.values()
         self.group_ms.append(group_span_ms(self.farm.engines, self.tiles_per_step))
 
     def drain(self):
@@ -230,7 +238,7 @@ class FarmJob:
             if previous is not None:
                 self._finish(previous)
             return self.last_loss
-        self.image_ops.step_stats(self.eng, avg, self.old)
+        self.last_stats = self.image_ops.step_stats(self.eng, avg, self.old)
         self.last_loss = float(loss)
         self.group_ms.append(group_span_ms(self.farm.engines, self.tiles_per_step))
         return self.last_loss
@@ -608,11 +616,46 @@ def fp32_kernels_leg(opts, net, weights, device_index, rows, cols):
             'conv_flop_issued_over_direct': conv_issued / conv_alg if conv_alg else None}
 
 
+DUMP_WHOLE_MAX = 3 * 2048 * 2048       # elements: the metric's picture is written whole (48 MiB)
+DUMP_SAMPLE = 1 << 20                  # elements of the seeded sample of anything larger, and of the gradient
+
+
+def _seeded_sample(flat, n):
+    """A fixed sample of `flat`: the same positions for the same size in every run."""
+    if flat.size <= n:
+        return flat
+    return flat[np.sort(np.random.RandomState(0).choice(flat.size, n, replace=False))]
+
+
+def dump_outputs(path, avg, grad, loss, stats):
+    """--dump-outputs: what the last timed step handed back to its caller, for comparing two builds
+    output for output (same arguments, same inputs: every input of the step loop is seeded).
+      image.npy        float32 [3, H, W]  the optimizer's averaged iterate (the picture the command
+                                          line writes); a seeded sample of it above DUMP_WHOLE_MAX
+      loss.npy         float64 [1]        the step's loss (tiles + regularizers)
+      step_stats.npy   float64 [2]        the step's statistics (image_ops.step_stats)
+      grad_sample.npy  float32 [2^20]     a seeded sample of the step's image gradient
+    55 MB at the metric's 2048 x 2048 image, never more than 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(avg.get(), np.float32)
+    if img.size > DUMP_WHOLE_MAX:
+        img = _seeded_sample(img.ravel(), DUMP_SAMPLE)
+    np.save(os.path.join(path, 'image.npy'), img)
+    np.save(os.path.join(path, 'loss.npy'), np.float64([loss]))
+    np.save(os.path.join(path, 'step_stats.npy'), np.float64(stats))
+    np.save(os.path.join(path, 'grad_sample.npy'),
+            _seeded_sample(np.asarray(grad.get(), np.float32).ravel(), DUMP_SAMPLE))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='also run the sub-records, checks and extra legs (off: the headline only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-wall-clock', action='store_true',
                     help='skip the whole-run wall-clock leg (about 10 s)')
@@ -633,6 +676,8 @@ def main():
                     help='RxC tile grid instead of the 2x2 of the metric (tests only: lets a single '
                          'process evaluate the image of a larger job)')
     opts = ap.parse_args()
+    if opts.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if opts.farm_leg:
         r, c = (int(v) for v in opts.debug_grid.split('x'))
@@ -675,7 +720,7 @@ def main():
     if rank != 0:
         return
     devices = list(range(world)) if not debug_one_gpu else [0] * world
-    if world > 1 and not opts.no_farm_leg:
+    if world > 1 and opts.full and not opts.no_farm_leg:
         # north_star's layout: one host process, N GPUs.  The other ranks have left (their process
         # group is gone, their engines are closed).
         line['farm'] = farm_leg_in_child(devices, rows, cols, opts.steps, opts.warmup,
@@ -683,14 +728,14 @@ def main():
         line['config4'] = farm_leg_in_child(devices, CONFIG4_GRID[0], CONFIG4_GRID[1],
                                             max(2, opts.steps // 2), min(opts.warmup, 2), 'lbfgs',
                                             force_staging=debug_one_gpu)
-    if not opts.no_wall_clock:
+    if opts.full and not opts.no_wall_clock:
         # the whole command-line run on this job's GPUs, one host process
         try:
             line.update(whole_run_wall_clock(devices))
         except Exception as err:      # pylint: disable=broad-except
             line['wall_clock_s'] = None
             line['wall_clock_error'] = '%s: %s' % (type(err).__name__, err)
-    if world == 1 and not opts.no_cpu_baseline:
+    if world == 1 and opts.full and not opts.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline(net)
     print(json.dumps(line), flush=True)
 
@@ -727,20 +772,22 @@ def bench_single(opts, net, weights, device_index, rows, cols):
     job = FarmJob(net, weights, [device_index], rows, cols)
     elapsed, loss = job.timed(opts.steps, opts.warmup)
     timed_group_ms = list(job.group_ms)
+    if opts.dump_outputs:
+        dump_outputs(opts.dump_outputs, job.opt.avg, job.grad, loss, job.last_stats)
     line = base_line(opts, 1, rows, cols, elapsed, loss, job.eng, timed_group_ms)
-    if opts.steady_seconds > 0:
+    if opts.full and opts.steady_seconds > 0:
         n_steady = max(1, int(np.ceil(opts.steady_seconds / (elapsed / opts.steps))))
         dt, _ = job.timed(n_steady, 0, clock_marks=True)
         add_clock(line['roofline'], job.clock)
         line['steady'] = {'steps': n_steady, 'seconds': dt, 'ms_per_step': dt / n_steady * 1e3,
                           'value': job.tiles_per_step * n_steady / dt, 'unit': 'tile-iterations/s'}
     line['tile_evals'] = int(sum(e.query(lib.Q_TILE_EVALS) for e in job.farm.engines))
-    if not opts.no_kernel_records:
+    if opts.full and not opts.no_kernel_records:
         line['roofline']['per_kernel'] = kernel_records(job)
         if 'dominant' in line['roofline']['per_kernel']:
             line['roofline']['dominant'] = line['roofline']['per_kernel']['dominant']
     job.close()
-    if not opts.no_fp32_leg and DTYPE != 'f32':
+    if opts.full and not opts.no_fp32_leg and DTYPE != 'f32':
         line['fp32_kernels'] = fp32_kernels_leg(opts, net, weights, device_index, rows, cols)
     return line
 
@@ -839,7 +886,7 @@ class RankJob:
             self.eng.sync()
             return loss + reg.value, self.grad
         avg, loss = self.opt.update(opfunc)
-        self.image_ops.step_stats(self.eng, avg, self.old)
+        self.last_stats = self.image_ops.step_stats(self.eng, avg, self.old)
         return loss
 
     def fence(self):
@@ -910,14 +957,16 @@ def bench_ranks(opts, net, rank, world, local_rank, device, rows, cols, debug_on
 
     # ---- the headline: BASELINE's literal workload (strong scaling)
     job = RankJob(net, engines, rank, world, device, rows, cols, wire)
-    same = job.bit_identical()
+    same = job.bit_identical() if opts.full else None
     elapsed, loss = job.timed(opts.steps, opts.warmup)
     timed_group_ms = list(job.group_ms)
+    if opts.dump_outputs and rank == 0:
+        dump_outputs(opts.dump_outputs, job.opt.avg, job.grad, loss, job.last_stats)
 
     # ---- a second, longer measurement of the same loop (the timed region above is short)
     steady = None
     clock = None
-    if opts.steady_seconds > 0:
+    if opts.full and opts.steady_seconds > 0:
         t = torch.tensor([max(1, int(np.ceil(opts.steady_seconds / (elapsed / opts.steps))))],
                          dtype=torch.int64, device=wire)
         dist.broadcast(t, 0)
@@ -944,7 +993,7 @@ def bench_ranks(opts, net, rank, world, local_rank, device, rows, cols, debug_on
             line['steady'] = steady
 
     # ---- the weak-scaling sub-record (rounds 1-3's headline): four tiles per GPU, growing image
-    if not opts.no_weak and not opts.debug_grid:
+    if opts.full and not opts.no_weak and not opts.debug_grid:
         wr, wc = WEAK_GRIDS[world]
         weak = RankJob(net, engines, rank, world, device, wr, wc, wire)
         weak_same = weak.bit_identical()

@@ -1,7 +1,6 @@
 import os
 import sys
 
-import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,10 +14,10 @@ def pytest_configure(config):
 
 @pytest.fixture(scope='session')
 def golden():
-    """Vectors produced by the reference's own Python (tests/golden/make_golden.py)."""
-    path = os.path.join(REPO, 'tests', 'golden', 'reference_vectors.npz')
-    z = np.load(path)
-    return {k: z[k] for k in z.files}
+    """Vectors produced by the reference's own Python (tests/golden/make_golden.py), stored in parts
+    (tests/golden/vectors.py)."""
+    from tests.golden import vectors
+    return vectors.load()
 
 
 @pytest.fixture(autouse=True)

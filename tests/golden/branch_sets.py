@@ -170,7 +170,8 @@ def main():
             results.append((name, log, raw))
             print('%-14s done: losses %s' % (name, ' '.join('%.7e' % v for v in log[:, 2])), flush=True)
     base = next(r for r in results if r[0] == 'as_is') if not a.only else results[0]
-    golden = np.load(os.path.join(HERE, 'reference_vectors.npz'))
+    import vectors
+    golden = vectors.load()
     key = {'cfg4': 'e2e_cfg4', 'lbfgs': 'e2e_lbfgs', 'stable': 'e2e_stable'}[a.fixture]
     have = key + '.log' in golden
     ref_log = golden[key + '.log'] if have else base[1]

@@ -583,19 +583,20 @@ def main():
     defaults = {k: getattr(args, k) for k in args}
     out['args/defaults_repr'] = np.array(repr(sorted((k, str(v)) for k, v in defaults.items())))
 
-    path = os.path.join(HERE, 'reference_vectors.npz')
+    import vectors      # (HERE is on sys.path: reference_vectors*.npz, parts of at most 1 MiB)
     # STX_GOLDEN_APPEND=<section>: keep the committed arrays as they are (a regeneration differs
     # from them at the 1e-7 level: the thread order of the reference's BLAS calls) and only add
     # the arrays of that section
     section = os.environ.get('STX_GOLDEN_APPEND')
-    if section and os.path.exists(path):
-        old = dict(np.load(path, allow_pickle=False))
+    if section and os.path.exists(vectors.part_path(0)):
+        old = vectors.load()
         old.update({k.replace('/', '.'): v for k, v in out.items() if k.startswith(section + '/')})
-        np.savez_compressed(path, **old)
         out = old
     else:
-        np.savez_compressed(path, **{k.replace('/', '.'): v for k, v in out.items()})
-    print('wrote %s (%d arrays, %.1f KiB)' % (path, len(out), os.path.getsize(path) / 1024))
+        out = {k.replace('/', '.'): v for k, v in out.items()}
+    paths = vectors.save(out)
+    print('wrote %s (%d arrays, %.1f KiB)' % (', '.join(paths), len(out),
+                                             sum(os.path.getsize(p) for p in paths) / 1024))
     num_utils.POOL.shutdown()
 
 

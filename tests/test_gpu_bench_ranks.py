@@ -36,7 +36,7 @@ def _line(stdout):
 @pytest.mark.timeout(900)
 def test_two_rank_bench_matches_single_process_loss():
     env = dict(os.environ, STX_BENCH_DEBUG_ONE_GPU='1', MASTER_ADDR='127.0.0.1')
-    common = ['--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-wall-clock',
+    common = ['--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-wall-clock',
               '--steady-seconds', '0']
     for attempt in range(2):                # (a second try with another port: the rendezvous, not the bench, is what can fail)
         two = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
@@ -112,6 +112,35 @@ def test_farm_leg_over_two_device_entries_matches_one():
         losses.append(loss)
         job.close()
     assert losses[0] == losses[1]
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` (no --full) times exactly --steps steps and carries the headline only;
+    --dump-outputs writes what the last timed step handed back, float32 / float64, 64 MB at most."""
+    import numpy as np
+    out = tmp_path / 'outputs'
+    proc = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2',
+                           '--warmup', '1', '--dump-outputs', str(out)], cwd=REPO,
+                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=500)
+    assert proc.returncode == 0, proc.stdout[-3000:]
+    line = _line(proc.stdout)
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in line, key
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['unit'] == 'tile-iterations/s'
+    assert line['value'] == pytest.approx(4 * 1e3 / line['ms_per_step'], rel=1e-9)
+    assert line['tile_evals'] == 4 * (1 + 2)           # warm-up and timed steps, nothing else ran
+    for key in ('cpu_baseline', 'steady', 'fp32_kernels', 'wall_clock_s', 'weak', 'farm', 'config4'):
+        assert key not in line, key
+    assert 'per_kernel' not in line['roofline']
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ['grad_sample.npy', 'image.npy', 'loss.npy', 'step_stats.npy'], files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64e6
+    arrays = {p.stem: np.load(p) for p in out.iterdir()}
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    assert arrays['image'].shape == (3, 2048, 2048) and arrays['grad_sample'].shape == (1 << 20,)
+    assert arrays['loss'][0] == line['config']['final_loss']
 
 
 def test_farm_leg_child_process_prints_its_record():

@@ -1,5 +1,5 @@
 """The numpy oracle must reproduce what the reference's own Python produced
-(tests/golden/reference_vectors.npz, made by tests/golden/make_golden.py)."""
+(tests/golden/reference_vectors*.npz, made by tests/golden/make_golden.py)."""
 
 import numpy as np
 import pytest

@@ -13,8 +13,8 @@ from style_transfer_amd.netspec import builtin_net
 from style_transfer_amd.transfer import StyleTransfer
 from style_transfer_amd.weights import synthetic_weights
 from style_transfer_amd import image_ops
-z = np.load(os.path.join(REPO, 'tests', 'golden', 'reference_vectors.npz'))
-golden = {k: z[k] for k in z.files}
+from tests.golden import vectors
+golden = vectors.load()
 orig = image_ops.regularizers
 for mode in ('rolled', 'unrolled'):
     if mode == 'unrolled':

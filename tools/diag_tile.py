@@ -4,7 +4,8 @@ sys.path.insert(0,'.')
 from tests.gpu_helpers import gpu_engine
 from tests.helpers import *
 from tests.test_gpu_tile_path import _targets
-z=np.load('tests/golden/reference_vectors.npz'); golden={k:z[k] for k in z.files}
+from tests.golden import vectors
+golden=vectors.load()
 T={}
 for tag,model in [('vgg16avg','vgg16_avgpool'),('vgg19','vgg19')]:
     T[tag]=_targets(golden, tag, model)

@@ -26,5 +26,5 @@ timeout 1500 python -m pytest tests/test_gpu_end_to_end.py tests/test_gpu_cli.py
 echo "e2e rc $?"
 timeout 2400 python -m pytest tests/test_gpu_fullsize.py -q -s -k "sc_grad_tile" > "$OUT/pytest_fullsize.log" 2>&1
 echo "fullsize rc $?"
-python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench_line.json"

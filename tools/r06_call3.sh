@@ -9,7 +9,7 @@ export STX_PARITY_STATS=$OUT/tile_parity_stats.txt STX_E2E_DUMP=$OUT/e2e STX_PRE
 timeout 3000 python -m pytest tests -m gpu -q > "$OUT/pytest_all.log" 2>&1
 echo "all rc $?"; tail -5 "$OUT/pytest_all.log"
 unset STX_PARITY_STATS STX_E2E_DUMP STX_PRECISION_STATS
-python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 python -c "
 import json,sys
 d=json.load(open('$OUT/bench_line.json'))
