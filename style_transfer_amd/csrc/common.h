@@ -7,6 +7,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <functional>
 #include <string>
 
 #include "stx.h"
@@ -138,11 +139,11 @@ struct ConvProblem {
     bool wants_codes = false;
     // kEpiForward with a fused pooling that also writes window codes: nobody will read y itself
     // (the pooled blob feeds the next layer, the backward pooling runs from the codes) -- skip
-    // its stores.  Only honoured by the kernel that fuses (wino2_launch); ignored otherwise.
+    // its stores.  Only honoured by the kernels that fuse (conv_fuses_pool); ignored otherwise.
     bool skip_y = false;
     float *pool_out = nullptr;       // kEpiForward: also write the 2x2/2 ceil-mode pooling of y here
     int pool_mode = 0;               // (kernels that cannot do it leave it to the caller: see
-                                     // wino2_fuses_pool)
+                                     // conv_fuses_pool)
     float *splitk_ws = nullptr;      // scratch for split-K partial sums (optional)
     size_t splitk_ws_floats = 0;
     // stx_clock_marks: one workgroup of the launch (the eight-wave Winograd kernel only) stores
@@ -167,9 +168,15 @@ struct ConvProblem {
 #endif
 };
 
-// Tile configuration chosen for a problem; weights must be packed for the same (bm, kc).
+// The kernel families of the packed-weight 3x3 / 1x1 convolutions: the direct implicit GEMM (conv_mfma.hip),
+// the fp32 2-D Winograd F(2x2,3x3) (conv_wino2.hip) and the fp16-split 1-D Winograd F(2,3) (conv_h2.hip).
+// conv_dispatch.cpp is the one place that dispatches on the family.
+enum class ConvFamily { Direct, Wino2, H2 };
+
+// Tile configuration chosen for a problem; weights must be packed for the same configuration (conv_bank).
 struct ConvConfig {
-    int id;        // index into the instantiation table
+    ConvFamily family;
+    int id;        // the variant within its family (direct: index into the instantiation table)
     int bm;        // output channels per workgroup
     int kc;        // reduction channels per LDS stage
     int pr, pc;    // pixel tile rows x cols
@@ -179,6 +186,7 @@ struct ConvConfig {
 
 ConvConfig conv_pick_config(int ksize, int K, int M, int H, int W);
 ConvConfig conv_config_by_id(int id);
+bool direct_takes_inject(const ConvConfig &cfg);     // kEpiDgradInject is instantiated for it
 int conv_num_workgroups(const ConvConfig &cfg, int M, int H, int W);
 // Packed weight buffer size (floats) for a [M][K][ks][ks] filter bank under cfg.
 size_t conv_packed_floats(const ConvConfig &cfg, int K, int M, int ksize);
@@ -187,11 +195,10 @@ size_t conv_packed_floats(const ConvConfig &cfg, int K, int M, int ksize);
 int conv_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int ksize,
                       int transpose_flip, const ConvConfig &cfg, float *packed);
 int conv_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, bool packed_weights);
-// Number of K slices conv_launch will use for this problem (1 = no split) and the scratch floats
-// that requires.  Small planes yield fewer workgroups than the chip has CUs; slicing the
-// reduction over several workgroups and adding the slices in a fixed order fills the machine.
-int conv_splitk_factor(const ConvConfig &cfg, const ConvProblem &p, bool packed_weights);
-size_t conv_splitk_floats(const ConvConfig &cfg, const ConvProblem &p, bool packed_weights);
+// Number of K slices conv_launch will use for this problem (1 = no split).  Small planes yield fewer
+// workgroups than the chip has CUs; slicing the reduction over several workgroups and adding the slices
+// in a fixed order fills the machine.
+int direct_splitk_factor(const ConvConfig &cfg, const ConvProblem &p, bool packed_weights);
 
 int splitk_reduce_launch(hipStream_t s, const ConvProblem &p, int ksplit);
 // The same for the work items item_base .. item_base + items - 1 of a 2-D Winograd launch only (64
@@ -240,14 +247,6 @@ struct WinoArgs {
 #endif
 };
 
-// The Winograd configurations (cfg.id 200-202: conv_wino2.hip, fp32 2-D F(2x2,3x3); 300-302: conv_h2.hip,
-// fp16-split 1-D F(2,3)): these three dispatch on cfg.id (conv_wino2.hip).
-size_t wino_packed_floats(const ConvConfig &cfg, int K, int M);
-int wino_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int transpose_flip,
-                      const ConvConfig &cfg, float *packed);
-int wino_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ksplit);
-
-
 // First layer (at most 3 planes -> 64 channels, 3x3) with the Gram partials of its own output
 // (conv_first.hip).  gram_partials (or null): conv_first_workgroups(H, W) partial tiles of 64 x 64
 // floats, finished by gram_finish_launch with {C 64, HW, splits = that count, tiles 1, parts 1}.
@@ -256,7 +255,7 @@ int conv_first_workgroups(int H, int W);
 int conv_first_launch(hipStream_t s, const float *x, const float *w_caffe, const float *bias, float *y,
                       int K, int H, int W, int relu, float *gram_partials, unsigned *y_amax = nullptr);
 
-// 2-D Winograd F(2x2,3x3) variant (conv_wino2.hip); config id 200.
+// 2-D Winograd F(2x2,3x3) (conv_wino2.hip); the config id is the patch geometry.
 ConvConfig wino2_config(int geometry = 0);     // 0: 4 x 64 pixel patches, 1: 16 x 16, 2: 8 x 32
 int wino2_pick_geometry(int H, int W);
 size_t wino2_packed_floats(int K, int M);
@@ -264,11 +263,8 @@ int wino2_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int 
                        float *packed);
 int wino2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ksplit);
 bool wino2_fuses_pool(const ConvProblem &p);
-// True if a launch of p under cfg writes p.in_codes (forward) / reads p.mask_codes (backward).
-bool conv_uses_relu_codes(const ConvConfig &cfg, const ConvProblem &p, int ksplit);
-// True if a forward launch of p under cfg writes p.out_codes (an unsplit launch of the fp16-split or the
-// eight-wave fp32 kernel; shape and epilogue only)
-bool conv_writes_out_codes(const ConvConfig &cfg, const ConvProblem &p, int ksplit);
+bool wino2_uses_relu_codes(const ConvProblem &p, int ksplit);           // see conv_uses_relu_codes
+bool wino2_writes_out_codes(const ConvConfig &cfg, const ConvProblem &p);   // see conv_writes_out_codes
 int wino2_splitk_factor(const ConvConfig &cfg, const ConvProblem &p);
 // Tail split: a launch of n = 256 q + r work items (q >= 1) runs its last r items as r x slices K
 // slices -- one short round instead of a mostly empty full one -- and a reduce pass over those r
@@ -278,10 +274,10 @@ Wino2Tail wino2_tail_split(const ConvConfig &cfg, const ConvProblem &p);
 int wino2_max_slices(const ConvConfig &cfg, const ConvProblem &p);
 
 // 1-D Winograd F(2,3) on the fp16 matrix cores with two-piece operands (conv_h2.hip): fp32-class
-// accuracy at 0.28 of the fp32 2-D form's matrix time.  Config ids 300 (64 channels x 8 x 32 pixels per
-// workgroup), 301 (128 channels) and 302 (64 channels x 16 x 32 pixels); all read the same packed bank.
+// accuracy at 0.28 of the fp32 2-D form's matrix time.  Config ids 0 (64 channels x 8 x 32 pixels per
+// workgroup), 1 (128 channels) and 2 (64 channels x 16 x 32 pixels); all read the same packed bank.
 constexpr int kAmaxSlots = 64;
-ConvConfig h2_config(int mb, int pb = 1);     // (1, 1), (2, 1) or (1, 2): ids 300 / 301 / 302
+ConvConfig h2_config(int mb, int pb = 1);     // (1, 1), (2, 1) or (1, 2): ids 0 / 1 / 2
 ConvConfig h2_pick_config(const ConvProblem &p);    // the cheaper tiling by the round model (shape only)
 bool h2_usable(const ConvProblem &p);       // what the kernel takes (shape, epilogue, addressing)
 size_t h2_packed_floats(int K, int M);
@@ -299,6 +295,36 @@ int conv_small_pack(hipStream_t s, const float *w_caffe, int Mo, int Ko, int tra
                     float *packed);
 int conv_small_launch(hipStream_t s, const float *x, const float *packed, float *y,
                       const float *mask, int K, int M, int H, int W);
+
+// ------------------------------------------------------------------------------------------------
+// The packed-weight convolutions by family (conv_dispatch.cpp): choice, filter bank, launch, capabilities.
+// ------------------------------------------------------------------------------------------------
+bool conv_h2_enabled();    // some problem may take the fp16-split kernel (STX_CONV_H2 / _H2_BWD / STX_CONV_ALGO)
+// Times the direct candidates on `stream` with the two events, from the banks `bank` gives.
+struct ConvTuner { int device; hipStream_t stream; hipEvent_t ev0, ev1; std::function<int(const ConvConfig &, const float **)> bank; };
+// The fp16-split kernel, else the fp32 2-D Winograd one (`winograd`: the engine's switch), else a direct
+// variant -- by shape; tuner (or null) then times the direct variants, which all round alike.
+int conv_choose(const ConvProblem &p, bool winograd, const ConvTuner *tuner, ConvConfig *out);
+// Configurations with the same key read the same bank (one per direct variant, one for the Winograd
+// geometries, one for the fp16-split tilings; per direction).  pack: Caffe-layout weights -> `floats` floats.
+struct ConvBank { int key; size_t floats; std::function<int(hipStream_t, const float *w_caffe, float *packed)> pack; };
+ConvBank conv_bank(const ConvConfig &cfg, int dir, int Mo, int Ko, int ksize);   // dir: as conv_pack_weights
+ConvBank conv_small_bank(int Mo, int Ko);     // conv_small_launch's (backward)
+// Enqueues p; adds a direct convolution's FLOPs and those the kernel issues to the two counters.
+int conv_dispatch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, double *flop_algorithmic,
+                  double *flop_issued);
+// What a launch of p under cfg does (shape and epilogue only):
+int conv_splitk_factor(const ConvConfig &cfg, const ConvProblem &p);     // K slices (1: none)
+size_t conv_splitk_floats(const ConvConfig &cfg, const ConvProblem &p);  // scratch floats of its splits
+bool conv_takes_clock(const ConvConfig &cfg);                            // ConvProblem::clock_out
+bool conv_fuses_pool(const ConvConfig &cfg, const ConvProblem &p);       // writes p.pool_out itself
+bool conv_writes_pool_codes(const ConvConfig &cfg);                      // ... and p.pool_codes
+bool conv_reads_x_amax(const ConvConfig &cfg);                           // ConvProblem::x_amax
+bool conv_leaves_y_amax(const ConvConfig &cfg);                          // ConvProblem::y_amax
+bool conv_takes_inject(const ConvConfig &cfg);                           // ConvProblem::inject
+bool conv_takes_pooled_input(const ConvConfig &cfg, const ConvProblem &p);            // ConvProblem::pin_codes
+bool conv_uses_relu_codes(const ConvConfig &cfg, const ConvProblem &p, int ksplit);   // p.in_codes / mask_codes
+bool conv_writes_out_codes(const ConvConfig &cfg, const ConvProblem &p, int ksplit);  // p.out_codes
 
 int pool_forward_launch(hipStream_t s, const float *x, int C, int H, int W, int mode, float *y,
                         unsigned char *codes = nullptr);

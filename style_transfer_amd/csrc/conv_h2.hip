@@ -1012,17 +1012,11 @@ int h2_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int tra
     return STX_OK;
 }
 
-// ids 300: 64 channels x 8 x 32 pixels per workgroup, 301: 128 channels x 8 x 32, 302: 64 channels x 16 x 32
+// ids 0: 64 channels x 8 x 32 pixels per workgroup, 1: 128 channels x 8 x 32, 2: 64 channels x 16 x 32
 ConvConfig h2_config(int mb, int pb) {
-    ConvConfig c;
-    c.id = mb == 2 ? 301 : pb == 2 ? 302 : 300;
-    c.bm = mb == 2 ? 128 : 64;
-    c.kc = KC;
-    c.pr = c.id == 302 ? 16 : 8;
-    c.pc = PC;
-    c.threads = NT;
-    c.lds_bytes = c.id == 302 ? Geo<2>::kLds : Geo<1>::kLds;
-    return c;
+    const bool two = mb != 2 && pb == 2;
+    return {ConvFamily::H2, mb == 2 ? 1 : two ? 2 : 0, mb == 2 ? 128 : 64, KC, two ? 16 : 8, PC, NT,
+            two ? Geo<2>::kLds : Geo<1>::kLds};
 }
 
 // What the kernel takes: a multiple of 32 input channels (the chunk loop runs two chunks per trip), plane sets under 2 GiB, no ReLU nibbles.
@@ -1047,7 +1041,7 @@ static double h2_plan(const ConvConfig &cfg, const ConvProblem &p, int *factor) 
     const double out_mb = 4e-6 * p.M * (double)p.H * p.W;
     // (128 channels or two stacked patches: twice the matrix work per chunk; the stacked patches also
     // stage twice as much, 7 000 cycles per chunk against 5 400)
-    const double t_chunk = cfg.id == 301 ? 2.75 : cfg.id == 302 ? 3.5 : 2.0, t_fixed = cfg.id != 300 ? 17.0 : 8.5;
+    const double t_chunk = cfg.id == 1 ? 2.75 : cfg.id == 2 ? 3.5 : 2.0, t_fixed = cfg.id != 0 ? 17.0 : 8.5;
     const bool may_split = p.epilogue == kEpiForward || p.epilogue == kEpiDgrad;
     double best_cost = 0;
     int best = 1;
@@ -1089,7 +1083,7 @@ ConvConfig h2_pick_config(const ConvProblem &p) {
 // A backward launch that can take its input pooled (ConvProblem::pin_codes): unsplit ones -- the K slices
 // of a split launch would each un-pool the same patch again, and the planes that split are small.
 bool h2_takes_pooled_input(const ConvConfig &cfg, const ConvProblem &p) {
-    return cfg.id >= 300 && p.epilogue == kEpiDgrad && h2_usable(p) && h2_splitk_factor(cfg, p) == 1;
+    return p.epilogue == kEpiDgrad && h2_usable(p) && h2_splitk_factor(cfg, p) == 1;
 }
 
 bool h2_fuses_pool(const ConvProblem &p) {
@@ -1182,14 +1176,14 @@ int h2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ks
     const int epi = split ? kEpiPartial : inject ? kEpiDgradInject : p.epilogue;
 #define STX_H2_CASE(E)                                                                   \
     case E:                                                                              \
-        STX_TRY(cfg.id == 301   ? (h2_launch_epi<E, 2, 1>(s, a, n_wg))                   \
-                : cfg.id == 302 ? (h2_launch_epi<E, 1, 2>(s, a, n_wg))                   \
+        STX_TRY(cfg.id == 1   ? (h2_launch_epi<E, 2, 1>(s, a, n_wg))                   \
+                : cfg.id == 2 ? (h2_launch_epi<E, 1, 2>(s, a, n_wg))                   \
                                 : (h2_launch_epi<E, 1, 1>(s, a, n_wg)));                 \
         break;
 #define STX_H2_PIN_CASE(E, P)                                                            \
     case E:                                                                              \
-        STX_TRY(cfg.id == 301   ? (h2_launch_epi<E, 2, 1, P>(s, a, n_wg))                \
-                : cfg.id == 302 ? (h2_launch_epi<E, 1, 2, P>(s, a, n_wg))                \
+        STX_TRY(cfg.id == 1   ? (h2_launch_epi<E, 2, 1, P>(s, a, n_wg))                \
+                : cfg.id == 2 ? (h2_launch_epi<E, 1, 2, P>(s, a, n_wg))                \
                                 : (h2_launch_epi<E, 1, 1, P>(s, a, n_wg)));              \
         break;
     if (pin && p.pin_mode == STX_POOL_MAX) {

@@ -327,43 +327,38 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_kernel(ConvKernelAr
 // ------------------------------------------------------------------------------------------------
 struct ConvVariant {
     int ks, kc, tm, tn, wm, wn, pr, pc, db;
+    bool inject;   // with the loss-injecting backward epilogue and the K-split partials (3x3 only)
+    bool forced;   // STX_CONV_FORCE may pick it (a tuning aid for the middle layers)
 };
 
-static const ConvVariant kVariants[] = {
-    /*0*/ {3, 8, 2, 4, 2, 2, 8, 32},   // BM 128 x 256 px : wide middle layers
-    /*1*/ {3, 8, 2, 4, 1, 4, 8, 64},   // BM  64 x 512 px : 64-channel layers at full resolution
-    /*2*/ {3, 8, 2, 2, 1, 4, 8, 32},   // BM  64 x 256 px : deep layers with few pixels
-    /*3*/ {3, 8, 1, 2, 1, 4, 8, 32},   // BM  32 x 256 px : backward into the 3-channel image
-    /*4*/ {3, 4, 2, 4, 1, 4, 8, 64},   // BM  64 x 512 px, KC 4 : first layer (3 input channels)
-    /*5*/ {3, 8, 2, 1, 1, 4, 4, 32},   // BM  64 x 128 px : smallest planes
-    /*6*/ {1, 16, 2, 4, 2, 2, 8, 32},  // 1x1, BM 128 : style-gradient product, C >= 128
-    /*7*/ {1, 16, 2, 4, 1, 4, 8, 64},  // 1x1, BM  64 : style-gradient product, C == 64
-    /*8*/ {3, 4, 2, 1, 1, 4, 4, 32},   // BM  64 x 128 px, KC 4 : first layer, small tiles
-    /*9*/ {3, 8, 2, 1, 1, 4, 4, 32, 1},   // BM 64 x 128 px, two LDS stages
-    /*10*/ {3, 4, 2, 1, 1, 4, 4, 32, 1},  // BM 64 x 128 px, KC 4, two LDS stages
-    /*11*/ {3, 8, 2, 2, 1, 4, 8, 32, 1},  // BM 64 x 256 px, two LDS stages
-    /*12*/ {1, 32, 2, 1, 1, 4, 4, 32},    // 1x1, BM 64 x 128 px, KC 32 : many small workgroups
-    /*13*/ {1, 64, 2, 1, 1, 4, 4, 32},    // 1x1, BM 64 x 128 px, KC 64
-    /*14*/ {1, 32, 2, 2, 1, 4, 8, 32},    // 1x1, BM 64 x 256 px, KC 32
+static constexpr ConvVariant kVariants[] = {
+    /*0*/ {3, 8, 2, 4, 2, 2, 8, 32, 0, true, true},     // BM 128 x 256 px : wide middle layers
+    /*1*/ {3, 8, 2, 4, 1, 4, 8, 64, 0, true, true},     // BM  64 x 512 px : 64-channel layers at full resolution
+    /*2*/ {3, 8, 2, 2, 1, 4, 8, 32, 0, true, true},     // BM  64 x 256 px : deep layers with few pixels
+    /*3*/ {3, 8, 1, 2, 1, 4, 8, 32, 0, false, false},   // BM  32 x 256 px : backward into the 3-channel image
+    /*4*/ {3, 4, 2, 4, 1, 4, 8, 64, 0, false, false},   // BM  64 x 512 px, KC 4 : first layer (3 input channels)
+    /*5*/ {3, 8, 2, 1, 1, 4, 4, 32, 0, true, true},     // BM  64 x 128 px : smallest planes
+    /*6*/ {1, 16, 2, 4, 2, 2, 8, 32, 0, false, false},  // 1x1, BM 128 : style-gradient product, C >= 128
+    /*7*/ {1, 16, 2, 4, 1, 4, 8, 64, 0, false, false},  // 1x1, BM  64 : style-gradient product, C == 64
+    /*8*/ {3, 4, 2, 1, 1, 4, 4, 32, 0, false, false},   // BM  64 x 128 px, KC 4 : first layer, small tiles
+    /*9*/ {3, 8, 2, 1, 1, 4, 4, 32, 1, true, true},     // BM 64 x 128 px, two LDS stages
+    /*10*/ {3, 4, 2, 1, 1, 4, 4, 32, 1, true, true},    // BM 64 x 128 px, KC 4, two LDS stages
+    /*11*/ {3, 8, 2, 2, 1, 4, 8, 32, 1, true, true},    // BM 64 x 256 px, two LDS stages
+    /*12*/ {1, 32, 2, 1, 1, 4, 4, 32, 0, false, false},   // 1x1, BM 64 x 128 px, KC 32 : many small workgroups
+    /*13*/ {1, 64, 2, 1, 1, 4, 4, 32, 0, false, false},   // 1x1, BM 64 x 128 px, KC 64
+    /*14*/ {1, 32, 2, 2, 1, 4, 8, 32, 0, false, false},   // 1x1, BM 64 x 256 px, KC 32
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 static ConvConfig make_config(int id) {
     const ConvVariant &v = kVariants[id];
-    ConvConfig c;
-    c.id = id;
-    c.bm = 32 * v.tm * v.wm;
-    c.kc = v.kc;
-    c.pr = v.pr;
-    c.pc = v.pc;
-    c.threads = 64 * v.wm * v.wn;
-    const int kk = v.ks * v.ks;
-    c.lds_bytes = sizeof(float) * (1 + v.db) * ((size_t)v.kc * kk * c.bm +
-                                   (size_t)v.kc * (v.pr + v.ks - 1) * (v.pc + v.ks - 1));
-    return c;
+    const int bm = 32 * v.tm * v.wm, kk = v.ks * v.ks;
+    return {ConvFamily::Direct, id, bm, v.kc, v.pr, v.pc, 64 * v.wm * v.wn,
+            sizeof(float) * (1 + v.db) * ((size_t)v.kc * kk * bm + (size_t)v.kc * (v.pr + v.ks - 1) * (v.pc + v.ks - 1))};
 }
 
 ConvConfig conv_config_by_id(int id) { return make_config(id); }
+bool direct_takes_inject(const ConvConfig &cfg) { return kVariants[cfg.id].inject; }
 
 int conv_num_workgroups(const ConvConfig &cfg, int M, int H, int W) {
     return ceil_div(M, cfg.bm) * ceil_div(H, cfg.pr) * ceil_div(W, cfg.pc);
@@ -385,8 +380,7 @@ ConvConfig conv_pick_config(int ksize, int K, int M, int H, int W) {
     if (M <= 32) return make_config(3);
     if (const char *force = sw_env("STX_CONV_FORCE")) {   // tuning aid: force one tile config
         const int id = atoi(force);
-        if (id >= 0 && id <= 11 && id != 3 && id != 4 && id != 6 && id != 7 && id != 8)
-            return make_config(id);
+        if (0 <= id && id < kNumVariants && kVariants[id].forced) return make_config(id);
     }
     // Static default (the engine autotunes per shape on top of this): measured on MI355X, many
     // small workgroups beat few large ones because co-resident workgroups run out of phase and
@@ -439,43 +433,22 @@ int conv_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int k
     return STX_OK;
 }
 
-#define STX_CONV_VARIANT(ID, KS, KC, TM, TN, WM, WN, PR, PC) \
-    STX_CONV_VARIANT_DB(ID, KS, KC, TM, TN, WM, WN, PR, PC, false)
-#define STX_CONV_VARIANT_DB(ID, KS, KC, TM, TN, WM, WN, PR, PC, DBUF)                             \
-    template <int EPI, bool PACKED>                                                               \
-    static int launch_##ID(hipStream_t s, const ConvConfig &cfg, const ConvKernelArgs &args,      \
-                           int n_wg) {                                                            \
-        auto kern = conv_mfma_kernel<KS, KC, TM, TN, WM, WN, PR, PC, EPI, PACKED, DBUF>;          \
-        if (cfg.lds_bytes > 64 * 1024) {                                                          \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),              \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,        \
-                                               (int)cfg.lds_bytes);                               \
-            if (e != hipSuccess) {                                                                \
-                set_error("hipFuncSetAttribute(lds=%zu): %s", cfg.lds_bytes,                      \
-                          hipGetErrorString(e));                                                  \
-                return STX_ERR_HIP;                                                               \
-            }                                                                                     \
-        }                                                                                         \
-        kern<<<n_wg, cfg.threads, cfg.lds_bytes, s>>>(args);                                      \
-        STX_CHECK_LAUNCH();                                                                       \
-        return STX_OK;                                                                            \
+template <int ID, int EPI, bool PACKED>
+static int launch_variant(hipStream_t s, const ConvConfig &cfg, const ConvKernelArgs &args, int n_wg) {
+    constexpr ConvVariant v = kVariants[ID];
+    auto kern = conv_mfma_kernel<v.ks, v.kc, v.tm, v.tn, v.wm, v.wn, v.pr, v.pc, EPI, PACKED, v.db != 0>;
+    if (cfg.lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfg.lds_bytes);
+        if (e != hipSuccess) {
+            set_error("hipFuncSetAttribute(lds=%zu): %s", cfg.lds_bytes, hipGetErrorString(e));
+            return STX_ERR_HIP;
+        }
     }
-
-STX_CONV_VARIANT(0, 3, 8, 2, 4, 2, 2, 8, 32)
-STX_CONV_VARIANT(1, 3, 8, 2, 4, 1, 4, 8, 64)
-STX_CONV_VARIANT(2, 3, 8, 2, 2, 1, 4, 8, 32)
-STX_CONV_VARIANT(3, 3, 8, 1, 2, 1, 4, 8, 32)
-STX_CONV_VARIANT(4, 3, 4, 2, 4, 1, 4, 8, 64)
-STX_CONV_VARIANT(5, 3, 8, 2, 1, 1, 4, 4, 32)
-STX_CONV_VARIANT(6, 1, 16, 2, 4, 2, 2, 8, 32)
-STX_CONV_VARIANT(7, 1, 16, 2, 4, 1, 4, 8, 64)
-STX_CONV_VARIANT(8, 3, 4, 2, 1, 1, 4, 4, 32)
-STX_CONV_VARIANT(12, 1, 32, 2, 1, 1, 4, 4, 32)
-STX_CONV_VARIANT(13, 1, 64, 2, 1, 1, 4, 4, 32)
-STX_CONV_VARIANT(14, 1, 32, 2, 2, 1, 4, 8, 32)
-STX_CONV_VARIANT_DB(9, 3, 8, 2, 1, 1, 4, 4, 32, true)
-STX_CONV_VARIANT_DB(10, 3, 4, 2, 1, 1, 4, 4, 32, true)
-STX_CONV_VARIANT_DB(11, 3, 8, 2, 2, 1, 4, 8, 32, true)
+    kern<<<n_wg, cfg.threads, cfg.lds_bytes, s>>>(args);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
 
 // Sums the K slices in a fixed order and applies the epilogue the unsplit kernel would have.
 struct SplitReduceArgs {
@@ -616,11 +589,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_items_kernel(SplitReduceArg
     splitk_reduce_amax(a, amax);
 }
 
-int conv_splitk_factor(const ConvConfig &cfg, const ConvProblem &p, bool packed) {
+int direct_splitk_factor(const ConvConfig &cfg, const ConvProblem &p, bool packed) {
     if (!packed || p.ksize != 3 || (p.epilogue != kEpiForward && p.epilogue != kEpiDgrad)) return 1;
-    if (cfg.id >= 300) return h2_splitk_factor(cfg, p);
-    if (cfg.id >= 200) return wino2_splitk_factor(cfg, p);
-    if (cfg.id == 3 || cfg.id == 4 || cfg.id == 8) return 1;   // (ids 100-102: 1-D Winograd, allowed)
+    if (!kVariants[cfg.id].inject) return 1;
     const int n_wg = conv_num_workgroups(cfg, p.M, p.H, p.W);
     const int n_chunks = ceil_div(p.K, cfg.kc);
     // All workgroups of a launch become resident at once while they fit (about five per CU for
@@ -639,11 +610,29 @@ int conv_splitk_factor(const ConvConfig &cfg, const ConvProblem &p, bool packed)
     return std::max(max_split, 1);
 }
 
-size_t conv_splitk_floats(const ConvConfig &cfg, const ConvProblem &p, bool packed) {
-    int f = conv_splitk_factor(cfg, p, packed);
-    if (packed && p.ksize == 3 && cfg.id >= 200 && cfg.id < 210)     // (the tail split's slices are whole planes too)
-        f = std::max(f, wino2_max_slices(cfg, p));
-    return f > 1 ? (size_t)f * p.M * p.H * p.W : 0;
+// The epilogues a variant is instantiated with: forward and backward-data on packed weights; the
+// injecting backward epilogue and the K-split partials where kVariants says so; the unpacked style-gradient
+// product (kEpiSymm) for the 1x1 ones.
+template <int ID>
+static int dispatch_variant(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, const ConvKernelArgs &a,
+                            int n_wg, bool packed, bool inject, int ksplit) {
+    constexpr ConvVariant v = kVariants[ID];
+    if constexpr (v.inject) {
+        if (ksplit > 1) {
+            STX_TRY((launch_variant<ID, kEpiPartial, true>(s, cfg, a, n_wg)));
+            return splitk_reduce_launch(s, p, ksplit);
+        }
+    }
+    if constexpr (v.ks == 1) {
+        if (p.epilogue == kEpiSymm && !packed) return launch_variant<ID, kEpiSymm, false>(s, cfg, a, n_wg);
+    }
+    if (p.epilogue == kEpiForward && packed) return launch_variant<ID, kEpiForward, true>(s, cfg, a, n_wg);
+    if constexpr (v.inject) {
+        if (inject && packed) return launch_variant<ID, kEpiDgradInject, true>(s, cfg, a, n_wg);
+    }
+    if (p.epilogue == kEpiDgrad && packed && !inject) return launch_variant<ID, kEpiDgrad, true>(s, cfg, a, n_wg);
+    set_error("conv_launch: no kernel for config %d epilogue %d packed %d", cfg.id, p.epilogue, (int)packed);
+    return STX_ERR_UNSUPPORTED;
 }
 
 int conv_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, bool packed) {
@@ -685,7 +674,7 @@ int conv_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, bool
     a.ksplit = 1;
     const bool inject = p.epilogue == kEpiDgrad && (p.inject.sgrad || p.inject.content);
     int n_wg = conv_num_workgroups(cfg, p.M, p.H, p.W);
-    const int ksplit = conv_splitk_factor(cfg, p, packed);
+    const int ksplit = direct_splitk_factor(cfg, p, packed);
     const bool split = ksplit > 1 && p.splitk_ws &&
                        p.splitk_ws_floats >= (size_t)ksplit * p.M * p.H * p.W;
     if (split) {
@@ -694,57 +683,28 @@ int conv_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, bool
         n_wg *= ksplit;
     }
 
-#define STX_DISPATCH(ID)                                                                          \
-    case ID:                                                                                      \
-        if (split) {                                                                              \
-            STX_TRY((launch_##ID<kEpiPartial, true>(s, cfg, a, n_wg)));                           \
-            goto reduce;                                                                          \
-        }                                                                                         \
-        if (p.epilogue == kEpiForward && packed)                                                  \
-            return launch_##ID<kEpiForward, true>(s, cfg, a, n_wg);                               \
-        if (inject && packed) return launch_##ID<kEpiDgradInject, true>(s, cfg, a, n_wg);          \
-        if (p.epilogue == kEpiDgrad && packed) return launch_##ID<kEpiDgrad, true>(s, cfg, a, n_wg); \
-        break;
-#define STX_DISPATCH_NOINJ(ID)                                                                    \
-    case ID:                                                                                      \
-        if (p.epilogue == kEpiForward && packed)                                                  \
-            return launch_##ID<kEpiForward, true>(s, cfg, a, n_wg);                               \
-        if (p.epilogue == kEpiDgrad && packed && !inject)                                         \
-            return launch_##ID<kEpiDgrad, true>(s, cfg, a, n_wg);                                 \
-        break;
-#define STX_DISPATCH_SYMM(ID)                                                                     \
-    case ID:                                                                                      \
-        if (p.epilogue == kEpiSymm && !packed) return launch_##ID<kEpiSymm, false>(s, cfg, a, n_wg); \
-        if (p.epilogue == kEpiForward && packed)                                                  \
-            return launch_##ID<kEpiForward, true>(s, cfg, a, n_wg);                               \
-        if (p.epilogue == kEpiDgrad && packed && !inject)                                         \
-            return launch_##ID<kEpiDgrad, true>(s, cfg, a, n_wg);                                 \
-        break;
     switch (cfg.id) {
+#define STX_DISPATCH(ID) \
+    case ID: return dispatch_variant<ID>(s, cfg, p, a, n_wg, packed, inject, split ? ksplit : 1);
         STX_DISPATCH(0)
         STX_DISPATCH(1)
         STX_DISPATCH(2)
-        STX_DISPATCH_NOINJ(3)
-        STX_DISPATCH_NOINJ(4)
-        STX_DISPATCH_NOINJ(8)
+        STX_DISPATCH(3)
+        STX_DISPATCH(4)
+        STX_DISPATCH(8)
         STX_DISPATCH(9)
         STX_DISPATCH(10)
         STX_DISPATCH(11)
         STX_DISPATCH(5)
-        STX_DISPATCH_SYMM(6)
-        STX_DISPATCH_SYMM(7)
-        STX_DISPATCH_SYMM(12)
-        STX_DISPATCH_SYMM(13)
-        STX_DISPATCH_SYMM(14)
-    }
+        STX_DISPATCH(6)
+        STX_DISPATCH(7)
+        STX_DISPATCH(12)
+        STX_DISPATCH(13)
+        STX_DISPATCH(14)
 #undef STX_DISPATCH
-#undef STX_DISPATCH_NOINJ
-#undef STX_DISPATCH_SYMM
-    set_error("conv_launch: no kernel for config %d epilogue %d packed %d", cfg.id, p.epilogue,
-              (int)packed);
+    }
+    set_error("conv_launch: no kernel for config %d epilogue %d packed %d", cfg.id, p.epilogue, (int)packed);
     return STX_ERR_UNSUPPORTED;
-reduce:
-    return splitk_reduce_launch(s, p, ksplit);
 }
 
 static SplitReduceArgs splitk_reduce_args(const ConvProblem &p, int ksplit) {

@@ -809,15 +809,8 @@ __global__ __launch_bounds__(NT) void conv_wino2_kernel(WinoArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 ConvConfig wino2_config(int geometry) {
-    ConvConfig c;
-    c.id = 200 + geometry;            // ids >= 200 mark the 2-D Winograd configurations
-    c.bm = BM;
-    c.kc = KC;
-    c.pr = geometry == 1 ? Geo<8>::PR : geometry == 2 ? Geo<16>::PR : Geo<32>::PR;
-    c.pc = geometry == 1 ? Geo<8>::PC : geometry == 2 ? Geo<16>::PC : Geo<32>::PC;
-    c.threads = NT;
-    c.lds_bytes = kLdsBytes;
-    return c;
+    return {ConvFamily::Wino2, geometry, BM, KC, geometry == 1 ? Geo<8>::PR : geometry == 2 ? Geo<16>::PR : Geo<32>::PR,
+            geometry == 1 ? Geo<8>::PC : geometry == 2 ? Geo<16>::PC : Geo<32>::PC, NT, kLdsBytes};
 }
 
 // 16 x 16 patches for narrow planes, where a 64-pixel-wide patch is mostly padding (measured:
@@ -849,7 +842,6 @@ static double wino2_round_us(int chunks) { return chunks * 2.05 + 6.0; }
 // (cost in model microseconds, 0 slices = not applicable)
 static Wino2Tail wino2_tail_plan(const ConvConfig &cfg, const ConvProblem &p, double *cost, bool any_epilogue = false) {
     const Wino2Tail none{0, 1};
-    if (cfg.id < 200 || cfg.id >= 210) return none;      // (the eight-wave kernel only)
     if (p.epilogue != kEpiForward && p.epilogue != kEpiDgrad) return none;
     // the fused pooling and the ReLU nibbles belong to the unsplit epilogue
     if (!any_epilogue && (p.pool_out || p.wants_codes || p.in_codes || p.mask_codes)) return none;
@@ -973,31 +965,25 @@ int wino2_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int 
 
 // The eight-wave kernel writes / reads ReLU sign nibbles unless the launch is sliced along K.
 // STX_RELU_CODES=0 (stx_reread_env after a change) keeps the fp32 masks, for A/B measurements and tests.
-bool conv_uses_relu_codes(const ConvConfig &cfg, const ConvProblem &p, int ksplit) {
-    const char *env = sw_env("STX_RELU_CODES");
-    if (env && atoi(env) == 0) return false;
-    if (cfg.id < 200 || cfg.id >= 210 || ksplit > 1) return false;
+// (nibbles need the kernel's buffer addressing: plane sets under 2 GiB, no STX_WINO_BIG=1)
+static bool wino2_codes_addressable(const ConvProblem &p) {
     const double xb = 4.0 * p.K * (double)p.H * p.W, yb = 4.0 * p.M * (double)p.H * p.W;
-    if (xb >= 2147483648.0 || yb >= 2147483648.0) return false;
     const char *force_big = sw_env("STX_WINO_BIG");
-    if (force_big && atoi(force_big) == 1) return false;
+    return xb < 2147483648.0 && yb < 2147483648.0 && !(force_big && atoi(force_big) == 1);
+}
+
+bool wino2_uses_relu_codes(const ConvProblem &p, int ksplit) {
+    const char *env = sw_env("STX_RELU_CODES");
+    if ((env && atoi(env) == 0) || ksplit > 1 || !wino2_codes_addressable(p)) return false;
     return p.epilogue == kEpiForward ? p.in_codes != nullptr
                                      : p.epilogue == kEpiDgrad && p.mask_codes != nullptr;
 }
 
-// The unsplit eight-wave fp32 kernel and the unsplit fp16-split kernel leave the sign nibbles of their
-// (rectified) output.  Mirrors wino2_launch / h2_launch: no K slices, no tail split, no re-based addressing.
-bool conv_writes_out_codes(const ConvConfig &cfg, const ConvProblem &p, int ksplit) {
-    const char *env = sw_env("STX_RELU_CODES");
-    if (env && atoi(env) == 0) return false;
-    if (p.epilogue != kEpiForward || !p.relu || !p.out_codes || ksplit > 1) return false;
-    if (cfg.id >= 300) return true;
-    if (cfg.id < 200 || cfg.id >= 210) return false;
-    const double xb = 4.0 * p.K * (double)p.H * p.W, yb = 4.0 * p.M * (double)p.H * p.W;
-    if (xb >= 2147483648.0 || yb >= 2147483648.0) return false;
-    const char *force_big = sw_env("STX_WINO_BIG");
-    if (force_big && atoi(force_big) == 1) return false;
-    const bool mk = conv_uses_relu_codes(cfg, p, 1);
+// An unsplit forward launch with out_codes (conv_writes_out_codes has checked that much) leaves the sign
+// nibbles of its rectified output.  Mirrors wino2_launch: no tail split, no re-based addressing.
+bool wino2_writes_out_codes(const ConvConfig &cfg, const ConvProblem &p) {
+    if (!wino2_codes_addressable(p)) return false;
+    const bool mk = wino2_uses_relu_codes(p, 1);
     const Wino2Tail tail = wino2_tail_split(cfg, p);
     const bool tail_taken = tail.items && p.splitk_ws &&
                             p.splitk_ws_floats >= (size_t)tail.slices * p.M * p.H * p.W && !mk && !wino2_fuses_pool(p);
@@ -1075,13 +1061,13 @@ int wino2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int
     a.x_bytes = big ? 0 : (int)xb;
     // ReLU sign nibbles (see ConvProblem): written by the plain forward kernel, read by the plain
     // backward kernels; K slices and the BIG variants keep the fp32 mask
-    const bool codes = conv_uses_relu_codes(cfg, p, split ? ksplit : 1) && !big;
+    const bool codes = wino2_uses_relu_codes(p, split ? ksplit : 1) && !big;
     a.clock_out = p.clock_out;
     a.y_amax = p.y_amax;              // (K slices: the reduce pass leaves it, splitk_reduce_args)
     a.in_codes = codes && p.epilogue == kEpiForward ? p.in_codes : nullptr;
     a.mask_codes = codes && p.epilogue == kEpiDgrad ? p.mask_codes : nullptr;
     const bool mk = a.mask_codes != nullptr || a.in_codes != nullptr;
-    // nibbles of the output: by the unsplit kernel only (conv_writes_out_codes below says the same)
+    // nibbles of the output: by the unsplit kernel only (wino2_writes_out_codes above says the same)
     a.out_codes = !split && !big && !(tail_ok && !mk && !wino2_fuses_pool(p)) && p.epilogue == kEpiForward && p.relu
                       ? p.out_codes : nullptr;
     if (split) {
@@ -1099,16 +1085,16 @@ int wino2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int
 #define STX_W2_CASE(E)                                                                            \
     case E:                                                                                       \
         if (big && E != kEpiPartial)                                                              \
-            STX_TRY(cfg.id == 201   ? (wino2_launch_epi<E, 8, true>(s, a, n_wg))                  \
-                    : cfg.id == 202 ? (wino2_launch_epi<E, 16, true>(s, a, n_wg))                 \
+            STX_TRY(cfg.id == 1   ? (wino2_launch_epi<E, 8, true>(s, a, n_wg))                  \
+                    : cfg.id == 2 ? (wino2_launch_epi<E, 16, true>(s, a, n_wg))                 \
                                     : (wino2_launch_epi<E, 32, true>(s, a, n_wg)));               \
         else if (mk && (E == kEpiForward || E == kEpiDgrad || E == kEpiDgradInject))              \
-            STX_TRY(cfg.id == 201   ? (wino2_launch_epi<E, 8, false, true>(s, a, n_wg))           \
-                    : cfg.id == 202 ? (wino2_launch_epi<E, 16, false, true>(s, a, n_wg))          \
+            STX_TRY(cfg.id == 1   ? (wino2_launch_epi<E, 8, false, true>(s, a, n_wg))           \
+                    : cfg.id == 2 ? (wino2_launch_epi<E, 16, false, true>(s, a, n_wg))          \
                                     : (wino2_launch_epi<E, 32, false, true>(s, a, n_wg)));        \
         else                                                                                      \
-            STX_TRY(cfg.id == 201   ? (wino2_launch_epi<E, 8>(s, a, n_wg))                        \
-                    : cfg.id == 202 ? (wino2_launch_epi<E, 16>(s, a, n_wg))                       \
+            STX_TRY(cfg.id == 1   ? (wino2_launch_epi<E, 8>(s, a, n_wg))                        \
+                    : cfg.id == 2 ? (wino2_launch_epi<E, 16>(s, a, n_wg))                       \
                                     : (wino2_launch_epi<E, 32>(s, a, n_wg)));                     \
         break;
     switch (epi) {
@@ -1139,8 +1125,8 @@ static int wino2_launch_tail(hipStream_t s, const ConvConfig &cfg, const ConvPro
     part.y_amax = nullptr;
 #define STX_W2_TAIL(E)                                                                            \
     case E:                                                                                       \
-        STX_TRY(cfg.id == 201   ? (wino2_launch_epi<E, 8>(s, whole, n_full))                      \
-                : cfg.id == 202 ? (wino2_launch_epi<E, 16>(s, whole, n_full))                     \
+        STX_TRY(cfg.id == 1   ? (wino2_launch_epi<E, 8>(s, whole, n_full))                      \
+                : cfg.id == 2 ? (wino2_launch_epi<E, 16>(s, whole, n_full))                     \
                                 : (wino2_launch_epi<E, 32>(s, whole, n_full)));                   \
         break;
     switch (epi) {
@@ -1153,33 +1139,10 @@ static int wino2_launch_tail(hipStream_t s, const ConvConfig &cfg, const ConvPro
     }
 #undef STX_W2_TAIL
     const int n_part = tail.items * tail.slices;
-    STX_TRY(cfg.id == 201   ? (wino2_launch_epi<kEpiPartial, 8>(s, part, n_part))
-            : cfg.id == 202 ? (wino2_launch_epi<kEpiPartial, 16>(s, part, n_part))
+    STX_TRY(cfg.id == 1   ? (wino2_launch_epi<kEpiPartial, 8>(s, part, n_part))
+            : cfg.id == 2 ? (wino2_launch_epi<kEpiPartial, 16>(s, part, n_part))
                             : (wino2_launch_epi<kEpiPartial, 32>(s, part, n_part)));
     return splitk_reduce_items_launch(s, p, cfg, tail.slices, n_full, tail.items);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The Winograd configurations of the library (cfg.id >= 200: this kernel; >= 300: conv_h2.hip), by id.
-// (Until round 6 two more fp32 families lived here -- 1-D F(2,3), ids 100+, and the four-wave form of this
-// kernel, ids 210+: reachable only through switches once conv_h2 took the 3x3 layers; they are kept under
-// tools/experiments/ with their tests' history, and this kernel is the library's one fp32 Winograd family.)
-size_t wino_packed_floats(const ConvConfig &cfg, int K, int M) {
-    return cfg.id >= 300 ? h2_packed_floats(K, M) : wino2_packed_floats(K, M);
-}
-
-int wino_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int transpose_flip,
-                      const ConvConfig &cfg, float *packed) {
-    if (cfg.id >= 300) return h2_pack_weights(s, w_caffe, Mo, Ko, transpose_flip, packed);
-    return wino2_pack_weights(s, w_caffe, Mo, Ko, transpose_flip, packed);
-}
-
-// Launches a Winograd configuration; `w` must come from wino_pack_weights.
-int wino_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ksplit) {
-    if (cfg.id >= 300) return h2_launch(s, cfg, p, ksplit);
-    if (cfg.id >= 200 && cfg.id < 210) return wino2_launch(s, cfg, p, ksplit);
-    set_error("wino_launch: no kernel for config %d", cfg.id);
-    return STX_ERR_UNSUPPORTED;
 }
 
 }  // namespace stx

@@ -94,7 +94,7 @@ struct ConvParams {
     int cin = 0, cout = 0, ks = 0;
     DevBuf w, b;                              // Caffe layout on the device
     bool set = false;
-    std::map<int, std::unique_ptr<DevBuf>> packed;  // key = dir * 1024 + config id
+    std::map<int, std::unique_ptr<DevBuf>> packed;  // key: ConvBank::key
 };
 
 struct ContentTarget {
@@ -199,7 +199,7 @@ struct stx_engine {
     DevBuf red_scratch;                // float partials for image-op reductions
 
     bool winograd = true;   // 1-D Winograd F(2,3) for the 3x3 layers (STX_WINOGRAD=0: direct only)
-    bool autotune = true;   // tile-config autotuning (process-wide cache, see choose_conv_config)
+    bool autotune = true;   // tile-config autotuning (process-wide cache, see conv_choose)
     bool pool_codes = true; // forward pooling leaves window codes for the backward pass (STX_POOL_CODES=0: off)
 
     // optional per-kernel-group timing (stx_profile_enable): event pairs around launch groups
@@ -342,119 +342,43 @@ void mark_ancestors(const stx_engine *e, int blob, std::vector<char> &needed) {
     }
 }
 
-int get_packed(stx_engine *e, int layer, int dir, const ConvConfig &cfg, const float **out) {
+// The bank of layer `layer`, packed from its weights the first time it is asked for.
+static int get_bank(stx_engine *e, int layer, const ConvBank &bank, const float **out) {
     std::lock_guard<std::mutex> lock(e->sh->mutex);
     ConvParams &cp = e->sh->conv[layer];
     if (!cp.set) {
         set_error("weights of layer %s were never set", e->layers[layer].name.c_str());
         return STX_ERR_STATE;
     }
-    // (the 2-D geometries share a bank, so do the two channel tilings of the fp16-split kernel)
-    const int key = dir * 1024 + (cfg.id >= 300 ? 300 : cfg.id >= 200 ? 200 : cfg.id);
-    auto it = cp.packed.find(key);
+    auto it = cp.packed.find(bank.key);
     if (it == cp.packed.end()) {
-        const int M = dir ? cp.cin : cp.cout, K = dir ? cp.cout : cp.cin;
         std::unique_ptr<DevBuf> buf(new DevBuf);
-        if (cfg.id >= 100) {   // Winograd-transformed bank
-            STX_TRY(buf->ensure(wino_packed_floats(cfg, K, M) * sizeof(float)));
-            STX_TRY(wino_pack_weights(e->stream, cp.w.f(), cp.cout, cp.cin, dir, cfg, buf->f()));
-        } else {
-            STX_TRY(buf->ensure(conv_packed_floats(cfg, K, M, cp.ks) * sizeof(float)));
-            STX_TRY(conv_pack_weights(e->stream, cp.w.f(), cp.cout, cp.cin, cp.ks, dir, cfg,
-                                      buf->f()));
-        }
+        STX_TRY(buf->ensure(bank.floats * sizeof(float)));
+        STX_TRY(bank.pack(e->stream, cp.w.f(), buf->f()));
         // the other engines of this GPU will read the bank from their own streams
         if (e->sh->members.size() > 1) STX_HIP(hipStreamSynchronize(e->stream));
-        it = cp.packed.emplace(key, std::move(buf)).first;
+        it = cp.packed.emplace(bank.key, std::move(buf)).first;
     }
     *out = it->second->f();
     return STX_OK;
 }
 
-// Picks the tile configuration of a packed-weight convolution.  All configurations accumulate k
-// in the same order, so they produce bit-identical results; which one is fastest depends on how
-// many workgroups the plane yields (co-resident workgroups hide each other's stage swaps and
-// epilogues).  The first time a shape is seen every candidate is timed with HIP events on the
-// engine stream (a few launches, once per shape and scale) and the winner is cached.
-// The cache is shared by all engines of the process (several engines drive the same GPU as
-// separate streams; they must agree, and later ones need not re-measure).  Key: device + shape.
-static std::mutex g_tuned_mutex;
-static std::map<std::vector<int>, int> g_tuned;
-
-// 3x3 layers with more than 32 output channels that the fp16-split kernel does not take (h2_choice) run the
-// fp32 2-D Winograd kernel F(2x2,3x3) (4/9 of the direct kernel's MFMAs); everything else the direct kernel.
-// The choice depends on the shape only, never on timing: the rounding differs between the kernels, and a
-// given shape must always take the same path.  STX_CONV_ALGO=direct|wino2|wino2a|wino2b|wino2c overrides it
-// for tests and measurements (a / b / c: one patch geometry only).
-static bool wino_choice(stx_engine *e, int ksize, int K, int M, int H, int W, ConvConfig *out,
-                        bool inject = false) {
-    (void)inject;
-    if (ksize != 3 || K < 8 || M <= 4) return false;
-    const char *algo = sw_env("STX_CONV_ALGO");
-    if (algo && *algo) {
-        if (!strcmp(algo, "direct")) return false;
-        if (!strcmp(algo, "wino2")) { *out = wino2_config(wino2_pick_geometry(H, W)); return true; }
-        if (!strcmp(algo, "wino2a")) { *out = wino2_config(0); return true; }   // one geometry only
-        if (!strcmp(algo, "wino2b")) { *out = wino2_config(1); return true; }
-        if (!strcmp(algo, "wino2c")) { *out = wino2_config(2); return true; }
-    }
-    if (!e->winograd || M <= 32) return false;
-    *out = wino2_config(wino2_pick_geometry(H, W));
-    return true;
+int get_packed(stx_engine *e, int layer, int dir, const ConvConfig &cfg, const float **out) {
+    const ConvParams &cp = e->sh->conv[layer];
+    return get_bank(e, layer, conv_bank(cfg, dir, cp.cout, cp.cin, cp.ks), out);
 }
 
-int choose_conv_config(stx_engine *e, int li, int dir, ConvProblem p, ConvConfig *out,
-                       bool inject = false) {
-    if (wino_choice(e, p.ksize, p.K, p.M, p.H, p.W, out, inject)) return STX_OK;
-    const ConvConfig fallback = conv_pick_config(p.ksize, p.K, p.M, p.H, p.W);
-    *out = fallback;
-    if (!e->autotune || p.ksize != 3 || p.K <= 4 || p.M <= 32) return STX_OK;
-    // planes too small to fill the chip run the small-tile config with a K split that depends on
-    // the shape only (split results differ in rounding from unsplit ones, so no timing here)
-    if (conv_splitk_factor(fallback, p, true) > 1 ||
-        conv_num_workgroups(conv_config_by_id(5), p.M, p.H, p.W) < 256)
-        return STX_OK;
-    const std::vector<int> key = {e->device, p.ksize, p.K, p.M, p.H, p.W, p.epilogue};
-    {
-        std::lock_guard<std::mutex> lock(g_tuned_mutex);
-        auto it = g_tuned.find(key);
-        if (it != g_tuned.end()) {
-            *out = conv_config_by_id(it->second);
-            return STX_OK;
-        }
-    }
-    const int candidates[] = {0, 1, 2, 5};
-    float best_ms = 1e30f;
-    int best = fallback.id;
-    for (int id : candidates) {
-        const ConvConfig cfg = conv_config_by_id(id);
-        if (cfg.bm > 64 && p.M <= 64) continue;            // half-empty channel tiles
-        const float *packed = nullptr;
-        STX_TRY(get_packed(e, li, dir, cfg, &packed));
-        p.w = packed;
-        STX_TRY(conv_launch(e->stream, cfg, p, true));     // warm (also builds nothing lazily)
-        STX_HIP(hipEventRecord(e->ev_tune0, e->stream));
-        for (int r = 0; r < 2; ++r) STX_TRY(conv_launch(e->stream, cfg, p, true));
-        STX_HIP(hipEventRecord(e->ev_tune1, e->stream));
-        STX_HIP(hipEventSynchronize(e->ev_tune1));
-        float ms = 0.f;
-        STX_HIP(hipEventElapsedTime(&ms, e->ev_tune0, e->ev_tune1));
-        if (ms < best_ms) {
-            best_ms = ms;
-            best = id;
-        }
-    }
-    {
-        std::lock_guard<std::mutex> lock(g_tuned_mutex);
-        g_tuned[key] = best;
-    }
-    *out = conv_config_by_id(best);
-    return STX_OK;
+// The configuration of convolution li in direction dir (conv_choose), tuned where the engine tunes.
+static int choose_conv(stx_engine *e, int li, int dir, const ConvProblem &p, ConvConfig *out) {
+    const ConvTuner tuner{e->device, e->stream, e->ev_tune0, e->ev_tune1, [=](const ConvConfig &cfg, const float **w) {
+                              return get_packed(e, li, dir, cfg, w);
+                          }};
+    return conv_choose(p, e->winograd, e->autotune ? &tuner : nullptr, out);
 }
 
 // Gives the problem a split-K scratch buffer when conv_launch will slice the reduction.
 int attach_splitk(stx_engine *e, const ConvConfig &cfg, ConvProblem &p) {
-    const size_t need = conv_splitk_floats(cfg, p, true);
+    const size_t need = conv_splitk_floats(cfg, p);
     if (!need) return STX_OK;
     STX_TRY(e->splitk.ensure(need * sizeof(float)));
     p.splitk_ws = e->splitk.f();
@@ -466,77 +390,13 @@ constexpr int kMaxClockMarks = 16384;
 
 int launch_conv(stx_engine *e, const ConvConfig &cfg, const ConvProblem &problem) {
     ConvProblem p = problem;
-    // stx_clock_marks: the eight-wave Winograd kernel times the chunk loop of one of its workgroups
     e->last_mark = -1;
-    if (e->clock_marks && ((cfg.id >= 200 && cfg.id < 210) || cfg.id >= 300) && e->marks_used < kMaxClockMarks) {
+    if (e->clock_marks && conv_takes_clock(cfg) && e->marks_used < kMaxClockMarks) {
         e->last_mark = e->marks_used++;
         p.clock_out = static_cast<long long *>(e->marks_buf.ptr) + 2 * (size_t)e->last_mark;
     }
-    // bookkeeping for stx_last_tile_flops: algorithmic = direct convolution, issued = what the
-    // chosen kernel puts on the matrix cores (tile padding not counted)
-    const double direct = 2.0 * p.M * p.K * p.ksize * p.ksize * (double)p.H * p.W;
-    e->flop_algorithmic += direct;
-    // (ids 300+: 6 of 9 multiplies, each as three fp16 products of 1/16 of an fp32 MFMA's time per k)
-    e->flop_issued += cfg.id >= 300   ? direct * (6.0 / 9.0) * (3.0 / 16.0)
-                      : cfg.id >= 200 ? direct * 4.0 / 9.0
-                      : cfg.id >= 100 ? direct * 2.0 / 3.0
-                                      : direct;
-    if (cfg.id >= 100) return wino_launch(e->stream, cfg, p, conv_splitk_factor(cfg, p, true));
-    return conv_launch(e->stream, cfg, p, true);
-}
-
-// Which fused-pooling kernels also leave the window codes the backward pooling runs from: the
-// eight-wave 2-D Winograd kernel does, the four-wave one (ids 210+) writes the pooled values only.
-static bool conv_writes_pool_codes(const ConvConfig &cfg) { return (cfg.id >= 200 && cfg.id < 210) || cfg.id >= 300; }
-
-// True if a launch of `p` under `cfg` writes p.pool_out itself (2-D Winograd, no K split).
-static bool conv_fuses_pool(const ConvConfig &cfg, const ConvProblem &p) {
-    // (STX_POOL_FWD_FUSE=0: the stand-alone pooling kernel everywhere, for A/B measurements and tests)
-    const char *env = sw_env("STX_POOL_FWD_FUSE");
-    if (env && atoi(env) == 0) return false;
-    if (cfg.id >= 300) return conv_splitk_factor(cfg, p, true) == 1 && h2_fuses_pool(p);
-    return cfg.id >= 200 && conv_splitk_factor(cfg, p, true) == 1 && wino2_fuses_pool(p);
-}
-
-// The fp16-split kernel (conv_h2.hip) for this problem?  By shape and epilogue only -- never by timing:
-// it rounds differently from the fp32 kernels, and a given shape must always take the same path.
-//   forward: layers with at least STX_CONV_H2 input channels (default 64; 0: never);
-//   backward: at least STX_CONV_H2_BWD channels of incoming gradient (default 64).
-// A forward blob that differs in its last bits flips ReLU / max-pooling near-ties, and the two 64-channel
-// layers hold most of a tile's decisions.  Every bound of tests/ holds with them on this kernel; the one
-// chaotic fixture -- the reference's L-BFGS run of BASELINE config 4 in miniature, tiles of 30 x 33 pixels
-// -- follows another of the REFERENCE'S OWN branches (tests/golden/cfg4_sensitivity.py: the reference with
-// its convolutions rounded at this level takes that branch in half of its runs).
-// The backward pass decides nothing: its rounding moves the gradient by 1e-7 and no further.
-// STX_CONV_ALGO=h2|h2a|h2b|h2c forces the kernel (any / the 64- / the 128-channel / the two-patch tiling)
-// wherever it applies.
-static bool h2_enabled() {
-    const char *algo = sw_env("STX_CONV_ALGO");
-    if (algo && *algo) return !strncmp(algo, "h2", 2);
-    // (the thresholds of h2_choice: with STX_CONV_H2=0 and no STX_CONV_H2_BWD neither direction takes the kernel)
-    const char *env = sw_env("STX_CONV_H2"), *envb = sw_env("STX_CONV_H2_BWD");
-    const int fwd_min = env ? atoi(env) : 64;
-    const int bwd_min = envb ? atoi(envb) : (env && atoi(env) <= 0 ? 0 : 64);
-    return fwd_min > 0 || bwd_min > 0;
-}
-
-static bool h2_choice(const ConvProblem &p, ConvConfig *out) {
-    const char *algo = sw_env("STX_CONV_ALGO");
-    int force = 0;
-    if (algo && *algo) {
-        if (!strcmp(algo, "h2")) force = 4;
-        else if (!strcmp(algo, "h2a")) force = 1;
-        else if (!strcmp(algo, "h2b")) force = 2;
-        else if (!strcmp(algo, "h2c")) force = 3;
-        else return false;             // some other kernel family was asked for
-    }
-    const char *env = sw_env("STX_CONV_H2"), *envb = sw_env("STX_CONV_H2_BWD");
-    const int min_k = p.epilogue == kEpiForward ? (env ? atoi(env) : 64)
-                                                : (envb ? atoi(envb) : env && atoi(env) <= 0 ? 0 : 64);
-    if (!force && (min_k <= 0 || p.K < min_k || p.M < 64)) return false;
-    if (!h2_usable(p)) return false;
-    *out = force == 1 ? h2_config(1) : force == 2 ? h2_config(2) : force == 3 ? h2_config(1, 2) : h2_pick_config(p);
-    return true;
+    // (bookkeeping for stx_last_tile_flops)
+    return conv_dispatch(e->stream, cfg, p, &e->flop_algorithmic, &e->flop_issued);
 }
 
 // The slots with max |x| of a blob's data / diff for a kernel that is about to read it: what its
@@ -582,7 +442,7 @@ int run_conv_forward(stx_engine *e, int li, bool force_relu, const Layer *pool =
         t.relu_codes_valid = false;
         unsigned *y_amax = nullptr;
         t.amax_data = -1;
-        if (h2_enabled()) {
+        if (conv_h2_enabled()) {
             y_amax = e->amax_slots(L.top_blob, false);
             t.amax_data = L.top_blob;
         }
@@ -602,22 +462,18 @@ int run_conv_forward(stx_engine *e, int li, bool force_relu, const Layer *pool =
         return conv_first_launch(e->stream, p.x, cp.w.f(), cp.b.f(), p.y, cp.cin, b.h, b.w, p.relu, gram, y_amax);
     }
     ConvConfig cfg;
-    // the fp16-split kernel where it applies (it neither writes nor reads ReLU nibbles)
-    const bool h2 = h2_choice(p, &cfg);
-    // (a blob whose producer already left its nibbles needs none from its consumer)
-    b.relu_codes_wanted = !h2 && !b.relu_codes_valid && relu_codes && b.relu && b.channels <= 128;      // (see below)
+    STX_TRY(choose_conv(e, li, 0, p, &cfg));
+    // (a blob whose producer already left its nibbles needs none from its consumer; the fp16-split kernel
+    // reads the maximum of its input instead)
+    b.relu_codes_wanted = !conv_reads_x_amax(cfg) && !b.relu_codes_valid && relu_codes && b.relu && b.channels <= 128;  // (see below)
     p.wants_codes = b.relu_codes_wanted;
-    if (!h2) STX_TRY(choose_conv_config(e, li, 0, p, &cfg));
     t.amax_data = -1;
-    if (h2) STX_TRY(amax_for(e, L.bottom_blob, false, &p.x_amax));
-    // the eight-wave fp32 kernel leaves its output's maximum too (conv3_1 feeds conv3_2)
-    if (h2 || (cfg.id >= 200 && cfg.id < 210 && h2_enabled())) {
+    if (conv_reads_x_amax(cfg)) STX_TRY(amax_for(e, L.bottom_blob, false, &p.x_amax));
+    if (conv_leaves_y_amax(cfg)) {
         p.y_amax = e->amax_slots(L.top_blob, false);
         t.amax_data = L.top_blob;          // (a K-sliced launch leaves it through its reduce pass)
     }
-    const float *packed = nullptr;
-    STX_TRY(get_packed(e, li, 0, cfg, &packed));
-    p.w = packed;
+    STX_TRY(get_packed(e, li, 0, cfg, &p.w));
     STX_TRY(attach_splitk(e, cfg, p));
     // a backward pass will follow: let this layer leave the sign nibbles of its (rectified) input
     // (up to 128 input channels -- conv1_2 and conv2_2 of a VGG: their backward pass is co-limited
@@ -628,7 +484,7 @@ int run_conv_forward(stx_engine *e, int li, bool force_relu, const Layer *pool =
         const size_t bytes = (size_t)b.channels * ((b.h + 1) / 2) * ((b.w + 1) / 2);
         STX_TRY(b.relu_codes.ensure(bytes));
         p.in_codes = static_cast<unsigned char *>(b.relu_codes.ptr);
-        b.relu_codes_valid = conv_uses_relu_codes(cfg, p, conv_splitk_factor(cfg, p, true));
+        b.relu_codes_valid = conv_uses_relu_codes(cfg, p, conv_splitk_factor(cfg, p));
         if (!b.relu_codes_valid) p.in_codes = nullptr;
     }
     if (pooled) *pooled = false;
@@ -661,11 +517,11 @@ int run_conv_forward(stx_engine *e, int li, bool force_relu, const Layer *pool =
     // and stores are a bandwidth-bound burst)
     t.relu_codes_valid = false;
     // (only beside the fp16-split kernels: STX_CONV_H2=0 keeps round 4's schedule to the letter)
-    if (relu_codes && t.relu && out_codes_wanted && h2_enabled()) {
+    if (relu_codes && t.relu && out_codes_wanted && conv_h2_enabled()) {
         const size_t bytes = (size_t)t.channels * ((t.h + 1) / 2) * ((t.w + 1) / 2);
         STX_TRY(t.relu_codes.ensure(bytes));
         p.out_codes = static_cast<unsigned char *>(t.relu_codes.ptr);
-        t.relu_codes_valid = conv_writes_out_codes(cfg, p, conv_splitk_factor(cfg, p, true));
+        t.relu_codes_valid = conv_writes_out_codes(cfg, p, conv_splitk_factor(cfg, p));
         if (!t.relu_codes_valid) p.out_codes = nullptr;
     }
     ProfScope scope(e, "fwd " + L.name, conv_flops(cp.cin, cp.cout, b.h, b.w, cp.ks));
@@ -696,7 +552,8 @@ static bool conv_backward_takes_pooled(stx_engine *e, int li) {
     if (env && atoi(env) == 0) return false;
     const ConvProblem p = conv_backward_shape(e, li);
     ConvConfig cfg;
-    return p.ksize == 3 && p.M > 4 && h2_choice(p, &cfg) && h2_takes_pooled_input(cfg, p);
+    return p.ksize == 3 && p.M > 4 && conv_choose(p, e->winograd, nullptr, &cfg) == STX_OK &&
+           conv_takes_pooled_input(cfg, p);
 }
 
 // `pooled` (or null): the pooling layer behind this convolution whose backward pass the caller skipped
@@ -722,32 +579,23 @@ int run_conv_backward(stx_engine *e, int li, const ConvInject *inj, bool *fused,
     if (cp.ks == 3 && cp.cin <= 4) {
         // backward into a <= 4-channel blob (the image): dedicated 4x4x1-MFMA kernel
         if (fused) *fused = false;
-        std::lock_guard<std::mutex> lock(e->sh->mutex);
-        ConvParams &cpm = e->sh->conv[li];
-        auto it = cpm.packed.find(1 * 1024 + 999);
-        if (it == cpm.packed.end()) {
-            std::unique_ptr<DevBuf> buf(new DevBuf);
-            STX_TRY(buf->ensure(conv_small_packed_floats(cp.cout) * sizeof(float)));
-            STX_TRY(conv_small_pack(e->stream, cp.w.f(), cp.cout, cp.cin, 1, buf->f()));
-            if (e->sh->members.size() > 1) STX_HIP(hipStreamSynchronize(e->stream));
-            it = cpm.packed.emplace(1 * 1024 + 999, std::move(buf)).first;
-        }
+        const float *packed = nullptr;
+        STX_TRY(get_bank(e, li, conv_small_bank(cp.cout, cp.cin), &packed));
         ProfScope scope(e, "bwd " + L.name, conv_flops(cp.cout, cp.cin, b.h, b.w, cp.ks));
         const double direct = 2.0 * p.M * p.K * 9 * (double)p.H * p.W;
         e->flop_algorithmic += direct;
         e->flop_issued += direct * 4.0 / p.M;    // the 4x4x1 MFMA computes four output channels
-        return conv_small_launch(e->stream, p.x, it->second->f(), p.y, p.mask, p.K, p.M, p.H, p.W);
+        return conv_small_launch(e->stream, p.x, packed, p.y, p.mask, p.K, p.M, p.H, p.W);
     }
     ConvConfig cfg;
-    const bool h2 = h2_choice(p, &cfg);      // (it reads the ReLU nibbles as the eight-wave fp32 kernel does)
-    if (!h2) STX_TRY(choose_conv_config(e, li, 1, p, &cfg, inj != nullptr));   // tuned without the injection terms
-    const bool can_fuse = cfg.id != 3 && cfg.id != 4 && cfg.id != 8;   // Winograd ids fuse too  // those two have no injecting epilogue
-    if (fused) *fused = inj && can_fuse;
-    if (inj && can_fuse) p.inject = *inj;
+    STX_TRY(choose_conv(e, li, 1, p, &cfg));   // (tuned without the injection terms)
+    const bool can_fuse = inj && conv_takes_inject(cfg);
+    if (fused) *fused = can_fuse;
+    if (can_fuse) p.inject = *inj;
     b.amax_diff = -1;
     if (pooled) {
         const Blob &pt = e->blobs[pooled->top_blob];
-        if (!h2 || !h2_takes_pooled_input(cfg, p) || !pt.codes_valid) {
+        if (!conv_takes_pooled_input(cfg, p) || !pt.codes_valid) {
             set_error("run_conv_backward: %s cannot take the gradient of %s pooled", L.name.c_str(), pt.name.c_str());
             return STX_ERR_UNSUPPORTED;
         }
@@ -756,16 +604,14 @@ int run_conv_backward(stx_engine *e, int li, const ConvInject *inj, bool *fused,
         p.pin_mode = pooled->pool_mode;
         p.pin_mask = t.relu;
         STX_TRY(amax_for(e, pooled->top_blob, true, &p.x_amax));    // (routing / averaging never raises the maximum)
-    } else if (h2) {
+    } else if (conv_reads_x_amax(cfg)) {
         STX_TRY(amax_for(e, L.top_blob, true, &p.x_amax));
     }
-    if (h2 || (cfg.id >= 200 && cfg.id < 210 && h2_enabled())) {
+    if (conv_leaves_y_amax(cfg)) {
         p.y_amax = e->amax_slots(L.bottom_blob, true);
         b.amax_diff = L.bottom_blob;
     }
-    const float *packed = nullptr;
-    STX_TRY(get_packed(e, li, 1, cfg, &packed));
-    p.w = packed;
+    STX_TRY(get_packed(e, li, 1, cfg, &p.w));
     STX_TRY(attach_splitk(e, cfg, p));
     ProfScope scope(e, "bwd " + L.name, conv_flops(cp.cout, cp.cin, b.h, b.w, cp.ks));
     return launch_conv(e, cfg, p);
@@ -1850,7 +1696,7 @@ int sc_grad_run(stx_engine *e, const TileCall &c, const TilePlan &plan, PendingL
             // the last term's kernel writes the blob's final gradient: it leaves its maximum for the
             // fp16-split convolution that reads it next (the slots were zeroed when the walk began)
             unsigned *amax = nullptr;
-            if (ti + 1 == terms[k].size() && h2_enabled()) {
+            if (ti + 1 == terms[k].size() && conv_h2_enabled()) {
                 amax = e->amax_slots(order[k].blob, true);
                 b.amax_diff = order[k].blob;
             }
@@ -2296,40 +2142,30 @@ int stx_image_to_u8(stx_engine *e, const float *img, int H, int W, const float m
 }
 
 // --------------------------------------------------------------------------- test hooks
-static int scratch_pack(stx_engine *e, const float *w, int Mo, int Ko, int ks, int dir,
-                        const ConvConfig &cfg, const float **packed) {
-    const int M = dir ? Ko : Mo, K = dir ? Mo : Ko;
-    if (cfg.id >= 100) {
-        STX_TRY(e->upload.ensure(wino_packed_floats(cfg, K, M) * sizeof(float)));
-        STX_TRY(wino_pack_weights(e->stream, w, Mo, Ko, dir, cfg, e->upload.f()));
-    } else {
-        STX_TRY(e->upload.ensure(conv_packed_floats(cfg, K, M, ks) * sizeof(float)));
-        STX_TRY(conv_pack_weights(e->stream, w, Mo, Ko, ks, dir, cfg, e->upload.f()));
-    }
+// Packs `bank` from the Caffe-layout weights w into the upload buffer.
+static int scratch_pack(stx_engine *e, const ConvBank &bank, const float *w, const float **packed) {
+    STX_TRY(e->upload.ensure(bank.floats * sizeof(float)));
+    STX_TRY(bank.pack(e->stream, w, e->upload.f()));
     *packed = e->upload.f();
     return STX_OK;
 }
 
-// Same shape-only selection as the tile path (Winograd where it applies), without the tuner.
-static ConvConfig hook_config(stx_engine *e, int ksize, int K, int M, int H, int W) {
+// A stand-alone operator call: the tile path's choice without the tuner; the input's maximum (where the kernel
+// reads it) comes from a pass over it, the output's goes to a scratch group of the table.
+static int hook_conv(stx_engine *e, ConvProblem &p, const float *w, int Mo, int Ko, int dir) {
     ConvConfig cfg;
-    if (wino_choice(e, ksize, K, M, H, W, &cfg)) return cfg;
-    return conv_pick_config(ksize, K, M, H, W);
-}
-
-// The fp16-split kernel for a stand-alone operator call, by the tile path's rule; the input's maximum
-// comes from a pass over it, the output's goes to a scratch group of the table.
-static int hook_h2(stx_engine *e, ConvProblem &p, ConvConfig *cfg) {
-    ConvConfig h;
-    if (!h2_choice(p, &h)) return STX_OK;
-    *cfg = h;
-    STX_TRY(e->amax.ensure((2 * e->blobs.size() + 2) * kAmaxSlots * sizeof(unsigned)));
-    unsigned *scratch = e->amax_slots((int)e->blobs.size(), true);
-    STX_TRY(absmax_launch(e->stream, p.x, (size_t)p.K * p.H * p.W, scratch));
-    STX_HIP(hipMemsetAsync(scratch + kAmaxSlots, 0, kAmaxSlots * sizeof(unsigned), e->stream));
-    p.x_amax = scratch;
-    p.y_amax = scratch + kAmaxSlots;
-    return STX_OK;
+    STX_TRY(conv_choose(p, e->winograd, nullptr, &cfg));
+    if (conv_reads_x_amax(cfg)) {
+        STX_TRY(e->amax.ensure((2 * e->blobs.size() + 2) * kAmaxSlots * sizeof(unsigned)));
+        unsigned *scratch = e->amax_slots((int)e->blobs.size(), true);
+        STX_TRY(absmax_launch(e->stream, p.x, (size_t)p.K * p.H * p.W, scratch));
+        STX_HIP(hipMemsetAsync(scratch + kAmaxSlots, 0, kAmaxSlots * sizeof(unsigned), e->stream));
+        p.x_amax = scratch;
+        p.y_amax = scratch + kAmaxSlots;
+    }
+    STX_TRY(scratch_pack(e, conv_bank(cfg, dir, Mo, Ko, p.ksize), w, &p.w));
+    STX_TRY(attach_splitk(e, cfg, p));
+    return launch_conv(e, cfg, p);
 }
 
 int stx_op_conv_forward(stx_engine *e, const float *x, int Cin, int H, int W, const float *w,
@@ -2338,7 +2174,6 @@ int stx_op_conv_forward(stx_engine *e, const float *x, int Cin, int H, int W, co
     STX_TRY(e->set_device());
     if (conv_first_usable(Cin, Cout, ksize))      // the tile path's first-layer kernel
         return conv_first_launch(e->stream, x, w, b, y, Cin, H, W, relu, nullptr);
-    ConvConfig cfg = hook_config(e, ksize, Cin, Cout, H, W);
     ConvProblem p{};
     p.x = x;
     p.y = y;
@@ -2350,12 +2185,7 @@ int stx_op_conv_forward(stx_engine *e, const float *x, int Cin, int H, int W, co
     p.ksize = ksize;
     p.relu = relu;
     p.epilogue = kEpiForward;
-    STX_TRY(hook_h2(e, p, &cfg));
-    const float *packed = nullptr;
-    STX_TRY(scratch_pack(e, w, Cout, Cin, ksize, 0, cfg, &packed));
-    p.w = packed;
-    STX_TRY(attach_splitk(e, cfg, p));
-    return launch_conv(e, cfg, p);
+    return hook_conv(e, p, w, Cout, Cin, 0);
 }
 
 int stx_op_conv_backward_data(stx_engine *e, const float *dy, int Cout, int H, int W, const float *w,
@@ -2363,11 +2193,10 @@ int stx_op_conv_backward_data(stx_engine *e, const float *dy, int Cout, int H, i
     if (!e || !dy || !w || !dx) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     if (ksize == 3 && Cin <= 4) {
-        STX_TRY(e->upload.ensure(conv_small_packed_floats(Cout) * sizeof(float)));
-        STX_TRY(conv_small_pack(e->stream, w, Cout, Cin, 1, e->upload.f()));
-        return conv_small_launch(e->stream, dy, e->upload.f(), dx, relu_mask_data, Cout, Cin, H, W);
+        const float *packed = nullptr;
+        STX_TRY(scratch_pack(e, conv_small_bank(Cout, Cin), w, &packed));
+        return conv_small_launch(e->stream, dy, packed, dx, relu_mask_data, Cout, Cin, H, W);
     }
-    ConvConfig cfg = hook_config(e, ksize, Cout, Cin, H, W);
     ConvProblem p{};
     p.x = dy;
     p.y = dx;
@@ -2378,12 +2207,7 @@ int stx_op_conv_backward_data(stx_engine *e, const float *dy, int Cout, int H, i
     p.W = W;
     p.ksize = ksize;
     p.epilogue = kEpiDgrad;
-    STX_TRY(hook_h2(e, p, &cfg));
-    const float *packed = nullptr;
-    STX_TRY(scratch_pack(e, w, Cout, Cin, ksize, 1, cfg, &packed));
-    p.w = packed;
-    STX_TRY(attach_splitk(e, cfg, p));
-    return launch_conv(e, cfg, p);
+    return hook_conv(e, p, w, Cout, Cin, 1);
 }
 
 int stx_op_pool_forward(stx_engine *e, const float *x, int C, int H, int W, int mode, float *y) {

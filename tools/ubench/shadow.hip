@@ -7,7 +7,7 @@
 // registers, 16 KB of LDS) on a second stream beside a run of real convolution launches and prints
 // the three times: convolutions alone, probe alone, both together.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I style_transfer_amd/csrc \
-//         tools/ubench/shadow.hip style_transfer_amd/csrc/conv_wino4.hip -o build_ubench/shadow
+//         tools/ubench/shadow.hip style_transfer_amd/csrc/conv_mfma.hip -o build_ubench/shadow
 #include "../../style_transfer_amd/csrc/conv_wino2.hip"
 
 #include <cstdarg>
@@ -23,7 +23,6 @@ void set_error(const char *fmt, ...) {
 }
 const char *sw_env(const char *name) { return getenv(name); }     // (the harness reads the environment as it is)
 void sw_reread() {}
-int splitk_reduce_launch(hipStream_t, const ConvProblem &, int) { return 0; }
 }  // namespace stx
 
 typedef short bf16x8s __attribute__((ext_vector_type(8)));

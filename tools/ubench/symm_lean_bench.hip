@@ -1,7 +1,7 @@
 // The register-lean SYMM kernel (tools/experiments/symm_lean.hip) against the shipped one: results,
 // time alone, and time beside a run of convolution launches on a second stream.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I style_transfer_amd/csrc \
-//         tools/ubench/symm_lean_bench.hip style_transfer_amd/csrc/conv_wino4.hip -o build_ubench/symm_lean_bench
+//         tools/ubench/symm_lean_bench.hip style_transfer_amd/csrc/conv_mfma.hip -o build_ubench/symm_lean_bench
 #include "../../style_transfer_amd/csrc/conv_wino2.hip"
 #include "../../style_transfer_amd/csrc/symm.hip"
 #include "../experiments/symm_lean.hip"
@@ -19,7 +19,6 @@ void set_error(const char *fmt, ...) {
 }
 const char *sw_env(const char *name) { return getenv(name); }     // (the harness reads the environment as it is)
 void sw_reread() {}
-int splitk_reduce_launch(hipStream_t, const ConvProblem &, int) { return 0; }
 }  // namespace stx
 
 static void run(int C, int HW) {

@@ -1,7 +1,6 @@
 // Standalone timing harness for conv_wino2.hip (tuning aid, not part of the library).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I style_transfer_amd/csrc \
-//         [-DSTX_WINO2_TIMING] tools/ubench/wino2_bench.hip -o /tmp/wino2_bench
-// (the four-wave form, ALGO=4, left the library in round 6: tools/experiments/conv_wino4.hip)
+//         [-DSTX_WINO2_TIMING] tools/ubench/wino2_bench.hip style_transfer_amd/csrc/conv_mfma.hip -o /tmp/wino2_bench
 // With STX_WINO2_TIMING the kernel accumulates, per wave of workgroup 0, the core-clock cycles
 // spent in its compute segments, hand-over segments and barrier waits; the harness prints them.
 #include "../../style_transfer_amd/csrc/conv_wino2.hip"
@@ -13,9 +12,6 @@
 #include <vector>
 
 namespace stx {
-#ifdef STX_WINO4_TIMING
-extern __device__ long long g_wino4_timing[4][4];
-#endif
 void set_error(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -25,7 +21,6 @@ void set_error(const char *fmt, ...) {
 }
 const char *sw_env(const char *name) { return getenv(name); }     // (the harness reads the environment as it is)
 void sw_reread() {}
-int splitk_reduce_launch(hipStream_t, const ConvProblem &, int) { return 0; }
 }  // namespace stx
 
 static void run(int K, int M, int H, int W, int epilogue) {
@@ -85,7 +80,7 @@ static void run(int K, int M, int H, int W, int epilogue) {
     printf("K %4d M %4d %4dx%-4d epi %d: %.3f ms  %.1f TFLOP/s (direct-equivalent)  %.1f%% of MFMA time\n",
            K, M, H, W, epilogue, ms, flop / ms / 1e9, 100.0 * (flop * 16 / 36 / 157.3e12) / (ms * 1e-3));
 #ifdef STX_WINO2_STAMPS
-    if (cfg.id < 210) {      // per CU: how long a workgroup runs, and how long the CU stands empty before the next one starts
+    {      // per CU: how long a workgroup runs, and how long the CU stands empty before the next one starts
         static stx::Wino2Stamp st[8192][8];
         hipMemcpyFromSymbol(st, HIP_SYMBOL(stx::g_wino2_stamps), sizeof(st));
         const int tiles = ((H + 1) / 2) * ((W + 1) / 2);
@@ -121,18 +116,8 @@ static void run(int K, int M, int H, int W, int epilogue) {
         hipMemcpyToSymbol(HIP_SYMBOL(stx::g_wino2_stamps), zero, sizeof(zero));
     }
 #endif
-#ifdef STX_WINO4_TIMING
-    if (cfg.id >= 210) {
-        long long t4[4][4];
-        hipMemcpyFromSymbol(t4, HIP_SYMBOL(stx::g_wino4_timing), sizeof(t4));
-        for (int wv = 0; wv < 4; wv += 3)
-            printf("   wave %d: prologue %6lld  chunk loop %7lld (%.0f per chunk)  epilogue %6lld cycles; workgroup %.2f us at %.0f MHz\n", wv,
-                   t4[wv][0], t4[wv][1], (double)t4[wv][1] / ((K + 7) / 8), t4[wv][2], t4[wv][3] / 100.0,
-                   (double)(t4[wv][0] + t4[wv][1] + t4[wv][2]) / (t4[wv][3] / 100.0));
-    }
-#endif
 #ifdef STX_WINO2_TIMING
-    if (cfg.id < 210) {
+    {
         unsigned long long sm[8];
         hipMemcpyFromSymbol(sm, HIP_SYMBOL(stx::g_wino2_sums), sizeof(sm));
         const double n = (double)sm[0];
