@@ -275,6 +275,18 @@ int stx_image_regularizers(stx_engine *e, const float *img, float *grad, int H, 
 int stx_image_swt_haar(stx_engine *e, const float *img, float *grad, int H, int W,
                        const int roll_xy[2], double scale, double power, double *loss_out);
 
+/* The same term for --swt-levels L >= 1 of the Haar wavelet (style_transfer.py:716-720 passes the
+ * level count to pywt.swt2 / iswt2 through num_utils.py:179-196).  Level j uses the two-tap filters
+ * dilated by 2^(j-1), periodic on the padded N x N square; with every approximation band zeroed the
+ * inverse drops the path through the deepest approximation band alone, which leaves
+ *   D = x - B_L x,  B_L = T_L along rows x T_L along columns,  T_L[k] = (2^L - |k|) / 4^L, |k| < 2^L
+ * (the product over j of [1 2 1]/4 at stride 2^(j-1)), x = roll(img)/127.5 padded symmetrically.
+ * grad, *loss_out and roll_xy are those of stx_image_swt_haar; asynchronous like it.
+ * levels < 1 or levels > log2(N), N = 2^ceil(log2(max(H, W))), is STX_ERR_ARG (PyWavelets refuses
+ * such a count too).  levels == 1 runs stx_image_swt_haar itself: bit-identical results. */
+int stx_image_swt_haar_levels(stx_engine *e, const float *img, float *grad, int H, int W, int levels,
+                              const int roll_xy[2], double scale, double power, double *loss_out);
+
 /* AdamOptimizer.update after the gradient is known (optimizers.py:35-42), fused:
  *   g1 = b1*g1 + (1-b1)*grad; g2 = b2*g2 + (1-b2)*grad^2; p1 likewise on the new params;
  *   params -= lr * (g1/c1) / (sqrt(g2/c2) + EPS);  avg_out = p1/cp

@@ -29,6 +29,7 @@ SOURCES = {
     'reduce.hip': [],
     # one rounding per float32 operation, like the reference's numpy expressions
     'image_ops.hip': ['-ffp-contract=off'],
+    'swt.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
 }

@@ -430,10 +430,22 @@ int resample_launch(hipStream_t s, int axis, const float *src, int C, int H, int
 int swt_haar_launch(hipStream_t s, const float *img, float *grad, int H, int W, int rx, int ry,
                     float scale, float power, double *loss_term, float *scratch,
                     size_t scratch_floats);
+// *out_dev = sum of n float partials, added in double in a fixed order
+int finish_partials_launch(hipStream_t s, const float *partials, int n, double *out_dev);
 int regularizers_launch(hipStream_t s, const float *img, float *grad, int H, int W,
                         const float mean[3], float tv_scale, float tv_power, float p_scale,
                         float p_power, const float *aux, float aux_scale, int aux_rx, int aux_ry,
                         double *loss_terms /*[3]*/, float *scratch, size_t scratch_floats);
+
+// swt.hip: the Haar SWT term at `levels` > 1 (two separable passes).  tmp and partials hold what
+// swt_haar_levels_scratch asks for; N = swt_padded_side(H, W) bounds the level count (2^levels <= N).
+int swt_padded_side(int H, int W);
+void swt_haar_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_floats);
+int swt_haar_levels_launch(hipStream_t s, const float *img, float *grad, int H, int W, int levels,
+                           int rx, int ry, float scale, float power, double *loss_term, float *tmp,
+                           float *partials);
+
+// image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,
                 float *avg, size_t n, double lr, double b1, double b2, double bp1, double c1,
                 double c2, double cp);

@@ -197,6 +197,7 @@ struct stx_engine {
     size_t fence_next = 0;
     size_t dscalars_cap = 64;
     DevBuf red_scratch;                // float partials for image-op reductions
+    DevBuf swt_scratch;                // stx_image_swt_haar_levels: row-filtered image + its partials
 
     bool winograd = true;   // 1-D Winograd F(2,3) for the 3x3 layers (STX_WINOGRAD=0: direct only)
     bool autotune = true;   // tile-config autotuning (process-wide cache, see conv_choose)
@@ -1157,7 +1158,7 @@ void stx_engine_destroy(stx_engine *e) {
         for (auto &s : e->sh->styles) s.gram->release();
     }
     DevBuf *bufs[] = {&e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
-                      &e->upload, &e->red_scratch, &e->first_gram};
+                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->first_gram};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::ScalarArena &a : e->arena) {
         a.scalars.release();
@@ -1984,6 +1985,37 @@ int stx_image_swt_haar(stx_engine *e, const float *img, float *grad, int H, int 
     STX_TRY(swt_haar_launch(e->stream, img, grad, H, W, roll_xy ? roll_xy[0] : 0,
                             roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
                             e->red_scratch.f(), e->red_scratch.bytes / sizeof(float)));
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
+                           e->stream));
+    PendingLoss pl;
+    pl.out = loss_out;
+    pl.dterms.push_back(LossTerm{di, scale});
+    e->A().pending.push_back(std::move(pl));
+    return STX_OK;
+}
+
+int stx_image_swt_haar_levels(stx_engine *e, const float *img, float *grad, int H, int W, int levels,
+                              const int roll_xy[2], double scale, double power, double *loss_out) {
+    if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
+    const int N = swt_padded_side(H, W);
+    if (levels < 1 || levels > 30 || (1 << levels) > N) {
+        set_error("stx_image_swt_haar_levels: levels = %d, but a %d x %d image (padded side %d) "
+                  "takes 1 to %d levels", levels, H, W, N, (int)std::lround(std::log2((double)N)));
+        return STX_ERR_ARG;
+    }
+    // one level is the shipped kernel: bit-identical to stx_image_swt_haar by construction
+    if (levels == 1) return stx_image_swt_haar(e, img, grad, H, W, roll_xy, scale, power, loss_out);
+    STX_TRY(e->set_device());
+    size_t tmp_floats, partial_floats;
+    swt_haar_levels_scratch(H, W, &tmp_floats, &partial_floats);
+    // growing frees the old buffer, which waits for the kernels that still read it
+    STX_TRY(e->swt_scratch.ensure((tmp_floats + partial_floats) * sizeof(float)));
+    size_t di;
+    STX_TRY(alloc_dscalars(e, 1, &di));
+    double *term = static_cast<double *>(e->A().dscalars.ptr) + di;
+    STX_TRY(swt_haar_levels_launch(e->stream, img, grad, H, W, levels, roll_xy ? roll_xy[0] : 0,
+                                   roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
+                                   e->swt_scratch.f(), e->swt_scratch.f() + tmp_floats));
     STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
                            e->stream));
     PendingLoss pl;

@@ -89,6 +89,12 @@ __global__ void finish_partials_kernel(const float *__restrict__ partials, int n
 
 static int blocks_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, kBlocks); }
 
+int finish_partials_launch(hipStream_t s, const float *partials, int n, double *out_dev) {
+    finish_partials_kernel<1><<<1, 256, 0, s>>>(partials, n, out_dev);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
 // ------------------------------------------------------------------------------ cut / put ---
 __device__ __forceinline__ int wrap(int v, int n) {
     v %= n;

@@ -1,0 +1,223 @@
+// The SWT regularizer of the reference for the Haar wavelet at L > 1 levels
+// (style_transfer.py:716-720, num_utils.py:179-196).  The one-level kernel is in image_ops.hip and
+// its header comment has the padding and the roll; what changes with the level count is the filter.
+//
+// Level j (j = 1..L) of the stationary Haar transform uses the two-tap filters dilated by
+// d = 2^(j-1), periodic on the padded N x N square.  Analysis followed by the shift-averaged
+// synthesis of the low band alone is [1 2 1]/4 at stride d, and pywt.iswt2 uses only the deepest
+// approximation band, so zeroing the approximation bands removes the path through that band alone:
+//     D = x - B_L x,   B_L = product over j of ([1 2 1]/4 at stride 2^(j-1)), rows x columns.
+// Per axis the product is the triangle T_L[k] = (2^L - |k|) / 4^L, |k| < 2^L
+// (tests/swt_levels_ref.py restates it and holds it to a band-by-band filterbank).
+//
+// Two passes, each a direct triangle out of LDS, so the work per pixel grows like 2^L:
+//   pass 1  rows:    R[c][y][x] = sum_k T[k] * x/127.5 at padded column qx + k   -> 3 x H x W floats
+//   pass 2  columns: blur = sum_k T[k] * R at padded row qy + k;  D = x/127.5 - blur;
+//                    sum |D|^p into per-workgroup partials;  grad += scale * dp_norm(D)
+// Every padded coordinate is a copy of a picture coordinate (swt_source), so the row-filtered value
+// on a padded row is the row-filtered value on its source row: the intermediate is picture-sized
+// and is kept in the un-rolled frame, like the image and the gradient.
+//
+// A workgroup stages its strip and the halo of 2^L - 1 on either side in LDS; a halo too long for
+// the LDS budget (L >= 10 along rows, L >= 7 along columns) is walked in chunks with the taps in
+// the same ascending order, so the sums do not depend on the chunking.  The triangle's integer
+// numerators are accumulated with one fused multiply-add per tap and scaled by the exact 4^-L at
+// the end: no running sums, the rounding error of a pixel is that of its own 2^(L+1) - 1 terms.
+// The file is compiled with -ffp-contract=off like image_ops.hip: D and the p-norm round per
+// operation like the one-level kernel's.
+
+#include <algorithm>
+
+#include "common.h"
+
+namespace stx {
+
+namespace {
+
+constexpr int kRowTile = 256;     // pass 1: output columns per workgroup (one per thread)
+constexpr int kRowRows = 4;       //         image rows per workgroup (share the column mapping)
+constexpr int kRowChunk = 2048;   //         staged columns per row at most (32 KiB with 4 rows)
+constexpr int kColTile = 64;      // pass 2: columns per workgroup (one 256-byte line per row)
+constexpr int kColRows = 64;      //         output rows per workgroup, 16 per thread
+constexpr int kColChunk = 192;    //         staged rows at most (48 KiB)
+
+__device__ __forceinline__ int swt_source(int q, int pad_lo, int n) {
+    // padded coordinate q in [0, N) -> coordinate of the rolled picture (numpy.pad 'symmetric')
+    int t = (q - pad_lo) % (2 * n);
+    if (t < 0) t += 2 * n;
+    return t < n ? t : 2 * n - 1 - t;
+}
+
+// un-rolled picture coordinate behind slot `s` of a strip that starts at padded coordinate `q0`
+// (q0 may be negative or beyond N: the square is periodic); shift = roll mod n, in [0, n)
+__device__ __forceinline__ int swt_unrolled(int q0, int s, int N, int pad_lo, int n, int shift) {
+    int q = (q0 + s) % N;
+    if (q < 0) q += N;
+    const int u = swt_source(q, pad_lo, n) - shift;
+    return u < 0 ? u + n : u;
+}
+
+// Pass 1.  grid (ceil(W / 256), ceil(H / 4), 3).  Thread t owns column X0 + t of the ROLLED picture
+// on four rows; slot s of the strip is padded column X0 + pad_x - h + s, the thread's centre slot is
+// t + h.  ONE: the strip fits one chunk (every level the command line is used with).
+template <bool ONE>
+__global__ __launch_bounds__(256) void swt_rows_kernel(const float *__restrict__ img,
+                                                       float *__restrict__ tmp, int H, int W, int N,
+                                                       int P, int shift_x, int chunk) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int h = P - 1, span = kRowTile + 2 * h;
+    const int X0 = blockIdx.x * kRowTile, y0 = blockIdx.y * kRowRows;
+    const int pad_x = (N - W) / 2;
+    const float *p = img + (size_t)blockIdx.z * H * W;
+    const int t = threadIdx.x;
+    float acc[kRowRows] = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < span; c0 += chunk) {
+        const int len = min(chunk, span - c0);
+        if (!ONE) __syncthreads();      // the previous chunk has been read
+        for (int s = t; s < len; s += 256) {
+            const int ux = swt_unrolled(X0 + pad_x - h, c0 + s, N, pad_x, W, shift_x);
+#pragma unroll
+            for (int r = 0; r < kRowRows; ++r)
+                lds[r * chunk + s] = y0 + r < H ? p[(size_t)(y0 + r) * W + ux] / 127.5f : 0.f;
+        }
+        __syncthreads();
+        // taps k = -h..h whose slot t + h + k lies in [c0, c0 + len)
+        const int lo = ONE ? -h : max(-h, c0 - (t + h));
+        const int hi = ONE ? h : min(h, c0 + len - 1 - (t + h));
+        const float *row = lds + (t + h - c0);
+        for (int k = lo; k <= hi; ++k) {
+            const float w = (float)(P - abs(k));
+#pragma unroll
+            for (int r = 0; r < kRowRows; ++r) acc[r] = __builtin_fmaf(w, row[r * chunk + k], acc[r]);
+        }
+    }
+    const int X = X0 + t;
+    if (X >= W) return;
+    const int x = X - shift_x < 0 ? X - shift_x + W : X - shift_x;
+    const float inv = 1.f / ((float)P * (float)P);      // 4^-L, exact
+    float *out = tmp + (size_t)blockIdx.z * H * W;
+#pragma unroll
+    for (int r = 0; r < kRowRows; ++r)
+        if (y0 + r < H) out[(size_t)(y0 + r) * W + x] = acc[r] * inv;
+}
+
+// Pass 2.  grid (ceil(W / 64), ceil(H / 64), 3).  Thread (col, g) owns column x0 + col (un-rolled:
+// columns need no mapping here) and rows Y0 + g + 4 o, o = 0..15, of the ROLLED picture; slot s of
+// the strip is padded row Y0 + pad_y - h + s.  A wavefront shares g, so its tap range and weights
+// are uniform and its LDS reads are one 256-byte line each.
+__global__ __launch_bounds__(256) void swt_cols_kernel(const float *__restrict__ img,
+                                                       const float *__restrict__ tmp,
+                                                       float *__restrict__ grad, int H, int W, int N,
+                                                       int P, int shift_y, int chunk, float scale,
+                                                       float power, float *__restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];     // [chunk][64], then 4 sums
+    constexpr int kPer = kColRows / 4;
+    const int h = P - 1, span = kColRows + 2 * h;
+    const int x0 = blockIdx.x * kColTile, Y0 = blockIdx.y * kColRows;
+    const int pad_y = (N - H) / 2;
+    const size_t plane = (size_t)H * W;
+    const float *r = tmp + blockIdx.z * plane;
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int x = x0 + col;
+    float acc[kPer];
+#pragma unroll
+    for (int o = 0; o < kPer; ++o) acc[o] = 0.f;
+    for (int c0 = 0; c0 < span; c0 += chunk) {
+        const int len = min(chunk, span - c0);
+        if (c0 > 0) __syncthreads();    // the previous chunk has been read
+        for (int s = g; s < len; s += 4) {
+            const int uy = swt_unrolled(Y0 + pad_y - h, c0 + s, N, pad_y, H, shift_y);
+            lds[s * kColTile + col] = x < W ? r[(size_t)uy * W + x] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int o = 0; o < kPer; ++o) {
+            const int centre = g + 4 * o + h;       // slot of this output's own row
+            const int lo = max(-h, c0 - centre), hi = min(h, c0 + len - 1 - centre);
+            const float *column = lds + (centre - c0) * kColTile + col;
+            float a = acc[o];
+            for (int k = lo; k <= hi; ++k) a = __builtin_fmaf((float)(P - abs(k)), column[k * kColTile], a);
+            acc[o] = a;
+        }
+    }
+    const float inv = 1.f / ((float)P * (float)P);      // 4^-L, exact
+    float sum = 0.f;
+#pragma unroll
+    for (int o = 0; o < kPer; ++o) {
+        const int Y = Y0 + g + 4 * o;
+        if (Y >= H || x >= W) continue;
+        const int y = Y - shift_y < 0 ? Y - shift_y + H : Y - shift_y;
+        const size_t i = blockIdx.z * plane + (size_t)y * W + x;
+        const float d = img[i] / 127.5f - acc[o] * inv;
+        const float ad = fabsf(d);
+        float gr;
+        if (power == 2.f) {
+            sum += d * d;
+            gr = 2.f * d;
+        } else if (power == 1.f) {
+            sum += ad;
+            gr = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        } else {
+            const float ap1 = powf(ad, power - 1.f);
+            sum += ap1 * ad;
+            gr = power * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ap1;
+        }
+        grad[i] = scale * gr + grad[i];
+    }
+    // one partial per workgroup, added in a fixed order (finish_partials_launch adds them in double)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    float *red = lds + chunk * kColTile;
+    if (col == 0) red[g] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
+            red[0] + red[1] + red[2] + red[3];
+}
+
+int wrapped(int v, int n) {
+    v %= n;
+    return v < 0 ? v + n : v;
+}
+
+}  // namespace
+
+int swt_padded_side(int H, int W) {
+    int N = 1;
+    while (N < std::max(H, W)) N *= 2;
+    return N;
+}
+
+void swt_haar_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_floats) {
+    *tmp_floats = (size_t)3 * H * W;
+    *partial_floats = (size_t)3 * ceil_div(H, kColRows) * ceil_div(W, kColTile);
+}
+
+int swt_haar_levels_launch(hipStream_t s, const float *img, float *grad, int H, int W, int levels,
+                           int rx, int ry, float scale, float power, double *loss_term, float *tmp,
+                           float *partials) {
+    const int N = swt_padded_side(H, W);
+    if (levels < 1 || levels > 30 || (1 << levels) > N) {
+        set_error("swt_haar_levels: %d levels on a padded side of %d", levels, N);
+        return STX_ERR_ARG;
+    }
+    const int P = 1 << levels, h = P - 1;
+    {
+        const int chunk = std::min(kRowTile + 2 * h, kRowChunk);
+        const dim3 grid(ceil_div(W, kRowTile), ceil_div(H, kRowRows), 3);
+        const size_t lds = (size_t)kRowRows * chunk * sizeof(float);
+        if (chunk == kRowTile + 2 * h)
+            swt_rows_kernel<true><<<grid, 256, lds, s>>>(img, tmp, H, W, N, P, wrapped(rx, W), chunk);
+        else
+            swt_rows_kernel<false><<<grid, 256, lds, s>>>(img, tmp, H, W, N, P, wrapped(rx, W), chunk);
+        STX_CHECK_LAUNCH();
+    }
+    const dim3 grid(ceil_div(W, kColTile), ceil_div(H, kColRows), 3);
+    const int chunk = std::min(kColRows + 2 * h, kColChunk);
+    swt_cols_kernel<<<grid, 256, ((size_t)chunk * kColTile + 4) * sizeof(float), s>>>(
+        img, tmp, grad, H, W, N, P, wrapped(ry, H), chunk, scale, power, partials);
+    STX_CHECK_LAUNCH();
+    return finish_partials_launch(s, partials, (int)(grid.x * grid.y * grid.z), loss_term);
+}
+
+}  // namespace stx

@@ -60,15 +60,25 @@ def regularizers(engine, img, grad, mean_bgr, tv_scale, tv_power, p_scale, p_pow
     return out
 
 
-def swt_haar(engine, img, grad, scale, power, roll=None):
+def swt_padded_side(h, w):
+    """Side of the power-of-two square the SWT term pads an h x w image to (num_utils.py:186-188);
+    the level count may not exceed its log2."""
+    return 1 << max(0, (max(h, w) - 1).bit_length())
+
+
+def swt_haar(engine, img, grad, scale, power, roll=None, levels=1):
     """grad += scale * (p-norm gradient at the Haar SWT detail image of the rolled picture / 127.5);
     returns a PendingScalar with scale * sum |detail|^power (style_transfer.py:716-720 for the
-    default wavelet and level count)."""
+    Haar wavelet; ``levels`` is --swt-levels, 1 to log2 of ``swt_padded_side``)."""
     _, H, W = img.shape
     out = engine.keep_until_sync(PendingScalar())
-    lib.call('stx_image_swt_haar', engine.handle, img.ptr, grad.ptr, H, W,
-             _xy(roll) if roll is not None else None, float(scale), float(power),
-             ctypes.byref(out._v))
+    xy = _xy(roll) if roll is not None else None
+    if levels == 1:
+        lib.call('stx_image_swt_haar', engine.handle, img.ptr, grad.ptr, H, W, xy, float(scale),
+                 float(power), ctypes.byref(out._v))
+    else:
+        lib.call('stx_image_swt_haar_levels', engine.handle, img.ptr, grad.ptr, H, W, int(levels),
+                 xy, float(scale), float(power), ctypes.byref(out._v))
     return out
 
 

@@ -147,14 +147,15 @@ class StyleTransfer:
         self._cb_calls = [None, 0]
         self._converted = {}        # id(PIL image) -> (image, float array), filled by the helper thread
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
-        # reference tree; its transform is restated for the command line's defaults only
+        # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
-        if (callable(raw) or raw) and (str(args.swt_wavelet) not in ('haar', 'db1') or
-                                       int(args.swt_levels) != 1):
-            raise NotImplementedError('--swt-wavelet %s --swt-levels %s: only the default '
-                                      '(haar, 1 level) is implemented'
-                                      % (args.swt_wavelet, args.swt_levels))
-        if callable(raw) or raw:
+        self._swt_on = bool(callable(raw) or raw)
+        if self._swt_on and str(args.swt_wavelet) not in ('haar', 'db1'):
+            raise NotImplementedError('--swt-wavelet %s: only the Haar wavelet (haar / db1) is '
+                                      'implemented' % args.swt_wavelet)
+        if self._swt_on and int(args.swt_levels) < 1:
+            raise ValueError('--swt-levels %s: at least one level is needed' % args.swt_levels)
+        if self._swt_on:
             import warnings
             warnings.warn('--swt-weight: the Haar SWT term is a restatement of PyWavelets\' '
                           'swt2 / iswt2, which is not part of the reference tree and not '
@@ -255,10 +256,10 @@ class StyleTransfer:
                 lw * args.aux_weight if aux_on else 0.0, aux_roll=roll)
             loss.add(reg, self.engine)
         if args.swt_weight:
-            # style_transfer.py:716-720.  Only the reference's default transform is restated
-            # (oracle/num_ops.py): PyWavelets, which it calls, is not part of its tree.
+            # style_transfer.py:716-720.  Only the Haar transform is restated (oracle/num_ops.py,
+            # tests/swt_levels_ref.py): PyWavelets, which it calls, is not part of its tree.
             swt = image_ops.swt_haar(self.engine, params, self.grad, lw * args.swt_weight,
-                                     args.swt_power, roll=roll)
+                                     args.swt_power, roll=roll, levels=int(args.swt_levels))
             loss.add(swt, self.engine)
         return loss, self.grad
 
@@ -270,6 +271,15 @@ class StyleTransfer:
         state.scale = state.scale + 1 if 'scale' in state else 0
         state.step, state.steps = 0, iterations
         state.img_size = self.img.shape[1:]
+        if self._swt_on:
+            # pywt.swt2 refuses more levels than log2 of the padded side (num_utils.py:186-191):
+            # the reference stops at its first evaluation of such a scale
+            side = image_ops.swt_padded_side(*self.img.shape[1:])
+            if 2 ** int(args.swt_levels) > side:
+                raise ValueError('--swt-levels %d: a %d x %d image is padded to a square of side %d, '
+                                 'which takes %d levels at most (raise --min-size or lower the level '
+                                 'count)' % (args.swt_levels, self.img.shape[2], self.img.shape[1],
+                                             side, side.bit_length() - 1))
 
         content_layers, content_weight = parse_weights(args.content_layers, args.content_weight)
         style_layers, style_weight = parse_weights(args.style_layers, 1)
