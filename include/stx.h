@@ -287,6 +287,25 @@ int stx_image_swt_haar(stx_engine *e, const float *img, float *grad, int H, int 
 int stx_image_swt_haar_levels(stx_engine *e, const float *img, float *grad, int H, int W, int levels,
                               const int roll_xy[2], double scale, double power, double *loss_out);
 
+/* The same term for --swt-wavelet dbN / symN: `order` = N vanishing moments, 1..38 (PyWavelets' db
+ * range; symN exists for N = 2..20).  An orthonormal bank's shift-averaged inverse is half the
+ * adjoint per level and axis, so zeroing the approximation bands leaves, as for Haar,
+ *   D = x - B_L x,  B_L per axis = product over j = 1..L of (r/2 at stride 2^(j-1)),
+ * r the autocorrelation of the low-pass filter.  r depends on |H|^2 alone, which dbN and symN share
+ * (one call serves both): the maximally flat half-band filter, r[0] = 1, r[+-(2k-1)] =
+ * prod over m != k of (1/2 - m)/(k - m), m, k = -N+1..N, zero at the other even offsets
+ * (N = 1: [1/2 1 1/2], the triangle above; N = 2: [-1/16 0 9/16 1 9/16 0 -1/16]).  The library
+ * builds the taps of B_L in double, folds them onto the periodic padded square, rounds them to
+ * float once and keeps them on the device per (order, levels, padded side): only the first call
+ * with a new triple uploads (and synchronises for) anything.  Parity with PyWavelets is unpinned
+ * as for Haar (the package is in neither tree).
+ * Everything else -- grad, *loss_out, roll_xy, padding, asynchrony, the level check -- is
+ * stx_image_swt_haar_levels'.  order outside 1..38 is STX_ERR_ARG.  order == 1 runs
+ * stx_image_swt_haar_levels itself: bit-identical results. */
+int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int H, int W,
+                              int order, int levels, const int *roll_xy,
+                              double scale, double power, double *loss_out);
+
 /* AdamOptimizer.update after the gradient is known (optimizers.py:35-42), fused:
  *   g1 = b1*g1 + (1-b1)*grad; g2 = b2*g2 + (1-b2)*grad^2; p1 likewise on the new params;
  *   params -= lr * (g1/c1) / (sqrt(g2/c2) + EPS);  avg_out = p1/cp

@@ -444,6 +444,15 @@ void swt_haar_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_f
 int swt_haar_levels_launch(hipStream_t s, const float *img, float *grad, int H, int W, int levels,
                            int rx, int ry, float scale, float power, double *loss_term, float *tmp,
                            float *partials);
+// The same term for the orthogonal Daubechies / symlet filter with `order` vanishing moments.
+// swt_daub_table builds, in double on the host, the per-axis taps of `levels` levels folded onto the
+// periodic square of side N (at most N taps; tap i weighs padded coordinate q + i - *hl) and
+// rounds them to float once; swt_table_launch runs the two passes with a device copy of them
+// (scratch as for swt_haar_levels_launch).
+void swt_daub_table(int order, int levels, int N, std::vector<float> *taps, int *hl);
+int swt_table_launch(hipStream_t s, const float *img, float *grad, int H, int W, const float *table,
+                     int ntaps, int hl, int rx, int ry, float scale, float power,
+                     double *loss_term, float *tmp, float *partials);
 
 // image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,

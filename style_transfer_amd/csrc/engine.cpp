@@ -198,6 +198,11 @@ struct stx_engine {
     size_t dscalars_cap = 64;
     DevBuf red_scratch;                // float partials for image-op reductions
     DevBuf swt_scratch;                // stx_image_swt_haar_levels: row-filtered image + its partials
+    struct SwtTable {                  // stx_image_swt_daub_levels: the taps of one (order, levels, N)
+        int order, levels, N, ntaps, hl;
+        DevBuf taps;
+    };
+    std::vector<SwtTable> swt_tables;  // built at first use, kept: a step uploads nothing
 
     bool winograd = true;   // 1-D Winograd F(2,3) for the 3x3 layers (STX_WINOGRAD=0: direct only)
     bool autotune = true;   // tile-config autotuning (process-wide cache, see conv_choose)
@@ -1160,6 +1165,7 @@ void stx_engine_destroy(stx_engine *e) {
     DevBuf *bufs[] = {&e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->first_gram};
     for (DevBuf *b : bufs) b->release();
+    for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
     for (stx_engine::ScalarArena &a : e->arena) {
         a.scalars.release();
         a.dscalars.release();
@@ -2016,6 +2022,65 @@ int stx_image_swt_haar_levels(stx_engine *e, const float *img, float *grad, int 
     STX_TRY(swt_haar_levels_launch(e->stream, img, grad, H, W, levels, roll_xy ? roll_xy[0] : 0,
                                    roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
                                    e->swt_scratch.f(), e->swt_scratch.f() + tmp_floats));
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
+                           e->stream));
+    PendingLoss pl;
+    pl.out = loss_out;
+    pl.dterms.push_back(LossTerm{di, scale});
+    e->A().pending.push_back(std::move(pl));
+    return STX_OK;
+}
+
+int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int H, int W, int order,
+                              int levels, const int roll_xy[2], double scale, double power,
+                              double *loss_out) {
+    if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
+    if (order < 1 || order > 38) {
+        set_error("stx_image_swt_daub_levels: order = %d, but db1 to db38 exist", order);
+        return STX_ERR_ARG;
+    }
+    // one vanishing moment is the Haar wavelet: bit-identical to stx_image_swt_haar_levels by
+    // construction (which also checks the level count)
+    if (order == 1)
+        return stx_image_swt_haar_levels(e, img, grad, H, W, levels, roll_xy, scale, power, loss_out);
+    const int N = swt_padded_side(H, W);
+    if (levels < 1 || levels > 30 || (1 << levels) > N) {
+        set_error("stx_image_swt_daub_levels: levels = %d, but a %d x %d image (padded side %d) "
+                  "takes 1 to %d levels", levels, H, W, N, (int)std::lround(std::log2((double)N)));
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    const stx_engine::SwtTable *tab = nullptr;
+    for (const stx_engine::SwtTable &t : e->swt_tables)
+        if (t.order == order && t.levels == levels && t.N == N) tab = &t;
+    if (!tab) {
+        std::vector<float> taps;
+        int hl;
+        swt_daub_table(order, levels, N, &taps, &hl);
+        stx_engine::SwtTable t{order, levels, N, (int)taps.size(), hl, DevBuf()};
+        STX_TRY(t.taps.ensure(taps.size() * sizeof(float)));
+        // once per table and synchronous: the host copy does not outlive this call
+        hipError_t err = hipMemcpy(t.taps.ptr, taps.data(), taps.size() * sizeof(float),
+                                   hipMemcpyHostToDevice);
+        if (err != hipSuccess) {
+            t.taps.release();
+            set_error("stx_image_swt_daub_levels: hipMemcpy of %zu taps failed: %s", taps.size(),
+                      hipGetErrorString(err));
+            return STX_ERR_HIP;
+        }
+        e->swt_tables.push_back(t);
+        tab = &e->swt_tables.back();
+    }
+    size_t tmp_floats, partial_floats;
+    swt_haar_levels_scratch(H, W, &tmp_floats, &partial_floats);
+    STX_TRY(e->swt_scratch.ensure((tmp_floats + partial_floats) * sizeof(float)));
+    size_t di;
+    STX_TRY(alloc_dscalars(e, 1, &di));
+    double *term = static_cast<double *>(e->A().dscalars.ptr) + di;
+    STX_TRY(swt_table_launch(e->stream, img, grad, H, W, tab->taps.f(), tab->ntaps, tab->hl,
+                             roll_xy ? roll_xy[0] : 0, roll_xy ? roll_xy[1] : 0, (float)scale,
+                             (float)power, term, e->swt_scratch.f(),
+                             e->swt_scratch.f() + tmp_floats));
     STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
                            e->stream));
     PendingLoss pl;

@@ -175,6 +175,150 @@ __global__ __launch_bounds__(256) void swt_cols_kernel(const float *__restrict__
             red[0] + red[1] + red[2] + red[3];
 }
 
+// ---- the same term for any orthogonal Daubechies / symlet filter (stx_image_swt_daub_levels) ----
+// Per level and axis, analysis followed by the shift-averaged synthesis of the low band is r/2 at
+// stride 2^(j-1), r the autocorrelation of the low-pass filter; r depends on |H|^2 alone, which dbN
+// and symN share.  The product over the levels is a table of taps built on the host
+// (swt_daub_table), already normalised and already folded onto the periodic square, so that it
+// never has more than N taps: tap i of `ntaps` is the weight of padded coordinate q + i - hl.
+//
+// The passes are those above with the weight read from the table, and both walk the TAPS in chunks
+// of at most T, ascending: a chunk stages the T taps and the T + tile - 1 slots they reach, so every
+// output of the tile takes every tap of the chunk and no tap range depends on the thread.
+constexpr int kTabRowTaps = 1408;   // pass 1: 4 x (1408 + 255) strip + 1408 taps = 31.5 KiB
+constexpr int kTabColTaps = 113;    // pass 2: (113 + 63) x 64 strip + 143 taps = 44.6 KiB; 16 m + 1
+constexpr int kTabColOwn = 16;      //         consecutive output rows per thread
+
+// Pass 1.  grid and thread mapping of swt_rows_kernel; slot s of a chunk that starts at tap k0 is
+// padded column X0 + pad_x - hl + k0 + s, and tap k0 + j of thread t reads slot t + j.
+__global__ __launch_bounds__(256) void swt_rows_table_kernel(const float *__restrict__ img,
+                                                             float *__restrict__ tmp,
+                                                             const float *__restrict__ table, int H,
+                                                             int W, int N, int ntaps, int hl,
+                                                             int shift_x, int T) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];     // [4][T + 255], then T taps
+    const int stride = T + kRowTile - 1;
+    float *wl = lds + kRowRows * stride;
+    const int X0 = blockIdx.x * kRowTile, y0 = blockIdx.y * kRowRows;
+    const int pad_x = (N - W) / 2;
+    const float *p = img + (size_t)blockIdx.z * H * W;
+    const int t = threadIdx.x;
+    float acc[kRowRows] = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < ntaps; k0 += T) {
+        const int n = min(T, ntaps - k0), len = n + kRowTile - 1;
+        if (k0 > 0) __syncthreads();    // the previous chunk has been read
+        for (int s = t; s < len; s += 256) {
+            const int ux = swt_unrolled(X0 + pad_x - hl + k0, s, N, pad_x, W, shift_x);
+#pragma unroll
+            for (int r = 0; r < kRowRows; ++r)
+                lds[r * stride + s] = y0 + r < H ? p[(size_t)(y0 + r) * W + ux] / 127.5f : 0.f;
+        }
+        for (int j = t; j < n; j += 256) wl[j] = table[k0 + j];
+        __syncthreads();
+        const float *row = lds + t;
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const float w = wl[j];
+#pragma unroll
+            for (int r = 0; r < kRowRows; ++r) acc[r] = __builtin_fmaf(w, row[r * stride + j], acc[r]);
+        }
+    }
+    const int X = X0 + t;
+    if (X >= W) return;
+    const int x = X - shift_x < 0 ? X - shift_x + W : X - shift_x;
+    float *out = tmp + (size_t)blockIdx.z * H * W;
+#pragma unroll
+    for (int r = 0; r < kRowRows; ++r)
+        if (y0 + r < H) out[(size_t)(y0 + r) * W + x] = acc[r];
+}
+
+// Pass 2.  grid of swt_cols_kernel.  Thread (col, g) owns column x0 + col and the 16 consecutive
+// rows Y0 + 16 g + o of the ROLLED picture, so that one staged value serves 16 outputs: at step s
+// the thread reads slot 16 g + s once and adds it to output o with tap s - o, o = 0..15.  The 16
+// taps in flight sit in registers, c[i & 15] = tap i, one new tap per step; 15 zero taps before
+// and after the chunk's own (wz) let every output start and end inside the same loop -- a zero tap
+// leaves its sum as it is, so each output still adds its own taps once, in ascending order.
+// T is 16 m + 1: the T + 15 steps of a full chunk are whole blocks of 16.
+__global__ __launch_bounds__(256) void swt_cols_table_kernel(
+    const float *__restrict__ img, const float *__restrict__ tmp, float *__restrict__ grad,
+    const float *__restrict__ table, int H, int W, int N, int ntaps, int hl, int shift_y, int T,
+    float scale, float power, float *__restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];     // [T + 63][64], wz[T + 30], 4 sums
+    constexpr int kOwn = kTabColOwn;
+    const int rows = T + kColRows - 1;
+    float *wz = lds + rows * kColTile;
+    float *red = wz + T + 2 * (kOwn - 1);
+    const int x0 = blockIdx.x * kColTile, Y0 = blockIdx.y * kColRows;
+    const int pad_y = (N - H) / 2;
+    const size_t plane = (size_t)H * W;
+    const float *r = tmp + blockIdx.z * plane;
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int x = x0 + col;
+    float acc[kOwn];
+#pragma unroll
+    for (int o = 0; o < kOwn; ++o) acc[o] = 0.f;
+    for (int k0 = 0; k0 < ntaps; k0 += T) {
+        const int n = min(T, ntaps - k0);
+        const int steps = (n + 2 * (kOwn - 1)) / kOwn * kOwn;       // n + 15 rounded up; <= T + 15
+        if (k0 > 0) __syncthreads();    // the previous chunk has been read
+        // slots the taps reach, and zeros up to the last slot a block of steps reads (<= rows)
+        for (int s = g; s < kColRows - kOwn + steps; s += 4) {
+            float v = 0.f;
+            if (s < n + kColRows - 1 && x < W)
+                v = r[(size_t)swt_unrolled(Y0 + pad_y - hl + k0, s, N, pad_y, H, shift_y) * W + x];
+            lds[s * kColTile + col] = v;
+        }
+        for (int i = threadIdx.x; i < steps + kOwn - 1; i += 256)
+            wz[i] = i >= kOwn - 1 && i < kOwn - 1 + n ? table[k0 + i - (kOwn - 1)] : 0.f;
+        __syncthreads();
+        float c[kOwn];
+#pragma unroll
+        for (int o = 0; o < kOwn; ++o) c[o] = 0.f;
+        const float *strip = lds + g * kOwn * kColTile + col;
+        for (int b = 0; b < steps; b += kOwn) {
+#pragma unroll
+            for (int u = 0; u < kOwn; ++u) {
+                c[u] = wz[b + u + kOwn - 1];
+                const float v = strip[(b + u) * kColTile];
+#pragma unroll
+                for (int o = 0; o < kOwn; ++o)
+                    acc[o] = __builtin_fmaf(c[(u - o) & (kOwn - 1)], v, acc[o]);
+            }
+        }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int o = 0; o < kOwn; ++o) {
+        const int Y = Y0 + g * kOwn + o;
+        if (Y >= H || x >= W) continue;
+        const int y = Y - shift_y < 0 ? Y - shift_y + H : Y - shift_y;
+        const size_t i = blockIdx.z * plane + (size_t)y * W + x;
+        const float d = img[i] / 127.5f - acc[o];
+        const float ad = fabsf(d);
+        float gr;
+        if (power == 2.f) {
+            sum += d * d;
+            gr = 2.f * d;
+        } else if (power == 1.f) {
+            sum += ad;
+            gr = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        } else {
+            const float ap1 = powf(ad, power - 1.f);
+            sum += ap1 * ad;
+            gr = power * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ap1;
+        }
+        grad[i] = scale * gr + grad[i];
+    }
+    // one partial per workgroup, added in a fixed order (finish_partials_launch adds them in double)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if (col == 0) red[g] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
+            red[0] + red[1] + red[2] + red[3];
+}
+
 int wrapped(int v, int n) {
     v %= n;
     return v < 0 ? v + n : v;
@@ -216,6 +360,91 @@ int swt_haar_levels_launch(hipStream_t s, const float *img, float *grad, int H, 
     const int chunk = std::min(kColRows + 2 * h, kColChunk);
     swt_cols_kernel<<<grid, 256, ((size_t)chunk * kColTile + 4) * sizeof(float), s>>>(
         img, tmp, grad, H, W, N, P, wrapped(ry, H), chunk, scale, power, partials);
+    STX_CHECK_LAUNCH();
+    return finish_partials_launch(s, partials, (int)(grid.x * grid.y * grid.z), loss_term);
+}
+
+void swt_daub_table(int order, int levels, int N, std::vector<float> *taps, int *hl) {
+    // r[+-(2k-1)], k = 1..order: the Lagrange weight of node k at the point 1/2 among the nodes
+    // -order+1 .. order (every factor of one k has the sign pattern of the others: no cancellation)
+    std::vector<double> r(order + 1, 0.0);
+    for (int k = 1; k <= order; ++k) {
+        double w = 1.0;
+        for (int m = -order + 1; m <= order; ++m)
+            if (m != k) w *= (0.5 - m) / (double)(k - m);
+        r[k] = w;
+    }
+    // cur[i] is the tap at offset i - half while the cascade fits the square, and the tap at
+    // offset i modulo N from the level at which it no longer does
+    std::vector<double> cur(1, 1.0);
+    long half = 0;
+    bool folded = false;
+    for (int j = 0; j < levels; ++j) {
+        const long d = 1L << j, grow = (long)(2 * order - 1) * d;
+        if (!folded && 2 * (half + grow) + 1 > N) {
+            std::vector<double> circ(N, 0.0);
+            for (long i = 0; i < (long)cur.size(); ++i) circ[(((i - half) % N) + N) % N] += cur[i];
+            cur.swap(circ);
+            folded = true;
+        }
+        if (folded) {
+            std::vector<double> nxt(N, 0.0);
+            for (long i = 0; i < N; ++i) {
+                double a = 0.5 * cur[i];
+                for (int k = 1; k <= order; ++k) {
+                    const long o = (long)(2 * k - 1) * d % N;
+                    a += 0.5 * r[k] * (cur[(i + o) % N] + cur[(i - o + N) % N]);
+                }
+                nxt[i] = a;
+            }
+            cur.swap(nxt);
+        } else {
+            std::vector<double> nxt(cur.size() + 2 * grow, 0.0);
+            for (long i = 0; i < (long)cur.size(); ++i) {
+                nxt[i + grow] += 0.5 * cur[i];
+                for (int k = 1; k <= order; ++k) {
+                    const long o = (long)(2 * k - 1) * d;
+                    nxt[i + grow + o] += 0.5 * r[k] * cur[i];
+                    nxt[i + grow - o] += 0.5 * r[k] * cur[i];
+                }
+            }
+            cur.swap(nxt);
+            half += grow;
+        }
+    }
+    if (folded) {       // offsets -N/2 .. N/2 - 1
+        *hl = N / 2;
+        taps->resize(N);
+        for (int i = 0; i < N; ++i) (*taps)[i] = (float)cur[(i - N / 2 + N) % N];
+    } else {
+        *hl = (int)half;
+        taps->resize(cur.size());
+        for (size_t i = 0; i < cur.size(); ++i) (*taps)[i] = (float)cur[i];
+    }
+}
+
+int swt_table_launch(hipStream_t s, const float *img, float *grad, int H, int W, const float *table,
+                     int ntaps, int hl, int rx, int ry, float scale, float power,
+                     double *loss_term, float *tmp, float *partials) {
+    const int N = swt_padded_side(H, W);
+    if (ntaps < 1 || ntaps > std::max(N, 1) || hl < 0 || hl >= ntaps) {
+        set_error("swt_table: %d taps (centre %d) on a padded side of %d", ntaps, hl, N);
+        return STX_ERR_ARG;
+    }
+    {
+        const int T = std::min(ntaps, kTabRowTaps);
+        const dim3 grid(ceil_div(W, kRowTile), ceil_div(H, kRowRows), 3);
+        const size_t lds = ((size_t)kRowRows * (T + kRowTile - 1) + T) * sizeof(float);
+        swt_rows_table_kernel<<<grid, 256, lds, s>>>(img, tmp, table, H, W, N, ntaps, hl,
+                                                     wrapped(rx, W), T);
+        STX_CHECK_LAUNCH();
+    }
+    const int T = std::min(ceil_div(ntaps - 1, kTabColOwn) * kTabColOwn + 1, kTabColTaps);
+    const dim3 grid(ceil_div(W, kColTile), ceil_div(H, kColRows), 3);
+    const size_t lds =
+        ((size_t)(T + kColRows - 1) * kColTile + T + 2 * (kTabColOwn - 1) + 4) * sizeof(float);
+    swt_cols_table_kernel<<<grid, 256, lds, s>>>(img, tmp, grad, table, H, W, N, ntaps, hl,
+                                                 wrapped(ry, H), T, scale, power, partials);
     STX_CHECK_LAUNCH();
     return finish_partials_launch(s, partials, (int)(grid.x * grid.y * grid.z), loss_term);
 }

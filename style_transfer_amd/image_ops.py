@@ -8,6 +8,7 @@ engine's GPU and stay UN-rolled: the per-iteration shift is an index offset in c
 """
 
 import ctypes
+import re
 
 import numpy as np
 
@@ -79,6 +80,41 @@ def swt_haar(engine, img, grad, scale, power, roll=None, levels=1):
     else:
         lib.call('stx_image_swt_haar_levels', engine.handle, img.ptr, grad.ptr, H, W, int(levels),
                  xy, float(scale), float(power), ctypes.byref(out._v))
+    return out
+
+
+def swt_wavelet_order(wavelet):
+    """Vanishing moments of an orthogonal Daubechies / symlet wavelet by its PyWavelets name: haar
+    and db1 -> 1, dbN (1..38) and symN (2..20) -> N.  The SWT term depends on the filter through
+    |H|^2 alone, which dbN and symN share.  Any other name raises NotImplementedError."""
+    name = str(wavelet)
+    if name == 'haar':
+        return 1
+    m = re.fullmatch(r'(db|sym)([1-9][0-9]?)', name)
+    if m:
+        order = int(m.group(2))
+        if (1 if m.group(1) == 'db' else 2) <= order <= (38 if m.group(1) == 'db' else 20):
+            return order
+    raise NotImplementedError('SWT wavelet %r: only haar, db1..db38 and sym2..sym20 are '
+                              'implemented' % (wavelet,))
+
+
+def swt_wavelet(engine, img, grad, scale, power, wavelet, levels=1, roll=None):
+    """``swt_haar`` for the wavelets of ``swt_wavelet_order`` (num_utils.py:184-196 passes any
+    PyWavelets name on): grad += scale * (p-norm gradient at the detail image), returns a
+    PendingScalar with scale * sum |detail|^power.  A level count outside 1 .. log2 of
+    ``swt_padded_side`` raises ValueError, as PyWavelets would."""
+    order = swt_wavelet_order(wavelet)
+    _, H, W = img.shape
+    levels = int(levels)
+    if levels < 1 or 2 ** levels > swt_padded_side(H, W):
+        raise ValueError('%d SWT levels: a %d x %d image is padded to a square of side %d, which '
+                         'takes 1 to %d levels' % (levels, W, H, swt_padded_side(H, W),
+                                                   swt_padded_side(H, W).bit_length() - 1))
+    out = engine.keep_until_sync(PendingScalar())
+    lib.call('stx_image_swt_daub_levels', engine.handle, img.ptr, grad.ptr, H, W, order, levels,
+             _xy(roll) if roll is not None else None, float(scale), float(power),
+             ctypes.byref(out._v))
     return out
 
 

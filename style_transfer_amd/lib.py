@@ -92,6 +92,7 @@ SIGNATURES = {
                                c_int_p, c_double_p],
     'stx_image_swt_haar': [_vp, _vp, _vp, _i, _i, c_int_p, _d, _d, c_double_p],
     'stx_image_swt_haar_levels': [_vp, _vp, _vp, _i, _i, _i, c_int_p, _d, _d, c_double_p],
+    'stx_image_swt_daub_levels': [_vp, _vp, _vp, _i, _i, _i, _i, c_int_p, _d, _d, c_double_p],
     'stx_adam_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _d, _d, _d, _d, _d, _d, _d],
     'stx_vec_dot': [_vp, _vp, _vp, _sz, c_double_p],
     'stx_vec_axpy': [_vp, _d, _vp, _vp, _sz],
