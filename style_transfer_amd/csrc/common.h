@@ -56,7 +56,37 @@ void sw_reread();
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int pooled_len(int n) { return n >= 2 ? (n - 2 + 1) / 2 + 1 : 1; }  // ceil((n-2)/2)+1
+// Workgroups of a grid-stride reduction over n elements (image_ops.hip, swt.hip): at most kBlocks,
+// which the engine's reduction scratch is sized for.
+constexpr int kBlocks = 1024;
+inline int blocks_for(size_t n) {
+    const size_t b = (n + 255) / 256;
+    return b < (size_t)kBlocks ? (int)b : kBlocks;
+}
 #ifdef __HIPCC__
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// Block-reduces up to NV values (256 threads) and writes partials[v * gridDim.x + blockIdx.x].
+template <int NV>
+__device__ __forceinline__ void block_partials(float (&v)[NV], float *partials) {
+    __shared__ float red[NV][4];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const float s = wave_sum_f(v[k]);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+            partials[k * gridDim.x + blockIdx.x] = red[k][0] + red[k][1] + red[k][2] + red[k][3];
+    }
+}
+
 // Window codes of the 2x2/2 pooling (pool.hip): what the backward pass needs to know about a window.
 // MAX: index of the FIRST maximum in row-major order (strict '>' scan, as Caffe's) | 4 if it is > 0.
 __device__ __forceinline__ unsigned pool_max_code(float v00, float v01, float v10, float v11, bool hx,
@@ -427,9 +457,6 @@ int roll_add_launch(hipStream_t s, float *acc, const float *src, int C, int h, i
                     float alpha, bool init);
 int resample_launch(hipStream_t s, int axis, const float *src, int C, int H, int W, float *dst,
                     int OH, int OW, const int *bounds, const double *k, int ksize, int clamp);
-int swt_haar_launch(hipStream_t s, const float *img, float *grad, int H, int W, int rx, int ry,
-                    float scale, float power, double *loss_term, float *scratch,
-                    size_t scratch_floats);
 // *out_dev = sum of n float partials, added in double in a fixed order
 int finish_partials_launch(hipStream_t s, const float *partials, int n, double *out_dev);
 int regularizers_launch(hipStream_t s, const float *img, float *grad, int H, int W,
@@ -437,18 +464,21 @@ int regularizers_launch(hipStream_t s, const float *img, float *grad, int H, int
                         float p_power, const float *aux, float aux_scale, int aux_rx, int aux_ry,
                         double *loss_terms /*[3]*/, float *scratch, size_t scratch_floats);
 
-// swt.hip: the Haar SWT term at `levels` > 1 (two separable passes).  tmp and partials hold what
-// swt_haar_levels_scratch asks for; N = swt_padded_side(H, W) bounds the level count (2^levels <= N).
+// swt.hip: the SWT term.  One Haar level is a single pass over `scratch` (blocks_for(3 H W) floats);
+// more levels and the table form are two separable passes: tmp and partials hold what
+// swt_levels_scratch asks for, N = swt_padded_side(H, W) bounds the level count (2^levels <= N).
 int swt_padded_side(int H, int W);
-void swt_haar_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_floats);
+int swt_haar_launch(hipStream_t s, const float *img, float *grad, int H, int W, int rx, int ry,
+                    float scale, float power, double *loss_term, float *scratch,
+                    size_t scratch_floats);
+void swt_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_floats);
 int swt_haar_levels_launch(hipStream_t s, const float *img, float *grad, int H, int W, int levels,
                            int rx, int ry, float scale, float power, double *loss_term, float *tmp,
                            float *partials);
 // The same term for the orthogonal Daubechies / symlet filter with `order` vanishing moments.
 // swt_daub_table builds, in double on the host, the per-axis taps of `levels` levels folded onto the
 // periodic square of side N (at most N taps; tap i weighs padded coordinate q + i - *hl) and
-// rounds them to float once; swt_table_launch runs the two passes with a device copy of them
-// (scratch as for swt_haar_levels_launch).
+// rounds them to float once; swt_table_launch runs the two passes with a device copy of them.
 void swt_daub_table(int order, int levels, int N, std::vector<float> *taps, int *hl);
 int swt_table_launch(hipStream_t s, const float *img, float *grad, int H, int W, const float *table,
                      int ntaps, int hl, int rx, int ry, float scale, float power,

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1956,28 +1957,87 @@ int stx_image_resample(stx_engine *e, const float *src, int channels, int H, int
     return STX_OK;
 }
 
+// Queues n = coefs.size() double-precision loss terms: `launch` enqueues the kernels that leave them at the
+// device pointer it is handed, they are mirrored to the host arena, and at the next sync *loss_out becomes
+// sum coefs[i] * term[i].
+static int queue_dterms(stx_engine *e, std::initializer_list<double> coefs, double *loss_out,
+                        const std::function<int(double *)> &launch) {
+    size_t di;
+    STX_TRY(alloc_dscalars(e, coefs.size(), &di));
+    double *terms = static_cast<double *>(e->A().dscalars.ptr) + di;
+    STX_TRY(launch(terms));
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, terms, coefs.size() * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    PendingLoss pl;
+    pl.out = loss_out;
+    size_t i = di;
+    for (double coef : coefs) pl.dterms.push_back(LossTerm{i++, coef});
+    e->A().pending.push_back(std::move(pl));
+    return STX_OK;
+}
+
 int stx_image_regularizers(stx_engine *e, const float *img, float *grad, int H, int W,
                            const float mean_bgr[3], double tv_scale, double tv_power, double p_scale,
                            double p_power, const float *aux, double aux_scale,
                            const int aux_roll_xy[2], double *loss_out) {
     if (!e || !img || !grad || !mean_bgr || H <= 0 || W <= 0) return STX_ERR_ARG;
     STX_TRY(e->set_device());
-    size_t di;
-    STX_TRY(alloc_dscalars(e, 3, &di));
-    double *terms = static_cast<double *>(e->A().dscalars.ptr) + di;
-    STX_TRY(regularizers_launch(e->stream, img, grad, H, W, mean_bgr, (float)tv_scale,
-                                (float)tv_power, (float)p_scale, (float)p_power, aux,
-                                (float)aux_scale, aux_roll_xy ? aux_roll_xy[0] : 0,
-                                aux_roll_xy ? aux_roll_xy[1] : 0, terms, e->red_scratch.f(),
-                                e->red_scratch.bytes / sizeof(float)));
-    STX_HIP(hipMemcpyAsync(e->A().dhost + di, terms, 3 * sizeof(double), hipMemcpyDeviceToHost,
-                           e->stream));
-    PendingLoss pl;
-    pl.out = loss_out;
-    pl.dterms.push_back(LossTerm{di + 0, tv_scale});
-    pl.dterms.push_back(LossTerm{di + 1, p_scale});
-    pl.dterms.push_back(LossTerm{di + 2, aux ? aux_scale * 0.5 : 0.0});
-    e->A().pending.push_back(std::move(pl));
+    return queue_dterms(e, {tv_scale, p_scale, aux ? aux_scale * 0.5 : 0.0}, loss_out, [&](double *terms) {
+        return regularizers_launch(e->stream, img, grad, H, W, mean_bgr, (float)tv_scale,
+                                   (float)tv_power, (float)p_scale, (float)p_power, aux,
+                                   (float)aux_scale, aux_roll_xy ? aux_roll_xy[0] : 0,
+                                   aux_roll_xy ? aux_roll_xy[1] : 0, terms, e->red_scratch.f(),
+                                   e->red_scratch.bytes / sizeof(float));
+    });
+}
+
+// ---- the SWT term (swt.hip): order 1 is Haar and goes to the Haar levels entry, one level of it to the
+// one-level kernel, so that the three entries agree bit for bit where they overlap ----
+
+// pywt.swt2 takes 1 to log2(padded side) levels
+static int swt_check_levels(const char *name, int H, int W, int levels) {
+    const int N = swt_padded_side(H, W);
+    if (levels < 1 || levels > 30 || (1 << levels) > N) {
+        set_error("%s: levels = %d, but a %d x %d image (padded side %d) takes 1 to %d levels", name,
+                  levels, H, W, N, (int)std::lround(std::log2((double)N)));
+        return STX_ERR_ARG;
+    }
+    return STX_OK;
+}
+
+// The scratch of the two separable passes: the row-filtered image and the column pass's partials.
+static int swt_scratch_for(stx_engine *e, int H, int W, float **tmp, float **partials) {
+    size_t tmp_floats, partial_floats;
+    swt_levels_scratch(H, W, &tmp_floats, &partial_floats);
+    // growing frees the old buffer, which waits for the kernels that still read it
+    STX_TRY(e->swt_scratch.ensure((tmp_floats + partial_floats) * sizeof(float)));
+    *tmp = e->swt_scratch.f();
+    *partials = *tmp + tmp_floats;
+    return STX_OK;
+}
+
+// The device copy of swt_daub_table(order, levels, N): built and uploaded at first use, then kept.
+static int swt_table_for(stx_engine *e, int order, int levels, int N, const stx_engine::SwtTable **out) {
+    for (const stx_engine::SwtTable &t : e->swt_tables)
+        if (t.order == order && t.levels == levels && t.N == N) {
+            *out = &t;
+            return STX_OK;
+        }
+    std::vector<float> taps;
+    int hl;
+    swt_daub_table(order, levels, N, &taps, &hl);
+    stx_engine::SwtTable t{order, levels, N, (int)taps.size(), hl, DevBuf()};
+    STX_TRY(t.taps.ensure(taps.size() * sizeof(float)));
+    // once per table and synchronous: the host copy does not outlive this call
+    hipError_t err = hipMemcpy(t.taps.ptr, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        t.taps.release();
+        set_error("stx_image_swt_daub_levels: hipMemcpy of %zu taps failed: %s", taps.size(),
+                  hipGetErrorString(err));
+        return STX_ERR_HIP;
+    }
+    e->swt_tables.push_back(t);
+    *out = &e->swt_tables.back();
     return STX_OK;
 }
 
@@ -1985,50 +2045,26 @@ int stx_image_swt_haar(stx_engine *e, const float *img, float *grad, int H, int 
                        const int roll_xy[2], double scale, double power, double *loss_out) {
     if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
     STX_TRY(e->set_device());
-    size_t di;
-    STX_TRY(alloc_dscalars(e, 1, &di));
-    double *term = static_cast<double *>(e->A().dscalars.ptr) + di;
-    STX_TRY(swt_haar_launch(e->stream, img, grad, H, W, roll_xy ? roll_xy[0] : 0,
-                            roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
-                            e->red_scratch.f(), e->red_scratch.bytes / sizeof(float)));
-    STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
-                           e->stream));
-    PendingLoss pl;
-    pl.out = loss_out;
-    pl.dterms.push_back(LossTerm{di, scale});
-    e->A().pending.push_back(std::move(pl));
-    return STX_OK;
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return swt_haar_launch(e->stream, img, grad, H, W, roll_xy ? roll_xy[0] : 0,
+                               roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
+                               e->red_scratch.f(), e->red_scratch.bytes / sizeof(float));
+    });
 }
 
 int stx_image_swt_haar_levels(stx_engine *e, const float *img, float *grad, int H, int W, int levels,
                               const int roll_xy[2], double scale, double power, double *loss_out) {
     if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
-    const int N = swt_padded_side(H, W);
-    if (levels < 1 || levels > 30 || (1 << levels) > N) {
-        set_error("stx_image_swt_haar_levels: levels = %d, but a %d x %d image (padded side %d) "
-                  "takes 1 to %d levels", levels, H, W, N, (int)std::lround(std::log2((double)N)));
-        return STX_ERR_ARG;
-    }
-    // one level is the shipped kernel: bit-identical to stx_image_swt_haar by construction
+    STX_TRY(swt_check_levels("stx_image_swt_haar_levels", H, W, levels));
     if (levels == 1) return stx_image_swt_haar(e, img, grad, H, W, roll_xy, scale, power, loss_out);
     STX_TRY(e->set_device());
-    size_t tmp_floats, partial_floats;
-    swt_haar_levels_scratch(H, W, &tmp_floats, &partial_floats);
-    // growing frees the old buffer, which waits for the kernels that still read it
-    STX_TRY(e->swt_scratch.ensure((tmp_floats + partial_floats) * sizeof(float)));
-    size_t di;
-    STX_TRY(alloc_dscalars(e, 1, &di));
-    double *term = static_cast<double *>(e->A().dscalars.ptr) + di;
-    STX_TRY(swt_haar_levels_launch(e->stream, img, grad, H, W, levels, roll_xy ? roll_xy[0] : 0,
-                                   roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
-                                   e->swt_scratch.f(), e->swt_scratch.f() + tmp_floats));
-    STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
-                           e->stream));
-    PendingLoss pl;
-    pl.out = loss_out;
-    pl.dterms.push_back(LossTerm{di, scale});
-    e->A().pending.push_back(std::move(pl));
-    return STX_OK;
+    float *tmp, *partials;
+    STX_TRY(swt_scratch_for(e, H, W, &tmp, &partials));
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return swt_haar_levels_launch(e->stream, img, grad, H, W, levels, roll_xy ? roll_xy[0] : 0,
+                                      roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term, tmp,
+                                      partials);
+    });
 }
 
 int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int H, int W, int order,
@@ -2039,55 +2075,19 @@ int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int 
         set_error("stx_image_swt_daub_levels: order = %d, but db1 to db38 exist", order);
         return STX_ERR_ARG;
     }
-    // one vanishing moment is the Haar wavelet: bit-identical to stx_image_swt_haar_levels by
-    // construction (which also checks the level count)
-    if (order == 1)
+    if (order == 1)     // (the Haar entry checks the level count)
         return stx_image_swt_haar_levels(e, img, grad, H, W, levels, roll_xy, scale, power, loss_out);
-    const int N = swt_padded_side(H, W);
-    if (levels < 1 || levels > 30 || (1 << levels) > N) {
-        set_error("stx_image_swt_daub_levels: levels = %d, but a %d x %d image (padded side %d) "
-                  "takes 1 to %d levels", levels, H, W, N, (int)std::lround(std::log2((double)N)));
-        return STX_ERR_ARG;
-    }
+    STX_TRY(swt_check_levels("stx_image_swt_daub_levels", H, W, levels));
     STX_TRY(e->set_device());
-    const stx_engine::SwtTable *tab = nullptr;
-    for (const stx_engine::SwtTable &t : e->swt_tables)
-        if (t.order == order && t.levels == levels && t.N == N) tab = &t;
-    if (!tab) {
-        std::vector<float> taps;
-        int hl;
-        swt_daub_table(order, levels, N, &taps, &hl);
-        stx_engine::SwtTable t{order, levels, N, (int)taps.size(), hl, DevBuf()};
-        STX_TRY(t.taps.ensure(taps.size() * sizeof(float)));
-        // once per table and synchronous: the host copy does not outlive this call
-        hipError_t err = hipMemcpy(t.taps.ptr, taps.data(), taps.size() * sizeof(float),
-                                   hipMemcpyHostToDevice);
-        if (err != hipSuccess) {
-            t.taps.release();
-            set_error("stx_image_swt_daub_levels: hipMemcpy of %zu taps failed: %s", taps.size(),
-                      hipGetErrorString(err));
-            return STX_ERR_HIP;
-        }
-        e->swt_tables.push_back(t);
-        tab = &e->swt_tables.back();
-    }
-    size_t tmp_floats, partial_floats;
-    swt_haar_levels_scratch(H, W, &tmp_floats, &partial_floats);
-    STX_TRY(e->swt_scratch.ensure((tmp_floats + partial_floats) * sizeof(float)));
-    size_t di;
-    STX_TRY(alloc_dscalars(e, 1, &di));
-    double *term = static_cast<double *>(e->A().dscalars.ptr) + di;
-    STX_TRY(swt_table_launch(e->stream, img, grad, H, W, tab->taps.f(), tab->ntaps, tab->hl,
-                             roll_xy ? roll_xy[0] : 0, roll_xy ? roll_xy[1] : 0, (float)scale,
-                             (float)power, term, e->swt_scratch.f(),
-                             e->swt_scratch.f() + tmp_floats));
-    STX_HIP(hipMemcpyAsync(e->A().dhost + di, term, sizeof(double), hipMemcpyDeviceToHost,
-                           e->stream));
-    PendingLoss pl;
-    pl.out = loss_out;
-    pl.dterms.push_back(LossTerm{di, scale});
-    e->A().pending.push_back(std::move(pl));
-    return STX_OK;
+    const stx_engine::SwtTable *tab;
+    STX_TRY(swt_table_for(e, order, levels, swt_padded_side(H, W), &tab));
+    float *tmp, *partials;
+    STX_TRY(swt_scratch_for(e, H, W, &tmp, &partials));
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return swt_table_launch(e->stream, img, grad, H, W, tab->taps.f(), tab->ntaps, tab->hl,
+                                roll_xy ? roll_xy[0] : 0, roll_xy ? roll_xy[1] : 0, (float)scale,
+                                (float)power, term, tmp, partials);
+    });
 }
 
 int stx_adam_step(stx_engine *e, float *params, const float *grad, float *g1, float *g2, float *p1,

@@ -1,11 +1,23 @@
-// The SWT regularizer of the reference for the Haar wavelet at L > 1 levels
-// (style_transfer.py:716-720, num_utils.py:179-196).  The one-level kernel is in image_ops.hip and
-// its header comment has the padding and the roll; what changes with the level count is the filter.
+// The SWT regularizer of the reference (style_transfer.py:716-720, num_utils.py:179-196): the whole
+// term lives in this file -- one Haar level (the reference's default), Haar at L levels, and the
+// orthogonal Daubechies / symlet filters from a table.
 //
-// Level j (j = 1..L) of the stationary Haar transform uses the two-tap filters dilated by
-// d = 2^(j-1), periodic on the padded N x N square.  Analysis followed by the shift-averaged
-// synthesis of the low band alone is [1 2 1]/4 at stride d, and pywt.iswt2 uses only the deepest
-// approximation band, so zeroing the approximation bands removes the path through that band alone:
+// Padding, roll, and D = x - B x.  Every channel of img / 127.5 is padded symmetrically to a square
+// of side N = 2^ceil(log2(max(H, W))) (an odd amount puts the extra row / column behind),
+// transformed with the stationary wavelet transform (periodic on the square), the approximation
+// band is dropped and the rest transformed back.  For one Haar level what comes out is
+//     D = x - B x,   B = [1 2 1]/4 along rows x [1 2 1]/4 along columns, circular on the square
+// (oracle/num_ops.py has the derivation and a band-by-band check).  loss = sum |D|^p over the
+// H x W crop; the reference adds the p-norm's OWN gradient at D to the image gradient, not its
+// chain through D, and so does this.  The reference transforms the image rolled by the
+// iteration's shift; here the image stays un-rolled: pixel (y, x) sits at ((y + ry) mod H,
+// (x + rx) mod W) of the rolled picture.  swt_haar_kernel does all of that in one pass.
+//
+// The L-level triangle.  Level j (j = 1..L) of the stationary Haar transform uses the two-tap
+// filters dilated by d = 2^(j-1), periodic on the padded N x N square.  Analysis followed by the
+// shift-averaged synthesis of the low band alone is [1 2 1]/4 at stride d, and pywt.iswt2 uses only
+// the deepest approximation band, so zeroing the approximation bands removes the path through that
+// band alone:
 //     D = x - B_L x,   B_L = product over j of ([1 2 1]/4 at stride 2^(j-1)), rows x columns.
 // Per axis the product is the triangle T_L[k] = (2^L - |k|) / 4^L, |k| < 2^L
 // (tests/swt_levels_ref.py restates it and holds it to a band-by-band filterbank).
@@ -23,8 +35,19 @@
 // the same ascending order, so the sums do not depend on the chunking.  The triangle's integer
 // numerators are accumulated with one fused multiply-add per tap and scaled by the exact 4^-L at
 // the end: no running sums, the rounding error of a pixel is that of its own 2^(L+1) - 1 terms.
-// The file is compiled with -ffp-contract=off like image_ops.hip: D and the p-norm round per
-// operation like the one-level kernel's.
+//
+// The table for dbN / symN.  Per level and axis, analysis followed by the shift-averaged synthesis
+// of the low band is r/2 at stride 2^(j-1), r the autocorrelation of the low-pass filter; r depends
+// on |H|^2 alone, which dbN and symN share.  The product over the levels is a table of taps built
+// on the host (swt_daub_table), already normalised and already folded onto the periodic square, so
+// that it never has more than N taps: tap i of `ntaps` is the weight of padded coordinate
+// q + i - hl.  The passes are the two above with the weight read from the table, and both walk the
+// TAPS in chunks of at most T, ascending: a chunk stages the T taps and the T + tile - 1 slots they
+// reach, so every output of the tile takes every tap of the chunk and no tap range depends on the
+// thread.
+//
+// The file is compiled with -ffp-contract=off: D and the p-norm (swt_pnorm) round once per
+// operation, like the reference's numpy expressions, in all three forms of the term.
 
 #include <algorithm>
 
@@ -55,6 +78,79 @@ __device__ __forceinline__ int swt_unrolled(int q0, int s, int N, int pad_lo, in
     if (q < 0) q += N;
     const int u = swt_source(q, pad_lo, n) - shift;
     return u < 0 ? u + n : u;
+}
+
+// The p-norm at one pixel: |d|^power is added to `sum`; returns the norm's own gradient at d.
+__device__ __forceinline__ float swt_pnorm(float d, float power, float &sum) {
+    const float ad = fabsf(d);
+    float g;
+    if (power == 2.f) {
+        sum += d * d;
+        g = 2.f * d;
+    } else if (power == 1.f) {
+        sum += ad;
+        g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    } else {
+        const float ap1 = powf(ad, power - 1.f);
+        sum += ap1 * ad;
+        g = power * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ap1;
+    }
+    return g;
+}
+
+// The end of a column pass: one partial per workgroup of its 3-D grid, added in a fixed order
+// (finish_partials_launch adds the partials in double).  red: 4 floats of LDS.
+__device__ __forceinline__ void swt_cols_partial(float sum, float *red, float *partials) {
+    sum = wave_sum_f(sum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
+            red[0] + red[1] + red[2] + red[3];
+}
+
+// One Haar level in a single pass: a grid-stride loop over the 3 H W pixels, nine loads each.
+__global__ __launch_bounds__(256) void swt_haar_kernel(const float *__restrict__ img,
+                                                       float *__restrict__ grad, int H, int W, int N,
+                                                       int rx, int ry, float scale, float power,
+                                                       float *__restrict__ partials) {
+    const size_t plane = (size_t)H * W, total = 3 * plane;
+    const int pad_y = (N - H) / 2, pad_x = (N - W) / 2;
+    float sums[1] = {0.f};
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int x = i % W;
+        const int y = (i / W) % H;
+        const int c = i / plane;
+        const float *p = img + (size_t)c * plane;
+        // position in the rolled picture and on the padded square
+        int Y = (y + ry) % H, X = (x + rx) % W;
+        if (Y < 0) Y += H;
+        if (X < 0) X += W;
+        const int qy = Y + pad_y, qx = X + pad_x;
+        // rows first (vertical [1 2 1]/4), then columns, like the oracle's two passes
+        int uy[3];
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int sy = swt_source((qy + dy + N) % N, pad_y, H);
+            uy[dy + 1] = (sy - ry) % H;
+            if (uy[dy + 1] < 0) uy[dy + 1] += H;
+        }
+        float cols[3], centre = 0.f;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int sx = swt_source((qx + dx + N) % N, pad_x, W);
+            int ux = (sx - rx) % W;
+            if (ux < 0) ux += W;
+            const float up = p[(size_t)uy[0] * W + ux] / 127.5f, mid = p[(size_t)uy[1] * W + ux] / 127.5f;
+            const float down = p[(size_t)uy[2] * W + ux] / 127.5f;
+            cols[dx + 1] = (up + 2.f * mid + down) / 4.f;
+            if (dx == 0) centre = mid;
+        }
+        const float blur = (cols[0] + 2.f * cols[1] + cols[2]) / 4.f;
+        const float d = centre - blur;
+        grad[i] = scale * swt_pnorm(d, power, sums[0]) + grad[i];
+    }
+    block_partials<1>(sums, partials);
 }
 
 // Pass 1.  grid (ceil(W / 256), ceil(H / 4), 3).  Thread t owns column X0 + t of the ROLLED picture
@@ -149,42 +245,12 @@ __global__ __launch_bounds__(256) void swt_cols_kernel(const float *__restrict__
         const int y = Y - shift_y < 0 ? Y - shift_y + H : Y - shift_y;
         const size_t i = blockIdx.z * plane + (size_t)y * W + x;
         const float d = img[i] / 127.5f - acc[o] * inv;
-        const float ad = fabsf(d);
-        float gr;
-        if (power == 2.f) {
-            sum += d * d;
-            gr = 2.f * d;
-        } else if (power == 1.f) {
-            sum += ad;
-            gr = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        } else {
-            const float ap1 = powf(ad, power - 1.f);
-            sum += ap1 * ad;
-            gr = power * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ap1;
-        }
-        grad[i] = scale * gr + grad[i];
+        grad[i] = scale * swt_pnorm(d, power, sum) + grad[i];
     }
-    // one partial per workgroup, added in a fixed order (finish_partials_launch adds them in double)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-    float *red = lds + chunk * kColTile;
-    if (col == 0) red[g] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
-            red[0] + red[1] + red[2] + red[3];
+    swt_cols_partial(sum, lds + chunk * kColTile, partials);
 }
 
-// ---- the same term for any orthogonal Daubechies / symlet filter (stx_image_swt_daub_levels) ----
-// Per level and axis, analysis followed by the shift-averaged synthesis of the low band is r/2 at
-// stride 2^(j-1), r the autocorrelation of the low-pass filter; r depends on |H|^2 alone, which dbN
-// and symN share.  The product over the levels is a table of taps built on the host
-// (swt_daub_table), already normalised and already folded onto the periodic square, so that it
-// never has more than N taps: tap i of `ntaps` is the weight of padded coordinate q + i - hl.
-//
-// The passes are those above with the weight read from the table, and both walk the TAPS in chunks
-// of at most T, ascending: a chunk stages the T taps and the T + tile - 1 slots they reach, so every
-// output of the tile takes every tap of the chunk and no tap range depends on the thread.
+// ---- the two passes with the weights from a table (dbN / symN) ----
 constexpr int kTabRowTaps = 1408;   // pass 1: 4 x (1408 + 255) strip + 1408 taps = 31.5 KiB
 constexpr int kTabColTaps = 113;    // pass 2: (113 + 63) x 64 strip + 143 taps = 44.6 KiB; 16 m + 1
 constexpr int kTabColOwn = 16;      //         consecutive output rows per thread
@@ -294,29 +360,9 @@ __global__ __launch_bounds__(256) void swt_cols_table_kernel(
         const int y = Y - shift_y < 0 ? Y - shift_y + H : Y - shift_y;
         const size_t i = blockIdx.z * plane + (size_t)y * W + x;
         const float d = img[i] / 127.5f - acc[o];
-        const float ad = fabsf(d);
-        float gr;
-        if (power == 2.f) {
-            sum += d * d;
-            gr = 2.f * d;
-        } else if (power == 1.f) {
-            sum += ad;
-            gr = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        } else {
-            const float ap1 = powf(ad, power - 1.f);
-            sum += ap1 * ad;
-            gr = power * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * ap1;
-        }
-        grad[i] = scale * gr + grad[i];
+        grad[i] = scale * swt_pnorm(d, power, sum) + grad[i];
     }
-    // one partial per workgroup, added in a fixed order (finish_partials_launch adds them in double)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-    if (col == 0) red[g] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
-            red[0] + red[1] + red[2] + red[3];
+    swt_cols_partial(sum, red, partials);
 }
 
 int wrapped(int v, int n) {
@@ -332,19 +378,30 @@ int swt_padded_side(int H, int W) {
     return N;
 }
 
-void swt_haar_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_floats) {
+int swt_haar_launch(hipStream_t s, const float *img, float *grad, int H, int W, int rx, int ry,
+                    float scale, float power, double *loss_term, float *scratch,
+                    size_t scratch_floats) {
+    const int blocks = blocks_for((size_t)3 * H * W);
+    if (scratch_floats < (size_t)blocks) {
+        set_error("swt_haar: scratch too small");
+        return STX_ERR_STATE;
+    }
+    swt_haar_kernel<<<blocks, 256, 0, s>>>(img, grad, H, W, swt_padded_side(H, W), rx, ry, scale,
+                                           power, scratch);
+    STX_CHECK_LAUNCH();
+    return finish_partials_launch(s, scratch, blocks, loss_term);
+}
+
+void swt_levels_scratch(int H, int W, size_t *tmp_floats, size_t *partial_floats) {
     *tmp_floats = (size_t)3 * H * W;
     *partial_floats = (size_t)3 * ceil_div(H, kColRows) * ceil_div(W, kColTile);
 }
 
+// 1 <= levels and 2^levels <= N: the caller has checked (stx_image_swt_haar_levels)
 int swt_haar_levels_launch(hipStream_t s, const float *img, float *grad, int H, int W, int levels,
                            int rx, int ry, float scale, float power, double *loss_term, float *tmp,
                            float *partials) {
     const int N = swt_padded_side(H, W);
-    if (levels < 1 || levels > 30 || (1 << levels) > N) {
-        set_error("swt_haar_levels: %d levels on a padded side of %d", levels, N);
-        return STX_ERR_ARG;
-    }
     const int P = 1 << levels, h = P - 1;
     {
         const int chunk = std::min(kRowTile + 2 * h, kRowChunk);

@@ -67,22 +67,6 @@ def swt_padded_side(h, w):
     return 1 << max(0, (max(h, w) - 1).bit_length())
 
 
-def swt_haar(engine, img, grad, scale, power, roll=None, levels=1):
-    """grad += scale * (p-norm gradient at the Haar SWT detail image of the rolled picture / 127.5);
-    returns a PendingScalar with scale * sum |detail|^power (style_transfer.py:716-720 for the
-    Haar wavelet; ``levels`` is --swt-levels, 1 to log2 of ``swt_padded_side``)."""
-    _, H, W = img.shape
-    out = engine.keep_until_sync(PendingScalar())
-    xy = _xy(roll) if roll is not None else None
-    if levels == 1:
-        lib.call('stx_image_swt_haar', engine.handle, img.ptr, grad.ptr, H, W, xy, float(scale),
-                 float(power), ctypes.byref(out._v))
-    else:
-        lib.call('stx_image_swt_haar_levels', engine.handle, img.ptr, grad.ptr, H, W, int(levels),
-                 xy, float(scale), float(power), ctypes.byref(out._v))
-    return out
-
-
 def swt_wavelet_order(wavelet):
     """Vanishing moments of an orthogonal Daubechies / symlet wavelet by its PyWavelets name: haar
     and db1 -> 1, dbN (1..38) and symN (2..20) -> N.  The SWT term depends on the filter through
@@ -99,11 +83,28 @@ def swt_wavelet_order(wavelet):
                               'implemented' % (wavelet,))
 
 
+def _swt(engine, img, grad, scale, power, order, levels, roll):
+    """The SWT term through the entry point of its own form: the one-level Haar kernel, Haar at
+    several levels, or the dbN / symN table (the library delegates the same way, bit for bit)."""
+    _, H, W = img.shape
+    out = engine.keep_until_sync(PendingScalar())
+    if order == 1 and levels == 1:
+        name, form = 'stx_image_swt_haar', ()
+    elif order == 1:
+        name, form = 'stx_image_swt_haar_levels', (int(levels),)
+    else:
+        name, form = 'stx_image_swt_daub_levels', (int(order), int(levels))
+    lib.call(name, engine.handle, img.ptr, grad.ptr, H, W, *form,
+             _xy(roll) if roll is not None else None, float(scale), float(power),
+             ctypes.byref(out._v))
+    return out
+
+
 def swt_wavelet(engine, img, grad, scale, power, wavelet, levels=1, roll=None):
-    """``swt_haar`` for the wavelets of ``swt_wavelet_order`` (num_utils.py:184-196 passes any
-    PyWavelets name on): grad += scale * (p-norm gradient at the detail image), returns a
-    PendingScalar with scale * sum |detail|^power.  A level count outside 1 .. log2 of
-    ``swt_padded_side`` raises ValueError, as PyWavelets would."""
+    """grad += scale * (p-norm gradient at the SWT detail image of the rolled picture / 127.5) for
+    the wavelets of ``swt_wavelet_order`` (style_transfer.py:716-720; num_utils.py:184-196 passes
+    any PyWavelets name on); returns a PendingScalar with scale * sum |detail|^power.  A level count
+    outside 1 .. log2 of ``swt_padded_side`` raises ValueError, as PyWavelets would."""
     order = swt_wavelet_order(wavelet)
     _, H, W = img.shape
     levels = int(levels)
@@ -111,11 +112,13 @@ def swt_wavelet(engine, img, grad, scale, power, wavelet, levels=1, roll=None):
         raise ValueError('%d SWT levels: a %d x %d image is padded to a square of side %d, which '
                          'takes 1 to %d levels' % (levels, W, H, swt_padded_side(H, W),
                                                    swt_padded_side(H, W).bit_length() - 1))
-    out = engine.keep_until_sync(PendingScalar())
-    lib.call('stx_image_swt_daub_levels', engine.handle, img.ptr, grad.ptr, H, W, order, levels,
-             _xy(roll) if roll is not None else None, float(scale), float(power),
-             ctypes.byref(out._v))
-    return out
+    return _swt(engine, img, grad, scale, power, order, levels, roll)
+
+
+def swt_haar(engine, img, grad, scale, power, roll=None, levels=1):
+    """``swt_wavelet`` for the Haar wavelet (``levels`` is --swt-levels), except that a level count
+    outside the range is left to the library to refuse (lib.StxError)."""
+    return _swt(engine, img, grad, scale, power, 1, levels, roll)
 
 
 def adam_step(engine, params, grad, g1, g2, p1, avg, lr, b1, b2, bp1, corr1, corr2, corrp):

@@ -1,5 +1,6 @@
 """Helpers for the -m gpu parity tests (HIP path through the C ABI vs the numpy oracle)."""
 
+import ctypes
 import os
 
 import numpy as np
@@ -35,6 +36,36 @@ def gpu_engine(model='vgg19', seed=0):
         net = builtin_net(model)
         _ENGINES[key] = TileEngine(net, 0, synthetic_weights(net.as_dicts(), seed))
     return _ENGINES[key]
+
+
+def swt_inputs(shape, seed):
+    """(image, gradient to add to) of the SWT tests."""
+    rng = np.random.RandomState(seed)
+    img = rng.uniform(-120, 130, shape).astype(np.float32)
+    g0 = rng.standard_normal(shape).astype(np.float32)
+    return img, g0
+
+
+def swt_rolled(img, roll):
+    """What the SWT term transforms: the picture rolled by the iteration's shift, over 127.5."""
+    return np.roll(img, (roll[1], roll[0]), (1, 2)) / np.float32(127.5)        # roll = (x, y)
+
+
+def swt_call(eng, d_img, d_grad, roll, scale, power, levels=None, order=None):
+    """The C entry points of the SWT term themselves, not image_ops' choice among them:
+    stx_image_swt_haar (no levels), stx_image_swt_haar_levels (levels) or stx_image_swt_daub_levels
+    (order and levels).  Returns the PendingScalar of the loss."""
+    from style_transfer_amd import image_ops, lib
+    name, form = 'stx_image_swt_haar', ()
+    if order is not None:
+        name, form = 'stx_image_swt_daub_levels', (order, levels)
+    elif levels is not None:
+        name, form = 'stx_image_swt_haar_levels', (levels,)
+    _, H, W = d_img.shape
+    out = eng.keep_until_sync(image_ops.PendingScalar())
+    lib.call(name, eng.handle, d_img.ptr, d_grad.ptr, H, W, *form, (ctypes.c_int * 2)(*roll),
+             float(scale), float(power), ctypes.byref(out._v))
+    return out
 
 
 def max_rel(a, b):

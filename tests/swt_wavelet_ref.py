@@ -25,10 +25,7 @@ from math import comb
 import numpy as np
 
 from oracle import num_ops
-
-
-def padded_side(h, w):
-    return 2 ** int(np.ceil(np.log2(max(h, w))))
+from tests.swt_levels_ref import padded_side
 
 
 def _mul(a, b):

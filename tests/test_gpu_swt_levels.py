@@ -3,7 +3,6 @@ num_utils.py:179-196) against the float64 restatement in tests/swt_levels_ref.py
 tests/test_swt_levels_host.py holds to a band-by-band transform.  PyWavelets is in neither tree:
 no reference vectors exist, parity with it is unpinned as for one level."""
 
-import ctypes
 from argparse import Namespace
 
 import numpy as np
@@ -17,7 +16,7 @@ from style_transfer_amd.netspec import builtin_net
 from style_transfer_amd.transfer import StyleTransfer
 from style_transfer_amd.weights import synthetic_weights
 from tests import swt_levels_ref as ref
-from tests.gpu_helpers import gpu_engine
+from tests.gpu_helpers import gpu_engine, swt_call, swt_inputs, swt_rolled
 
 pytestmark = pytest.mark.gpu
 
@@ -54,31 +53,11 @@ CASES = [
 ]
 
 
-def _inputs(shape, seed):
-    rng = np.random.RandomState(seed)
-    img = rng.uniform(-120, 130, shape).astype(np.float32)
-    g0 = rng.standard_normal(shape).astype(np.float32)
-    return img, g0
-
-
-def _rolled(img, roll):
-    return np.roll(img, (roll[1], roll[0]), (1, 2)) / np.float32(127.5)        # roll = (x, y)
-
-
-def _levels_call(eng, d_img, d_grad, levels, roll, scale, power):
-    """The new entry point itself (image_ops.swt_haar keeps one level on stx_image_swt_haar)."""
-    _, H, W = d_img.shape
-    out = eng.keep_until_sync(image_ops.PendingScalar())
-    lib.call('stx_image_swt_haar_levels', eng.handle, d_img.ptr, d_grad.ptr, H, W, levels,
-             (ctypes.c_int * 2)(*roll), float(scale), float(power), ctypes.byref(out._v))
-    return out
-
-
 @pytest.mark.parametrize('shape,levels,roll,power,seed', CASES)
 def test_swt_haar_levels_against_restatement(shape, levels, roll, power, seed):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, seed)
-    rolled = _rolled(img, roll)
+    img, g0 = swt_inputs(shape, seed)
+    rolled = swt_rolled(img, roll)
     if power == 1:
         d = np.abs(ref.swt_haar_detail(rolled, levels))
         assert d.min() >= 1e-5 * d.max(), 'seed %d puts a pixel on the sign change' % seed
@@ -101,11 +80,11 @@ def test_swt_haar_levels_against_restatement(shape, levels, roll, power, seed):
                                               ((3, 300, 520), (16, 8), 1.5)])
 def test_one_level_through_the_new_entry_is_the_shipped_kernel(shape, roll, power):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, 3)
+    img, g0 = swt_inputs(shape, 3)
     d_img = eng.to_device(img)
     d_old, d_new = eng.to_device(g0), eng.to_device(g0)
     old = image_ops.swt_haar(eng, d_img, d_old, SCALE, power, roll=roll)
-    new = _levels_call(eng, d_img, d_new, 1, roll, SCALE, power)
+    new = swt_call(eng, d_img, d_new, roll, SCALE, power, levels=1)
     eng.sync()
     assert np.array_equal(d_old.get(), d_new.get())
     assert old.value == new.value and np.isfinite(new.value)
@@ -116,7 +95,7 @@ def test_one_level_through_the_new_entry_is_the_shipped_kernel(shape, roll, powe
 @pytest.mark.parametrize('shape,levels,power', [((3, 300, 520), 5, 1.5), ((3, 724, 1024), 3, 2)])
 def test_two_runs_are_bit_identical(shape, levels, power):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, 9)
+    img, g0 = swt_inputs(shape, 9)
     d_img = eng.to_device(img)
     runs = []
     for _ in range(2):
@@ -133,16 +112,16 @@ def test_two_runs_are_bit_identical(shape, levels, power):
 
 def test_level_counts_outside_the_range_are_refused():
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs((3, 37, 53), 1)                       # padded side 64: 1 to 6 levels
+    img, g0 = swt_inputs((3, 37, 53), 1)                       # padded side 64: 1 to 6 levels
     d_img, d_grad = eng.to_device(img), eng.to_device(g0)
     for levels in (0, 7, -2, 40):
         with pytest.raises(lib.StxError) as err:
-            _levels_call(eng, d_img, d_grad, levels, (0, 0), SCALE, 2)
+            swt_call(eng, d_img, d_grad, (0, 0), SCALE, 2, levels=levels)
         assert err.value.code != 0
         assert 'levels = %d' % levels in str(err.value) and 'padded side 64' in str(err.value)
     with pytest.raises(lib.StxError):
         image_ops.swt_haar(eng, d_img, d_grad, SCALE, 2, levels=7)
-    _levels_call(eng, d_img, d_grad, 6, (0, 0), SCALE, 2)
+    swt_call(eng, d_img, d_grad, (0, 0), SCALE, 2, levels=6)
     eng.sync()
     assert not np.array_equal(d_grad.get(), g0)
     d_img.free()

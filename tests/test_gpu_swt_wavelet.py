@@ -4,14 +4,12 @@ tests/swt_wavelet_ref.py, which tests/test_swt_wavelet_host.py holds to a band-b
 with factorised filters.  PyWavelets is in neither tree: no reference vectors exist, parity with it
 is unpinned as for Haar.  Tolerances are those of tests/test_gpu_swt_levels.py."""
 
-import ctypes
-
 import numpy as np
 import pytest
 
 from style_transfer_amd import image_ops, lib
 from tests import swt_wavelet_ref as ref
-from tests.gpu_helpers import gpu_engine
+from tests.gpu_helpers import gpu_engine, swt_call, swt_inputs, swt_rolled
 
 pytestmark = pytest.mark.gpu
 
@@ -65,38 +63,11 @@ CASES = [
 ]
 
 
-def _inputs(shape, seed):
-    rng = np.random.RandomState(seed)
-    img = rng.uniform(-120, 130, shape).astype(np.float32)
-    g0 = rng.standard_normal(shape).astype(np.float32)
-    return img, g0
-
-
-def _rolled(img, roll):
-    return np.roll(img, (roll[1], roll[0]), (1, 2)) / np.float32(127.5)        # roll = (x, y)
-
-
-def _daub_call(eng, d_img, d_grad, order, levels, roll, scale, power):
-    _, H, W = d_img.shape
-    out = eng.keep_until_sync(image_ops.PendingScalar())
-    lib.call('stx_image_swt_daub_levels', eng.handle, d_img.ptr, d_grad.ptr, H, W, order, levels,
-             (ctypes.c_int * 2)(*roll), float(scale), float(power), ctypes.byref(out._v))
-    return out
-
-
-def _haar_call(eng, d_img, d_grad, levels, roll, scale, power):
-    _, H, W = d_img.shape
-    out = eng.keep_until_sync(image_ops.PendingScalar())
-    lib.call('stx_image_swt_haar_levels', eng.handle, d_img.ptr, d_grad.ptr, H, W, levels,
-             (ctypes.c_int * 2)(*roll), float(scale), float(power), ctypes.byref(out._v))
-    return out
-
-
 @pytest.mark.parametrize('shape,order,levels,roll,power,seed', CASES)
 def test_swt_wavelet_against_restatement(shape, order, levels, roll, power, seed):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, seed)
-    rolled = _rolled(img, roll)
+    img, g0 = swt_inputs(shape, seed)
+    rolled = swt_rolled(img, roll)
     if power == 1:
         d = np.abs(ref.swt_wavelet_detail(rolled, order, levels))
         assert d.min() >= 1e-5 * d.max(), 'seed %d puts a pixel on the sign change' % seed
@@ -123,11 +94,11 @@ def test_swt_wavelet_against_restatement(shape, order, levels, roll, power, seed
                                                      ((3, 300, 520), 4, (16, 8), 1.5)])
 def test_order_one_is_the_haar_entry_bit_for_bit(shape, levels, roll, power):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, 3)
+    img, g0 = swt_inputs(shape, 3)
     d_img = eng.to_device(img)
     d_old, d_new, d_name = eng.to_device(g0), eng.to_device(g0), eng.to_device(g0)
-    old = _haar_call(eng, d_img, d_old, levels, roll, SCALE, power)
-    new = _daub_call(eng, d_img, d_new, 1, levels, roll, SCALE, power)
+    old = swt_call(eng, d_img, d_old, roll, SCALE, power, levels=levels)
+    new = swt_call(eng, d_img, d_new, roll, SCALE, power, levels=levels, order=1)
     named = image_ops.swt_wavelet(eng, d_img, d_name, SCALE, power, 'haar', levels=levels, roll=roll)
     eng.sync()
     assert np.array_equal(d_old.get(), d_new.get()) and np.array_equal(d_old.get(), d_name.get())
@@ -140,7 +111,7 @@ def test_order_one_is_the_haar_entry_bit_for_bit(shape, levels, roll, power):
 @pytest.mark.parametrize('shape,levels,power', [((3, 37, 53), 2, 1.5), ((3, 300, 520), 3, 2)])
 def test_sym4_is_db4_bit_for_bit(shape, levels, power):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, 4)
+    img, g0 = swt_inputs(shape, 4)
     d_img = eng.to_device(img)
     d_db, d_sym = eng.to_device(g0), eng.to_device(g0)
     db = image_ops.swt_wavelet(eng, d_img, d_db, SCALE, power, 'db4', levels=levels, roll=(-33, 14))
@@ -157,12 +128,12 @@ def test_sym4_is_db4_bit_for_bit(shape, levels, power):
                                                       ((3, 724, 1024), 8, 3, 2)])
 def test_two_runs_are_bit_identical(shape, order, levels, power):
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs(shape, 9)
+    img, g0 = swt_inputs(shape, 9)
     d_img = eng.to_device(img)
     runs = []
     for _ in range(2):
         d_grad = eng.to_device(g0)
-        out = _daub_call(eng, d_img, d_grad, order, levels, (-33, 14), SCALE, power)
+        out = swt_call(eng, d_img, d_grad, (-33, 14), SCALE, power, levels=levels, order=order)
         eng.sync()
         runs.append((out.value, d_grad.get()))
         d_grad.free()
@@ -174,16 +145,16 @@ def test_two_runs_are_bit_identical(shape, order, levels, power):
 
 def test_orders_and_level_counts_outside_the_range_are_refused():
     eng = gpu_engine('vgg19')
-    img, g0 = _inputs((3, 37, 53), 1)                       # padded side 64: 1 to 6 levels
+    img, g0 = swt_inputs((3, 37, 53), 1)                       # padded side 64: 1 to 6 levels
     d_img, d_grad = eng.to_device(img), eng.to_device(g0)
     for order in (0, 39, -1):
         with pytest.raises(lib.StxError) as err:
-            _daub_call(eng, d_img, d_grad, order, 2, (0, 0), SCALE, 2)
+            swt_call(eng, d_img, d_grad, (0, 0), SCALE, 2, levels=2, order=order)
         assert err.value.code == STX_ERR_ARG and 'order = %d' % order in str(err.value)
     for order in (1, 2, 38):
         for levels in (0, 7, -2, 40):
             with pytest.raises(lib.StxError) as err:
-                _daub_call(eng, d_img, d_grad, order, levels, (0, 0), SCALE, 2)
+                swt_call(eng, d_img, d_grad, (0, 0), SCALE, 2, levels=levels, order=order)
             assert err.value.code == STX_ERR_ARG
             assert 'levels = %d' % levels in str(err.value) and 'padded side 64' in str(err.value)
     with pytest.raises(ValueError):
@@ -192,7 +163,7 @@ def test_orders_and_level_counts_outside_the_range_are_refused():
         image_ops.swt_wavelet(eng, d_img, d_grad, SCALE, 2, 'coif1', levels=2)
     eng.sync()
     assert np.array_equal(d_grad.get(), g0)                 # nothing has run
-    _daub_call(eng, d_img, d_grad, 38, 6, (0, 0), SCALE, 2)
+    swt_call(eng, d_img, d_grad, (0, 0), SCALE, 2, levels=6, order=38)
     eng.sync()
     assert not np.array_equal(d_grad.get(), g0)
     d_img.free()
