@@ -366,6 +366,26 @@ int stx_image_step_stats_async(stx_engine *e, const float *avg, float *old, int 
 int stx_image_to_u8(stx_engine *e, const float *img, int H, int W, const float mean_bgr[3],
                     uint8_t *out_rgb_u8);
 
+/* Colour-preserving transfer (Gatys et al., "Preserving Color in Neural Artistic Style Transfer").
+ * Pictures are [3][H][W] float32 STX_DEVICE arrays in the network's input format: BGR planes with
+ * mean_bgr subtracted.
+ *   stx_image_to_u8_luma:   the luminance of img on the chroma of content.  Per pixel and channel
+ *                           x = clip(img + mean, 0, 255), c = clip(content + mean, 0, 255), Y(v) =
+ *                           0.299 v_R + 0.587 v_G + 0.114 v_B; out = uint8(clip(c + (Y(x) - Y(c)), 0,
+ *                           255)), RGB HWC and truncated like stx_image_to_u8 (which it equals when
+ *                           content == img).  One pass.
+ *   stx_image_color_stats:  out_host_sync = the three channel sums (b, g, r) and the six distinct
+ *                           second-moment sums (bb, bg, br, gg, gr, rr) of the stored values: float
+ *                           per-block partials added in double in a fixed order -- the same input
+ *                           gives the same nine doubles.  Synchronous, like stx_image_step_stats.
+ *   stx_image_color_affine: dst_i = clip(sum_j A[3 i + j] src_j + b[i] + mean[i], 0, 255) - mean[i];
+ *                           dst may be src.  A and b are used as float32.                          */
+int stx_image_to_u8_luma(stx_engine *e, const float *img, const float *content, int H, int W,
+                         const float mean_bgr[3], uint8_t *out_rgb_u8);
+int stx_image_color_stats(stx_engine *e, const float *img, int H, int W, double out_host_sync[9]);
+int stx_image_color_affine(stx_engine *e, const float *src, float *dst, int H, int W, const double A[9],
+                           const double b[3], const float mean_bgr[3]);
+
 /* ------------------------------------------------------------- single-kernel test hooks */
 /* Direct entry points to the individual kernels, used by tests/ to check each against the
  * oracle (x, w, b, y: STX_DEVICE).  w is the Caffe layout [Cout][Cin][k][k]. */

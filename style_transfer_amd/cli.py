@@ -14,7 +14,7 @@ import time
 import numpy as np
 from PIL import Image
 
-from . import fastpng, image_ops, lib
+from . import fastpng, lib
 from .config_system import parse_args
 from .farm import TileFarm
 from .netspec import load_net
@@ -96,7 +96,7 @@ class Progress:
         self.stats.update(update_size=update_size, loss=loss, tv_norm=tv_loss)
         if self.save_every and self.step % self.save_every == 0:
             # the pixels leave the GPU now; deflate and file I/O run beside the next steps
-            rgb = image_ops.to_u8(transfer.engine, transfer.current_raw, transfer.mean)
+            rgb = transfer.output_u8()
             self.writes = [w for w in self.writes if not w.done() or w.exception() is not None]
             while sum(not w.done() for w in self.writes) >= self.MAX_PENDING_WRITES:
                 next(w for w in self.writes if not w.done()).exception()     # (waits for it)
@@ -180,7 +180,7 @@ def main(argv=None):
     if transfer.current_raw is not None:
         path = args.output_image or run + '_out.png'
         print('Saving output as %s.' % path)
-        rgb = image_ops.to_u8(transfer.engine, transfer.current_raw, transfer.mean)
+        rgb = transfer.output_u8()
         comment = [('Comment', image_comment(args, argv))]
         if path.lower().endswith('.png'):
             # the reference's image.save(path, pnginfo=...) (style_transfer.py:1003-1010): same

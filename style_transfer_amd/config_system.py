@@ -98,12 +98,28 @@ _OPTIONS = [
 ]
 
 
+# Options the reference does not have.  The option namespace (and with it the PNG comment) holds the
+# reference's names and nothing else unless one of these is SET -- on the command line, in config.py
+# or in the --config file -- so they have no default there: read them with
+# getattr(args, name, <the default named in the help text>).
+_EXTENSIONS = [
+    (('--preserve-color',), dict(choices=['none', 'luma', 'match'],
+                                 help="keep the content picture's colours: 'luma' puts the luminance "
+                                      "of the result on the chroma of the content picture when a "
+                                      "picture is written, 'match' recolours every style picture to "
+                                      "the content picture's colour mean and covariance before its "
+                                      "Grams are taken (default: none)")),
+]
+
+
 def build_parser():
     parser = argparse.ArgumentParser(
         description='Tiled neural style transfer on AMD MI355X.',
         formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     for flags, kwargs in _OPTIONS:
         parser.add_argument(*flags, **kwargs)
+    for flags, kwargs in _EXTENSIONS:
+        parser.add_argument(*flags, default=argparse.SUPPRESS, **kwargs)
     return parser
 
 
@@ -168,7 +184,8 @@ def parse_args(state=None, argv=None, config_py=None):
         config_py = Path(__file__).resolve().parent.parent / 'config.py'
     if config_py and Path(config_py).exists():
         merged.update(eval_config(config_py))
-    merged.update({k: v for k, v in given.items() if defaults[k] != v})
+    # (an extension option is in `given` only when the command line names it, and never in `defaults`)
+    merged.update({k: v for k, v in given.items() if k not in defaults or defaults[k] != v})
     if given['config']:
         merged.update(eval_config(given['config']))
     args = LazyArgs(state, **merged)

@@ -508,5 +508,13 @@ int scale2_axpy_launch(hipStream_t s, float c1, float c2, float *sv, float *para
 int step_stats_launch(hipStream_t s, const float *avg, float *old, int H, int W,
                       double *out_dev /*[2]*/, float *scratch, size_t scratch_floats);
 int to_u8_launch(hipStream_t s, const float *img, int H, int W, const float mean[3], uint8_t *out);
+// --preserve-color: the luminance of img on the chroma of content as RGB HWC bytes; the nine colour sums
+// (b, g, r, bb, bg, br, gg, gr, rr) of img into out_dev; dst = clip(A src + b + mean, 0, 255) - mean
+int to_u8_luma_launch(hipStream_t s, const float *img, const float *content, int H, int W,
+                      const float mean[3], uint8_t *out);
+int color_stats_launch(hipStream_t s, const float *img, int H, int W, double *out_dev /*[9]*/,
+                       float *scratch, size_t scratch_floats);
+int color_affine_launch(hipStream_t s, const float *src, float *dst, int H, int W, const double A[9],
+                        const double b[3], const float mean[3]);
 
 }  // namespace stx

@@ -198,6 +198,7 @@ struct stx_engine {
     size_t fence_next = 0;
     size_t dscalars_cap = 64;
     DevBuf red_scratch;                // float partials for image-op reductions
+    DevBuf color_sums;                 // stx_image_color_stats: its nine sums (made at first use)
     DevBuf swt_scratch;                // stx_image_swt_haar_levels: row-filtered image + its partials
     struct SwtTable {                  // stx_image_swt_daub_levels: the taps of one (order, levels, N)
         int order, levels, N, ntaps, hl;
@@ -1092,7 +1093,7 @@ static int build_engine(int device, const stx_layer_desc *layers, int n_layers,
                               hipHostMallocDefault));
         STX_HIP(hipEventCreateWithFlags(&a.fence, hipEventDisableTiming));
     }
-    STX_TRY(e->red_scratch.ensure(4 * 1024 * sizeof(float)));
+    STX_TRY(e->red_scratch.ensure(9 * kBlocks * sizeof(float)));   // nine sums: stx_image_color_stats
     {
         std::lock_guard<std::mutex> lock(e->sh->mutex);
         e->sh->members.push_back(e.get());
@@ -1164,7 +1165,7 @@ void stx_engine_destroy(stx_engine *e) {
         for (auto &s : e->sh->styles) s.gram->release();
     }
     DevBuf *bufs[] = {&e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
-                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->first_gram};
+                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
     for (stx_engine::ScalarArena &a : e->arena) {
@@ -2236,6 +2237,32 @@ int stx_image_to_u8(stx_engine *e, const float *img, int H, int W, const float m
     if (!e || !img || !mean_bgr || !out_rgb_u8 || H <= 0 || W <= 0) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return to_u8_launch(e->stream, img, H, W, mean_bgr, out_rgb_u8);
+}
+
+int stx_image_to_u8_luma(stx_engine *e, const float *img, const float *content, int H, int W,
+                         const float mean_bgr[3], uint8_t *out_rgb_u8) {
+    if (!e || !img || !content || !mean_bgr || !out_rgb_u8 || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return to_u8_luma_launch(e->stream, img, content, H, W, mean_bgr, out_rgb_u8);
+}
+
+int stx_image_color_stats(stx_engine *e, const float *img, int H, int W, double out_host_sync[9]) {
+    if (!e || !img || !out_host_sync || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    STX_TRY(e->color_sums.ensure(9 * sizeof(double)));
+    double *dev = static_cast<double *>(e->color_sums.ptr);
+    STX_TRY(color_stats_launch(e->stream, img, H, W, dev, e->red_scratch.f(),
+                               e->red_scratch.bytes / sizeof(float)));
+    STX_HIP(hipMemcpyAsync(out_host_sync, dev, 9 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_image_color_affine(stx_engine *e, const float *src, float *dst, int H, int W, const double A[9],
+                           const double b[3], const float mean_bgr[3]) {
+    if (!e || !src || !dst || !A || !b || !mean_bgr || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return color_affine_launch(e->stream, src, dst, H, W, A, b, mean_bgr);
 }
 
 // --------------------------------------------------------------------------- test hooks

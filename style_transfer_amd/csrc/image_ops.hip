@@ -654,4 +654,194 @@ int to_u8_launch(hipStream_t s, const float *img, int H, int W, const float mean
     return STX_OK;
 }
 
+// ------------------------------------------------------------------------- colour preservation ---
+// --preserve-color (Gatys et al., "Preserving Color in Neural Artistic Style Transfer"): the
+// luminance-only output, the colour statistics of a picture and the affine recolouring that
+// matches them.  Pictures are [3][H][W] BGR planes with mean_bgr subtracted.  All three kernels
+// stream: a thread takes four neighbouring pixels of each plane per trip, as one 16-byte load per
+// plane where the plane size and the bases allow (VEC), element by element with a bounds check
+// otherwise (pixels past the end read as zero and are not written).
+template <bool VEC>
+__device__ __forceinline__ void load_px4(const float *plane_base, size_t p, size_t plane, float (&v)[4]) {
+    if (VEC) {
+        const f32x4_t q = *reinterpret_cast<const f32x4_t *>(plane_base + p);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = p + k < plane ? plane_base[p + k] : 0.f;
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void store_px4(float *plane_base, size_t p, size_t plane, const float (&v)[4]) {
+    if (VEC) {
+        f32x4_t q;
+        q.x = v[0], q.y = v[1], q.z = v[2], q.w = v[3];
+        *reinterpret_cast<f32x4_t *>(plane_base + p) = q;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (p + k < plane) plane_base[p + k] = v[k];
+    }
+}
+static bool px4_vec(size_t plane, const void *a, const void *b) {
+    return plane % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+static int px4_blocks(size_t groups) { return (int)std::min<size_t>((groups + 255) / 256, 8192); }
+
+__device__ __forceinline__ float clip255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
+__device__ __forceinline__ float luma601(float r, float g, float b) {
+    return 0.299f * r + 0.587f * g + 0.114f * b;
+}
+
+// out = uint8(clip(c + (Y(x) - Y(c)), 0, 255)), x = clip(img + mean), c = clip(content + mean): the
+// luminance of the result on the chroma of the content picture (adding the luminance difference to
+// all three channels is that, in any linear luma / chroma space).  RGB HWC like to_u8_kernel; the
+// twelve bytes of four pixels leave as three dwords (DW: `out` is dword-aligned).
+template <bool VEC, bool DW>
+__global__ __launch_bounds__(256) void to_u8_luma_kernel(const float *__restrict__ img,
+                                                         const float *__restrict__ content, size_t plane,
+                                                         float m0, float m1, float m2,
+                                                         uint8_t *__restrict__ out) {
+    const size_t groups = (plane + 3) / 4;
+    for (size_t gi = blockIdx.x * (size_t)256 + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * 256) {
+        const size_t p = 4 * gi;
+        float xb[4], xg[4], xr[4], cb[4], cg[4], cr[4];
+        load_px4<VEC>(img, p, plane, xb);
+        load_px4<VEC>(img + plane, p, plane, xg);
+        load_px4<VEC>(img + 2 * plane, p, plane, xr);
+        load_px4<VEC>(content, p, plane, cb);
+        load_px4<VEC>(content + plane, p, plane, cg);
+        load_px4<VEC>(content + 2 * plane, p, plane, cr);
+        uint8_t px[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float b = clip255(cb[k] + m0), g = clip255(cg[k] + m1), r = clip255(cr[k] + m2);
+            const float d = luma601(clip255(xr[k] + m2), clip255(xg[k] + m1), clip255(xb[k] + m0)) -
+                            luma601(r, g, b);
+            px[3 * k + 0] = (uint8_t)clip255(r + d);     // truncation toward zero, like to_u8_kernel
+            px[3 * k + 1] = (uint8_t)clip255(g + d);
+            px[3 * k + 2] = (uint8_t)clip255(b + d);
+        }
+        if (DW && (VEC || p + 4 <= plane)) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(out) + 3 * gi;
+#pragma unroll
+            for (int w = 0; w < 3; ++w)
+                o[w] = (uint32_t)px[4 * w] | (uint32_t)px[4 * w + 1] << 8 | (uint32_t)px[4 * w + 2] << 16 |
+                       (uint32_t)px[4 * w + 3] << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k)
+                if (p + k / 3 < plane) out[3 * p + k] = px[k];
+        }
+    }
+}
+
+int to_u8_luma_launch(hipStream_t s, const float *img, const float *content, int H, int W,
+                      const float mean[3], uint8_t *out) {
+    const size_t plane = (size_t)H * W;
+    const int blocks = px4_blocks((plane + 3) / 4);
+    const bool vec = px4_vec(plane, img, content), dw = (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+#define STX_LUMA(V, D) \
+    to_u8_luma_kernel<V, D><<<blocks, 256, 0, s>>>(img, content, plane, mean[0], mean[1], mean[2], out)
+    if (vec && dw) STX_LUMA(true, true);
+    else if (vec) STX_LUMA(true, false);
+    else if (dw) STX_LUMA(false, true);
+    else STX_LUMA(false, false);
+#undef STX_LUMA
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+// The three channel sums and the six distinct second-moment sums (bb, bg, br, gg, gr, rr) of the
+// stored values: float per-block partials, finished in double in a fixed order.
+template <bool VEC>
+__global__ __launch_bounds__(256) void color_stats_kernel(const float *__restrict__ img, size_t plane,
+                                                          float *__restrict__ partials) {
+    const size_t groups = (plane + 3) / 4;
+    float sums[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (size_t gi = blockIdx.x * (size_t)256 + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * 256) {
+        const size_t p = 4 * gi;
+        float b[4], g[4], r[4];
+        load_px4<VEC>(img, p, plane, b);
+        load_px4<VEC>(img + plane, p, plane, g);
+        load_px4<VEC>(img + 2 * plane, p, plane, r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            sums[0] += b[k];
+            sums[1] += g[k];
+            sums[2] += r[k];
+            sums[3] += b[k] * b[k];
+            sums[4] += b[k] * g[k];
+            sums[5] += b[k] * r[k];
+            sums[6] += g[k] * g[k];
+            sums[7] += g[k] * r[k];
+            sums[8] += r[k] * r[k];
+        }
+    }
+    block_partials<9>(sums, partials);
+}
+
+int color_stats_launch(hipStream_t s, const float *img, int H, int W, double *out_dev, float *scratch,
+                       size_t scratch_floats) {
+    const size_t plane = (size_t)H * W;
+    const int blocks = blocks_for((plane + 3) / 4);
+    if (scratch_floats < (size_t)9 * blocks) {
+        set_error("color_stats: scratch too small");
+        return STX_ERR_STATE;
+    }
+    if (px4_vec(plane, img, img))
+        color_stats_kernel<true><<<blocks, 256, 0, s>>>(img, plane, scratch);
+    else
+        color_stats_kernel<false><<<blocks, 256, 0, s>>>(img, plane, scratch);
+    STX_CHECK_LAUNCH();
+    finish_partials_kernel<9><<<1, 256, 0, s>>>(scratch, blocks, out_dev);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+// dst_i = clip(sum_j A[i][j] src_j + c_i, 0, 255) - mean_i with c_i = b_i + mean_i; dst may be src
+// (a thread reads the three channels of its pixels before it writes them).
+struct ColorAffine {
+    float A[9], c[3], mean[3];
+};
+template <bool VEC>
+__global__ __launch_bounds__(256) void color_affine_kernel(const float *src, float *dst, size_t plane,
+                                                           ColorAffine t) {
+    const size_t groups = (plane + 3) / 4;
+    for (size_t gi = blockIdx.x * (size_t)256 + threadIdx.x; gi < groups; gi += (size_t)gridDim.x * 256) {
+        const size_t p = 4 * gi;
+        float v[3][4], o[4];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) load_px4<VEC>(src + j * plane, p, plane, v[j]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float a = fmaf(t.A[3 * i + 2], v[2][k],
+                                     fmaf(t.A[3 * i + 1], v[1][k], fmaf(t.A[3 * i], v[0][k], t.c[i])));
+                o[k] = clip255(a) - t.mean[i];
+            }
+            store_px4<VEC>(dst + i * plane, p, plane, o);
+        }
+    }
+}
+
+int color_affine_launch(hipStream_t s, const float *src, float *dst, int H, int W, const double A[9],
+                        const double b[3], const float mean[3]) {
+    const size_t plane = (size_t)H * W;
+    ColorAffine t;
+    for (int i = 0; i < 9; ++i) t.A[i] = (float)A[i];
+    for (int i = 0; i < 3; ++i) {
+        t.c[i] = (float)(b[i] + (double)mean[i]);
+        t.mean[i] = mean[i];
+    }
+    const int blocks = px4_blocks((plane + 3) / 4);
+    if (px4_vec(plane, src, dst))
+        color_affine_kernel<true><<<blocks, 256, 0, s>>>(src, dst, plane, t);
+    else
+        color_affine_kernel<false><<<blocks, 256, 0, s>>>(src, dst, plane, t);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
 }  // namespace stx

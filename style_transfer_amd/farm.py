@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import image_ops
-from .engine import TileEngine
+from .engine import DeviceArray, TileEngine
 
 
 def tile_grid(img_hw, tile_size):
@@ -235,13 +235,18 @@ class TileFarm:
         which is the reference's roll-accumulate-unroll of the accumulator, bit for bit).
         Returns {layer: DeviceArray}.  Same RNG draws as the reference.  ``roll``: the maps of
         roll2(img, roll) instead (preprocess_images(..., roll=xy) of the reference's --jitter
-        mode, style_transfer.py:789-794); the result stays in that rolled frame."""
+        mode, style_transfer.py:789-794); the result stays in that rolled frame.  ``img`` may be a
+        DeviceArray on the master GPU already: it is read where it is and stays the caller's."""
         eng = self.master
-        img = np.ascontiguousarray(img, np.float32)
+        on_device = isinstance(img, DeviceArray)
+        if on_device:
+            assert img.engine is eng and img.dtype == np.float32, 'a float32 picture on the master GPU'
+        else:
+            img = np.ascontiguousarray(img, np.float32)
         hw = np.array(img.shape[-2:])
         if max(hw) <= tile_size:
             passes = 1
-        d_img = eng.to_device(img)
+        d_img = img if on_device else eng.to_device(img)
         rects = tile_grid(hw, tile_size)
         if len(rects) > 1 and self.verbose:
             nx = (hw[1] - 1) // tile_size + 1
@@ -281,7 +286,7 @@ class TileFarm:
         for bufs in list(tile_feats.values()):
             for b in bufs.values():
                 b.free()
-        for b in list(tiles.values()) + list(full.values()) + [d_img]:
+        for b in list(tiles.values()) + list(full.values()) + ([] if on_device else [d_img]):
             b.free()
         return acc
 

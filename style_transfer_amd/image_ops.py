@@ -243,3 +243,67 @@ def to_u8(engine, img, mean_bgr):
     host = out.get()
     out.free()
     return host
+
+
+# ---------------------------------------------------------------------- --preserve-color
+def _mean3(mean_bgr):
+    return (ctypes.c_float * 3)(*[float(m) for m in np.ravel(mean_bgr)])
+
+
+def to_u8_luma(engine, img, content, mean_bgr):
+    """RGB HWC uint8 ndarray with the luminance of ``img`` and the chroma of ``content`` (both
+    [3,H,W] on the engine's GPU): clip(c + (Y(x) - Y(c)), 0, 255) truncated, where x and c are the
+    two pictures with the mean added and clipped and Y is the Rec. 601 luma."""
+    _, H, W = img.shape
+    assert content.shape == img.shape, (content.shape, img.shape)
+    out = engine.empty((H, W, 3), np.uint8)
+    lib.call('stx_image_to_u8_luma', engine.handle, img.ptr, content.ptr, H, W, _mean3(mean_bgr),
+             out.ptr)
+    host = out.get()
+    out.free()
+    return host
+
+
+def color_stats(engine, img):
+    """(mean[3], cov[3,3]) in float64 of the stored BGR values of a device picture [3,H,W], from the
+    nine sums of stx_image_color_stats (the covariance is the population one)."""
+    _, H, W = img.shape
+    raw = (ctypes.c_double * 9)()
+    lib.call('stx_image_color_stats', engine.handle, img.ptr, H, W, raw)
+    n = float(H) * W
+    mean = np.array(raw[:3], np.float64) / n
+    second = np.empty((3, 3), np.float64)
+    for k, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        second[i, j] = second[j, i] = raw[3 + k] / n
+    return mean, second - np.outer(mean, mean)
+
+
+def color_affine(engine, src, dst, A, b, mean_bgr):
+    """dst = clip(A src + b + mean, 0, 255) - mean per pixel (A [3,3], b [3] over the BGR channels,
+    used as float32); ``dst`` may be ``src``."""
+    _, H, W = src.shape
+    assert dst.shape == src.shape, (dst.shape, src.shape)
+    A = np.ascontiguousarray(A, np.float64).reshape(9)
+    b = np.ascontiguousarray(b, np.float64).reshape(3)
+    lib.call('stx_image_color_affine', engine.handle, src.ptr, dst.ptr, H, W,
+             A.ctypes.data_as(lib.c_double_p), b.ctypes.data_as(lib.c_double_p), _mean3(mean_bgr))
+    return dst
+
+
+def _sym_power(cov, power):
+    """cov^power of a symmetric positive semi-definite matrix; eigenvalues are floored at 1e-8 of
+    the trace, so that a flat-colour picture does not divide by zero."""
+    w, v = np.linalg.eigh(np.asarray(cov, np.float64))
+    trace = float(np.trace(cov))
+    w = np.maximum(w, 1e-8 * trace if trace > 0 else 1.0)
+    return (v * w ** power) @ v.T
+
+
+def color_match_transform(stats_style, stats_content):
+    """(A, b) of the affine colour map that gives a picture with statistics ``stats_style`` =
+    (mean, cov) those of ``stats_content``: A = cov_c^(1/2) cov_s^(-1/2), b = mean_c - A mean_s
+    (symmetric square roots, float64)."""
+    mean_s, cov_s = stats_style
+    mean_c, cov_c = stats_content
+    A = _sym_power(cov_c, 0.5) @ _sym_power(cov_s, -0.5)
+    return A, np.asarray(mean_c, np.float64) - A @ np.asarray(mean_s, np.float64)

@@ -108,6 +108,9 @@ SIGNATURES = {
     'stx_image_step_stats': [_vp, _vp, _vp, _i, _i, c_double_p],
     'stx_image_step_stats_async': [_vp, _vp, _vp, _i, _i, c_double_p],
     'stx_image_to_u8': [_vp, _vp, _i, _i, c_float_p, _vp],
+    'stx_image_to_u8_luma': [_vp, _vp, _vp, _i, _i, c_float_p, _vp],
+    'stx_image_color_stats': [_vp, _vp, _i, _i, c_double_p],
+    'stx_image_color_affine': [_vp, _vp, _vp, _i, _i, c_double_p, c_double_p, c_float_p],
     'stx_op_conv_forward': [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp],
     'stx_op_conv_backward_data': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp],
     'stx_op_pool_forward': [_vp, _vp, _i, _i, _i, _i, _vp],

@@ -108,6 +108,9 @@ def style_pyramid(args):
         sizes.append(nxt)
 
 
+PRESERVE_COLOR = ('none', 'luma', 'match')
+
+
 def parse_weights(args, master_weight):
     """['name', 'name:2', ...] -> (names, {name: weight normalised to sum |w| = master})
     (style_transfer.py:684-698)."""
@@ -146,6 +149,15 @@ class StyleTransfer:
         # calls made to the callback object at hand (transfer's run-ahead loop asks it about its n-th call)
         self._cb_calls = [None, 0]
         self._converted = {}        # id(PIL image) -> (image, float array), filled by the helper thread
+        # --preserve-color (not an option of the reference: absent from the namespace unless set).
+        # 'luma': pictures are written with the luminance of the iterate on the chroma of this scale's
+        # first content picture, kept on the master GPU; 'match': the style pictures are recoloured
+        # to that picture's colour statistics before their Grams are taken.  Neither changes a step.
+        self.preserve_color = str(getattr(args, 'preserve_color', 'none'))
+        if self.preserve_color not in PRESERVE_COLOR:
+            raise ValueError('--preserve-color %s: one of %s' % (self.preserve_color,
+                                                                 ', '.join(PRESERVE_COLOR)))
+        self._luma_content = None   # DeviceArray [3,H,W] ('luma' only)
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
         # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
@@ -174,8 +186,19 @@ class StyleTransfer:
 
     def get_image(self, params=None):
         """PIL image of a device iterate (style_transfer.py:378-386)."""
+        return Image.fromarray(self.output_u8(params))
+
+    def output_u8(self, params=None):
+        """RGB HWC uint8 array of a device iterate (default: the current one), as every picture of
+        the run is written: under --preserve-color luma with the content picture's chroma."""
         params = self.current_raw if params is None else params
-        return Image.fromarray(image_ops.to_u8(self.engine, params, self.mean))
+        if self.preserve_color == 'luma':
+            if self._luma_content is None or self._luma_content.shape != params.shape:
+                raise ValueError('--preserve-color luma: no content picture of size %dx%d is kept '
+                                 '(pictures are written at the size of the scale being optimised)'
+                                 % (params.shape[2], params.shape[1]))
+            return image_ops.to_u8_luma(self.engine, params, self._luma_content, self.mean)
+        return image_ops.to_u8(self.engine, params, self.mean)
 
     @property
     def current_output(self):
@@ -198,21 +221,40 @@ class StyleTransfer:
             if last:
                 return
 
+    def _recolored(self, picture, target):
+        """The host picture [3,H,W] on the master GPU with its colours mapped towards ``target`` =
+        (mean, cov) (--preserve-color match): uploaded, measured, transformed in place."""
+        dev = self.engine.to_device(picture)
+        A, b = image_ops.color_match_transform(image_ops.color_stats(self.engine, dev), target)
+        return image_ops.color_affine(self.engine, dev, dev, A, b, self.mean)
+
     def preprocess_images(self, content_images, style_images, content_layers, style_layers,
-                          roll=None):
+                          roll=None, color_from=None):
         """Targets of one scale: the style Grams, averaged with equal weight over every style
         image and ladder size, and the tiling-averaged content features
         (style_transfer.py:488-554).  Everything stays on the master GPU.  ``roll`` (--jitter,
-        once per iteration): features of the pictures rolled by it, one pass, no messages."""
+        once per iteration): features of the pictures rolled by it, one pass, no messages.
+        ``color_from`` (--preserve-color match): every style variant is recoloured on the GPU to the
+        colour mean and covariance of this picture before its features are taken."""
         farm, tile = self.farm, self.args.tile_size
         if roll is None:
             print('Preprocessing the style image(s)...')
         if not self.styles:
             total, count = {}, 0
+            target = None
+            if color_from is not None and style_images:
+                kept = self.engine.to_device(self.pil_to_image(color_from))
+                target = image_ops.color_stats(self.engine, kept)
+                kept.free()
             for index, image in enumerate(style_images):
                 for variant in self._style_variants(index, image):
-                    feats = farm.prepare_features_device(self.pil_to_image(variant), style_layers,
-                                                         tile, passes=1, roll=roll)
+                    picture = self.pil_to_image(variant)
+                    if target is not None:
+                        picture = self._recolored(picture, target)
+                    feats = farm.prepare_features_device(picture, style_layers, tile, passes=1,
+                                                         roll=roll)
+                    if target is not None:
+                        picture.free()
                     for layer, feat in feats.items():
                         gram = farm.gram_matrix(feat)
                         feat.free()
@@ -290,8 +332,13 @@ class StyleTransfer:
             self.styles = []
         # --jitter: the content maps are recomputed every iteration from the shifted picture
         # (style_transfer.py:757-763,789-794), only the style targets are fixed per scale
+        if self.preserve_color == 'luma':
+            if self._luma_content is not None:
+                self._luma_content.free()
+            self._luma_content = self.engine.to_device(self.pil_to_image(content_images[0]))
         self.preprocess_images([] if jitter else content_images, style_images,
-                               [] if jitter else content_layers, style_layers)
+                               [] if jitter else content_layers, style_layers,
+                               color_from=content_images[0] if self.preserve_color == 'match' else None)
         self.farm.set_contents_and_styles(self.contents, self.styles)
 
         if self.grad is None or self.grad.shape != self.img.shape:
