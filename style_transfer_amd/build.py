@@ -32,6 +32,9 @@ SOURCES = {
     'swt.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
+    'tile_path.cpp': [],
+    'image_api.cpp': [],
+    'op_hooks.cpp': [],
 }
 EXTRA = os.environ.get('STX_HIPCC_EXTRA', '').split()
 COMMON = EXTRA + ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-I' + INCLUDE, '-I' + CSRC,
@@ -49,7 +52,7 @@ def _compile(src, extra, force):
     obj = os.path.join(CSRC, os.path.splitext(src)[0] + '.o')
     path = os.path.join(CSRC, src)
     deps = [path, os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'bf16x3.h'),
-            os.path.join(CSRC, 'f16x2.h'), os.path.join(INCLUDE, 'stx.h')]
+            os.path.join(CSRC, 'f16x2.h'), os.path.join(CSRC, 'engine.h'), os.path.join(INCLUDE, 'stx.h')]
     if force or _stale(obj, deps):
         cmd = [HIPCC] + COMMON + extra + ['-c', path, '-o', obj]
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

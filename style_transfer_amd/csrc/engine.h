@@ -1,0 +1,276 @@
+// The engine's state and the few helpers that more than one host file uses.  Internal: not installed.
+//   engine.cpp     engine life cycle, weights and targets, scalar arenas and fences, profiling readers
+//   tile_path.cpp  the tile evaluation: forward pass, loss terms, backward walk
+//   image_api.cpp  whole-image and vector entries, the SWT regulariser's tables
+//   op_hooks.cpp   stx_op_*: single operators for the tests
+#pragma once
+
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+namespace stx {
+
+// Growable device buffer.  Growth frees and reallocates (hipFree synchronises the device, so
+// kernels still reading the old allocation have finished); it happens only when a larger tile
+// than ever before arrives.
+struct DevBuf {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    int ensure(size_t need) {
+        if (need <= bytes) return STX_OK;
+        if (ptr) STX_HIP(hipFree(ptr));
+        ptr = nullptr;
+        bytes = 0;
+        const size_t want = (need + 255) & ~(size_t)255;
+        hipError_t err = hipMalloc(&ptr, want);
+        if (err != hipSuccess) {
+            set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(err));
+            ptr = nullptr;
+            return STX_ERR_NOMEM;
+        }
+        bytes = want;
+        return STX_OK;
+    }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    float *f() const { return static_cast<float *>(ptr); }
+};
+
+struct Layer {
+    std::string name, bottom, top;
+    int type = 0, num_output = 0, ksize = 0, pad = 0, stride = 1, pool_mode = 0;
+    int bottom_blob = -1, top_blob = -1;
+};
+
+struct Blob {
+    std::string name;
+    int channels = 0;
+    int producer = -1;   // layer index that writes it (conv / pool / input)
+    bool relu = false;   // an in-place ReLU layer follows the producer
+    int scale = 1;       // 224 // height at a 224 input (CaffeModel.layer_info, style_transfer.py:415-419)
+    int h = 0, w = 0;    // current tile
+    DevBuf data, diff;
+    DevBuf codes;             // pooled blobs: one window code per element (pool.hip), written by the
+    bool codes_valid = false; // forward pass that produced `data` if its kernel can
+    DevBuf relu_codes;        // rectified blobs: sign nibbles per 2x2 window (ConvProblem::out_codes / in_codes),
+    bool relu_codes_valid = false;   // written by the convolution that produces the blob, or by the one that reads it
+    bool relu_codes_wanted = false;  // ... or would have been, had its kernel taken them (ConvProblem::wants_codes)
+    // max |data| / max |diff| (or an upper bound of it) on the device, for the fp16-split convolution
+    // that reads the blob (conv_h2.hip): the slot group (a blob index) of the engine's table that
+    // holds it -- the blob's own when its producer tracked it, the blob's below / above when a
+    // pooling layer passed the bound on -- or -1 when nobody has left one in this pass
+    int amax_data = -1, amax_diff = -1;
+    size_t count() const { return (size_t)channels * h * w; }
+};
+
+struct ConvParams {
+    int cin = 0, cout = 0, ks = 0;
+    DevBuf w, b;                              // Caffe layout on the device
+    bool set = false;
+    std::map<int, std::unique_ptr<DevBuf>> packed;  // key: ConvBank::key
+};
+
+struct ContentTarget {
+    int index, blob, C, h, w;
+    std::unique_ptr<DevBuf> feat;
+};
+
+struct StyleTarget {
+    int index, blob, C;
+    std::unique_ptr<DevBuf> gram;
+};
+
+struct LossTerm {
+    size_t scalar_index;   // float in the host mirror of the scalar buffer
+    double coef;
+};
+
+struct PendingLoss {
+    double *out;
+    std::vector<LossTerm> terms;       // sum coef * scalar
+    std::vector<LossTerm> dterms;      // sum coef * double scalar (image ops)
+};
+
+// What the engines of one GPU have in common: the network's weights, the banks packed for the
+// kernels and the current targets.  A farm runs several engines (HIP streams + activation
+// buffers) per GPU; each holding its own copy cost 4 x (80 MB of weights + ~200 MB of packed
+// banks + the per-scale content maps: 537 MB at 4096^2) per GPU and as many uploads over xGMI.
+struct SharedState {
+    std::map<int, ConvParams> conv;    // layer index -> params
+    std::vector<ContentTarget> contents;
+    std::vector<StyleTarget> styles;
+    int n_contents = 0, n_styles = 0;
+    std::vector<stx_engine *> members;
+    std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
+    size_t target_uploads = 0;         // stx_set_contents_and_styles calls that copied data
+    double target_bytes = 0;           // bytes those calls copied (cumulative)
+};
+
+}  // namespace stx
+
+using namespace stx;   // (an internal header: every file that includes it is the library's own host code)
+
+struct stx_engine {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool clock_marks = false;              // stx_clock_marks: one mark per 2-D Winograd launch
+    DevBuf marks_buf;
+    int marks_used = 0, last_mark = -1;    // (last_mark: the slot of the launch just queued, or -1)
+    std::vector<std::unique_ptr<DevBuf>> sgrad_tap;   // S = sym(D) F of every style tap
+    // start / stop of the last few tile calls (a ring: stx_last_tile_ms reports the newest call
+    // that has finished, so a host that runs ahead does not wait for the call it just queued)
+    static constexpr int kTimed = 4;
+    hipEvent_t ev_start[kTimed] = {}, ev_stop[kTimed] = {};
+    int ev_cur = 0;
+    int ev_recorded = 0;               // ring slots that hold a recorded pair (at most kTimed)
+    hipEvent_t ev_tune0 = nullptr, ev_tune1 = nullptr;
+    bool timed = false;
+    double flop_algorithmic = 0, flop_issued = 0;   // matrix work of the current / last tile call
+    std::vector<Layer> layers;
+    std::vector<Blob> blobs;
+    std::map<std::string, int> blob_index, layer_index;
+    std::shared_ptr<SharedState> sh;   // weights, packed banks, targets (shared per GPU)
+
+    DevBuf splitk;                     // split-K partial sums of small-plane convolutions
+    DevBuf amax;                       // [data | diff][blob][kAmaxSlots] words of float bits (Blob::amax_data)
+    unsigned *amax_slots(int blob, bool diff) const {
+        return static_cast<unsigned *>(amax.ptr) + ((size_t)(diff ? blobs.size() : 0) + blob) * kAmaxSlots;
+    }
+    int amax_ensure() {     // (+ 2: the scratch groups behind the blobs' own, see amax_scratch)
+        return amax.ensure((2 * blobs.size() + 2) * kAmaxSlots * sizeof(unsigned));
+    }
+    // the first layer leaves the Gram partials of its own output when that blob is a style tap of
+    // the call (conv_first.hip): which blob, whether this call's forward pass wrote them, how many
+    DevBuf first_gram;
+    int first_gram_blob = -1, first_gram_parts = 0;
+    bool first_gram_valid = false;
+    DevBuf gram_partials, gram, dsym, dsym_pieces, symm_partials, upload;
+    DevBuf term_scratch;               // per style term of a tile call: block sums / maxima + SYMM partials (sum jobs)
+    // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
+    // reductions), each with a pinned host mirror, and the losses that will be published from
+    // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
+    // that a step loop can queue iteration i + 1 before it waits (stx_fence_wait) for the
+    // scalars of iteration i -- the host runs one iteration ahead of the GPU instead of letting
+    // it idle while the statistics of a step travel home.
+    struct ScalarArena {
+        DevBuf scalars;                    // device floats
+        float *host = nullptr;             // pinned mirror
+        size_t used = 0;
+        DevBuf dscalars;                   // device doubles (image-op reductions)
+        double *dhost = nullptr;
+        size_t dused = 0;
+        std::vector<PendingLoss> pending;
+        hipEvent_t fence = nullptr;
+        unsigned long long ticket = 0;     // 0: open; else closed by stx_fence and not yet published
+    };
+    ScalarArena arena[2];
+    int cur = 0;
+    unsigned long long next_ticket = 1;
+    ScalarArena &A() { return arena[cur]; }
+    size_t scalars_cap = 0;
+    size_t n_tile_evals = 0;               // stx_sc_grad_tile calls (STX_Q_TILE_EVALS)
+    std::vector<hipEvent_t> fence_events;     // stx_engine_wait: ring of events recorded on this stream
+    size_t fence_next = 0;
+    size_t dscalars_cap = 64;
+    DevBuf red_scratch;                // float partials for image-op reductions
+    DevBuf color_sums;                 // stx_image_color_stats: its nine sums (made at first use)
+    DevBuf swt_scratch;                // stx_image_swt_haar_levels: row-filtered image + its partials
+    struct SwtTable {                  // stx_image_swt_daub_levels: the taps of one (order, levels, N)
+        int order, levels, N, ntaps, hl;
+        DevBuf taps;
+    };
+    std::vector<SwtTable> swt_tables;  // built at first use, kept: a step uploads nothing
+
+    bool winograd = true;   // 1-D Winograd F(2,3) for the 3x3 layers (STX_WINOGRAD=0: direct only)
+    bool autotune = true;   // tile-config autotuning (process-wide cache, see conv_choose)
+    bool pool_codes = true; // forward pooling leaves window codes for the backward pass (STX_POOL_CODES=0: off)
+
+    // optional per-kernel-group timing (stx_profile_enable): event pairs around launch groups
+    bool profiling = false;
+    struct ProfEntry {
+        std::string label;
+        double flops;
+        hipEvent_t start, stop;
+        int mark = -1;      // clock mark of the group's convolution launch (stx_clock_marks), or -1
+    };
+    std::vector<ProfEntry> prof;
+    std::vector<hipEvent_t> event_pool;
+
+    int set_device() {
+        STX_HIP(hipSetDevice(device));
+        return STX_OK;
+    }
+    int find_blob(const char *name) const {
+        if (!name) return -1;
+        auto it = blob_index.find(name);
+        return it == blob_index.end() ? -1 : it->second;
+    }
+};
+
+namespace stx {
+#pragma GCC visibility push(hidden)     // what follows is internal to the library: not exported
+
+// RAII timing of one launch group when profiling is on (no-op otherwise).
+struct ProfScope {
+    stx_engine *e;
+    int index = -1;
+    hipStream_t stream;
+    ProfScope(stx_engine *eng, const std::string &label, double flops, hipStream_t on = nullptr)
+        : e(eng), stream(on ? on : eng->stream) {
+        if (!e->profiling) return;
+        auto take = [&]() {
+            hipEvent_t ev = nullptr;
+            if (!e->event_pool.empty()) {
+                ev = e->event_pool.back();
+                e->event_pool.pop_back();
+            } else if (hipEventCreate(&ev) != hipSuccess) {
+                ev = nullptr;
+            }
+            return ev;
+        };
+        stx_engine::ProfEntry pe{label, flops, take(), take()};
+        if (!pe.start || !pe.stop) return;
+        (void)hipEventRecord(pe.start, stream);
+        e->prof.push_back(pe);
+        index = (int)e->prof.size() - 1;
+    }
+    ~ProfScope() {
+        if (index < 0) return;
+        (void)hipEventRecord(e->prof[index].stop, stream);
+        e->prof[index].mark = e->last_mark;
+        e->last_mark = -1;
+    }
+};
+
+constexpr int kMaxClockMarks = 16384;   // stx_clock_marks: launches that can leave a mark between two reads
+
+// ---- helpers that more than one host file uses
+// engine.cpp
+int alloc_scalars(stx_engine *e, size_t n, size_t *index);
+int alloc_dscalars(stx_engine *e, size_t n, size_t *index);
+int copy_in(stx_engine *e, void *dst, const void *src, int mem, size_t bytes);
+int copy_out(stx_engine *e, void *dst, int mem, const void *src, size_t bytes);
+int do_sync(stx_engine *e);
+// tile_path.cpp
+ConvProblem conv_fwd_problem(const float *x, float *y, const float *bias, int Cin, int Cout, int H, int W,
+                             int ks, int relu);
+ConvProblem conv_bwd_problem(const float *dy, float *dx, const float *mask, int Cout, int Cin, int H, int W,
+                             int ks);
+int attach_splitk(stx_engine *e, const ConvConfig &cfg, ConvProblem &p);
+int launch_conv(stx_engine *e, const ConvConfig &cfg, const ConvProblem &problem);
+int amax_scratch(stx_engine *e, unsigned **out);
+int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                       const float *target, float *sgrad, float *sc, const std::string &name,
+                       const unsigned *f_amax = nullptr, float *term_scratch = nullptr,
+                       std::vector<SumJob> *defer = nullptr);
+#pragma GCC visibility pop
+
+}  // namespace stx

@@ -1,0 +1,389 @@
+// libstx host side: the entries that work on whole images, feature maps and parameter vectors
+// (stx_image_*, stx_map_*, stx_vec_*, stx_adam_step) -- thin wrappers that check their arguments and
+// queue one or two launches of image_ops.hip / reduce.hip / swt.hip on the engine's stream.
+
+#include <cmath>
+#include <functional>
+#include <initializer_list>
+
+#include "engine.h"
+
+extern "C" {
+
+int stx_image_cut_tile(stx_engine *e, const float *img, int H, int W, const int roll_xy[2], int y0,
+                       int x0, int th, int tw, float *tile) {
+    if (!e || !img || !tile || H <= 0 || W <= 0 || th <= 0 || tw <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return cut_tile_launch(e->stream, img, H, W, roll_xy ? roll_xy[0] : 0, roll_xy ? roll_xy[1] : 0,
+                           y0, x0, th, tw, tile);
+}
+
+int stx_image_put_tile(stx_engine *e, float *grad, int H, int W, const int roll_xy[2], int y0,
+                       int x0, int th, int tw, const float *tile_grad) {
+    if (!e || !grad || !tile_grad || H <= 0 || W <= 0 || th <= 0 || tw <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return put_tile_launch(e->stream, grad, H, W, roll_xy ? roll_xy[0] : 0,
+                           roll_xy ? roll_xy[1] : 0, y0, x0, th, tw, tile_grad);
+}
+
+int stx_map_place(stx_engine *e, float *dst, int channels, int dst_h, int dst_w, int y0, int x0,
+                  const float *src, int h, int w) {
+    if (!e || !dst || !src || channels <= 0 || h <= 0 || w <= 0 || y0 < 0 || x0 < 0 ||
+        y0 + h > dst_h || x0 + w > dst_w) {
+        set_error("stx_map_place: window [%d+%d, %d+%d] does not fit a %dx%d map", y0, h, x0, w,
+                  dst_h, dst_w);
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    return place_window_launch(e->stream, dst, dst_h, dst_w, y0, x0, src, channels, h, w);
+}
+
+int stx_map_roll_add(stx_engine *e, float *acc, const float *src, int channels, int h, int w,
+                     const int roll_xy[2], double alpha, double init_divisor) {
+    if (!e || !acc || !src || channels <= 0 || h <= 0 || w <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const bool init = init_divisor != 0.0;
+    return roll_add_launch(e->stream, acc, src, channels, h, w, roll_xy ? roll_xy[0] : 0,
+                           roll_xy ? roll_xy[1] : 0, (float)(init ? init_divisor : alpha), init);
+}
+
+int stx_image_resample(stx_engine *e, const float *src, int channels, int H, int W, float *dst,
+                       int out_h, int out_w, const int *bounds_x, const double *weights_x,
+                       int ksize_x, const int *bounds_y, const double *weights_y, int ksize_y,
+                       int clamp_min_zero) {
+    if (!e || !src || !dst || !bounds_x || !weights_x || !bounds_y || !weights_y || channels <= 0 ||
+        H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || ksize_x <= 0 || ksize_y <= 0)
+        return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    // device scratch: [bounds_x | bounds_y] ints, [kx | ky] doubles, horizontal-pass image
+    const size_t nbx = 2 * (size_t)out_w, nby = 2 * (size_t)out_h;
+    const size_t nkx = (size_t)out_w * ksize_x, nky = (size_t)out_h * ksize_y;
+    const size_t tmp_floats = (size_t)channels * H * out_w;
+    const size_t k_off = ((nbx + nby) * sizeof(int) + 7) & ~(size_t)7;
+    const size_t t_off = (k_off + (nkx + nky) * sizeof(double) + 255) & ~(size_t)255;
+    STX_TRY(e->upload.ensure(t_off + tmp_floats * sizeof(float)));
+    char *base = static_cast<char *>(e->upload.ptr);
+    int *d_bx = reinterpret_cast<int *>(base), *d_by = d_bx + nbx;
+    double *d_kx = reinterpret_cast<double *>(base + k_off), *d_ky = d_kx + nkx;
+    float *tmp = reinterpret_cast<float *>(base + t_off);
+    STX_HIP(hipMemcpyAsync(d_bx, bounds_x, nbx * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    STX_HIP(hipMemcpyAsync(d_by, bounds_y, nby * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    STX_HIP(hipMemcpyAsync(d_kx, weights_x, nkx * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    STX_HIP(hipMemcpyAsync(d_ky, weights_y, nky * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    // Pillow runs the horizontal pass first, then the vertical pass on its float32 result
+    STX_TRY(resample_launch(e->stream, 0, src, channels, H, W, tmp, H, out_w, d_bx, d_kx, ksize_x, 0));
+    STX_TRY(resample_launch(e->stream, 1, tmp, channels, H, out_w, dst, out_h, out_w, d_by, d_ky,
+                            ksize_y, clamp_min_zero));
+    // the coefficient tables are host memory of the caller: finish the copies before returning
+    STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+// Queues n = coefs.size() double-precision loss terms: `launch` enqueues the kernels that leave them at the
+// device pointer it is handed, they are mirrored to the host arena, and at the next sync *loss_out becomes
+// sum coefs[i] * term[i].
+static int queue_dterms(stx_engine *e, std::initializer_list<double> coefs, double *loss_out,
+                        const std::function<int(double *)> &launch) {
+    size_t di;
+    STX_TRY(alloc_dscalars(e, coefs.size(), &di));
+    double *terms = static_cast<double *>(e->A().dscalars.ptr) + di;
+    STX_TRY(launch(terms));
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, terms, coefs.size() * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+    PendingLoss pl;
+    pl.out = loss_out;
+    size_t i = di;
+    for (double coef : coefs) pl.dterms.push_back(LossTerm{i++, coef});
+    e->A().pending.push_back(std::move(pl));
+    return STX_OK;
+}
+
+int stx_image_regularizers(stx_engine *e, const float *img, float *grad, int H, int W,
+                           const float mean_bgr[3], double tv_scale, double tv_power, double p_scale,
+                           double p_power, const float *aux, double aux_scale,
+                           const int aux_roll_xy[2], double *loss_out) {
+    if (!e || !img || !grad || !mean_bgr || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return queue_dterms(e, {tv_scale, p_scale, aux ? aux_scale * 0.5 : 0.0}, loss_out, [&](double *terms) {
+        return regularizers_launch(e->stream, img, grad, H, W, mean_bgr, (float)tv_scale,
+                                   (float)tv_power, (float)p_scale, (float)p_power, aux,
+                                   (float)aux_scale, aux_roll_xy ? aux_roll_xy[0] : 0,
+                                   aux_roll_xy ? aux_roll_xy[1] : 0, terms, e->red_scratch.f(),
+                                   e->red_scratch.bytes / sizeof(float));
+    });
+}
+
+// ---- the SWT term (swt.hip): order 1 is Haar and goes to the Haar levels entry, one level of it to the
+// one-level kernel, so that the three entries agree bit for bit where they overlap ----
+
+// pywt.swt2 takes 1 to log2(padded side) levels
+static int swt_check_levels(const char *name, int H, int W, int levels) {
+    const int N = swt_padded_side(H, W);
+    if (levels < 1 || levels > 30 || (1 << levels) > N) {
+        set_error("%s: levels = %d, but a %d x %d image (padded side %d) takes 1 to %d levels", name,
+                  levels, H, W, N, (int)std::lround(std::log2((double)N)));
+        return STX_ERR_ARG;
+    }
+    return STX_OK;
+}
+
+// The scratch of the two separable passes: the row-filtered image and the column pass's partials.
+static int swt_scratch_for(stx_engine *e, int H, int W, float **tmp, float **partials) {
+    size_t tmp_floats, partial_floats;
+    swt_levels_scratch(H, W, &tmp_floats, &partial_floats);
+    // growing frees the old buffer, which waits for the kernels that still read it
+    STX_TRY(e->swt_scratch.ensure((tmp_floats + partial_floats) * sizeof(float)));
+    *tmp = e->swt_scratch.f();
+    *partials = *tmp + tmp_floats;
+    return STX_OK;
+}
+
+// The device copy of swt_daub_table(order, levels, N): built and uploaded at first use, then kept.
+static int swt_table_for(stx_engine *e, int order, int levels, int N, const stx_engine::SwtTable **out) {
+    for (const stx_engine::SwtTable &t : e->swt_tables)
+        if (t.order == order && t.levels == levels && t.N == N) {
+            *out = &t;
+            return STX_OK;
+        }
+    std::vector<float> taps;
+    int hl;
+    swt_daub_table(order, levels, N, &taps, &hl);
+    stx_engine::SwtTable t{order, levels, N, (int)taps.size(), hl, DevBuf()};
+    STX_TRY(t.taps.ensure(taps.size() * sizeof(float)));
+    // once per table and synchronous: the host copy does not outlive this call
+    hipError_t err = hipMemcpy(t.taps.ptr, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        t.taps.release();
+        set_error("stx_image_swt_daub_levels: hipMemcpy of %zu taps failed: %s", taps.size(),
+                  hipGetErrorString(err));
+        return STX_ERR_HIP;
+    }
+    e->swt_tables.push_back(t);
+    *out = &e->swt_tables.back();
+    return STX_OK;
+}
+
+int stx_image_swt_haar(stx_engine *e, const float *img, float *grad, int H, int W,
+                       const int roll_xy[2], double scale, double power, double *loss_out) {
+    if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return swt_haar_launch(e->stream, img, grad, H, W, roll_xy ? roll_xy[0] : 0,
+                               roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term,
+                               e->red_scratch.f(), e->red_scratch.bytes / sizeof(float));
+    });
+}
+
+int stx_image_swt_haar_levels(stx_engine *e, const float *img, float *grad, int H, int W, int levels,
+                              const int roll_xy[2], double scale, double power, double *loss_out) {
+    if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
+    STX_TRY(swt_check_levels("stx_image_swt_haar_levels", H, W, levels));
+    if (levels == 1) return stx_image_swt_haar(e, img, grad, H, W, roll_xy, scale, power, loss_out);
+    STX_TRY(e->set_device());
+    float *tmp, *partials;
+    STX_TRY(swt_scratch_for(e, H, W, &tmp, &partials));
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return swt_haar_levels_launch(e->stream, img, grad, H, W, levels, roll_xy ? roll_xy[0] : 0,
+                                      roll_xy ? roll_xy[1] : 0, (float)scale, (float)power, term, tmp,
+                                      partials);
+    });
+}
+
+int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int H, int W, int order,
+                              int levels, const int roll_xy[2], double scale, double power,
+                              double *loss_out) {
+    if (!e || !img || !grad || H <= 0 || W <= 0 || power <= 0) return STX_ERR_ARG;
+    if (order < 1 || order > 38) {
+        set_error("stx_image_swt_daub_levels: order = %d, but db1 to db38 exist", order);
+        return STX_ERR_ARG;
+    }
+    if (order == 1)     // (the Haar entry checks the level count)
+        return stx_image_swt_haar_levels(e, img, grad, H, W, levels, roll_xy, scale, power, loss_out);
+    STX_TRY(swt_check_levels("stx_image_swt_daub_levels", H, W, levels));
+    STX_TRY(e->set_device());
+    const stx_engine::SwtTable *tab;
+    STX_TRY(swt_table_for(e, order, levels, swt_padded_side(H, W), &tab));
+    float *tmp, *partials;
+    STX_TRY(swt_scratch_for(e, H, W, &tmp, &partials));
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return swt_table_launch(e->stream, img, grad, H, W, tab->taps.f(), tab->ntaps, tab->hl,
+                                roll_xy ? roll_xy[0] : 0, roll_xy ? roll_xy[1] : 0, (float)scale,
+                                (float)power, term, tmp, partials);
+    });
+}
+
+int stx_adam_step(stx_engine *e, float *params, const float *grad, float *g1, float *g2, float *p1,
+                  float *avg_out, size_t n, double lr, double b1, double b2, double bp1, double corr1,
+                  double corr2, double corrp) {
+    if (!e || !params || !grad || !g1 || !g2 || !p1 || !avg_out) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return adam_launch(e->stream, params, grad, g1, g2, p1, avg_out, n, lr, b1, b2, bp1, corr1,
+                       corr2, corrp);
+}
+
+static int sync_scalar(stx_engine *e, size_t di, int n, double *out) {
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, static_cast<double *>(e->A().dscalars.ptr) + di,
+                           n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    for (int i = 0; i < n; ++i) out[i] = e->A().dhost[di + i];
+    return STX_OK;
+}
+
+int stx_vec_dot(stx_engine *e, const float *x, const float *y, size_t n, double *out) {
+    if (!e || !x || !y || !out) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const size_t di = e->dscalars_cap - 2;   // reserved slot for synchronous scalar results
+    STX_TRY(dot_launch(e->stream, x, y, n, static_cast<double *>(e->A().dscalars.ptr) + di,
+                       e->red_scratch.f(), e->red_scratch.bytes / sizeof(float)));
+    return sync_scalar(e, di, 1, out);
+}
+
+int stx_vec_mean_abs(stx_engine *e, const float *x, size_t n, double *out) {
+    if (!e || !x || !out || !n) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const size_t di = e->dscalars_cap - 2;
+    STX_TRY(abs_sum_launch(e->stream, x, n, static_cast<double *>(e->A().dscalars.ptr) + di,
+                           e->red_scratch.f(), e->red_scratch.bytes / sizeof(float)));
+    STX_TRY(sync_scalar(e, di, 1, out));
+    *out /= (double)n;
+    return STX_OK;
+}
+
+int stx_vec_dot_async(stx_engine *e, const float *x, const float *y, size_t n, double *out_dev) {
+    if (!e || !x || !y || !out_dev) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return dot_launch(e->stream, x, y, n, out_dev, e->red_scratch.f(),
+                      e->red_scratch.bytes / sizeof(float));
+}
+
+int stx_vec_abs_sum_async(stx_engine *e, const float *x, size_t n, double *out_dev) {
+    if (!e || !x || !out_dev) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return abs_sum_launch(e->stream, x, n, out_dev, e->red_scratch.f(),
+                          e->red_scratch.bytes / sizeof(float));
+}
+
+int stx_vec_axpy_dev(stx_engine *e, double c1, const double *a_dev, double da, double c2,
+                     const double *b_dev, double db, const float *x, float *y, size_t n) {
+    if (!e || !a_dev || !x || !y || da == 0.0 || (b_dev && db == 0.0)) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return axpy_dev_launch(e->stream, c1, a_dev, da, c2, b_dev, db, x, y, n);
+}
+
+int stx_vec_scale_dev(stx_engine *e, double c, const double *den_dev, double den_div, float *x,
+                      size_t n) {
+    if (!e || !den_dev || !x || den_div == 0.0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return scale_dev_launch(e->stream, c, den_dev, den_div, x, n);
+}
+
+int stx_vec_axpy_dot_dev(stx_engine *e, double c1, const double *a_dev, double da, double c2,
+                         const double *b_dev, double db, double scale_c, const double *scale_den_dev,
+                         double scale_div, const float *x, const float *src, float *y, const float *z,
+                         size_t n, double *out_dev) {
+    if (!e || !a_dev || !x || !src || !y || !z || !out_dev || da == 0.0 || (b_dev && db == 0.0) ||
+        (scale_den_dev && scale_div == 0.0))
+        return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return axpy_dot_dev_launch(e->stream, c1, a_dev, da, c2, b_dev, db, scale_c, scale_den_dev, scale_div, x,
+                               src, y, z, n, out_dev, e->red_scratch.f(), e->red_scratch.bytes / sizeof(float));
+}
+
+int stx_vec_lbfgs_pair(stx_engine *e, const float *g_new, float *g_old, const float *s, float *y, size_t n,
+                       double *out_dev2, double *sy_host_sync) {
+    if (!e || !g_new || !g_old || !s || !y || !out_dev2 || !sy_host_sync) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    STX_TRY(lbfgs_pair_launch(e->stream, g_new, g_old, s, y, n, out_dev2, e->red_scratch.f(),
+                              e->red_scratch.bytes / sizeof(float)));
+    const size_t di = e->dscalars_cap - 2;   // the pinned mirror's slot for synchronous scalar results
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, out_dev2, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    *sy_host_sync = e->A().dhost[di];
+    return STX_OK;
+}
+
+int stx_vec_scale2_axpy(stx_engine *e, double c1, double c2, float *s, float *params, size_t n) {
+    if (!e || !s || !params) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return scale2_axpy_launch(e->stream, (float)c1, (float)c2, s, params, n);
+}
+
+int stx_vec_axpy(stx_engine *e, double a, const float *x, float *y, size_t n) {
+    if (!e || !x || !y) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return axpy_launch(e->stream, (float)a, x, y, n);
+}
+
+int stx_vec_scale(stx_engine *e, double a, float *x, size_t n) {
+    if (!e || !x) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return scale_launch(e->stream, (float)a, x, n);
+}
+
+int stx_image_step_stats(stx_engine *e, const float *avg, float *old, int H, int W, double stats[2]) {
+    if (!e || !avg || !old || !stats || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const size_t di = e->dscalars_cap - 2;
+    STX_TRY(step_stats_launch(e->stream, avg, old, H, W, static_cast<double *>(e->A().dscalars.ptr) + di,
+                              e->red_scratch.f(), e->red_scratch.bytes / sizeof(float)));
+    double raw[2];
+    STX_TRY(sync_scalar(e, di, 2, raw));
+    const double n = 3.0 * H * W;
+    stats[0] = raw[0] / n;
+    stats[1] = std::sqrt(raw[1] / n);
+    return STX_OK;
+}
+
+int stx_image_step_stats_async(stx_engine *e, const float *avg, float *old, int H, int W,
+                               double raw_sums[2]) {
+    if (!e || !avg || !old || !raw_sums || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    size_t di;
+    STX_TRY(alloc_dscalars(e, 2, &di));
+    double *dev = static_cast<double *>(e->A().dscalars.ptr) + di;
+    STX_TRY(step_stats_launch(e->stream, avg, old, H, W, dev, e->red_scratch.f(),
+                              e->red_scratch.bytes / sizeof(float)));
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, dev, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    for (int i = 0; i < 2; ++i) {
+        PendingLoss pl;
+        pl.out = raw_sums + i;
+        pl.dterms.push_back(LossTerm{di + (size_t)i, 1.0});
+        e->A().pending.push_back(std::move(pl));
+    }
+    return STX_OK;
+}
+
+int stx_image_to_u8(stx_engine *e, const float *img, int H, int W, const float mean_bgr[3],
+                    uint8_t *out_rgb_u8) {
+    if (!e || !img || !mean_bgr || !out_rgb_u8 || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return to_u8_launch(e->stream, img, H, W, mean_bgr, out_rgb_u8);
+}
+
+int stx_image_to_u8_luma(stx_engine *e, const float *img, const float *content, int H, int W,
+                         const float mean_bgr[3], uint8_t *out_rgb_u8) {
+    if (!e || !img || !content || !mean_bgr || !out_rgb_u8 || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return to_u8_luma_launch(e->stream, img, content, H, W, mean_bgr, out_rgb_u8);
+}
+
+int stx_image_color_stats(stx_engine *e, const float *img, int H, int W, double out_host_sync[9]) {
+    if (!e || !img || !out_host_sync || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    STX_TRY(e->color_sums.ensure(9 * sizeof(double)));
+    double *dev = static_cast<double *>(e->color_sums.ptr);
+    STX_TRY(color_stats_launch(e->stream, img, H, W, dev, e->red_scratch.f(),
+                               e->red_scratch.bytes / sizeof(float)));
+    STX_HIP(hipMemcpyAsync(out_host_sync, dev, 9 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_image_color_affine(stx_engine *e, const float *src, float *dst, int H, int W, const double A[9],
+                           const double b[3], const float mean_bgr[3]) {
+    if (!e || !src || !dst || !A || !b || !mean_bgr || H <= 0 || W <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return color_affine_launch(e->stream, src, dst, H, W, A, b, mean_bgr);
+}
+
+}  // extern "C"

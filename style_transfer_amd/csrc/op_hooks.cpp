@@ -1,0 +1,135 @@
+// libstx host side: the stx_op_* test hooks -- single operators of the tile path, launched the way the
+// tile path launches them, on caller-owned device arrays.
+
+#include "engine.h"
+
+extern "C" {
+
+// Packs `bank` from the Caffe-layout weights w into the upload buffer.
+static int scratch_pack(stx_engine *e, const ConvBank &bank, const float *w, const float **packed) {
+    STX_TRY(e->upload.ensure(bank.floats * sizeof(float)));
+    STX_TRY(bank.pack(e->stream, w, e->upload.f()));
+    *packed = e->upload.f();
+    return STX_OK;
+}
+
+// A stand-alone operator call: the tile path's choice without the tuner; the input's maximum (where the kernel
+// reads it) comes from a pass over it, the output's goes to a scratch group of the table.
+static int hook_conv(stx_engine *e, ConvProblem &p, const float *w, int Mo, int Ko, int dir) {
+    ConvConfig cfg;
+    STX_TRY(conv_choose(p, e->winograd, nullptr, &cfg));
+    if (conv_reads_x_amax(cfg)) {
+        unsigned *scratch;
+        STX_TRY(amax_scratch(e, &scratch));
+        STX_TRY(absmax_launch(e->stream, p.x, (size_t)p.K * p.H * p.W, scratch));
+        STX_HIP(hipMemsetAsync(scratch + kAmaxSlots, 0, kAmaxSlots * sizeof(unsigned), e->stream));
+        p.x_amax = scratch;
+        p.y_amax = scratch + kAmaxSlots;
+    }
+    STX_TRY(scratch_pack(e, conv_bank(cfg, dir, Mo, Ko, p.ksize), w, &p.w));
+    STX_TRY(attach_splitk(e, cfg, p));
+    return launch_conv(e, cfg, p);
+}
+
+int stx_op_conv_forward(stx_engine *e, const float *x, int Cin, int H, int W, const float *w,
+                        const float *b, int Cout, int ksize, int relu, float *y) {
+    if (!e || !x || !w || !y) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    if (conv_first_usable(Cin, Cout, ksize))      // the tile path's first-layer kernel
+        return conv_first_launch(e->stream, x, w, b, y, Cin, H, W, relu, nullptr);
+    ConvProblem p = conv_fwd_problem(x, y, b, Cin, Cout, H, W, ksize, relu);
+    return hook_conv(e, p, w, Cout, Cin, 0);
+}
+
+int stx_op_conv_backward_data(stx_engine *e, const float *dy, int Cout, int H, int W, const float *w,
+                              int Cin, int ksize, const float *relu_mask_data, float *dx) {
+    if (!e || !dy || !w || !dx) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    if (ksize == 3 && Cin <= 4) {
+        const float *packed = nullptr;
+        STX_TRY(scratch_pack(e, conv_small_bank(Cout, Cin), w, &packed));
+        return conv_small_launch(e->stream, dy, packed, dx, relu_mask_data, Cout, Cin, H, W);
+    }
+    ConvProblem p = conv_bwd_problem(dy, dx, relu_mask_data, Cout, Cin, H, W, ksize);
+    return hook_conv(e, p, w, Cout, Cin, 1);
+}
+
+int stx_op_pool_forward(stx_engine *e, const float *x, int C, int H, int W, int mode, float *y) {
+    if (!e || !x || !y) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return pool_forward_launch(e->stream, x, C, H, W, mode, y);
+}
+
+int stx_op_pool_backward(stx_engine *e, const float *dy, const float *x, int C, int H, int W,
+                         int mode, const float *relu_mask_data, float *dx) {
+    if (!e || !dy || !x || !dx) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    // the mask source is the pool input itself (post-ReLU data of the blob below)
+    return pool_backward_launch(e->stream, dy, x, C, H, W, mode, relu_mask_data != nullptr, dx);
+}
+
+int stx_op_style_terms(stx_engine *e, const float *feat, int C, int h, int w,
+                       const float *gram_target, float *s_out, float *normalized_out,
+                       double *half_sumsq, double *abs_sum) {
+    if (!e || !feat || !gram_target || C <= 0 || C % 4 || h <= 0 || w <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const int HW = h * w;
+    const size_t count = (size_t)C * HW;
+    // the launches of the style branch of stx_sc_grad_tile, in the same order
+    STX_TRY(e->upload.ensure(count * sizeof(float)));
+    float *sgrad = s_out ? s_out : e->upload.f();
+    STX_TRY(do_sync(e));
+    size_t si;
+    STX_TRY(alloc_scalars(e, 2, &si));
+    float *sc = e->A().scalars.f() + si;
+    STX_TRY(launch_style_terms(e, e->stream, feat, C, h, w, gram_target, sgrad, sc, "op"));
+    if (normalized_out)
+        STX_TRY(inject_style_launch(e->stream, normalized_out, sgrad, count, sc + 1, 1.0f, false));
+    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
+                           hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    if (half_sumsq) *half_sumsq = 0.5 * (double)e->A().host[si];
+    if (abs_sum) *abs_sum = (double)e->A().host[si + 1];
+    e->A().used = 0;
+    return STX_OK;
+}
+
+int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,
+                         const float *content, int content_h, int content_w, int oy, int ox,
+                         const int roll_xy[2], float *normalized_out, double sums[2]) {
+    if (!e || !feat || !content || C <= 0 || h <= 0 || w <= 0) return STX_ERR_ARG;
+    if (oy < 0 || ox < 0 || oy + h > content_h || ox + w > content_w) {
+        set_error("stx_op_content_terms: window exceeds the content map");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    // (the caller gives the window and the roll in the map's own pixels: nothing to divide by a scale)
+    ContentWindow win;
+    win.C = C;
+    win.fh = h;
+    win.fw = w;
+    win.ch = content_h;
+    win.cw = content_w;
+    win.oy = oy;
+    win.ox = ox;
+    win.sx = roll_xy ? roll_xy[0] : 0;
+    win.sy = roll_xy ? roll_xy[1] : 0;
+    STX_TRY(do_sync(e));
+    size_t si;
+    STX_TRY(alloc_scalars(e, 2 + 2 * 1024, &si));
+    float *s = e->A().scalars.f() + si;
+    STX_TRY(content_sums_launch(e->stream, feat, content, win, s));
+    if (normalized_out)
+        STX_TRY(inject_content_launch(e->stream, normalized_out, feat, content, win, s, 1.0f, false));
+    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, (si + 2) * sizeof(float),
+                           hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    if (sums) {
+        sums[0] = (double)e->A().host[si];
+        sums[1] = (double)e->A().host[si + 1];
+    }
+    e->A().used = 0;
+    return STX_OK;
+}
+
+}  // extern "C"
