@@ -162,6 +162,34 @@ typedef struct stx_style_target {
 int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *contents, int n_contents,
                                 const stx_style_target *styles, int n_styles);
 
+/* Spatial control (Gatys et al., "Controlling Perceptual Factors in Neural Style Transfer"; no
+ * counterpart in the reference, whose styles act on the whole picture): style `style_index` applies
+ * where its mask is white.  mask is [H][W] float32 in [0, 1] (values are not checked), H x W the image
+ * frame of the current targets.  For a style layer b of scale s the library keeps the mask map
+ *   m_b[y][x] = mean of mask over [y s, min((y + 1) s, H)) x [x s, min((x + 1) s, W)),
+ * ceil(H/s) x ceil(W/s) (receptive-field growth is ignored), and a tile evaluation takes the tile's window
+ * of it exactly as a content map's (start // s, roll // s, wrapping; the same range error).  With F the
+ * tile's blob [C][fh][fw], HW = fh fw, m that window and Gs the style's Gram (of the WHOLE style picture):
+ *   a     = sum m^2 / HW
+ *   Fm    = F . m                                     (every channel)
+ *   D     = tril(Fm Fm^T)/(C HW) - a Gs
+ *   loss += lw sw[b] 1/2 |D|^2 / n_styles
+ *   S     = m . (sym(D) Fm)
+ *   diff += lw sw[b] / n_styles * a S / (sum|S| / S.size + EPS)
+ * m == 1 is the unmasked term bit for bit; m == 0 adds nothing (0 / EPS).  The factor a keeps the
+ * per-pixel strength inside a region what it is in an unmasked run.  Styles without a mask are untouched. */
+typedef struct stx_style_mask {
+    int style_index;        /* the style_index of the stx_style_target entries it restricts */
+    int H, W;
+    const float *mask;
+    int mem;
+} stx_style_mask;
+/* Replaces all masks of the engine's group (n = 0: none).  Call it after stx_set_contents_and_styles,
+ * which clears them: the maps are built for every layer that has a style target of that index and are
+ * shared like the targets (stx_engine_create_shared).  A mask of another size than the content frame
+ * surfaces as the window range error at evaluation. */
+int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -234,6 +262,8 @@ int stx_image_put_tile(stx_engine *e, float *grad, int H, int W, const int roll_
  * rolled-tiling average (style_transfer.py:476-485) on [C][h][w] maps:
  * init_divisor != 0:  acc  = roll2(src, roll_xy) / init_divisor   (features = feats / passes)
  * init_divisor == 0:  acc += alpha * roll2(src, roll_xy)          (saxpy(1 / passes, ...)) */
+/* One layer's mask map (stx_set_style_masks): out [ceil(H/scale)][ceil(W/scale)] = block means of mask. */
+int stx_image_mask_map(stx_engine *e, const float *mask, int H, int W, int scale, float *out);
 int stx_map_place(stx_engine *e, float *dst, int channels, int dst_h, int dst_w, int y0, int x0,
                   const float *src, int h, int w);
 int stx_map_roll_add(stx_engine *e, float *acc, const float *src, int channels, int h, int w,
@@ -410,6 +440,12 @@ int stx_op_pool_backward(stx_engine *e, const float *dy, const float *x, int C, 
 int stx_op_style_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                        const float *gram_target, float *s_out, float *normalized_out,
                        double *half_sumsq, double *abs_sum);
+/* stx_op_style_terms through a mask, the launches of a masked style target (stx_set_style_masks) on given
+ * arrays: mask_map [mh][mw], the window at (oy, ox) of roll2(mask_map, roll_xy) in the map's own pixels.
+ * out = {1/2 sum D^2, sum |m . S|, a}; sgrad_out = a m . (sym(D) Fm). */
+int stx_op_masked_style_terms(stx_engine *e, const float *feat, int channels, int h, int w,
+                              const float *mask_map, int mh, int mw, int oy, int ox, const int roll_xy[2],
+                              const float *gram_target, float *sgrad_out, double out[3]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

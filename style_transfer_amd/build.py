@@ -30,6 +30,7 @@ SOURCES = {
     # one rounding per float32 operation, like the reference's numpy expressions
     'image_ops.hip': ['-ffp-contract=off'],
     'swt.hip': ['-ffp-contract=off'],
+    'style_mask.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'tile_path.cpp': [],

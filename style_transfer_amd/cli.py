@@ -15,7 +15,7 @@ import numpy as np
 from PIL import Image
 
 from . import fastpng, lib
-from .config_system import parse_args
+from .config_system import check_style_masks, parse_args
 from .farm import TileFarm
 from .netspec import load_net
 from .transfer import StyleTransfer
@@ -154,6 +154,7 @@ def main(argv=None):
         print('Initializing %s on device(s) %s.' % (args.weights, devices))
         content_image = Image.open(args.content_image).convert('RGB')
         style_images = [Image.open(p).convert('RGB') for p in args.style_images]
+        style_masks = [Image.open(p).convert('L') for p in check_style_masks(args)]
         initial_image = Image.open(args.init_image).convert('RGB') if args.init_image else None
         aux_image = Image.open(args.aux_image).convert('RGB') if args.aux_image else None
         farm = farm_future.result()
@@ -169,7 +170,7 @@ def main(argv=None):
     failed = True
     try:
         transfer.transfer_multiscale([content_image], style_images, initial_image, aux_image,
-                                     callback=progress)
+                                     callback=progress, **({'style_masks': style_masks} if style_masks else {}))
         failed = False
     except (EOFError, KeyboardInterrupt):
         print()

@@ -109,6 +109,11 @@ _EXTENSIONS = [
                                       "picture is written, 'match' recolours every style picture to "
                                       "the content picture's colour mean and covariance before its "
                                       "Grams are taken (default: none)")),
+    (('--style-masks',), dict(nargs='+', metavar='MASK',
+                              help='spatial control: one greyscale picture per style image, in the content '
+                                   "picture's frame; a style applies where its mask is white.  With masks "
+                                   'every style image is a style set of its own instead of one average '
+                                   '(default: no masks)')),
 ]
 
 
@@ -171,6 +176,15 @@ def eval_config(path):
     return scope
 
 
+def check_style_masks(args):
+    """--style-masks names one mask per style image: anything else is refused before any GPU work."""
+    masks = getattr(args, 'style_masks', None)
+    if masks and len(masks) != len(args.style_images):
+        raise ValueError('--style-masks: %d mask(s) for %d style image(s); one per style image is needed'
+                         % (len(masks), len(args.style_images)))
+    return list(masks) if masks else []
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -194,4 +208,5 @@ def parse_args(state=None, argv=None, config_py=None):
     if not args.list_layers and (not args.content_image or not args.style_images):
         parser.print_help()
         sys.exit(1)
+    check_style_masks(args)
     return args

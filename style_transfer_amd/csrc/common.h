@@ -446,6 +446,22 @@ int sum_partials_launch(hipStream_t s, const float *partials, int n, float *out)
 int sum_partials2_launch(hipStream_t s, const float *a, int na, float *out_a, const float *b, int nb,
                          float *out_b);
 
+// style_mask.hip: a style term restricted to a region by a mask map m (values in [0, 1]; the tile's
+// window of it is addressed like a content map's).  Partials are added in sum_partials_kernel's order.
+constexpr int kMaskParts = 1024;         // most partials of sum m^2 (mask_apply_launch)
+constexpr int kMaskSgradParts = 2048;    // most partials of sum |m . S| (mask_sgrad_launch)
+// out [ceil(H/scale)][ceil(W/scale)] = block means of the H x W mask (edge blocks over what exists)
+int mask_map_launch(hipStream_t s, const float *mask, int H, int W, int scale, float *out);
+// fm = feat . m (every channel); *n_parts partials of sum m^2 over the window into m2_partials
+int mask_apply_launch(hipStream_t s, const float *feat, const float *map, const ContentWindow &win, float *fm,
+                      float *m2_partials, int *n_parts);
+// a = sum m^2 / HW from the partials; out = a gs (C x C), a_out[0] = a
+int mask_target_launch(hipStream_t s, const float *gs, int C, const float *m2_partials, int n_parts, int HW,
+                       float *out, float *a_out);
+// sgrad <- a[0] (m . sgrad) in place; *n_parts partials of sum |m . sgrad| (without a) into partials
+int mask_sgrad_launch(hipStream_t s, float *sgrad, const float *map, const ContentWindow &win, const float *a,
+                      float *partials, int *n_parts);
+
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,
                     int th, int tw, float *tile);

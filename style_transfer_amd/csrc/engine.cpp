@@ -416,8 +416,9 @@ void stx_engine_destroy(stx_engine *e) {
         }
         for (auto &c : e->sh->contents) c.feat->release();
         for (auto &s : e->sh->styles) s.gram->release();
+        for (auto &m : e->sh->masks) m.map->release();
     }
-    DevBuf *bufs[] = {&e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
+    DevBuf *bufs[] = {&e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
@@ -611,8 +612,10 @@ int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *content
     double copied = 0;
     for (auto &c : e->sh->contents) c.feat->release();
     for (auto &s : e->sh->styles) s.gram->release();
+    for (auto &m : e->sh->masks) m.map->release();
     e->sh->contents.clear();
     e->sh->styles.clear();
+    e->sh->masks.clear();
     e->sh->n_contents = e->sh->n_styles = 0;
     bool host_src = false;
     for (int i = 0; i < n_contents; ++i) {
@@ -663,6 +666,60 @@ int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *content
     e->sh->target_uploads += 1;
     e->sh->target_bytes += copied;
     return STX_OK;
+}
+
+int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n) {
+    if (!e || n < 0 || (n && !masks)) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    std::lock_guard<std::mutex> lock(e->sh->mutex);
+    // the previous maps may still be in use by queued kernels (of any engine that shares them)
+    STX_TRY(quiesce_members(e));
+    for (auto &m : e->sh->masks) m.map->release();
+    e->sh->masks.clear();
+    DevBuf staged;      // a host mask on its way to the device
+    int rc = STX_OK;
+    for (int i = 0; i < n && rc == STX_OK; ++i) {
+        const stx_style_mask &sm = masks[i];
+        bool any = false;
+        for (const StyleTarget &st : e->sh->styles) any |= st.index == sm.style_index;
+        if (!sm.mask || sm.H <= 0 || sm.W <= 0 || !any) {
+            set_error("style mask %d: no mask, a bad size or no style target of index %d", i, sm.style_index);
+            rc = STX_ERR_ARG;
+            break;
+        }
+        const float *src = sm.mask;
+        if (sm.mem == STX_HOST) {
+            const size_t bytes = (size_t)sm.H * sm.W * sizeof(float);
+            if ((rc = staged.ensure(bytes)) != STX_OK) break;
+            if ((rc = copy_in(e, staged.ptr, sm.mask, STX_HOST, bytes)) != STX_OK) break;
+            src = staged.f();
+        }
+        for (const StyleTarget &st : e->sh->styles) {
+            if (st.index != sm.style_index) continue;
+            bool have = false;
+            for (const StyleMask &m : e->sh->masks) have |= m.index == st.index && m.blob == st.blob;
+            if (have) continue;
+            const int scale = e->blobs[st.blob].scale;
+            StyleMask m{st.index, st.blob, ceil_div(sm.H, scale), ceil_div(sm.W, scale),
+                        std::unique_ptr<DevBuf>(new DevBuf)};
+            if ((rc = m.map->ensure((size_t)m.h * m.w * sizeof(float))) != STX_OK) break;
+            rc = mask_map_launch(e->stream, src, sm.H, sm.W, scale, m.map->f());
+            e->sh->masks.push_back(std::move(m));
+            if (rc != STX_OK) break;
+        }
+    }
+    // (host sources may be reused right away; the sharing engines read the maps from their own streams)
+    const hipError_t err = hipStreamSynchronize(e->stream);
+    staged.release();
+    if (rc == STX_OK && err != hipSuccess) {
+        set_error("stx_set_style_masks: %s", hipGetErrorString(err));
+        rc = STX_ERR_HIP;
+    }
+    if (rc != STX_OK) {
+        for (auto &m : e->sh->masks) m.map->release();
+        e->sh->masks.clear();
+    }
+    return rc;
 }
 
 int stx_profile_enable(stx_engine *e, int on) {

@@ -88,6 +88,13 @@ struct StyleTarget {
     std::unique_ptr<DevBuf> gram;
 };
 
+// The mask of style `index` at one tapped blob (stx_set_style_masks): the block means of the
+// image-resolution mask at the blob's scale, [h][w], addressed like a content map.
+struct StyleMask {
+    int index, blob, h, w;
+    std::unique_ptr<DevBuf> map;
+};
+
 struct LossTerm {
     size_t scalar_index;   // float in the host mirror of the scalar buffer
     double coef;
@@ -107,6 +114,7 @@ struct SharedState {
     std::map<int, ConvParams> conv;    // layer index -> params
     std::vector<ContentTarget> contents;
     std::vector<StyleTarget> styles;
+    std::vector<StyleMask> masks;      // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -154,6 +162,7 @@ struct stx_engine {
     bool first_gram_valid = false;
     DevBuf gram_partials, gram, dsym, dsym_pieces, symm_partials, upload;
     DevBuf term_scratch;               // per style term of a tile call: block sums / maxima + SYMM partials (sum jobs)
+    DevBuf masked_feat, masked_target; // a masked style term's F . m and a Gs (style_mask.hip), one term at a time
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
     // reductions), each with a pinned host mirror, and the losses that will be published from
     // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
@@ -271,6 +280,14 @@ int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int
                        const float *target, float *sgrad, float *sc, const std::string &name,
                        const unsigned *f_amax = nullptr, float *term_scratch = nullptr,
                        std::vector<SumJob> *defer = nullptr);
+// The same term through a mask (style_mask.hip): F . m and a Gs, launch_style_terms on them, S <- a m . S.
+// sc[4] = {sum tril(D)^2, (sum |S| before the mask), sum |m . S|, a}; mask_scratch: kMaskScratchFloats floats
+// that outlive the call like term_scratch.
+constexpr size_t kMaskScratchFloats = kMaskParts + kMaskSgradParts;
+int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                              const float *mask_map, const ContentWindow &win, const float *target,
+                              float *sgrad, float *sc, const std::string &name, const unsigned *f_amax,
+                              float *term_scratch, float *mask_scratch, std::vector<SumJob> *defer);
 #pragma GCC visibility pop
 
 }  // namespace stx

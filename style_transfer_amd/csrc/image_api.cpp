@@ -26,6 +26,12 @@ int stx_image_put_tile(stx_engine *e, float *grad, int H, int W, const int roll_
                            roll_xy ? roll_xy[1] : 0, y0, x0, th, tw, tile_grad);
 }
 
+int stx_image_mask_map(stx_engine *e, const float *mask, int H, int W, int scale, float *out) {
+    if (!e || !mask || !out || H <= 0 || W <= 0 || scale <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    return mask_map_launch(e->stream, mask, H, W, scale, out);
+}
+
 int stx_map_place(stx_engine *e, float *dst, int channels, int dst_h, int dst_w, int y0, int x0,
                   const float *src, int h, int w) {
     if (!e || !dst || !src || channels <= 0 || h <= 0 || w <= 0 || y0 < 0 || x0 < 0 ||

@@ -94,6 +94,45 @@ int stx_op_style_terms(stx_engine *e, const float *feat, int C, int h, int w,
     return STX_OK;
 }
 
+int stx_op_masked_style_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *mask_map,
+                              int mh, int mw, int oy, int ox, const int roll_xy[2], const float *gram_target,
+                              float *sgrad_out, double out[3]) {
+    if (!e || !feat || !mask_map || !gram_target || !sgrad_out || !out || C <= 0 || C % 4 || h <= 0 || w <= 0)
+        return STX_ERR_ARG;
+    if (oy < 0 || ox < 0 || oy + h > mh || ox + w > mw) {
+        set_error("stx_op_masked_style_terms: window exceeds the mask map");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    // (the window and the roll in the map's own pixels, like stx_op_content_terms)
+    ContentWindow win;
+    win.C = C;
+    win.fh = h;
+    win.fw = w;
+    win.ch = mh;
+    win.cw = mw;
+    win.oy = oy;
+    win.ox = ox;
+    win.sx = roll_xy ? roll_xy[0] : 0;
+    win.sy = roll_xy ? roll_xy[1] : 0;
+    STX_TRY(do_sync(e));
+    size_t si;
+    STX_TRY(alloc_scalars(e, 4, &si));
+    float *sc = e->A().scalars.f() + si;
+    STX_TRY(e->term_scratch.ensure(kMaskScratchFloats * sizeof(float)));
+    // the launches of a masked style target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_masked_style_terms(e, e->stream, feat, C, h, w, mask_map, win, gram_target, sgrad_out, sc, "op",
+                                      nullptr, nullptr, e->term_scratch.f(), nullptr));
+    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
+                           hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    out[0] = 0.5 * (double)e->A().host[si];
+    out[1] = (double)e->A().host[si + 2];
+    out[2] = (double)e->A().host[si + 3];
+    e->A().used = 0;
+    return STX_OK;
+}
+
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]) {

@@ -468,6 +468,34 @@ int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int
     return sum_partials2_launch(stream, block_sumsq, fin_blocks, sc, e->symm_partials.f(), n_wg, sc + 1);
 }
 
+// The style term of a masked style (style_mask.hip), around launch_style_terms as it stands:
+//   Fm = feat . m with the partials of sum m^2  ->  T' = a target, a = sum m^2 / HW  ->  Gram / SYMM on (Fm, T')
+//   ->  S <- a m . S with the partials of sum |m . S|, whose final sum joins `defer` or is launched here.
+// |Fm| <= |feat|: the producer's f_amax stays a valid bound for the fp16-split kernels.  Fm is not the
+// first layer's blob, so that layer's fused Gram partials are never taken for it.
+int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                              const float *mask_map, const ContentWindow &win, const float *target,
+                              float *sgrad, float *sc, const std::string &name, const unsigned *f_amax,
+                              float *term_scratch, float *mask_scratch, std::vector<SumJob> *defer) {
+    STX_TRY(e->masked_feat.ensure((size_t)C * h * w * sizeof(float)));
+    STX_TRY(e->masked_target.ensure((size_t)C * C * sizeof(float)));
+    float *const m2_partials = mask_scratch, *const ms_partials = mask_scratch + kMaskParts;
+    {
+        ProfScope scope(e, "mask " + name, 0.0, stream);
+        int n_m2 = 0;
+        STX_TRY(mask_apply_launch(stream, feat, mask_map, win, e->masked_feat.f(), m2_partials, &n_m2));
+        STX_TRY(mask_target_launch(stream, target, C, m2_partials, n_m2, h * w, e->masked_target.f(), sc + 3));
+    }
+    STX_TRY(launch_style_terms(e, stream, e->masked_feat.f(), C, h, w, e->masked_target.f(), sgrad, sc, name,
+                               f_amax, term_scratch, defer));
+    ProfScope scope(e, "smask " + name, 0.0, stream);
+    int n_ms = 0;
+    STX_TRY(mask_sgrad_launch(stream, sgrad, mask_map, win, sc + 3, ms_partials, &n_ms));
+    if (!defer) return sum_partials_launch(stream, ms_partials, n_ms, sc + 2);
+    defer->push_back(SumJob{ms_partials, n_ms, sc + 2});
+    return STX_OK;
+}
+
 static int begin_timing(stx_engine *e) {
     e->ev_cur = (e->ev_cur + 1) % stx_engine::kTimed;
     STX_HIP(hipEventRecord(e->ev_start[e->ev_cur], e->stream));
@@ -650,6 +678,45 @@ static int queue_content_terms(TileRun &run, size_t k) {
     return STX_OK;
 }
 
+// The mask map of style `index` at `blob` (stx_set_style_masks), or null.
+static const StyleMask *style_mask_of(const stx_engine *e, int index, int blob) {
+    for (const StyleMask &m : e->sh->masks)
+        if (m.index == index && m.blob == blob) return &m;
+    return nullptr;
+}
+
+// The term of a masked style target of tap k: the tile's window of the mask map, taken as a content
+// map's is, then launch_masked_style_terms.
+static int queue_masked_style_term(TileRun &run, size_t k, const StyleTarget &st, const StyleMask &mk, float *sgrad) {
+    stx_engine *e = run.e;
+    const Tap &tp = run.plan.order[k];
+    const Blob &b = e->blobs[tp.blob];
+    const ContentWindow win = content_window(b, mk.h, mk.w, run.c.start, run.c.rx, run.c.ry);
+    if (win.oy < 0 || win.ox < 0 || win.oy + win.fh > win.ch || win.ox + win.fw > win.cw) {
+        set_error("style mask window [%d+%d, %d+%d] exceeds the %dx%d mask map of layer %s",
+                  win.oy, win.fh, win.ox, win.fw, win.ch, win.cw, b.name.c_str());
+        return STX_ERR_ARG;
+    }
+    size_t si;
+    STX_TRY(alloc_scalars(e, 4, &si));
+    float *sc = e->A().scalars.f() + si;   // [0] = sum tril(D)^2, [2] = sum |m . S|, [3] = a
+    const unsigned *f_amax = b.amax_data >= 0 ? e->amax_slots(b.amax_data, false) : nullptr;
+    float *scratch = nullptr;
+    if (run.sums_late) {
+        scratch = e->term_scratch.f() + run.scratch_used;
+        run.scratch_used += style_term_scratch_floats(b.channels, b.h * b.w);
+    }
+    float *mask_scratch = e->term_scratch.f() + run.scratch_used;
+    run.scratch_used += kMaskScratchFloats;
+    STX_TRY(launch_masked_style_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, mk.map->f(), win,
+                                      st.gram->f(), sgrad, sc, b.name, f_amax, scratch, mask_scratch, run.defer()));
+    const double lw = tp.t->layer_weight;
+    run.pl.terms.push_back(LossTerm{si, lw * tp.t->style_weight * 0.5 / e->sh->n_styles});
+    run.terms[k].push_back(Term{true, sgrad, sc + 2, (float)(lw * tp.t->style_weight / e->sh->n_styles),
+                                ContentWindow{}});
+    return STX_OK;
+}
+
 // Gram -> G - Gs -> SYMM against every style target of tap k (launch_style_terms).
 static int queue_style_terms(TileRun &run, size_t k) {
     stx_engine *e = run.e;
@@ -673,6 +740,10 @@ static int queue_style_terms(TileRun &run, size_t k) {
             return STX_ERR_UNSUPPORTED;
         }
         float *sgrad = e->sgrad_tap[k]->f() + (size_t)slot++ * b.count();
+        if (const StyleMask *mk = style_mask_of(e, st.index, tp.blob)) {
+            STX_TRY(queue_masked_style_term(run, k, st, *mk, sgrad));
+            continue;
+        }
         size_t si;
         STX_TRY(alloc_scalars(e, 2, &si));
         float *sc = e->A().scalars.f() + si;   // [0] = sum tril(D)^2, [1] = sum |S|
@@ -898,7 +969,11 @@ static void first_gram_setup(stx_engine *e, const TilePlan &plan) {
     e->first_gram_valid = false;
     for (const Tap &tp : plan.order) {
         const int pl = e->blobs[tp.blob].producer;
-        if (tp.t->is_style && pl > 0 && e->layers[pl].type == STX_LAYER_CONV &&
+        // (a masked style takes the Gram of F . m: the partials are for the unmasked targets of the blob)
+        bool unmasked = e->sh->masks.empty();
+        for (const StyleTarget &st : e->sh->styles)
+            unmasked |= st.blob == tp.blob && !style_mask_of(e, st.index, tp.blob);
+        if (tp.t->is_style && unmasked && pl > 0 && e->layers[pl].type == STX_LAYER_CONV &&
             e->layers[pl].bottom_blob == data_blob && e->blobs[tp.blob].channels == 64)
             e->first_gram_blob = tp.blob;
     }
@@ -913,13 +988,17 @@ static int sc_grad_run(stx_engine *e, const TileCall &c, const TilePlan &plan, P
                 !(sw_env("STX_TERMS_LATE") && atoi(sw_env("STX_TERMS_LATE"))),
                 std::vector<std::vector<Term>>(order.size()), {}, 0};
     while (e->sgrad_tap.size() < order.size()) e->sgrad_tap.emplace_back(new DevBuf);
-    if (run.sums_late) {
+    {
         size_t need = 0;
         for (const Tap &tp : order) {
             if (!tp.t->is_style) continue;
             const Blob &b = e->blobs[tp.blob];
-            for (const StyleTarget &st : e->sh->styles)
-                if (st.blob == tp.blob) need += style_term_scratch_floats(b.channels, b.h * b.w);
+            for (const StyleTarget &st : e->sh->styles) {
+                if (st.blob != tp.blob) continue;
+                if (run.sums_late) need += style_term_scratch_floats(b.channels, b.h * b.w);
+                // (a masked term's partials live there too, with or without the late sums)
+                if (style_mask_of(e, st.index, tp.blob)) need += kMaskScratchFloats;
+            }
         }
         STX_TRY(e->term_scratch.ensure(need * sizeof(float)));
     }

@@ -179,6 +179,15 @@ class DistributedTiles:
         return None
 
 
+def refuse_style_masks(args):
+    """--style-masks with one process per GPU: the masks would have to travel to every rank with the
+    targets, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
+    if getattr(args, 'style_masks', None):
+        raise NotImplementedError('--style-masks is not implemented for the one-process-per-GPU layout '
+                                  '(style_transfer_amd.dist): the masks are not broadcast to the ranks; '
+                                  'run the single-process tile farm (--devices) instead')
+
+
 def _wire_device(device, group):
     if torch.device(device).type == 'cuda' and dist.get_backend(group) == 'gloo':
         return torch.device('cpu')          # host-staged debug path, see DistributedTiles
@@ -215,7 +224,7 @@ def broadcast_weights(weights, device, group=None):
     return out
 
 
-def broadcast_targets(contents, styles, device, group=None):
+def broadcast_targets(contents, styles, device, group=None, args=None):
     """Broadcasts rank 0's targets (lists of {layer: array}) to every rank, once per scale.
     Sources may be numpy arrays, torch tensors or DeviceArrays (``__cuda_array_interface__``:
     broadcast in place on RCCL; ``.get()`` on the gloo debug wire); the result is lists of
@@ -224,7 +233,10 @@ def broadcast_targets(contents, styles, device, group=None):
     Ownership: on rank 0 a tensor made from a DeviceArray IS that array's memory (no copy: the
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
-    The other ranks get allocations of their own."""
+    The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
+    a run with --style-masks is refused here (refuse_style_masks)."""
+    if args is not None:
+        refuse_style_masks(args)
     rank = dist.get_rank(group)
     wire = _wire_device(device, group)
     meta = [None]

@@ -298,6 +298,26 @@ class TileEngine:
         lib.call('stx_set_contents_and_styles', self.handle, ctargets, n_c, starget, n_s)
         self.n_styles = len(styles)
 
+    def set_style_masks(self, masks):
+        """masks: one entry per style set of the current targets, in their order -- an [H, W] array
+        in [0, 1] in the content picture's frame (numpy, DeviceArray or torch tensor; white = the style
+        applies) or None (that style acts everywhere) -- or an empty list: no masks
+        (stx_set_style_masks).  Call it after ``set_contents_and_styles``, which clears them."""
+        keep, entries = [], []
+        for si, mask in enumerate(masks):
+            if mask is None:
+                continue
+            ptr, mem, obj = _as_arg(mask)
+            if len(obj.shape) != 2:
+                raise ValueError('style mask %d: an [H, W] array is expected, not %s' % (si, tuple(obj.shape)))
+            keep.append(obj)
+            entries.append((si, int(obj.shape[0]), int(obj.shape[1]), ptr, mem))
+        table = (lib.StyleMask * max(1, len(entries)))()
+        for t, (si, h, w, ptr, mem) in zip(table, entries):
+            t.style_index, t.H, t.W, t.mask, t.mem = si, h, w, ptr, mem
+        lib.call('stx_set_style_masks', self.handle, table, len(entries))
+        del keep
+
     # --------------------------------------------------------------------- FeatureMapRequest
     def features_tile(self, img, layers):
         """Post-ReLU feature maps of one tile: {layer: [C, ceil(th/s), ceil(tw/s)] ndarray}."""

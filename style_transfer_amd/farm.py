@@ -168,6 +168,14 @@ class TileFarm:
         for e in self.primaries():
             e.set_contents_and_styles(contents, styles)
 
+    def set_style_masks(self, masks):
+        """Hands the style masks (TileEngine.set_style_masks) to every GPU, once each, the way the
+        targets are handed; call it behind ``set_contents_and_styles``."""
+        for e in self.engines:
+            e.sync()
+        for e in self.primaries():
+            e.set_style_masks(masks)
+
     def _engines_for(self, n_tiles):
         """The engines that share a step of n_tiles tiles, creating extra per-GPU engines on
         demand (engine i lives on device i mod n_devices, like the reference's round-robin)."""

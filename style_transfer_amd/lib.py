@@ -47,6 +47,11 @@ class StyleTarget(ctypes.Structure):
                 ('channels', ctypes.c_int), ('gram', ctypes.c_void_p), ('mem', ctypes.c_int)]
 
 
+class StyleMask(ctypes.Structure):
+    _fields_ = [('style_index', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int),
+                ('mask', ctypes.c_void_p), ('mem', ctypes.c_int)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -76,6 +81,7 @@ SIGNATURES = {
     'stx_memcpy_async': [_vp, _vp, _i, _vp, _i, _sz],
     'stx_set_contents_and_styles': [_vp, ctypes.POINTER(ContentTarget), _i,
                                     ctypes.POINTER(StyleTarget), _i],
+    'stx_set_style_masks': [_vp, ctypes.POINTER(StyleMask), _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
     'stx_sc_grad_tile': [_vp, _vp, _i, _i, _i, c_int_p, c_int_p, ctypes.POINTER(Tap), _i,
@@ -84,6 +90,7 @@ SIGNATURES = {
     'stx_gram_matrix': [_vp, _vp, _i, _i, _i, _vp, _i],
     'stx_image_cut_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
     'stx_image_put_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
+    'stx_image_mask_map': [_vp, _vp, _i, _i, _i, _vp],
     'stx_map_place': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i],
     'stx_map_roll_add': [_vp, _vp, _vp, _i, _i, _i, c_int_p, _d, _d],
     'stx_image_resample': [_vp, _vp, _i, _i, _i, _vp, _i, _i, c_int_p, c_double_p, _i, c_int_p,
@@ -116,6 +123,7 @@ SIGNATURES = {
     'stx_op_pool_forward': [_vp, _vp, _i, _i, _i, _i, _vp],
     'stx_op_pool_backward': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     'stx_op_style_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p, c_double_p],
+    'stx_op_masked_style_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],
     'stx_last_tile_flops': [_vp, c_double_p, c_double_p],

@@ -158,6 +158,12 @@ class StyleTransfer:
             raise ValueError('--preserve-color %s: one of %s' % (self.preserve_color,
                                                                  ', '.join(PRESERVE_COLOR)))
         self._luma_content = None   # DeviceArray [3,H,W] ('luma' only)
+        # --style-masks (spatial control; not an option of the reference): one greyscale PIL picture per
+        # style image in the content picture's frame, handed to transfer_multiscale.  With masks every
+        # style picture is a style set of its own, and the masks -- resized to the scale's content size --
+        # go to the engines behind the targets.  None: no new code runs.
+        self.style_masks = None
+        self._scale_masks = None    # [H, W] float32 arrays in [0, 1] of the scale being optimised
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
         # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
@@ -228,10 +234,27 @@ class StyleTransfer:
         A, b = image_ops.color_match_transform(image_ops.color_stats(self.engine, dev), target)
         return image_ops.color_affine(self.engine, dev, dev, A, b, self.mean)
 
+    def _masks_for(self, size_hw):
+        """The style masks at one scale: Lanczos-resized to the content size, clipped to [0, 1]."""
+        h, w = int(size_hw[0]), int(size_hw[1])
+        return [np.clip(np.float32(mask.convert('L').resize((w, h), Image.LANCZOS)) / np.float32(255), 0, 1)
+                for mask in self.style_masks]
+
+    def _send_masks(self, roll=None):
+        """The scale's masks to the engines, behind the targets (which clear them).  ``roll`` (--jitter):
+        the engines hold content maps of the rolled picture and shift nothing, so the masks are rolled too."""
+        if self._scale_masks is None:
+            return
+        masks = self._scale_masks
+        if roll is not None:
+            masks = [np.roll(m, (int(roll[1]), int(roll[0])), (0, 1)) for m in masks]
+        self.farm.set_style_masks(masks)
+
     def preprocess_images(self, content_images, style_images, content_layers, style_layers,
                           roll=None, color_from=None):
         """Targets of one scale: the style Grams, averaged with equal weight over every style
-        image and ladder size, and the tiling-averaged content features
+        image and ladder size (with --style-masks: over the ladder sizes of each style image, one
+        style set per image), and the tiling-averaged content features
         (style_transfer.py:488-554).  Everything stays on the master GPU.  ``roll`` (--jitter,
         once per iteration): features of the pictures rolled by it, one pass, no messages.
         ``color_from`` (--preserve-color match): every style variant is recoloured on the GPU to the
@@ -260,7 +283,11 @@ class StyleTransfer:
                         feat.free()
                         total[layer] = gram if layer not in total else total[layer] + gram
                     count += 1
-            self.styles.append({layer: gram / count for layer, gram in total.items()})
+                if self.style_masks is not None and count:     # one style set per picture
+                    self.styles.append({layer: gram / count for layer, gram in total.items()})
+                    total, count = {}, 0
+            if self.style_masks is None:
+                self.styles.append({layer: gram / count for layer, gram in total.items()})
         if roll is None:
             print('Preprocessing the content image(s)...')
         self.contents += [farm.prepare_features_device(self.pil_to_image(image), content_layers,
@@ -340,6 +367,12 @@ class StyleTransfer:
                                [] if jitter else content_layers, style_layers,
                                color_from=content_images[0] if self.preserve_color == 'match' else None)
         self.farm.set_contents_and_styles(self.contents, self.styles)
+        if self.style_masks is not None:
+            if len(self.styles) != len(self.style_masks):
+                raise ValueError('--style-masks: %d mask(s) for %d style set(s)'
+                                 % (len(self.style_masks), len(self.styles)))
+            self._scale_masks = self._masks_for(self.img.shape[1:])
+            self._send_masks()
 
         if self.grad is None or self.grad.shape != self.img.shape:
             for buf in (self.grad, self.old_avg):
@@ -431,6 +464,7 @@ class StyleTransfer:
                 self._drop_contents()
                 self.preprocess_images(content_images, [], content_layers, [], roll=roll)
                 self.farm.set_contents_and_styles(self.contents, self.styles)
+                self._send_masks(roll=roll)
                 content_roll = (0, 0)
             sc_args = (roll, content_layers, style_layers, content_weight, style_weight,
                        dd_layers, dd_weight, content_roll)
@@ -479,12 +513,19 @@ class StyleTransfer:
         raise ValueError(args.optimizer)
 
     def transfer_multiscale(self, content_images, style_images, initial_image=None, aux_image=None,
-                            callback=None):
+                            callback=None, style_masks=None):
         """Runs the planned pyramid (plan_scales), coarsest level first; every level starts from
-        the Lanczos-upsampled averaged iterate of the one before (style_transfer.py:832-909)."""
+        the Lanczos-upsampled averaged iterate of the one before (style_transfer.py:832-909).
+        ``style_masks`` (--style-masks): one greyscale PIL picture per style image."""
         args = self.args
         if any(image.size != content_images[0].size for image in content_images):
             raise ValueError('All of the content images must be the same size')
+        if style_masks:
+            if len(style_masks) != len(style_images):
+                raise ValueError('--style-masks: %d mask(s) for %d style image(s); one per style image '
+                                 'is needed' % (len(style_masks), len(style_images)))
+            self.style_masks = list(style_masks)
+            self.styles = []
         plans = plan_scales(args, content_images[0].size, [image.size for image in style_images])
         if callback is not None and hasattr(callback, 'set_steps'):
             callback.set_steps(sum(plan.iterations for plan in plans))
