@@ -416,6 +416,36 @@ int stx_image_color_stats(stx_engine *e, const float *img, int H, int W, double 
 int stx_image_color_affine(stx_engine *e, const float *src, float *dst, int H, int W, const double A[9],
                            const double b[3], const float mean_bgr[3]);
 
+/* The Laplacian loss (Li, Xu, Nie, Liu, "Laplacian-Steered Neural Style Transfer", 2017): holds the
+ * iterate to the edges of a content picture.  Pictures are [3][H][W] float32 STX_DEVICE arrays, BGR
+ * planes with the mean subtracted, un-rolled; the term ignores the iteration's shift.  For a pool
+ * size p:
+ *   u(x)  = (x_B + x_G + x_R) / 382.5
+ *   P_p u = block means over p x p blocks from the picture's origin: hp x wp = ceil(H / p) x
+ *           ceil(W / p) cells, edge cells over the pixels that exist
+ *   D v   = sum over the 4-neighbours n inside the grid of (v - v_n)   ([0 -1 0; -1 4 -1; 0 -1 0]
+ *           with a replicated border: symmetric, and zero on constants, so the mean never enters)
+ *   T_p   = D P_p u(content),   e_p = D P_p u(img) - T_p
+ *   loss  = scale * sum_p weights[p] * sum_cells e_p^2
+ *   grad[ch][y][x] += scale * sum_p weights[p] * 2 (D e_p)[y / p][x / p] / (n_cell * 382.5), every ch
+ * pools: n_pools = 1..4 distinct powers of two in 1..64; anything else, or a null pointer, is
+ * STX_ERR_ARG.  The image is read once whatever n_pools is, and the gradient is read and written
+ * once: the per-pixel sum over the sizes is formed first and added to each plane in one float32
+ * addition (pixels whose sum is zero are not touched).  The target and the image run through the
+ * same device code: img == content gives a loss of exactly 0 and leaves grad as it is.  No atomics:
+ * the same inputs give the same bits.
+ *   stx_image_lap_floats:  floats of a target = sum over pools of hp * wp (0 on a bad argument)
+ *   stx_image_lap_target:  target_out (STX_DEVICE) = [T_p for p in pools], map after map; asynchronous
+ *   stx_image_lap:         *loss_out (host) is written at the next stx_sync; asynchronous like
+ *                          stx_image_regularizers.  target: what stx_image_lap_target left for the
+ *                          same H, W and pools. */
+size_t stx_image_lap_floats(int H, int W, int n_pools, const int *pools);
+int stx_image_lap_target(stx_engine *e, const float *content, int H, int W, int n_pools,
+                         const int *pools, float *target_out);
+int stx_image_lap(stx_engine *e, const float *img, float *grad, int H, int W, int n_pools,
+                  const int *pools, const double *weights, const float *target, double scale,
+                  double *loss_out);
+
 /* ------------------------------------------------------------- single-kernel test hooks */
 /* Direct entry points to the individual kernels, used by tests/ to check each against the
  * oracle (x, w, b, y: STX_DEVICE).  w is the Caffe layout [Cout][Cin][k][k]. */

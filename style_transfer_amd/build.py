@@ -31,6 +31,7 @@ SOURCES = {
     'image_ops.hip': ['-ffp-contract=off'],
     'swt.hip': ['-ffp-contract=off'],
     'style_mask.hip': ['-ffp-contract=off'],
+    'lap.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'tile_path.cpp': [],

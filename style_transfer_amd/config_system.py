@@ -114,6 +114,14 @@ _EXTENSIONS = [
                                    "picture's frame; a style applies where its mask is white.  With masks "
                                    'every style image is a style set of its own instead of one average '
                                    '(default: no masks)')),
+    (('--lap-weight',), dict(metavar='WEIGHT', type=ffloat,
+                             help="Laplacian loss factor: holds the result to the content picture's edges "
+                                  '(the Laplacian of the average-pooled result against that of the '
+                                  'average-pooled content picture); 0 or absent: off (default: 0)')),
+    (('--lap-pools',), dict(nargs='+', metavar='POOL',
+                            help='pool sizes of the Laplacian loss as P or P:weight, one to four distinct '
+                                 'powers of two from 1 to 64; the weights are normalised to --lap-weight '
+                                 'like those of a layer list (default: 4)')),
 ]
 
 
@@ -185,6 +193,38 @@ def check_style_masks(args):
     return list(masks) if masks else []
 
 
+LAP_POOLS_DEFAULT = ('4',)
+LAP_POOL_SIZES = (1, 2, 4, 8, 16, 32, 64)
+
+
+def check_lap_pools(args):
+    """The pool sizes of --lap-pools (``P`` or ``P:weight`` each), or of its default when only --lap-weight
+    is set, as integers: one to four distinct powers of two from 1 to 64.  Anything else is refused
+    before any GPU work.  [] when neither option is set."""
+    if getattr(args, 'lap_pools', None) is None and not hasattr(args, 'lap_weight'):
+        return []
+    given = getattr(args, 'lap_pools', None) or LAP_POOLS_DEFAULT
+    if isinstance(given, str):
+        given = [given]
+    pools = []
+    for item in given:
+        name, _, weight = str(item).partition(':')
+        try:
+            size = int(name)
+            if weight:
+                ffloat(weight)
+        except (ValueError, ZeroDivisionError):
+            raise ValueError('--lap-pools %s: P or P:weight is expected' % item) from None
+        if size not in LAP_POOL_SIZES:
+            raise ValueError('--lap-pools %s: the pool size must be a power of two from 1 to 64' % item)
+        if size in pools:
+            raise ValueError('--lap-pools: pool size %d is given twice' % size)
+        pools.append(size)
+    if len(pools) > 4:
+        raise ValueError('--lap-pools: %d pool sizes, but four at most are taken' % len(pools))
+    return pools
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -209,4 +249,5 @@ def parse_args(state=None, argv=None, config_py=None):
         parser.print_help()
         sys.exit(1)
     check_style_masks(args)
+    check_lap_pools(args)
     return args

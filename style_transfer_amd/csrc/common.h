@@ -475,6 +475,8 @@ int resample_launch(hipStream_t s, int axis, const float *src, int C, int H, int
                     int OH, int OW, const int *bounds, const double *k, int ksize, int clamp);
 // *out_dev = sum of n float partials, added in double in a fixed order
 int finish_partials_launch(hipStream_t s, const float *partials, int n, double *out_dev);
+// the same for nv = 1..4 values: out_dev[k] = sum of partials[k * n .. k * n + n)
+int finish_partials_n_launch(hipStream_t s, const float *partials, int n, int nv, double *out_dev);
 int regularizers_launch(hipStream_t s, const float *img, float *grad, int H, int W,
                         const float mean[3], float tv_scale, float tv_power, float p_scale,
                         float p_power, const float *aux, float aux_scale, int aux_rx, int aux_ry,
@@ -499,6 +501,24 @@ void swt_daub_table(int order, int levels, int N, std::vector<float> *taps, int 
 int swt_table_launch(hipStream_t s, const float *img, float *grad, int H, int W, const float *table,
                      int ntaps, int hl, int rx, int ry, float scale, float power,
                      double *loss_term, float *tmp, float *partials);
+
+// lap.hip: the Laplacian loss.  lap_levels describes the pooled grids of the pool sizes (distinct powers
+// of two, 1..64, at most kLapMaxPools: the caller has checked) and returns their floats in all, which is
+// the size of a target; map k starts at off[k].  scratch holds lap_scratch_floats(that count) floats.
+constexpr int kLapMaxPools = 4;
+struct LapLevels {
+    int n;
+    int lp[kLapMaxPools], hp[kLapMaxPools], wp[kLapMaxPools], off[kLapMaxPools];    // log2 p, grid, offset
+};
+size_t lap_levels(int H, int W, int n_pools, const int *pools, LapLevels *lv);
+size_t lap_scratch_floats(size_t map_floats);
+// target = [D P_p u(content) for p in pools]
+int lap_target_launch(hipStream_t s, const float *content, int H, int W, const LapLevels &lv,
+                      float *target, float *scratch);
+// grad += sum_p 2 coefs[p] (D e_p) / (n_cell 382.5) per pixel, loss_terms[p] = sum e_p^2
+int lap_launch(hipStream_t s, const float *img, float *grad, int H, int W, const LapLevels &lv,
+               size_t map_floats, const float *coefs, const float *target, double *loss_terms,
+               float *scratch);
 
 // image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,

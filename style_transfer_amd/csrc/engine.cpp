@@ -419,7 +419,7 @@ void stx_engine_destroy(stx_engine *e) {
         for (auto &m : e->sh->masks) m.map->release();
     }
     DevBuf *bufs[] = {&e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
-                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->first_gram, &e->color_sums};
+                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
     for (stx_engine::ScalarArena &a : e->arena) {

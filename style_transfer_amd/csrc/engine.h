@@ -1,7 +1,7 @@
 // The engine's state and the few helpers that more than one host file uses.  Internal: not installed.
 //   engine.cpp     engine life cycle, weights and targets, scalar arenas and fences, profiling readers
 //   tile_path.cpp  the tile evaluation: forward pass, loss terms, backward walk
-//   image_api.cpp  whole-image and vector entries, the SWT regulariser's tables
+//   image_api.cpp  whole-image and vector entries, the SWT regulariser's tables, the Laplacian loss
 //   op_hooks.cpp   stx_op_*: single operators for the tests
 #pragma once
 
@@ -197,6 +197,7 @@ struct stx_engine {
         DevBuf taps;
     };
     std::vector<SwtTable> swt_tables;  // built at first use, kept: a step uploads nothing
+    DevBuf lap_scratch;                // stx_image_lap / _target: pooled maps, cell values, partials
 
     bool winograd = true;   // 1-D Winograd F(2,3) for the 3x3 layers (STX_WINOGRAD=0: direct only)
     bool autotune = true;   // tile-config autotuning (process-wide cache, see conv_choose)

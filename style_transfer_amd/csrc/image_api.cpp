@@ -1,8 +1,9 @@
 // libstx host side: the entries that work on whole images, feature maps and parameter vectors
 // (stx_image_*, stx_map_*, stx_vec_*, stx_adam_step) -- thin wrappers that check their arguments and
-// queue one or two launches of image_ops.hip / reduce.hip / swt.hip on the engine's stream.
+// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip on the engine's stream.
 
 #include <cmath>
+#include <cstdint>
 #include <functional>
 #include <initializer_list>
 
@@ -85,23 +86,26 @@ int stx_image_resample(stx_engine *e, const float *src, int channels, int H, int
     return STX_OK;
 }
 
-// Queues n = coefs.size() double-precision loss terms: `launch` enqueues the kernels that leave them at the
-// device pointer it is handed, they are mirrored to the host arena, and at the next sync *loss_out becomes
+// Queues n double-precision loss terms: `launch` enqueues the kernels that leave them at the device
+// pointer it is handed, they are mirrored to the host arena, and at the next sync *loss_out becomes
 // sum coefs[i] * term[i].
-static int queue_dterms(stx_engine *e, std::initializer_list<double> coefs, double *loss_out,
+static int queue_dterms(stx_engine *e, const double *coefs, size_t n, double *loss_out,
                         const std::function<int(double *)> &launch) {
     size_t di;
-    STX_TRY(alloc_dscalars(e, coefs.size(), &di));
+    STX_TRY(alloc_dscalars(e, n, &di));
     double *terms = static_cast<double *>(e->A().dscalars.ptr) + di;
     STX_TRY(launch(terms));
-    STX_HIP(hipMemcpyAsync(e->A().dhost + di, terms, coefs.size() * sizeof(double),
-                           hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipMemcpyAsync(e->A().dhost + di, terms, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     PendingLoss pl;
     pl.out = loss_out;
-    size_t i = di;
-    for (double coef : coefs) pl.dterms.push_back(LossTerm{i++, coef});
+    for (size_t i = 0; i < n; ++i) pl.dterms.push_back(LossTerm{di + i, coefs[i]});
     e->A().pending.push_back(std::move(pl));
     return STX_OK;
+}
+
+static int queue_dterms(stx_engine *e, std::initializer_list<double> coefs, double *loss_out,
+                        const std::function<int(double *)> &launch) {
+    return queue_dterms(e, coefs.begin(), coefs.size(), loss_out, launch);
 }
 
 int stx_image_regularizers(stx_engine *e, const float *img, float *grad, int H, int W,
@@ -215,6 +219,97 @@ int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int 
         return swt_table_launch(e->stream, img, grad, H, W, tab->taps.f(), tab->ntaps, tab->hl,
                                 roll_xy ? roll_xy[0] : 0, roll_xy ? roll_xy[1] : 0, (float)scale,
                                 (float)power, term, tmp, partials);
+    });
+}
+
+// ---- the Laplacian loss (lap.hip) ----
+
+// 1..4 distinct powers of two in 1..64; on success *lv describes the grids and *floats is their size
+static int lap_check(const char *name, int H, int W, int n_pools, const int *pools, LapLevels *lv,
+                     size_t *floats) {
+    if (!pools) {
+        set_error("%s: pools is null", name);
+        return STX_ERR_ARG;
+    }
+    if (H <= 0 || W <= 0) {
+        set_error("%s: a %d x %d picture", name, H, W);
+        return STX_ERR_ARG;
+    }
+    if (n_pools < 1 || n_pools > kLapMaxPools) {
+        set_error("%s: n_pools = %d, but 1 to %d pool sizes are taken", name, n_pools, kLapMaxPools);
+        return STX_ERR_ARG;
+    }
+    for (int k = 0; k < n_pools; ++k) {
+        const int p = pools[k];
+        if (p < 1 || p > 64 || (p & (p - 1))) {
+            set_error("%s: pool size %d is not a power of two in 1..64", name, p);
+            return STX_ERR_ARG;
+        }
+        for (int j = 0; j < k; ++j)
+            if (pools[j] == p) {
+                set_error("%s: pool size %d is given twice", name, p);
+                return STX_ERR_ARG;
+            }
+    }
+    *floats = lap_levels(H, W, n_pools, pools, lv);
+    if (*floats > (size_t)INT32_MAX) {
+        set_error("%s: %zu cells on the pooled grids of a %d x %d picture (at most 2^31 - 1)", name, *floats,
+                  H, W);
+        return STX_ERR_ARG;
+    }
+    return STX_OK;
+}
+
+static int lap_scratch_for(stx_engine *e, size_t floats, float **scratch) {
+    // growing frees the old buffer, which waits for the kernels that still read it
+    STX_TRY(e->lap_scratch.ensure(lap_scratch_floats(floats) * sizeof(float)));
+    *scratch = e->lap_scratch.f();
+    return STX_OK;
+}
+
+size_t stx_image_lap_floats(int H, int W, int n_pools, const int *pools) {
+    LapLevels lv;
+    size_t floats;
+    return lap_check("stx_image_lap_floats", H, W, n_pools, pools, &lv, &floats) == STX_OK ? floats : 0;
+}
+
+int stx_image_lap_target(stx_engine *e, const float *content, int H, int W, int n_pools, const int *pools,
+                         float *target_out) {
+    if (!e || !content || !target_out) {
+        set_error("stx_image_lap_target: %s is null", !e ? "the engine" : !content ? "content" : "target_out");
+        return STX_ERR_ARG;
+    }
+    LapLevels lv;
+    size_t floats;
+    STX_TRY(lap_check("stx_image_lap_target", H, W, n_pools, pools, &lv, &floats));
+    STX_TRY(e->set_device());
+    float *scratch;
+    STX_TRY(lap_scratch_for(e, floats, &scratch));
+    return lap_target_launch(e->stream, content, H, W, lv, target_out, scratch);
+}
+
+int stx_image_lap(stx_engine *e, const float *img, float *grad, int H, int W, int n_pools, const int *pools,
+                  const double *weights, const float *target, double scale, double *loss_out) {
+    if (!e || !img || !grad || !weights || !target || !loss_out) {
+        set_error("stx_image_lap: %s is null", !e ? "the engine" : !img ? "img" : !grad ? "grad" :
+                  !weights ? "weights" : !target ? "target" : "loss_out");
+        return STX_ERR_ARG;
+    }
+    LapLevels lv;
+    size_t floats;
+    STX_TRY(lap_check("stx_image_lap", H, W, n_pools, pools, &lv, &floats));
+    STX_TRY(e->set_device());
+    float *scratch;
+    STX_TRY(lap_scratch_for(e, floats, &scratch));
+    // one loss term per pool size, sum e_p^2, with coefficient scale * w_p; the cells get 2 scale w_p (D e_p)
+    double coefs[kLapMaxPools];
+    float cell_coefs[kLapMaxPools];
+    for (int k = 0; k < n_pools; ++k) {
+        coefs[k] = scale * weights[k];
+        cell_coefs[k] = (float)(2.0 * coefs[k]);
+    }
+    return queue_dterms(e, coefs, (size_t)n_pools, loss_out, [&](double *terms) {
+        return lap_launch(e->stream, img, grad, H, W, lv, floats, cell_coefs, target, terms, scratch);
     });
 }
 

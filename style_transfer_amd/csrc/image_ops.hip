@@ -68,6 +68,18 @@ int finish_partials_launch(hipStream_t s, const float *partials, int n, double *
     return STX_OK;
 }
 
+int finish_partials_n_launch(hipStream_t s, const float *partials, int n, int nv, double *out_dev) {
+    switch (nv) {
+        case 1: finish_partials_kernel<1><<<1, 256, 0, s>>>(partials, n, out_dev); break;
+        case 2: finish_partials_kernel<2><<<1, 256, 0, s>>>(partials, n, out_dev); break;
+        case 3: finish_partials_kernel<3><<<1, 256, 0, s>>>(partials, n, out_dev); break;
+        case 4: finish_partials_kernel<4><<<1, 256, 0, s>>>(partials, n, out_dev); break;
+        default: set_error("finish_partials: %d values", nv); return STX_ERR_ARG;
+    }
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
 // ------------------------------------------------------------------------------ cut / put ---
 __device__ __forceinline__ int wrap(int v, int n) {
     v %= n;

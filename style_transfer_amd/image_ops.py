@@ -121,6 +121,49 @@ def swt_haar(engine, img, grad, scale, power, roll=None, levels=1):
     return _swt(engine, img, grad, scale, power, 1, levels, roll)
 
 
+# ---------------------------------------------------------------------- --lap-weight
+def _pools(pools):
+    return len(pools), (ctypes.c_int * len(pools))(*[int(p) for p in pools])
+
+
+def lap_floats(h, w, pools):
+    """Floats of the Laplacian term's target for an h x w picture: the cells of the pooled grids,
+    sum over pools of ceil(h / p) * ceil(w / p) (0 when the library refuses the pool sizes)."""
+    return int(lib.load().stx_image_lap_floats(int(h), int(w), *_pools(pools)))
+
+
+def lap_target(engine, content, pools):
+    """The Laplacian term's target for the content picture [3,H,W] on the engine's GPU: a
+    DeviceArray holding, map after map, D P_p u(content) for every pool size p (include/stx.h has the
+    definition).  ``pools``: one to four distinct powers of two in 1..64."""
+    _, H, W = content.shape
+    n = lap_floats(H, W, pools)
+    target = engine.empty((max(n, 1),))
+    try:
+        lib.call('stx_image_lap_target', engine.handle, content.ptr, H, W, *_pools(pools), target.ptr)
+    except lib.StxError:
+        target.free()
+        raise
+    return target
+
+
+def lap_loss(engine, img, grad, target, pools, weights, scale):
+    """grad += the gradient of scale * sum_p weights[p] * sum |D P_p u(img) - T_p|^2 (the Laplacian
+    loss; ``target`` is ``lap_target`` of the same size and pools); returns a PendingScalar with
+    the loss (valid after sync)."""
+    _, H, W = img.shape
+    assert len(weights) == len(pools), (weights, pools)
+    n = lap_floats(H, W, pools)         # 0: the library refuses the pools below, in its own words
+    if n and target.size != n:
+        raise ValueError('lap_loss: a target of %d floats, but a %d x %d picture with pools %s has %d cells'
+                         % (target.size, H, W, list(pools), n))
+    out = engine.keep_until_sync(PendingScalar())
+    w = (ctypes.c_double * len(weights))(*[float(v) for v in weights])
+    lib.call('stx_image_lap', engine.handle, img.ptr, grad.ptr, H, W, *_pools(pools), w, target.ptr,
+             float(scale), ctypes.byref(out._v))
+    return out
+
+
 def adam_step(engine, params, grad, g1, g2, p1, avg, lr, b1, b2, bp1, corr1, corr2, corrp):
     lib.call('stx_adam_step', engine.handle, params.ptr, grad.ptr, g1.ptr, g2.ptr, p1.ptr, avg.ptr,
              params.size, float(lr), float(b1), float(b2), float(bp1), float(corr1), float(corr2),

@@ -59,7 +59,7 @@ class Tap(ctypes.Structure):
                 ('is_dd', ctypes.c_int), ('dd_weight', ctypes.c_double)]
 
 
-# name -> argtypes; every function returns int status except the three noted below.
+# name -> argtypes; every function returns int status except the few noted below.
 _vp, _i, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
 SIGNATURES = {
     'stx_reread_env': [],
@@ -100,6 +100,8 @@ SIGNATURES = {
     'stx_image_swt_haar': [_vp, _vp, _vp, _i, _i, c_int_p, _d, _d, c_double_p],
     'stx_image_swt_haar_levels': [_vp, _vp, _vp, _i, _i, _i, c_int_p, _d, _d, c_double_p],
     'stx_image_swt_daub_levels': [_vp, _vp, _vp, _i, _i, _i, _i, c_int_p, _d, _d, c_double_p],
+    'stx_image_lap_target': [_vp, _vp, _i, _i, _i, c_int_p, _vp],
+    'stx_image_lap': [_vp, _vp, _vp, _i, _i, _i, c_int_p, c_double_p, _vp, _d, c_double_p],
     'stx_adam_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _d, _d, _d, _d, _d, _d, _d],
     'stx_vec_dot': [_vp, _vp, _vp, _sz, c_double_p],
     'stx_vec_axpy': [_vp, _d, _vp, _vp, _sz],
@@ -133,7 +135,8 @@ SIGNATURES = {
     'stx_profile_read': [_vp, ctypes.c_char_p, _sz, ctypes.POINTER(_sz)],
 }
 NON_STATUS = {'stx_version': (ctypes.c_char_p, []), 'stx_last_error': (ctypes.c_char_p, []),
-              'stx_engine_destroy': (None, [_vp])}
+              'stx_engine_destroy': (None, [_vp]),
+              'stx_image_lap_floats': (_sz, [_i, _i, _i, c_int_p])}
 
 _lib = None
 

@@ -23,7 +23,7 @@ import numpy as np
 from PIL import Image
 
 from . import image_ops, lib
-from .config_system import ffloat
+from .config_system import LAP_POOLS_DEFAULT, check_lap_pools, ffloat
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
 
@@ -123,6 +123,13 @@ def parse_weights(args, master_weight):
     return names, {n: w * master_weight / total for n, w in weights.items()}
 
 
+def lap_pool_weights(pools, lap_weight):
+    """--lap-pools ['4', '16:3'] and --lap-weight 30 -> ([4, 16], [7.5, 22.5]): the pool sizes and their
+    weights, normalised to sum |w| = lap_weight exactly as a layer list's are (parse_weights)."""
+    names, weights = parse_weights(list(pools), lap_weight)
+    return [int(name) for name in names], [weights[name] for name in names]
+
+
 class StyleTransfer:
     """Runs style transfer on a ``TileFarm``.  ``args`` is the option namespace of
     ``config_system.parse_args`` (any object with the same attributes works)."""
@@ -164,6 +171,14 @@ class StyleTransfer:
         # go to the engines behind the targets.  None: no new code runs.
         self.style_masks = None
         self._scale_masks = None    # [H, W] float32 arrays in [0, 1] of the scale being optimised
+        # --lap-weight / --lap-pools (the Laplacian loss; not options of the reference): the target of the
+        # scale being optimised, D P_p u of its first content picture for every pool size, on the master
+        # GPU.  Without the options nothing here runs.
+        raw = getattr(getattr(args, 'ns', args), 'lap_weight', 0)
+        self._lap_on = bool(callable(raw) or raw)
+        self._lap_pools = check_lap_pools(args) if self._lap_on else []
+        self._lap_target = None
+        self._lap_weights_key = self._lap_weights_now = None    # the last (--lap-pools, lap_weight) parsed
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
         # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
@@ -330,7 +345,28 @@ class StyleTransfer:
             swt = image_ops.swt_haar(self.engine, params, self.grad, lw * args.swt_weight,
                                      args.swt_power, roll=roll, levels=int(args.swt_levels))
             loss.add(swt, self.engine)
+        lap_weight = getattr(args, 'lap_weight', 0) if self._lap_target is not None else 0
+        if lap_weight:
+            # the pool weights carry --lap-weight (sum |w| = lap_weight), the scale the data layer's factor
+            lap = image_ops.lap_loss(self.engine, params, self.grad, self._lap_target, self._lap_pools,
+                                     self._lap_weights(args, lap_weight), lw)
+            loss.add(lap, self.engine)
         return loss, self.grad
+
+    def _lap_weights(self, args, lap_weight):
+        """The weights of the target's pool sizes for this evaluation.  The sizes are those the target was
+        made for: the target's layout follows from them, so an ``args.lap_pools`` that names other sizes
+        by now is refused and never reaches the kernels."""
+        spec = getattr(args, 'lap_pools', None) or LAP_POOLS_DEFAULT
+        key = (tuple([spec] if isinstance(spec, str) else spec), lap_weight)
+        if key != self._lap_weights_key:
+            pools, weights = lap_pool_weights(key[0], lap_weight)
+            if pools != self._lap_pools:
+                raise ValueError('--lap-pools changed from %s to %s during the run; the pool sizes are fixed '
+                                 'when the run starts, only their weights may move'
+                                 % (self._lap_pools, pools))
+            self._lap_weights_key, self._lap_weights_now = key, weights
+        return self._lap_weights_now
 
     # --------------------------------------------------------------------------- one scale
     def transfer(self, iterations, content_images, style_images, callback=None):
@@ -363,6 +399,16 @@ class StyleTransfer:
             if self._luma_content is not None:
                 self._luma_content.free()
             self._luma_content = self.engine.to_device(self.pil_to_image(content_images[0]))
+        if self._lap_on:
+            picture = self._luma_content
+            if picture is None:
+                picture = self.engine.to_device(self.pil_to_image(content_images[0]))
+            target = image_ops.lap_target(self.engine, picture, self._lap_pools)
+            if self._lap_target is not None:
+                self._lap_target.free()
+            self._lap_target = target
+            if picture is not self._luma_content:
+                picture.free()
         self.preprocess_images([] if jitter else content_images, style_images,
                                [] if jitter else content_layers, style_layers,
                                color_from=content_images[0] if self.preserve_color == 'match' else None)
