@@ -190,6 +190,39 @@ typedef struct stx_style_mask {
  * surfaces as the window range error at evaluation. */
 int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n);
 
+/* The mean / std style term (not in the reference): the BN-statistics loss of Li et al., "Demystifying
+ * Neural Style Transfer", the quantity AdaIN aligns.  A tapped blob F [C][h][w] -- the array the Gram term
+ * reads -- is held to per-channel targets MU, SD.  With n = h w and eps = 1e-5:
+ *   mu_c  = (1/n) sum_x F_c(x)
+ *   var_c = (1/n) sum_x (F_c(x) - mu_c)^2                  (population variance)
+ *   sd_c  = sqrt(var_c + eps)
+ *   E     = sum_c [ (mu_c - MU_c)^2 + (sd_c - SD_c)^2 ]
+ *   S_c(x) = (mu_c - MU_c) + (sd_c - SD_c) (F_c(x) - mu_c) / sd_c        ( = n d(E/2)/dF_c(x) )
+ *   loss        += lw weight E / 2
+ *   diff[layer] += lw weight S / (sum|S| / (C n) + EPS)
+ * The last line is the reference's normalize, exactly as for the Gram term (EPS: float32 epsilon).  A
+ * tile's statistics are the tile's own, as its Gram is.  mu and sd are rounded to float32 once and
+ * everything else is formed from the rounded values: a tile whose statistics equal the targets (those
+ * stx_feature_stats gives for the same array) contributes exactly 0 to the loss and to the gradient.
+ * No atomics; the partial sums are added in a fixed order: the same inputs give the same bits. */
+typedef struct stx_stat_target {
+    const char *layer;
+    int channels;
+    const float *mean;      /* [channels] */
+    const float *sd;        /* [channels] */
+    int mem;
+    double weight;
+} stx_stat_target;
+/* Replaces all statistics targets of the engine's group (n = 0: none); one per layer at most.  They are
+ * shared like the style targets (stx_engine_create_shared) and stx_set_contents_and_styles clears them:
+ * call this behind it.  A channel count other than the layer's is STX_ERR_ARG here.  A layer with a
+ * target is part of every stx_sc_grad_tile evaluation: with the layer_weight of its tap if the tap list
+ * names it (whatever else the tap asks for, nothing included), with lw = 1 otherwise; a tap list without
+ * a content, style or Deep-Dream layer is then accepted, an empty one (n_taps = 0) too; the tapped layers
+ * and these still lie on one path (STX_ERR_UNSUPPORTED otherwise, at the evaluation).  The term follows the blob's style terms in the loss and in the gradient, in the same order on
+ * every call. */
+int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -239,6 +272,11 @@ int stx_tile_buffers(stx_engine *e, int th, int tw, float **tile_in, float **gra
  * (num_utils.py:143-147) as used for the style targets (style_transfer.py:534). */
 int stx_gram_matrix(stx_engine *e, const float *feat, int feat_mem, int channels, int hw,
                     float *gram_out, int gram_mem);
+
+/* Per-channel mean and sd = sqrt(population variance + 1e-5) of a feature map [channels][hw], as float32:
+ * what stx_set_stat_targets takes, by the launches the term itself runs on a tile's blob. */
+int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channels, int hw,
+                      float *mean_out, float *sd_out, int out_mem);
 
 /* ------------------------------------------------- full-image ops (device-resident state) */
 /* All pointers in this group are STX_DEVICE memory on the engine's GPU, images are [3][H][W].
@@ -476,6 +514,10 @@ int stx_op_style_terms(stx_engine *e, const float *feat, int channels, int h, in
 int stx_op_masked_style_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                               const float *mask_map, int mh, int mw, int oy, int ox, const int roll_xy[2],
                               const float *gram_target, float *sgrad_out, double out[3]);
+/* The launches of a statistics target (stx_set_stat_targets) on given arrays (all STX_DEVICE; MU, SD [channels]):
+ * out = {E / 2, sum |S|}; s_out = S. */
+int stx_op_stat_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *MU,
+                      const float *SD, float *s_out, double out[2]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

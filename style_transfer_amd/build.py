@@ -32,6 +32,7 @@ SOURCES = {
     'swt.hip': ['-ffp-contract=off'],
     'style_mask.hip': ['-ffp-contract=off'],
     'lap.hip': ['-ffp-contract=off'],
+    'stat.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'tile_path.cpp': [],

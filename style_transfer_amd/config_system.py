@@ -122,6 +122,17 @@ _EXTENSIONS = [
                             help='pool sizes of the Laplacian loss as P or P:weight, one to four distinct '
                                  'powers of two from 1 to 64; the weights are normalised to --lap-weight '
                                  'like those of a layer list (default: 4)')),
+    (('--stat-weight',), dict(metavar='WEIGHT', type=ffloat,
+                              help="mean / std style factor: holds every channel's mean and standard deviation "
+                                   'at the --stat-layers to those of the style picture(s) -- palette, contrast '
+                                   "and texture energy without the Gram's patterns; read once per scale; "
+                                   '0 or absent: off (default: 0)')),
+    (('--stat-layers',), dict(nargs='+', metavar='LAYER',
+                              help='layers of the mean / std style term as name or name:weight; the weights are '
+                                   'normalised to --stat-weight like those of a layer list and read once per '
+                                   'scale; with --style-multiscale the layers themselves stay those of the '
+                                   "first scale, whose targets are kept (default: the --style-layers' names "
+                                   'with weight 1 each; its built-in list when --style-layers is empty)')),
 ]
 
 
@@ -225,6 +236,52 @@ def check_lap_pools(args):
     return pools
 
 
+# the built-in --style-layers list (read from its entry above: one statement of it)
+STYLE_LAYERS_DEFAULT = tuple(next(kw['default'] for flags, kw in _OPTIONS if flags[0] == '--style-layers'))
+
+
+def stat_layer_args(args):
+    """The layer list of the mean / std style term (``name`` or ``name:weight`` each): --stat-layers, or the
+    names of the --style-layers when only --stat-weight is set (of its built-in list when it is empty: the
+    Gram term can be switched off that way).  [] when the term is off (no --stat-weight, or 0)."""
+    raw = getattr(getattr(args, 'ns', args), 'stat_weight', 0)
+    if not (callable(raw) or raw):
+        return []
+    given = getattr(args, 'stat_layers', None)
+    if not given:
+        given = [str(item).partition(':')[0] for item in args.style_layers] or STYLE_LAYERS_DEFAULT
+    return [given] if isinstance(given, str) else list(given)
+
+
+def check_stat_options(args, known_layers=None):
+    """--stat-weight / --stat-layers: refused before any GPU work together with --style-masks (there is one
+    statistics set and, with masks, one style set per picture), with a malformed entry, with a layer named
+    twice, with weights that are all 0 or -- when the network's layers are known -- with a layer it does not
+    have.  Returns the layer names."""
+    items = stat_layer_args(args)
+    if not items:
+        return []
+    if getattr(args, 'style_masks', None):
+        raise ValueError('--stat-weight cannot be combined with --style-masks: there is one set of statistics '
+                         'targets, and masks make every style picture a style set of its own')
+    names, total = [], 0.0
+    for item in items:
+        name, _, weight = str(item).partition(':')
+        try:
+            total += abs(ffloat(weight)) if weight else 1.0
+        except (ValueError, ZeroDivisionError):
+            raise ValueError('--stat-layers %s: LAYER or LAYER:weight is expected' % item) from None
+        if not name or name in names:
+            raise ValueError('--stat-layers %s: a layer name, given once, is expected' % item)
+        if known_layers is not None and (name not in known_layers or name == 'data'):
+            raise ValueError("--stat-layers %s: the network has no layer '%s'" % (item, name))
+        names.append(name)
+    if not total:
+        raise ValueError('--stat-layers %s: at least one layer weight must not be 0 (they are normalised '
+                         'to --stat-weight)' % ' '.join(map(str, items)))
+    return names
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -250,4 +307,5 @@ def parse_args(state=None, argv=None, config_py=None):
         sys.exit(1)
     check_style_masks(args)
     check_lap_pools(args)
+    check_stat_options(args)
     return args

@@ -462,6 +462,23 @@ int mask_target_launch(hipStream_t s, const float *gs, int C, const float *m2_pa
 int mask_sgrad_launch(hipStream_t s, float *sgrad, const float *map, const ContentWindow &win, const float *a,
                       float *partials, int *n_parts);
 
+// stat.hip: the mean / std style term of a blob [C][HW] against per-channel targets (include/stx.h,
+// stx_set_stat_targets).  A workgroup owns kStatSlice pixels of one channel; everything the three
+// launches hand to each other lives in stat_scratch_floats(C, HW) floats of the caller's.
+constexpr int kStatSlice = 16384;
+constexpr float kStatEps = 1e-5f;        // sd = sqrt(var + kStatEps)
+int stat_slices(int HW);
+size_t stat_scratch_floats(int C, int HW);
+// partials [C][slices][4] = (count, mean as two floats, M2 about that mean) of every slice
+int stat_partials_launch(hipStream_t s, const float *feat, int C, int HW, float *partials);
+// Chan's merge in double, in slice order.  MU, SD given: table [C][4] = (mu, a = mu - MU, b = (sd - SD) / sd, 0)
+// and e_out[0] = E; null: mean_out[c] = mu, sd_out[c] = sd
+int stat_finish_launch(hipStream_t s, const float *partials, int C, int HW, const float *MU, const float *SD,
+                       float *table, float *e_out, float *mean_out, float *sd_out);
+// sgrad = a + b (feat - mu) per channel; *n_parts partials of sum |sgrad| into abs_partials
+int stat_grad_launch(hipStream_t s, const float *feat, int C, int HW, const float *table, float *sgrad,
+                     float *abs_partials, int *n_parts);
+
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,
                     int th, int tw, float *tile);

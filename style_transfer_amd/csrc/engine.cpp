@@ -392,6 +392,7 @@ void stx_engine_destroy(stx_engine *e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &b : e->sgrad_tap) b->release();
+    for (auto &b : e->sgrad_stat) b->release();
     e->marks_buf.release();
     e->amax.release();
     for (Blob &b : e->blobs) {
@@ -417,8 +418,9 @@ void stx_engine_destroy(stx_engine *e) {
         for (auto &c : e->sh->contents) c.feat->release();
         for (auto &s : e->sh->styles) s.gram->release();
         for (auto &m : e->sh->masks) m.map->release();
+        for (auto &t : e->sh->stats) t.ms->release();
     }
-    DevBuf *bufs[] = {&e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
+    DevBuf *bufs[] = {&e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
@@ -613,9 +615,11 @@ int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *content
     for (auto &c : e->sh->contents) c.feat->release();
     for (auto &s : e->sh->styles) s.gram->release();
     for (auto &m : e->sh->masks) m.map->release();
+    for (auto &t : e->sh->stats) t.ms->release();
     e->sh->contents.clear();
     e->sh->styles.clear();
     e->sh->masks.clear();
+    e->sh->stats.clear();
     e->sh->n_contents = e->sh->n_styles = 0;
     bool host_src = false;
     for (int i = 0; i < n_contents; ++i) {
@@ -719,6 +723,56 @@ int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n) {
         for (auto &m : e->sh->masks) m.map->release();
         e->sh->masks.clear();
     }
+    return rc;
+}
+
+int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    std::lock_guard<std::mutex> lock(e->sh->mutex);
+    const bool shared = e->sh->members.size() > 1;
+    // the previous targets may still be in use by queued kernels (of any engine that shares them)
+    STX_TRY(quiesce_members(e));
+    auto clear = [&]() {
+        for (auto &t : e->sh->stats) t.ms->release();
+        e->sh->stats.clear();
+    };
+    clear();
+    bool host_src = false;
+    int rc = STX_OK;
+    for (int i = 0; i < n && rc == STX_OK; ++i) {
+        const stx_stat_target &st = targets[i];
+        const int blob = e->find_blob(st.layer);
+        bool twice = false;
+        for (const StatTarget &t : e->sh->stats) twice |= t.blob == blob;
+        if (blob <= 0 || !st.mean || !st.sd || twice) {
+            set_error("statistics target %d: bad layer '%s' (unknown, the input, or given twice) or no data", i,
+                      st.layer ? st.layer : "(null)");
+            rc = STX_ERR_ARG;
+            break;
+        }
+        if (st.channels != e->blobs[blob].channels) {
+            set_error("statistics target %d: layer %s has %d channels, not %d", i, st.layer,
+                      e->blobs[blob].channels, st.channels);
+            rc = STX_ERR_ARG;
+            break;
+        }
+        StatTarget t{blob, st.channels, st.weight, std::unique_ptr<DevBuf>(new DevBuf)};
+        const size_t bytes = (size_t)t.C * sizeof(float);
+        if ((rc = t.ms->ensure(2 * bytes)) == STX_OK) rc = copy_in(e, t.ms->ptr, st.mean, st.mem, bytes);
+        if (rc == STX_OK) rc = copy_in(e, t.ms->f() + t.C, st.sd, st.mem, bytes);
+        host_src |= st.mem == STX_HOST;
+        e->sh->stats.push_back(std::move(t));
+    }
+    // (host sources may be reused right away; the sharing engines read the targets from their own streams)
+    if (host_src || shared || rc != STX_OK) {
+        const hipError_t err = hipStreamSynchronize(e->stream);
+        if (rc == STX_OK && err != hipSuccess) {
+            set_error("stx_set_stat_targets: %s", hipGetErrorString(err));
+            rc = STX_ERR_HIP;
+        }
+    }
+    if (rc != STX_OK) clear();
     return rc;
 }
 

@@ -95,6 +95,13 @@ struct StyleMask {
     std::unique_ptr<DevBuf> map;
 };
 
+// The mean / std targets of one tapped blob (stx_set_stat_targets): MU [C] then SD [C] on the device.
+struct StatTarget {
+    int blob, C;
+    double weight;
+    std::unique_ptr<DevBuf> ms;
+};
+
 struct LossTerm {
     size_t scalar_index;   // float in the host mirror of the scalar buffer
     double coef;
@@ -115,6 +122,7 @@ struct SharedState {
     std::vector<ContentTarget> contents;
     std::vector<StyleTarget> styles;
     std::vector<StyleMask> masks;      // (cleared with the targets)
+    std::vector<StatTarget> stats;     // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -133,6 +141,7 @@ struct stx_engine {
     DevBuf marks_buf;
     int marks_used = 0, last_mark = -1;    // (last_mark: the slot of the launch just queued, or -1)
     std::vector<std::unique_ptr<DevBuf>> sgrad_tap;   // S = sym(D) F of every style tap
+    std::vector<std::unique_ptr<DevBuf>> sgrad_stat;  // S of the mean / std term of every tap that has one
     // start / stop of the last few tile calls (a ring: stx_last_tile_ms reports the newest call
     // that has finished, so a host that runs ahead does not wait for the call it just queued)
     static constexpr int kTimed = 4;
@@ -163,6 +172,7 @@ struct stx_engine {
     DevBuf gram_partials, gram, dsym, dsym_pieces, symm_partials, upload;
     DevBuf term_scratch;               // per style term of a tile call: block sums / maxima + SYMM partials (sum jobs)
     DevBuf masked_feat, masked_target; // a masked style term's F . m and a Gs (style_mask.hip), one term at a time
+    DevBuf stat_scratch;               // stx_feature_stats / stx_op_stat_terms: partials, table, outputs
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
     // reductions), each with a pinned host mirror, and the losses that will be published from
     // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
@@ -289,6 +299,12 @@ int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *fe
                               const float *mask_map, const ContentWindow &win, const float *target,
                               float *sgrad, float *sc, const std::string &name, const unsigned *f_amax,
                               float *term_scratch, float *mask_scratch, std::vector<SumJob> *defer);
+// The mean / std term of a blob (stat.hip): partials -> finish against MU, SD -> S into sgrad.
+// sc[2] = {E, sum |S|}; the final sum of sum |S| joins `defer` or is launched here.  stat_scratch:
+// stat_scratch_floats(C, h * w) floats that outlive the call like term_scratch.
+int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *MU,
+                      const float *SD, float *sgrad, float *sc, const std::string &name, float *stat_scratch,
+                      std::vector<SumJob> *defer);
 #pragma GCC visibility pop
 
 }  // namespace stx

@@ -133,6 +133,26 @@ int stx_op_masked_style_terms(stx_engine *e, const float *feat, int C, int h, in
     return STX_OK;
 }
 
+int stx_op_stat_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *MU, const float *SD,
+                      float *s_out, double out[2]) {
+    if (!e || !feat || !MU || !SD || !s_out || !out || C <= 0 || h <= 0 || w <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    STX_TRY(do_sync(e));
+    size_t si;
+    STX_TRY(alloc_scalars(e, 2, &si));
+    float *sc = e->A().scalars.f() + si;
+    STX_TRY(e->stat_scratch.ensure(stat_scratch_floats(C, h * w) * sizeof(float)));
+    // the launches of a statistics target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_stat_terms(e, e->stream, feat, C, h, w, MU, SD, s_out, sc, "op", e->stat_scratch.f(), nullptr));
+    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
+                           hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    out[0] = 0.5 * (double)e->A().host[si];
+    out[1] = (double)e->A().host[si + 1];
+    e->A().used = 0;
+    return STX_OK;
+}
+
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]) {

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <deque>
 
 #include "engine.h"
 
@@ -496,6 +497,25 @@ int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *fe
     return STX_OK;
 }
 
+// The mean / std term of one tapped blob (stat.hip): the slices' partials, their merge against the targets
+// (table and E), S with the partials of sum |S|.  Everything in stat_scratch outlives the call.
+int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *MU,
+                      const float *SD, float *sgrad, float *sc, const std::string &name, float *stat_scratch,
+                      std::vector<SumJob> *defer) {
+    const int HW = h * w;
+    float *const partials = stat_scratch;
+    float *const table = partials + 4 * (size_t)C * stat_slices(HW);
+    float *const abs_partials = table + 4 * (size_t)C;
+    ProfScope scope(e, "stat " + name, 0.0, stream);
+    STX_TRY(stat_partials_launch(stream, feat, C, HW, partials));
+    STX_TRY(stat_finish_launch(stream, partials, C, HW, MU, SD, table, sc, nullptr, nullptr));
+    int n_parts = 0;
+    STX_TRY(stat_grad_launch(stream, feat, C, HW, table, sgrad, abs_partials, &n_parts));
+    if (!defer) return sum_partials_launch(stream, abs_partials, n_parts, sc + 1);
+    defer->push_back(SumJob{abs_partials, n_parts, sc + 1});
+    return STX_OK;
+}
+
 static int begin_timing(stx_engine *e) {
     e->ev_cur = (e->ev_cur + 1) % stx_engine::kTimed;
     STX_HIP(hipEventRecord(e->ev_start[e->ev_cur], e->stream));
@@ -531,6 +551,8 @@ struct TilePlan {
     std::vector<Tap> order;         // taps, deepest first
     std::vector<char> needed;       // blobs on the path
     std::vector<int> tap_of;        // blob -> index into order, or -1
+    std::deque<stx_tap> extra;      // taps of the layers that only a statistics target names (lw = 1);
+                                    // `order` points into it: a deque's elements stay where they are
 };
 
 // One loss term of a tapped blob, as the backward walk adds it to the blob's gradient.
@@ -561,6 +583,13 @@ struct TileRun {
 
 }  // namespace
 
+// The mean / std target of `blob` (stx_set_stat_targets), or null.
+static const StatTarget *stat_target_of(const stx_engine *e, int blob) {
+    for (const StatTarget &t : e->sh->stats)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
+
 // Validates the taps against the graph and the targets, orders them and shapes the blobs.
 static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
     // ---- taps in deep -> shallow order (style_transfer.py:231-233)
@@ -579,8 +608,18 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 set_error("stx_sc_grad_tile: layer '%s' is tapped twice", taps[i].layer);
                 return STX_ERR_ARG;
             }
-        if (!taps[i].is_content && !taps[i].is_style && !taps[i].is_dd) continue;
+        if (!taps[i].is_content && !taps[i].is_style && !taps[i].is_dd && !stat_target_of(e, blob)) continue;
         order.push_back(Tap{blob, &taps[i]});
+    }
+    // a layer with a statistics target is part of every evaluation, tapped or not
+    for (const StatTarget &st : e->sh->stats) {
+        bool tapped = false;
+        for (const Tap &o : order) tapped |= o.blob == st.blob;
+        if (tapped) continue;
+        stx_tap t{};
+        t.layer_weight = 1.0;
+        plan.extra.push_back(t);
+        order.push_back(Tap{st.blob, &plan.extra.back()});
     }
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");
@@ -763,6 +802,26 @@ static int queue_style_terms(TileRun &run, size_t k) {
     return STX_OK;
 }
 
+// The mean / std term of tap k against the blob's statistics target (launch_stat_terms).
+static int queue_stat_term(TileRun &run, size_t k, const StatTarget &st) {
+    stx_engine *e = run.e;
+    const Tap &tp = run.plan.order[k];
+    const Blob &b = e->blobs[tp.blob];
+    STX_TRY(e->sgrad_stat[k]->ensure(b.count() * sizeof(float)));
+    float *sgrad = e->sgrad_stat[k]->f();
+    size_t si;
+    STX_TRY(alloc_scalars(e, 2, &si));
+    float *sc = e->A().scalars.f() + si;   // [0] = E, [1] = sum |S|
+    float *scratch = e->term_scratch.f() + run.scratch_used;
+    run.scratch_used += stat_scratch_floats(b.channels, b.h * b.w);
+    STX_TRY(launch_stat_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, st.ms->f(), st.ms->f() + st.C,
+                              sgrad, sc, b.name, scratch, run.defer()));
+    const double coef = tp.t->layer_weight * st.weight;
+    run.pl.terms.push_back(LossTerm{si, coef * 0.5});
+    run.terms[k].push_back(Term{true, sgrad, sc + 1, (float)coef, ContentWindow{}});
+    return STX_OK;
+}
+
 // Deep-Dream term (style_transfer.py:602-604): the content term against a zero map with a negative
 // weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
 static int queue_dream_term(TileRun &run, size_t k) {
@@ -779,6 +838,7 @@ static int queue_tap_terms(TileRun &run, size_t k) {
     const stx_tap *t = run.plan.order[k].t;
     if (t->is_content) STX_TRY(queue_content_terms(run, k));
     if (t->is_style) STX_TRY(queue_style_terms(run, k));
+    if (const StatTarget *st = stat_target_of(run.e, run.plan.order[k].blob)) STX_TRY(queue_stat_term(run, k, *st));
     if (t->is_dd) STX_TRY(queue_dream_term(run, k));
     return STX_OK;
 }
@@ -988,11 +1048,15 @@ static int sc_grad_run(stx_engine *e, const TileCall &c, const TilePlan &plan, P
                 !(sw_env("STX_TERMS_LATE") && atoi(sw_env("STX_TERMS_LATE"))),
                 std::vector<std::vector<Term>>(order.size()), {}, 0};
     while (e->sgrad_tap.size() < order.size()) e->sgrad_tap.emplace_back(new DevBuf);
+    if (!e->sh->stats.empty())
+        while (e->sgrad_stat.size() < order.size()) e->sgrad_stat.emplace_back(new DevBuf);
     {
         size_t need = 0;
         for (const Tap &tp : order) {
-            if (!tp.t->is_style) continue;
             const Blob &b = e->blobs[tp.blob];
+            // (a statistics term's partials and table live there, with or without the late sums)
+            if (stat_target_of(e, tp.blob)) need += stat_scratch_floats(b.channels, b.h * b.w);
+            if (!tp.t->is_style) continue;
             for (const StyleTarget &st : e->sh->styles) {
                 if (st.blob != tp.blob) continue;
                 if (run.sums_late) need += style_term_scratch_floats(b.channels, b.h * b.w);
@@ -1028,7 +1092,7 @@ static int sc_grad_eager(stx_engine *e, const TileCall &c, double *loss_out) {
     // the scalar arena holds the reductions of every call queued since the last stx_sync; drain
     // it (publishing the pending losses) before it could overflow
     {
-        const size_t per_call = (size_t)c.n_taps * 2100 *
+        const size_t per_call = ((size_t)c.n_taps + e->sh->stats.size()) * 2100 *
                                 (size_t)std::max(1, e->sh->n_contents + e->sh->n_styles);
         if (e->A().used + per_call > e->scalars_cap) STX_TRY(do_sync(e));
         if (per_call > e->scalars_cap) {
@@ -1094,7 +1158,8 @@ int stx_features_tile(stx_engine *e, const float *img, int img_mem, int th, int 
 int stx_sc_grad_tile(stx_engine *e, const float *img, int img_mem, int th, int tw,
                      const int roll_xy[2], const int start_yx[2], const stx_tap *taps, int n_taps,
                      double *loss_out, float *grad_out, int grad_mem, int sync_now) {
-    if (!e || !img || th <= 0 || tw <= 0 || !taps || n_taps <= 0 || !grad_out || !start_yx) {
+    // (n_taps = 0: the layers of the statistics targets alone; without such targets sc_grad_prepare refuses it)
+    if (!e || !img || th <= 0 || tw <= 0 || n_taps < 0 || (!taps && n_taps > 0) || !grad_out || !start_yx) {
         set_error("stx_sc_grad_tile: bad arguments");
         return STX_ERR_ARG;
     }
@@ -1143,6 +1208,28 @@ int stx_gram_matrix(stx_engine *e, const float *feat, int feat_mem, int channels
                                nullptr, nullptr, f_amax));
     STX_TRY(copy_out(e, gram_out, gram_mem, e->gram.ptr, (size_t)channels * channels * sizeof(float)));
     if (feat_mem == STX_HOST || gram_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channels, int hw, float *mean_out,
+                      float *sd_out, int out_mem) {
+    if (!e || !feat || !mean_out || !sd_out || channels <= 0 || hw <= 0) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const float *src = feat;
+    if (feat_mem == STX_HOST) {
+        STX_TRY(e->upload.ensure((size_t)channels * hw * sizeof(float)));
+        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, (size_t)channels * hw * sizeof(float)));
+        src = e->upload.f();
+    }
+    const size_t parts = 4 * (size_t)channels * stat_slices(hw);
+    STX_TRY(e->stat_scratch.ensure((parts + 2 * (size_t)channels) * sizeof(float)));
+    float *mu = e->stat_scratch.f() + parts, *sd = mu + channels;
+    // the first two launches of the term itself (launch_stat_terms): a tile's own statistics are its targets
+    STX_TRY(stat_partials_launch(e->stream, src, channels, hw, e->stat_scratch.f()));
+    STX_TRY(stat_finish_launch(e->stream, e->stat_scratch.f(), channels, hw, nullptr, nullptr, nullptr, nullptr, mu, sd));
+    STX_TRY(copy_out(e, mean_out, out_mem, mu, (size_t)channels * sizeof(float)));
+    STX_TRY(copy_out(e, sd_out, out_mem, sd, (size_t)channels * sizeof(float)));
+    if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
     return STX_OK;
 }
 

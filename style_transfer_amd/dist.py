@@ -188,6 +188,16 @@ def refuse_style_masks(args):
                                   'run the single-process tile farm (--devices) instead')
 
 
+def refuse_stat_weight(args):
+    """--stat-weight with one process per GPU: the statistics targets would have to travel to every rank
+    with the others, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
+    raw = getattr(getattr(args, 'ns', args), 'stat_weight', 0)
+    if callable(raw) or raw:
+        raise NotImplementedError('--stat-weight is not implemented for the one-process-per-GPU layout '
+                                  '(style_transfer_amd.dist): the statistics targets are not broadcast to the '
+                                  'ranks; run the single-process tile farm (--devices) instead')
+
+
 def _wire_device(device, group):
     if torch.device(device).type == 'cuda' and dist.get_backend(group) == 'gloo':
         return torch.device('cpu')          # host-staged debug path, see DistributedTiles
@@ -234,9 +244,10 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks is refused here (refuse_style_masks)."""
+    a run with --style-masks or --stat-weight is refused here (refuse_style_masks, refuse_stat_weight)."""
     if args is not None:
         refuse_style_masks(args)
+        refuse_stat_weight(args)
     rank = dist.get_rank(group)
     wire = _wire_device(device, group)
     meta = [None]

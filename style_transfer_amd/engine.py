@@ -156,6 +156,7 @@ class TileEngine:
         self._results = []
         self._info = {b: net.layer_info(b) for b in net.blob_names()}
         self.n_styles = 0
+        self.stat_layers = []       # (of the primary: the layers of the group's statistics targets)
         if weights and share is None:
             for name, (w, b) in weights.items():
                 self.set_weights(name, w, b)
@@ -297,6 +298,36 @@ class TileEngine:
                 i += 1
         lib.call('stx_set_contents_and_styles', self.handle, ctargets, n_c, starget, n_s)
         self.n_styles = len(styles)
+        self.primary.stat_layers = []           # (the library clears the statistics targets with these)
+
+    def set_stat_targets(self, targets, weights=None):
+        """targets: {layer: (mean [C], sd [C])} -- what ``feature_stats`` gives for a style picture's
+        feature map -- and weights: {layer: factor} (default 1 each); an empty dict: no targets
+        (stx_set_stat_targets).  Call it after ``set_contents_and_styles``, which clears them.  A layer
+        with a target is part of every tile evaluation of the group from then on."""
+        keep, n = [], len(targets)
+        table = (lib.StatTarget * max(1, n))()
+        for t, (layer, (mean, sd)) in zip(table, targets.items()):
+            mp, mmem, mobj = _as_arg(mean)
+            sp, smem, sobj = _as_arg(sd)
+            if mmem != smem or mobj.shape != sobj.shape or len(mobj.shape) != 1:
+                raise ValueError('statistics target %s: mean and sd are two [C] arrays on the same side' % layer)
+            keep += [mobj, sobj]
+            t.layer, t.channels, t.mean, t.sd, t.mem = self._cstr(layer), int(mobj.shape[0]), mp, sp, mmem
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_stat_targets', self.handle, table, n)
+        self.primary.stat_layers = list(targets)
+        del keep
+
+    def feature_stats(self, feat):
+        """(mean [C], sd [C]) of a [C,h,w] feature map, sd = sqrt(population variance + 1e-5), as float32
+        (stx_feature_stats): the targets of the mean / std style term."""
+        ptr, mem, keep = _as_arg(feat)
+        c = keep.shape[0]
+        hw = int(np.prod(keep.shape[1:]))
+        mean, sd = np.empty(c, np.float32), np.empty(c, np.float32)
+        lib.call('stx_feature_stats', self.handle, ptr, mem, c, hw, mean.ctypes.data, sd.ctypes.data, lib.HOST)
+        return mean, sd
 
     def set_style_masks(self, masks):
         """masks: one entry per style set of the current targets, in their order -- an [H, W] array
@@ -366,7 +397,9 @@ class TileEngine:
     # --------------------------------------------------------------------------- SCGradRequest
     def _taps(self, content_layers, style_layers, layer_weights, content_weight, style_weight,
               dd_layers=(), dd_weight=None):
-        names = list(dict.fromkeys(list(content_layers) + list(style_layers) + list(dd_layers)))
+        # (a layer that only a statistics target names is tapped for nothing: the tap carries its layer weight)
+        names = list(dict.fromkeys(list(content_layers) + list(style_layers) + list(dd_layers) +
+                                   list(self.primary.stat_layers)))
         taps = (lib.Tap * len(names))()
         for t, name in zip(taps, names):
             t.layer = self._cstr(name)

@@ -176,6 +176,17 @@ class TileFarm:
         for e in self.primaries():
             e.set_style_masks(masks)
 
+    def set_stat_targets(self, targets, weights=None):
+        """Hands the statistics targets (TileEngine.set_stat_targets) to every GPU, once each; call it
+        behind ``set_contents_and_styles``."""
+        for e in self.engines:
+            e.sync()
+        for e in self.primaries():
+            e.set_stat_targets(targets, weights)
+
+    def feature_stats(self, feat):
+        return self.master.feature_stats(feat)
+
     def _engines_for(self, n_tiles):
         """The engines that share a step of n_tiles tiles, creating extra per-GPU engines on
         demand (engine i lives on device i mod n_devices, like the reference's round-robin)."""

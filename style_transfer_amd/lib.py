@@ -52,6 +52,11 @@ class StyleMask(ctypes.Structure):
                 ('mask', ctypes.c_void_p), ('mem', ctypes.c_int)]
 
 
+class StatTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('mean', ctypes.c_void_p),
+                ('sd', ctypes.c_void_p), ('mem', ctypes.c_int), ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -82,12 +87,14 @@ SIGNATURES = {
     'stx_set_contents_and_styles': [_vp, ctypes.POINTER(ContentTarget), _i,
                                     ctypes.POINTER(StyleTarget), _i],
     'stx_set_style_masks': [_vp, ctypes.POINTER(StyleMask), _i],
+    'stx_set_stat_targets': [_vp, ctypes.POINTER(StatTarget), _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
     'stx_sc_grad_tile': [_vp, _vp, _i, _i, _i, c_int_p, c_int_p, ctypes.POINTER(Tap), _i,
                          c_double_p, _vp, _i, _i],
     'stx_tile_buffers': [_vp, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
     'stx_gram_matrix': [_vp, _vp, _i, _i, _i, _vp, _i],
+    'stx_feature_stats': [_vp, _vp, _i, _i, _i, _vp, _vp, _i],
     'stx_image_cut_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
     'stx_image_put_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
     'stx_image_mask_map': [_vp, _vp, _i, _i, _i, _vp],
@@ -126,6 +133,7 @@ SIGNATURES = {
     'stx_op_pool_backward': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     'stx_op_style_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p, c_double_p],
     'stx_op_masked_style_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, _vp, c_double_p],
+    'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],
     'stx_last_tile_flops': [_vp, c_double_p, c_double_p],

@@ -23,7 +23,7 @@ import numpy as np
 from PIL import Image
 
 from . import image_ops, lib
-from .config_system import LAP_POOLS_DEFAULT, check_lap_pools, ffloat
+from .config_system import LAP_POOLS_DEFAULT, check_lap_pools, check_stat_options, ffloat, stat_layer_args
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
 
@@ -179,6 +179,12 @@ class StyleTransfer:
         self._lap_pools = check_lap_pools(args) if self._lap_on else []
         self._lap_target = None
         self._lap_weights_key = self._lap_weights_now = None    # the last (--lap-pools, lap_weight) parsed
+        # --stat-weight / --stat-layers (the mean / std style term; not options of the reference): per-channel
+        # mean and sd of the style pictures' feature maps, averaged like the Grams and kept where they are
+        # kept; sent to the engines behind the targets.  Without the options nothing here runs.
+        self._stat_on = bool(check_stat_options(args, farm.layers()))
+        self.stat_targets = None    # {layer: (mean [C], sd [C])}
+        self._stat_weights = None   # {layer: weight} of the scale being optimised
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
         # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
@@ -265,20 +271,37 @@ class StyleTransfer:
             masks = [np.roll(m, (int(roll[1]), int(roll[0])), (0, 1)) for m in masks]
         self.farm.set_style_masks(masks)
 
+    def _send_stats(self):
+        """The statistics targets of the scale's --stat-layers to the engines, behind the targets (which clear
+        them).  With --style-multiscale the targets are the first scale's: a layer that a later reading of
+        the list drops gets no term, and one that it adds has no target and is refused."""
+        if not self._stat_weights:
+            return
+        missing = [layer for layer in self._stat_weights if layer not in self.stat_targets]
+        if missing:
+            raise ValueError('--stat-layers %s: no statistics target was taken there; with --style-multiscale '
+                             'the layers are those of the first scale' % ' '.join(missing))
+        self.farm.set_stat_targets({layer: self.stat_targets[layer] for layer in self._stat_weights},
+                                   self._stat_weights)
+
     def preprocess_images(self, content_images, style_images, content_layers, style_layers,
-                          roll=None, color_from=None):
+                          roll=None, color_from=None, stat_layers=()):
         """Targets of one scale: the style Grams, averaged with equal weight over every style
         image and ladder size (with --style-masks: over the ladder sizes of each style image, one
         style set per image), and the tiling-averaged content features
         (style_transfer.py:488-554).  Everything stays on the master GPU.  ``roll`` (--jitter,
         once per iteration): features of the pictures rolled by it, one pass, no messages.
         ``color_from`` (--preserve-color match): every style variant is recoloured on the GPU to the
-        colour mean and covariance of this picture before its features are taken."""
+        colour mean and covariance of this picture before its features are taken.  ``stat_layers``
+        (--stat-weight): the per-channel mean and sd of the same feature maps at these layers, averaged the
+        same way, into ``self.stat_targets``; the features are taken at the union of both lists, once."""
         farm, tile = self.farm, self.args.tile_size
         if roll is None:
             print('Preprocessing the style image(s)...')
         if not self.styles:
             total, count = {}, 0
+            stat_total = {}
+            feature_layers = list(style_layers) + [l for l in stat_layers if l not in style_layers]
             target = None
             if color_from is not None and style_images:
                 kept = self.engine.to_device(self.pil_to_image(color_from))
@@ -289,11 +312,17 @@ class StyleTransfer:
                     picture = self.pil_to_image(variant)
                     if target is not None:
                         picture = self._recolored(picture, target)
-                    feats = farm.prepare_features_device(picture, style_layers, tile, passes=1,
+                    feats = farm.prepare_features_device(picture, feature_layers, tile, passes=1,
                                                          roll=roll)
                     if target is not None:
                         picture.free()
                     for layer, feat in feats.items():
+                        if layer in stat_layers:
+                            stats = np.stack(farm.feature_stats(feat))
+                            stat_total[layer] = stats if layer not in stat_total else stat_total[layer] + stats
+                        if layer not in style_layers:
+                            feat.free()
+                            continue
                         gram = farm.gram_matrix(feat)
                         feat.free()
                         total[layer] = gram if layer not in total else total[layer] + gram
@@ -303,6 +332,8 @@ class StyleTransfer:
                     total, count = {}, 0
             if self.style_masks is None:
                 self.styles.append({layer: gram / count for layer, gram in total.items()})
+            if stat_layers:
+                self.stat_targets = {layer: tuple(stats / np.float32(count)) for layer, stats in stat_total.items()}
         if roll is None:
             print('Preprocessing the content image(s)...')
         self.contents += [farm.prepare_features_device(self.pil_to_image(image), content_layers,
@@ -391,8 +422,12 @@ class StyleTransfer:
         dd_layers, dd_weight = parse_weights(args.dd_layers, args.dd_weight)
         jitter = bool(args.jitter)
         self._drop_contents()                  # device-resident maps of the previous scale
+        stat_layers, self._stat_weights = [], None
+        if self._stat_on:       # (read once per scale, like the layer lists above)
+            stat_layers, self._stat_weights = parse_weights(stat_layer_args(args), args.stat_weight)
         if not args.style_multiscale:
             self.styles = []
+            self.stat_targets = None
         # --jitter: the content maps are recomputed every iteration from the shifted picture
         # (style_transfer.py:757-763,789-794), only the style targets are fixed per scale
         if self.preserve_color == 'luma':
@@ -411,8 +446,10 @@ class StyleTransfer:
                 picture.free()
         self.preprocess_images([] if jitter else content_images, style_images,
                                [] if jitter else content_layers, style_layers,
-                               color_from=content_images[0] if self.preserve_color == 'match' else None)
+                               color_from=content_images[0] if self.preserve_color == 'match' else None,
+                               stat_layers=stat_layers)
         self.farm.set_contents_and_styles(self.contents, self.styles)
+        self._send_stats()
         if self.style_masks is not None:
             if len(self.styles) != len(self.style_masks):
                 raise ValueError('--style-masks: %d mask(s) for %d style set(s)'
@@ -511,6 +548,7 @@ class StyleTransfer:
                 self.preprocess_images(content_images, [], content_layers, [], roll=roll)
                 self.farm.set_contents_and_styles(self.contents, self.styles)
                 self._send_masks(roll=roll)
+                self._send_stats()
                 content_roll = (0, 0)
             sc_args = (roll, content_layers, style_layers, content_weight, style_weight,
                        dd_layers, dd_weight, content_roll)
