@@ -190,6 +190,27 @@ typedef struct stx_style_mask {
  * surfaces as the window range error at evaluation. */
 int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n);
 
+/* Spatial control of the content term (not in the reference; Gatys et al., "Controlling Perceptual Factors in
+ * Neural Style Transfer"): a greyscale mask in the content picture's frame, values in [0, 1], says where the
+ * content picture is held (white) and where the content term is off (black).  For a blob of scale s that has a
+ * content target the library keeps the block means of the mask, ceil(H/s) x ceil(W/s) -- the size of the
+ * blob's content maps -- and a tile evaluation takes the tile's window of it with the very window of the content
+ * map (start // s, roll // s, wrapping; the same range error).  With F the tile's blob [C][fh][fw], c the
+ * window of the content map and m that of the mask map (every channel):
+ *   d     = F - c
+ *   a     = sum m / (fh fw)                           (the window's mean weight)
+ *   loss += lw cw[b] 1/2 sum m d^2
+ *   S0    = m d
+ *   diff += lw cw[b] * a S0 / (sum|S0| / S0.size + EPS)
+ * m == 1 is the unmasked term (its sums bit for bit); m == 0 adds nothing (0 / EPS); a uniform m == k is the
+ * unmasked term with the content weight scaled by k, up to the EPS term -- the normalisation would otherwise
+ * undo the mask's overall level, which is what a is for.  One mask applies to every content target.
+ *
+ * mask == NULL clears.  Call it after stx_set_contents_and_styles, which clears the maps: they are built for
+ * every blob that has a content target and are shared like the targets (stx_engine_create_shared).  A mask
+ * whose map at such a blob has another size than the blob's content maps is STX_ERR_ARG here. */
+int stx_set_content_mask(stx_engine *e, const float *mask, int H, int W, int mem);
+
 /* The mean / std style term (not in the reference): the BN-statistics loss of Li et al., "Demystifying
  * Neural Style Transfer", the quantity AdaIN aligns.  A tapped blob F [C][h][w] -- the array the Gram term
  * reads -- is held to per-channel targets MU, SD.  With n = h w and eps = 1e-5:
@@ -514,6 +535,12 @@ int stx_op_style_terms(stx_engine *e, const float *feat, int channels, int h, in
 int stx_op_masked_style_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                               const float *mask_map, int mh, int mw, int oy, int ox, const int roll_xy[2],
                               const float *gram_target, float *sgrad_out, double out[3]);
+/* The launches of a masked content target (stx_set_content_mask) on given arrays: content [channels][ch][cw]
+ * and mask_map [ch][cw], the window at (oy, ox) of both rolled by roll_xy, in the maps' own pixels.
+ * out = {1/2 sum m d^2, sum |m d|, a}; sgrad_out = a (m d). */
+int stx_op_masked_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
+                                const float *content, int ch, int cw, const float *mask_map, int oy, int ox,
+                                const int roll_xy[2], float *sgrad_out, double out[3]);
 /* The launches of a statistics target (stx_set_stat_targets) on given arrays (all STX_DEVICE; MU, SD [channels]):
  * out = {E / 2, sum |S|}; s_out = S. */
 int stx_op_stat_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *MU,

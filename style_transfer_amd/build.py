@@ -27,6 +27,7 @@ SOURCES = {
     'symm.hip': [],
     'pool.hip': [],
     'reduce.hip': [],
+    'content_mask.hip': [],     # (compiled like reduce.hip: an all-ones mask gives content_sums' bits)
     # one rounding per float32 operation, like the reference's numpy expressions
     'image_ops.hip': ['-ffp-contract=off'],
     'swt.hip': ['-ffp-contract=off'],

@@ -15,7 +15,7 @@ import numpy as np
 from PIL import Image
 
 from . import fastpng, lib
-from .config_system import check_stat_options, check_style_masks, parse_args
+from .config_system import check_content_mask, check_stat_options, check_style_masks, parse_args
 from .farm import TileFarm
 from .netspec import load_net
 from .transfer import StyleTransfer
@@ -156,6 +156,8 @@ def main(argv=None):
         content_image = Image.open(args.content_image).convert('RGB')
         style_images = [Image.open(p).convert('RGB') for p in args.style_images]
         style_masks = [Image.open(p).convert('L') for p in check_style_masks(args)]
+        content_mask = check_content_mask(args)
+        content_mask = Image.open(content_mask).convert('L') if content_mask else None
         initial_image = Image.open(args.init_image).convert('RGB') if args.init_image else None
         aux_image = Image.open(args.aux_image).convert('RGB') if args.aux_image else None
         farm = farm_future.result()
@@ -171,7 +173,8 @@ def main(argv=None):
     failed = True
     try:
         transfer.transfer_multiscale([content_image], style_images, initial_image, aux_image,
-                                     callback=progress, **({'style_masks': style_masks} if style_masks else {}))
+                                     callback=progress, **({'style_masks': style_masks} if style_masks else {}),
+                                     **({'content_mask': content_mask} if content_mask is not None else {}))
         failed = False
     except (EOFError, KeyboardInterrupt):
         print()

@@ -114,6 +114,10 @@ _EXTENSIONS = [
                                    "picture's frame; a style applies where its mask is white.  With masks "
                                    'every style image is a style set of its own instead of one average '
                                    '(default: no masks)')),
+    (('--content-mask',), dict(metavar='MASK',
+                               help="spatial control of the content term: a greyscale picture in the content "
+                                    "picture's frame; the content picture is held where it is white and the "
+                                    'content term is off where it is black (default: no mask)')),
     (('--lap-weight',), dict(metavar='WEIGHT', type=ffloat,
                              help="Laplacian loss factor: holds the result to the content picture's edges "
                                   '(the Laplacian of the average-pooled result against that of the '
@@ -202,6 +206,15 @@ def check_style_masks(args):
         raise ValueError('--style-masks: %d mask(s) for %d style image(s); one per style image is needed'
                          % (len(masks), len(args.style_images)))
     return list(masks) if masks else []
+
+
+def check_content_mask(args):
+    """--content-mask weights the content term: without content layers there is nothing to weight, which is
+    refused before any GPU work.  Returns the path, or None."""
+    path = getattr(args, 'content_mask', None)
+    if path and not args.content_layers:
+        raise ValueError('--content-mask needs a content term: --content-layers is empty')
+    return path or None
 
 
 LAP_POOLS_DEFAULT = ('4',)
@@ -306,6 +319,7 @@ def parse_args(state=None, argv=None, config_py=None):
         parser.print_help()
         sys.exit(1)
     check_style_masks(args)
+    check_content_mask(args)
     check_lap_pools(args)
     check_stat_options(args)
     return args

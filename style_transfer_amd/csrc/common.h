@@ -462,6 +462,16 @@ int mask_target_launch(hipStream_t s, const float *gs, int C, const float *m2_pa
 int mask_sgrad_launch(hipStream_t s, float *sgrad, const float *map, const ContentWindow &win, const float *a,
                       float *partials, int *n_parts);
 
+// content_mask.hip: a content term weighted by a map m (values in [0, 1]; the tile's window of it is the
+// content map's own).  The pass takes content_sums_launch's grid, so that m == 1 leaves its partials.
+constexpr int kContentMaskParts = 1024;      // most workgroups of content_mask_term_launch (reduce.hip's cap)
+// a_out[0] = sum m / (fh fw) over the window, in double in a fixed order
+int content_mask_mean_launch(hipStream_t s, const float *map, const ContentWindow &win, float *a_out);
+// sgrad = a[0] (m . (feat - content[window])); *n_parts partials of sum m d^2, then as many of sum |m d|
+int content_mask_term_launch(hipStream_t s, const float *feat, const float *content, const float *map,
+                             const ContentWindow &win, const float *a, float *sgrad, float *partials,
+                             int *n_parts);
+
 // stat.hip: the mean / std style term of a blob [C][HW] against per-channel targets (include/stx.h,
 // stx_set_stat_targets).  A workgroup owns kStatSlice pixels of one channel; everything the three
 // launches hand to each other lives in stat_scratch_floats(C, HW) floats of the caller's.

@@ -393,6 +393,7 @@ void stx_engine_destroy(stx_engine *e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &b : e->sgrad_tap) b->release();
     for (auto &b : e->sgrad_stat) b->release();
+    for (auto &b : e->sgrad_content) b->release();
     e->marks_buf.release();
     e->amax.release();
     for (Blob &b : e->blobs) {
@@ -419,6 +420,7 @@ void stx_engine_destroy(stx_engine *e) {
         for (auto &s : e->sh->styles) s.gram->release();
         for (auto &m : e->sh->masks) m.map->release();
         for (auto &t : e->sh->stats) t.ms->release();
+        for (auto &m : e->sh->cmasks) m.map->release();
     }
     DevBuf *bufs[] = {&e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->first_gram, &e->color_sums};
@@ -616,10 +618,12 @@ int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *content
     for (auto &s : e->sh->styles) s.gram->release();
     for (auto &m : e->sh->masks) m.map->release();
     for (auto &t : e->sh->stats) t.ms->release();
+    for (auto &m : e->sh->cmasks) m.map->release();
     e->sh->contents.clear();
     e->sh->styles.clear();
     e->sh->masks.clear();
     e->sh->stats.clear();
+    e->sh->cmasks.clear();
     e->sh->n_contents = e->sh->n_styles = 0;
     bool host_src = false;
     for (int i = 0; i < n_contents; ++i) {
@@ -723,6 +727,61 @@ int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n) {
         for (auto &m : e->sh->masks) m.map->release();
         e->sh->masks.clear();
     }
+    return rc;
+}
+
+int stx_set_content_mask(stx_engine *e, const float *mask, int H, int W, int mem) {
+    if (!e || (mask && (H <= 0 || W <= 0))) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    std::lock_guard<std::mutex> lock(e->sh->mutex);
+    // the previous maps may still be in use by queued kernels (of any engine that shares them)
+    STX_TRY(quiesce_members(e));
+    auto clear = [&]() {
+        for (auto &m : e->sh->cmasks) m.map->release();
+        e->sh->cmasks.clear();
+    };
+    clear();
+    if (!mask) return STX_OK;
+    if (e->sh->contents.empty()) {
+        set_error("stx_set_content_mask: no content targets set (call it after stx_set_contents_and_styles)");
+        return STX_ERR_STATE;
+    }
+    // the map of a blob has the size of the blob's content maps: the tile's window is taken from both alike
+    for (const ContentTarget &ct : e->sh->contents) {
+        const int scale = e->blobs[ct.blob].scale;
+        if (ceil_div(H, scale) != ct.h || ceil_div(W, scale) != ct.w) {
+            set_error("stx_set_content_mask: a %dx%d mask gives a %dx%d map at layer %s, whose content map is "
+                      "%dx%d; the mask must have the content picture's size", H, W, ceil_div(H, scale),
+                      ceil_div(W, scale), e->blobs[ct.blob].name.c_str(), ct.h, ct.w);
+            return STX_ERR_ARG;
+        }
+    }
+    DevBuf staged;      // a host mask on its way to the device
+    int rc = STX_OK;
+    const float *src = mask;
+    if (mem == STX_HOST) {
+        const size_t bytes = (size_t)H * W * sizeof(float);
+        if ((rc = staged.ensure(bytes)) == STX_OK) rc = copy_in(e, staged.ptr, mask, STX_HOST, bytes);
+        src = staged.f();
+    }
+    for (const ContentTarget &ct : e->sh->contents) {
+        if (rc != STX_OK) break;
+        bool have = false;
+        for (const ContentMask &m : e->sh->cmasks) have |= m.blob == ct.blob;
+        if (have) continue;
+        ContentMask m{ct.blob, ct.h, ct.w, std::unique_ptr<DevBuf>(new DevBuf)};
+        if ((rc = m.map->ensure((size_t)m.h * m.w * sizeof(float))) == STX_OK)
+            rc = mask_map_launch(e->stream, src, H, W, e->blobs[ct.blob].scale, m.map->f());
+        e->sh->cmasks.push_back(std::move(m));
+    }
+    // (a host source may be reused right away; the sharing engines read the maps from their own streams)
+    const hipError_t err = hipStreamSynchronize(e->stream);
+    staged.release();
+    if (rc == STX_OK && err != hipSuccess) {
+        set_error("stx_set_content_mask: %s", hipGetErrorString(err));
+        rc = STX_ERR_HIP;
+    }
+    if (rc != STX_OK) clear();
     return rc;
 }
 

@@ -95,6 +95,13 @@ struct StyleMask {
     std::unique_ptr<DevBuf> map;
 };
 
+// The content mask at one blob that has a content target (stx_set_content_mask): the block means of the
+// image-resolution mask at the blob's scale, [h][w] -- the size of the blob's content maps.
+struct ContentMask {
+    int blob, h, w;
+    std::unique_ptr<DevBuf> map;
+};
+
 // The mean / std targets of one tapped blob (stx_set_stat_targets): MU [C] then SD [C] on the device.
 struct StatTarget {
     int blob, C;
@@ -123,6 +130,7 @@ struct SharedState {
     std::vector<StyleTarget> styles;
     std::vector<StyleMask> masks;      // (cleared with the targets)
     std::vector<StatTarget> stats;     // (cleared with the targets)
+    std::vector<ContentMask> cmasks;   // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -142,6 +150,7 @@ struct stx_engine {
     int marks_used = 0, last_mark = -1;    // (last_mark: the slot of the launch just queued, or -1)
     std::vector<std::unique_ptr<DevBuf>> sgrad_tap;   // S = sym(D) F of every style tap
     std::vector<std::unique_ptr<DevBuf>> sgrad_stat;  // S of the mean / std term of every tap that has one
+    std::vector<std::unique_ptr<DevBuf>> sgrad_content;   // S of the masked content terms of every tap that has some
     // start / stop of the last few tile calls (a ring: stx_last_tile_ms reports the newest call
     // that has finished, so a host that runs ahead does not wait for the call it just queued)
     static constexpr int kTimed = 4;
@@ -305,6 +314,13 @@ int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *fe
 int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *MU,
                       const float *SD, float *sgrad, float *sc, const std::string &name, float *stat_scratch,
                       std::vector<SumJob> *defer);
+// A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
+// sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
+// kContentMaskScratchFloats floats that outlive the call like term_scratch.
+constexpr size_t kContentMaskScratchFloats = 2 * kContentMaskParts;
+int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
+                                const float *mask_map, const ContentWindow &win, float *sgrad, float *sc,
+                                const std::string &name, float *partials, std::vector<SumJob> *defer);
 #pragma GCC visibility pop
 
 }  // namespace stx

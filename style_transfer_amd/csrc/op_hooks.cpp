@@ -153,6 +153,44 @@ int stx_op_stat_terms(stx_engine *e, const float *feat, int C, int h, int w, con
     return STX_OK;
 }
 
+int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *content,
+                                int content_h, int content_w, const float *mask_map, int oy, int ox,
+                                const int roll_xy[2], float *sgrad_out, double out[3]) {
+    if (!e || !feat || !content || !mask_map || !sgrad_out || !out || C <= 0 || h <= 0 || w <= 0) return STX_ERR_ARG;
+    if (oy < 0 || ox < 0 || oy + h > content_h || ox + w > content_w) {
+        set_error("stx_op_masked_content_terms: window exceeds the content map");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    // (the window and the roll in the maps' own pixels, like stx_op_content_terms)
+    ContentWindow win;
+    win.C = C;
+    win.fh = h;
+    win.fw = w;
+    win.ch = content_h;
+    win.cw = content_w;
+    win.oy = oy;
+    win.ox = ox;
+    win.sx = roll_xy ? roll_xy[0] : 0;
+    win.sy = roll_xy ? roll_xy[1] : 0;
+    STX_TRY(do_sync(e));
+    size_t si;
+    STX_TRY(alloc_scalars(e, 4, &si));
+    float *sc = e->A().scalars.f() + si;
+    STX_TRY(e->term_scratch.ensure(kContentMaskScratchFloats * sizeof(float)));
+    // the launches of a masked content target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_masked_content_terms(e, e->stream, feat, content, mask_map, win, sgrad_out, sc, "op",
+                                        e->term_scratch.f(), nullptr));
+    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
+                           hipMemcpyDeviceToHost, e->stream));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    out[0] = 0.5 * (double)e->A().host[si];
+    out[1] = (double)e->A().host[si + 1];
+    out[2] = (double)e->A().host[si + 2];
+    e->A().used = 0;
+    return STX_OK;
+}
+
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]) {

@@ -516,6 +516,21 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
     return STX_OK;
 }
 
+// A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
+// S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
+int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
+                                const float *mask_map, const ContentWindow &win, float *sgrad, float *sc,
+                                const std::string &name, float *partials, std::vector<SumJob> *defer) {
+    ProfScope scope(e, "cmask " + name, 0.0, stream);
+    STX_TRY(content_mask_mean_launch(stream, mask_map, win, sc + 2));
+    int n = 0;
+    STX_TRY(content_mask_term_launch(stream, feat, content, mask_map, win, sc + 2, sgrad, partials, &n));
+    if (!defer) return sum_partials2_launch(stream, partials, n, sc, partials + n, n, sc + 1);
+    defer->push_back(SumJob{partials, n, sc});
+    defer->push_back(SumJob{partials + n, n, sc + 1});
+    return STX_OK;
+}
+
 static int begin_timing(stx_engine *e) {
     e->ev_cur = (e->ev_cur + 1) % stx_engine::kTimed;
     STX_HIP(hipEventRecord(e->ev_start[e->ev_cur], e->stream));
@@ -694,11 +709,50 @@ static int queue_residual_term(TileRun &run, size_t k, const char *label, const 
     return STX_OK;
 }
 
+// The content mask map at `blob` (stx_set_content_mask), or null.
+static const ContentMask *content_mask_of(const stx_engine *e, int blob) {
+    for (const ContentMask &m : e->sh->cmasks)
+        if (m.blob == blob) return &m;
+    return nullptr;
+}
+
+// The term of content target `ct` of tap k through the mask map (its size is the content map's: `win` is the
+// window of both): launch_masked_content_terms into `sgrad`, which then rides as a gradient blob.
+static int queue_masked_content_term(TileRun &run, size_t k, const ContentTarget &ct, const ContentMask &mk,
+                                     const ContentWindow &win, float *sgrad) {
+    stx_engine *e = run.e;
+    const Tap &tp = run.plan.order[k];
+    const Blob &b = e->blobs[tp.blob];
+    if (win.oy < 0 || win.ox < 0) {
+        set_error("content mask window [%d+%d, %d+%d] exceeds the %dx%d mask map of layer %s",
+                  win.oy, win.fh, win.ox, win.fw, win.ch, win.cw, b.name.c_str());
+        return STX_ERR_ARG;
+    }
+    size_t si;
+    STX_TRY(alloc_scalars(e, 4, &si));
+    float *sc = e->A().scalars.f() + si;   // [0] = sum m d^2, [1] = sum |m d|, [2] = a
+    float *partials = e->term_scratch.f() + run.scratch_used;
+    run.scratch_used += kContentMaskScratchFloats;
+    STX_TRY(launch_masked_content_terms(e, e->stream, b.data.f(), ct.feat->f(), mk.map->f(), win, sgrad, sc,
+                                        b.name, partials, run.defer()));
+    const double weight = tp.t->layer_weight * tp.t->content_weight;
+    run.pl.terms.push_back(LossTerm{si, weight * 0.5});
+    run.terms[k].push_back(Term{true, sgrad, sc + 1, (float)weight, ContentWindow{}});
+    return STX_OK;
+}
+
 static int queue_content_terms(TileRun &run, size_t k) {
     stx_engine *e = run.e;
     const Tap &tp = run.plan.order[k];
     const Blob &b = e->blobs[tp.blob];
     bool any = false;
+    const ContentMask *mk = e->sh->cmasks.empty() ? nullptr : content_mask_of(e, tp.blob);
+    int slot = 0;
+    if (mk) {
+        int n_here = 0;
+        for (const ContentTarget &ct : e->sh->contents) n_here += ct.blob == tp.blob;
+        STX_TRY(e->sgrad_content[k]->ensure((size_t)n_here * b.count() * sizeof(float)));
+    }
     for (const ContentTarget &ct : e->sh->contents) {
         if (ct.blob != tp.blob) continue;
         any = true;
@@ -707,6 +761,11 @@ static int queue_content_terms(TileRun &run, size_t k) {
             set_error("content window [%d+%d, %d+%d] exceeds the %dx%d map of layer %s",
                       win.oy, win.fh, win.ox, win.fw, win.ch, win.cw, b.name.c_str());
             return STX_ERR_ARG;
+        }
+        if (mk) {
+            STX_TRY(queue_masked_content_term(run, k, ct, *mk, win,
+                                              e->sgrad_content[k]->f() + (size_t)slot++ * b.count()));
+            continue;
         }
         STX_TRY(queue_residual_term(run, k, "content ", ct.feat->f(), win, tp.t->layer_weight * tp.t->content_weight));
     }
@@ -1050,12 +1109,18 @@ static int sc_grad_run(stx_engine *e, const TileCall &c, const TilePlan &plan, P
     while (e->sgrad_tap.size() < order.size()) e->sgrad_tap.emplace_back(new DevBuf);
     if (!e->sh->stats.empty())
         while (e->sgrad_stat.size() < order.size()) e->sgrad_stat.emplace_back(new DevBuf);
+    if (!e->sh->cmasks.empty())
+        while (e->sgrad_content.size() < order.size()) e->sgrad_content.emplace_back(new DevBuf);
     {
         size_t need = 0;
         for (const Tap &tp : order) {
             const Blob &b = e->blobs[tp.blob];
             // (a statistics term's partials and table live there, with or without the late sums)
             if (stat_target_of(e, tp.blob)) need += stat_scratch_floats(b.channels, b.h * b.w);
+            // (and a masked content term's partials)
+            if (tp.t->is_content && !e->sh->cmasks.empty() && content_mask_of(e, tp.blob))
+                for (const ContentTarget &ct : e->sh->contents)
+                    if (ct.blob == tp.blob) need += kContentMaskScratchFloats;
             if (!tp.t->is_style) continue;
             for (const StyleTarget &st : e->sh->styles) {
                 if (st.blob != tp.blob) continue;

@@ -188,6 +188,15 @@ def refuse_style_masks(args):
                                   'run the single-process tile farm (--devices) instead')
 
 
+def refuse_content_mask(args):
+    """--content-mask with one process per GPU: the mask would have to travel to every rank with the
+    targets, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
+    if getattr(args, 'content_mask', None):
+        raise NotImplementedError('--content-mask is not implemented for the one-process-per-GPU layout '
+                                  '(style_transfer_amd.dist): the mask is not broadcast to the ranks; '
+                                  'run the single-process tile farm (--devices) instead')
+
+
 def refuse_stat_weight(args):
     """--stat-weight with one process per GPU: the statistics targets would have to travel to every rank
     with the others, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
@@ -244,9 +253,11 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks or --stat-weight is refused here (refuse_style_masks, refuse_stat_weight)."""
+    a run with --style-masks, --content-mask or --stat-weight is refused here (refuse_style_masks,
+    refuse_content_mask, refuse_stat_weight)."""
     if args is not None:
         refuse_style_masks(args)
+        refuse_content_mask(args)
         refuse_stat_weight(args)
     rank = dist.get_rank(group)
     wire = _wire_device(device, group)

@@ -349,6 +349,20 @@ class TileEngine:
         lib.call('stx_set_style_masks', self.handle, table, len(entries))
         del keep
 
+    def set_content_mask(self, mask):
+        """mask: an [H, W] array in [0, 1] in the content picture's frame (numpy, DeviceArray or torch tensor;
+        white = the content picture is held there, black = the content term is off there), applied to every
+        content target, or None: no mask (stx_set_content_mask).  Call it after ``set_contents_and_styles``,
+        which clears it."""
+        if mask is None:
+            lib.call('stx_set_content_mask', self.handle, None, 0, 0, lib.HOST)
+            return
+        ptr, mem, keep = _as_arg(mask)
+        if len(keep.shape) != 2:
+            raise ValueError('content mask: an [H, W] array is expected, not %s' % (tuple(keep.shape),))
+        lib.call('stx_set_content_mask', self.handle, ptr, int(keep.shape[0]), int(keep.shape[1]), mem)
+        del keep
+
     # --------------------------------------------------------------------- FeatureMapRequest
     def features_tile(self, img, layers):
         """Post-ReLU feature maps of one tile: {layer: [C, ceil(th/s), ceil(tw/s)] ndarray}."""

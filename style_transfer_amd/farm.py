@@ -176,6 +176,14 @@ class TileFarm:
         for e in self.primaries():
             e.set_style_masks(masks)
 
+    def set_content_mask(self, mask):
+        """Hands the content mask (TileEngine.set_content_mask) to every GPU, once each, the way the
+        targets are handed; call it behind ``set_contents_and_styles``."""
+        for e in self.engines:
+            e.sync()
+        for e in self.primaries():
+            e.set_content_mask(mask)
+
     def set_stat_targets(self, targets, weights=None):
         """Hands the statistics targets (TileEngine.set_stat_targets) to every GPU, once each; call it
         behind ``set_contents_and_styles``."""

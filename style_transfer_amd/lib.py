@@ -88,6 +88,7 @@ SIGNATURES = {
                                     ctypes.POINTER(StyleTarget), _i],
     'stx_set_style_masks': [_vp, ctypes.POINTER(StyleMask), _i],
     'stx_set_stat_targets': [_vp, ctypes.POINTER(StatTarget), _i],
+    'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
     'stx_sc_grad_tile': [_vp, _vp, _i, _i, _i, c_int_p, c_int_p, ctypes.POINTER(Tap), _i,
@@ -133,6 +134,7 @@ SIGNATURES = {
     'stx_op_pool_backward': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     'stx_op_style_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p, c_double_p],
     'stx_op_masked_style_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, _vp, c_double_p],
+    'stx_op_masked_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, c_int_p, _vp, c_double_p],
     'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],

@@ -111,6 +111,19 @@ def style_pyramid(args):
 PRESERVE_COLOR = ('none', 'luma', 'match')
 
 
+def mask_at_size(mask, size_hw):
+    """A greyscale PIL mask at one scale: Lanczos-resized to (H, W), as float32 in [0, 1] (clipped)."""
+    h, w = int(size_hw[0]), int(size_hw[1])
+    return np.clip(np.float32(mask.convert('L').resize((w, h), Image.LANCZOS)) / np.float32(255), 0, 1)
+
+
+def rolled_mask(mask, roll):
+    """An [H, W] mask moved with the picture by ``roll`` = (x, y) pixels (--jitter), wrapping; None: as it is."""
+    if roll is None:
+        return mask
+    return np.roll(mask, (int(roll[1]), int(roll[0])), (0, 1))
+
+
 def parse_weights(args, master_weight):
     """['name', 'name:2', ...] -> (names, {name: weight normalised to sum |w| = master})
     (style_transfer.py:684-698)."""
@@ -171,6 +184,11 @@ class StyleTransfer:
         # go to the engines behind the targets.  None: no new code runs.
         self.style_masks = None
         self._scale_masks = None    # [H, W] float32 arrays in [0, 1] of the scale being optimised
+        # --content-mask (spatial control of the content term; not an option of the reference): one greyscale
+        # PIL picture in the content picture's frame, handed to transfer_multiscale; resized to the scale's
+        # content size it goes to the engines behind the targets.  None: no new code runs.
+        self.content_mask = None
+        self._scale_content_mask = None
         # --lap-weight / --lap-pools (the Laplacian loss; not options of the reference): the target of the
         # scale being optimised, D P_p u of its first content picture for every pool size, on the master
         # GPU.  Without the options nothing here runs.
@@ -257,19 +275,17 @@ class StyleTransfer:
 
     def _masks_for(self, size_hw):
         """The style masks at one scale: Lanczos-resized to the content size, clipped to [0, 1]."""
-        h, w = int(size_hw[0]), int(size_hw[1])
-        return [np.clip(np.float32(mask.convert('L').resize((w, h), Image.LANCZOS)) / np.float32(255), 0, 1)
-                for mask in self.style_masks]
+        return [mask_at_size(mask, size_hw) for mask in self.style_masks]
 
     def _send_masks(self, roll=None):
-        """The scale's masks to the engines, behind the targets (which clear them).  ``roll`` (--jitter):
-        the engines hold content maps of the rolled picture and shift nothing, so the masks are rolled too."""
-        if self._scale_masks is None:
-            return
-        masks = self._scale_masks
-        if roll is not None:
-            masks = [np.roll(m, (int(roll[1]), int(roll[0])), (0, 1)) for m in masks]
-        self.farm.set_style_masks(masks)
+        """The scale's style masks and content mask to the engines, behind the targets (which clear them).
+        ``roll`` (--jitter): the engines hold content maps of the rolled picture and shift nothing, so the
+        masks are rolled too.  The content mask goes with content targets only (under --jitter there are none
+        until the first step)."""
+        if self._scale_masks is not None:
+            self.farm.set_style_masks([rolled_mask(m, roll) for m in self._scale_masks])
+        if self._scale_content_mask is not None and self.contents:
+            self.farm.set_content_mask(rolled_mask(self._scale_content_mask, roll))
 
     def _send_stats(self):
         """The statistics targets of the scale's --stat-layers to the engines, behind the targets (which clear
@@ -455,7 +471,9 @@ class StyleTransfer:
                 raise ValueError('--style-masks: %d mask(s) for %d style set(s)'
                                  % (len(self.style_masks), len(self.styles)))
             self._scale_masks = self._masks_for(self.img.shape[1:])
-            self._send_masks()
+        if self.content_mask is not None:
+            self._scale_content_mask = mask_at_size(self.content_mask, self.img.shape[1:])
+        self._send_masks()
 
         if self.grad is None or self.grad.shape != self.img.shape:
             for buf in (self.grad, self.old_avg):
@@ -597,10 +615,11 @@ class StyleTransfer:
         raise ValueError(args.optimizer)
 
     def transfer_multiscale(self, content_images, style_images, initial_image=None, aux_image=None,
-                            callback=None, style_masks=None):
+                            callback=None, style_masks=None, content_mask=None):
         """Runs the planned pyramid (plan_scales), coarsest level first; every level starts from
         the Lanczos-upsampled averaged iterate of the one before (style_transfer.py:832-909).
-        ``style_masks`` (--style-masks): one greyscale PIL picture per style image."""
+        ``style_masks`` (--style-masks): one greyscale PIL picture per style image; ``content_mask``
+        (--content-mask): one greyscale PIL picture that weights the content term."""
         args = self.args
         if any(image.size != content_images[0].size for image in content_images):
             raise ValueError('All of the content images must be the same size')
@@ -610,6 +629,10 @@ class StyleTransfer:
                                  'is needed' % (len(style_masks), len(style_images)))
             self.style_masks = list(style_masks)
             self.styles = []
+        if content_mask is not None:
+            if not args.content_layers:
+                raise ValueError('--content-mask needs a content term: --content-layers is empty')
+            self.content_mask = content_mask
         plans = plan_scales(args, content_images[0].size, [image.size for image in style_images])
         if callback is not None and hasattr(callback, 'set_steps'):
             callback.set_steps(sum(plan.iterations for plan in plans))
