@@ -398,7 +398,8 @@ int stx_image_swt_daub_levels(stx_engine *e, const float *img, float *grad, int 
 /* AdamOptimizer.update after the gradient is known (optimizers.py:35-42), fused:
  *   g1 = b1*g1 + (1-b1)*grad; g2 = b2*g2 + (1-b2)*grad^2; p1 likewise on the new params;
  *   params -= lr * (g1/c1) / (sqrt(g2/c2) + EPS);  avg_out = p1/cp
- * where c1, c2, cp are the EWMA bias corrections (1 - beta^t, or 1 when uncorrected). */
+ * where c1, c2, cp are the EWMA bias corrections (1 - beta^t, or 1 when uncorrected).
+ * n == 0 is STX_ERR_ARG, here and in every stx_vec_* call below: nothing is launched. */
 int stx_adam_step(stx_engine *e, float *params, const float *grad, float *g1, float *g2, float *p1,
                   float *avg_out, size_t n, double lr, double b1, double b2, double bp1,
                   double corr1, double corr2, double corrp);

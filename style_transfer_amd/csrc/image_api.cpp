@@ -316,7 +316,7 @@ int stx_image_lap(stx_engine *e, const float *img, float *grad, int H, int W, in
 int stx_adam_step(stx_engine *e, float *params, const float *grad, float *g1, float *g2, float *p1,
                   float *avg_out, size_t n, double lr, double b1, double b2, double bp1, double corr1,
                   double corr2, double corrp) {
-    if (!e || !params || !grad || !g1 || !g2 || !p1 || !avg_out) return STX_ERR_ARG;
+    if (!e || !params || !grad || !g1 || !g2 || !p1 || !avg_out || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return adam_launch(e->stream, params, grad, g1, g2, p1, avg_out, n, lr, b1, b2, bp1, corr1,
                        corr2, corrp);
@@ -331,7 +331,7 @@ static int sync_scalar(stx_engine *e, size_t di, int n, double *out) {
 }
 
 int stx_vec_dot(stx_engine *e, const float *x, const float *y, size_t n, double *out) {
-    if (!e || !x || !y || !out) return STX_ERR_ARG;
+    if (!e || !x || !y || !out || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     const size_t di = e->dscalars_cap - 2;   // reserved slot for synchronous scalar results
     STX_TRY(dot_launch(e->stream, x, y, n, static_cast<double *>(e->A().dscalars.ptr) + di,
@@ -351,14 +351,14 @@ int stx_vec_mean_abs(stx_engine *e, const float *x, size_t n, double *out) {
 }
 
 int stx_vec_dot_async(stx_engine *e, const float *x, const float *y, size_t n, double *out_dev) {
-    if (!e || !x || !y || !out_dev) return STX_ERR_ARG;
+    if (!e || !x || !y || !out_dev || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return dot_launch(e->stream, x, y, n, out_dev, e->red_scratch.f(),
                       e->red_scratch.bytes / sizeof(float));
 }
 
 int stx_vec_abs_sum_async(stx_engine *e, const float *x, size_t n, double *out_dev) {
-    if (!e || !x || !out_dev) return STX_ERR_ARG;
+    if (!e || !x || !out_dev || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return abs_sum_launch(e->stream, x, n, out_dev, e->red_scratch.f(),
                           e->red_scratch.bytes / sizeof(float));
@@ -366,14 +366,14 @@ int stx_vec_abs_sum_async(stx_engine *e, const float *x, size_t n, double *out_d
 
 int stx_vec_axpy_dev(stx_engine *e, double c1, const double *a_dev, double da, double c2,
                      const double *b_dev, double db, const float *x, float *y, size_t n) {
-    if (!e || !a_dev || !x || !y || da == 0.0 || (b_dev && db == 0.0)) return STX_ERR_ARG;
+    if (!e || !a_dev || !x || !y || !n || da == 0.0 || (b_dev && db == 0.0)) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return axpy_dev_launch(e->stream, c1, a_dev, da, c2, b_dev, db, x, y, n);
 }
 
 int stx_vec_scale_dev(stx_engine *e, double c, const double *den_dev, double den_div, float *x,
                       size_t n) {
-    if (!e || !den_dev || !x || den_div == 0.0) return STX_ERR_ARG;
+    if (!e || !den_dev || !x || !n || den_div == 0.0) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return scale_dev_launch(e->stream, c, den_dev, den_div, x, n);
 }
@@ -382,7 +382,7 @@ int stx_vec_axpy_dot_dev(stx_engine *e, double c1, const double *a_dev, double d
                          const double *b_dev, double db, double scale_c, const double *scale_den_dev,
                          double scale_div, const float *x, const float *src, float *y, const float *z,
                          size_t n, double *out_dev) {
-    if (!e || !a_dev || !x || !src || !y || !z || !out_dev || da == 0.0 || (b_dev && db == 0.0) ||
+    if (!e || !a_dev || !x || !src || !y || !z || !out_dev || !n || da == 0.0 || (b_dev && db == 0.0) ||
         (scale_den_dev && scale_div == 0.0))
         return STX_ERR_ARG;
     STX_TRY(e->set_device());
@@ -392,7 +392,7 @@ int stx_vec_axpy_dot_dev(stx_engine *e, double c1, const double *a_dev, double d
 
 int stx_vec_lbfgs_pair(stx_engine *e, const float *g_new, float *g_old, const float *s, float *y, size_t n,
                        double *out_dev2, double *sy_host_sync) {
-    if (!e || !g_new || !g_old || !s || !y || !out_dev2 || !sy_host_sync) return STX_ERR_ARG;
+    if (!e || !g_new || !g_old || !s || !y || !out_dev2 || !sy_host_sync || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     STX_TRY(lbfgs_pair_launch(e->stream, g_new, g_old, s, y, n, out_dev2, e->red_scratch.f(),
                               e->red_scratch.bytes / sizeof(float)));
@@ -404,19 +404,19 @@ int stx_vec_lbfgs_pair(stx_engine *e, const float *g_new, float *g_old, const fl
 }
 
 int stx_vec_scale2_axpy(stx_engine *e, double c1, double c2, float *s, float *params, size_t n) {
-    if (!e || !s || !params) return STX_ERR_ARG;
+    if (!e || !s || !params || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return scale2_axpy_launch(e->stream, (float)c1, (float)c2, s, params, n);
 }
 
 int stx_vec_axpy(stx_engine *e, double a, const float *x, float *y, size_t n) {
-    if (!e || !x || !y) return STX_ERR_ARG;
+    if (!e || !x || !y || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return axpy_launch(e->stream, (float)a, x, y, n);
 }
 
 int stx_vec_scale(stx_engine *e, double a, float *x, size_t n) {
-    if (!e || !x) return STX_ERR_ARG;
+    if (!e || !x || !n) return STX_ERR_ARG;
     STX_TRY(e->set_device());
     return scale_launch(e->stream, (float)a, x, n);
 }
