@@ -37,6 +37,7 @@ SOURCES = {
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'tile_path.cpp': [],
+    'tile_terms.cpp': [],
     'image_api.cpp': [],
     'op_hooks.cpp': [],
 }
@@ -69,7 +70,7 @@ def _compile(src, extra, force):
 
 def build(force=False, verbose=False):
     """Compiles every translation unit (in parallel) and links libstx.so.  Returns its path."""
-    with concurrent.futures.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(16, len(SOURCES))) as ex:
         futs = [ex.submit(_compile, src, extra, force) for src, extra in SOURCES.items()]
         objs = [f.result() for f in futs]
     if force or _stale(LIB, objs):

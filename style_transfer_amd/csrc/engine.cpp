@@ -391,9 +391,7 @@ void stx_engine_destroy(stx_engine *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto &b : e->sgrad_tap) b->release();
-    for (auto &b : e->sgrad_stat) b->release();
-    for (auto &b : e->sgrad_content) b->release();
+    for (auto &b : e->sgrad) b->release();
     e->marks_buf.release();
     e->amax.release();
     for (Blob &b : e->blobs) {

@@ -1,10 +1,12 @@
 // The engine's state and the few helpers that more than one host file uses.  Internal: not installed.
 //   engine.cpp     engine life cycle, weights and targets, scalar arenas and fences, profiling readers
-//   tile_path.cpp  the tile evaluation: forward pass, loss terms, backward walk
+//   tile_path.cpp  the tile evaluation: shaping, forward pass, backward walk
+//   tile_terms.cpp the loss terms of a tile evaluation: their plan, their launches, their injection
 //   image_api.cpp  whole-image and vector entries, the SWT regulariser's tables, the Laplacian loss
 //   op_hooks.cpp   stx_op_*: single operators for the tests
 #pragma once
 
+#include <deque>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -148,9 +150,7 @@ struct stx_engine {
     bool clock_marks = false;              // stx_clock_marks: one mark per 2-D Winograd launch
     DevBuf marks_buf;
     int marks_used = 0, last_mark = -1;    // (last_mark: the slot of the launch just queued, or -1)
-    std::vector<std::unique_ptr<DevBuf>> sgrad_tap;   // S = sym(D) F of every style tap
-    std::vector<std::unique_ptr<DevBuf>> sgrad_stat;  // S of the mean / std term of every tap that has one
-    std::vector<std::unique_ptr<DevBuf>> sgrad_content;   // S of the masked content terms of every tap that has some
+    std::vector<std::unique_ptr<DevBuf>> sgrad;       // per tap: the gradient blobs S of its terms (PlannedTerm::sgrad_off)
     // start / stop of the last few tile calls (a ring: stx_last_tile_ms reports the newest call
     // that has finished, so a host that runs ahead does not wait for the call it just queued)
     static constexpr int kTimed = 4;
@@ -179,7 +179,7 @@ struct stx_engine {
     int first_gram_blob = -1, first_gram_parts = 0;
     bool first_gram_valid = false;
     DevBuf gram_partials, gram, dsym, dsym_pieces, symm_partials, upload;
-    DevBuf term_scratch;               // per style term of a tile call: block sums / maxima + SYMM partials (sum jobs)
+    DevBuf term_scratch;               // per term of a tile call: what its launches leave for the sum jobs (TilePlan)
     DevBuf masked_feat, masked_target; // a masked style term's F . m and a Gs (style_mask.hip), one term at a time
     DevBuf stat_scratch;               // stx_feature_stats / stx_op_stat_terms: partials, table, outputs
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
@@ -296,6 +296,84 @@ ConvProblem conv_bwd_problem(const float *dy, float *dx, const float *mask, int 
 int attach_splitk(stx_engine *e, const ConvConfig &cfg, ConvProblem &p);
 int launch_conv(stx_engine *e, const ConvConfig &cfg, const ConvProblem &problem);
 int amax_scratch(stx_engine *e, unsigned **out);
+// ---- tile_terms.cpp: the loss terms of one tile evaluation
+struct Tap {
+    int blob;
+    const stx_tap *t;
+};
+
+// One stx_sc_grad_tile call.
+struct TileCall {
+    const float *img;
+    int img_mem, th, tw, rx, ry, start[2];
+    const stx_tap *taps;
+    int n_taps;
+    float *grad_out;
+    int grad_mem;
+};
+
+enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Dream };
+constexpr size_t kNoSlot = ~(size_t)0;
+constexpr size_t kResidualScalars = 2 + 2 * 1024;   // content_sums_launch: two sums and their partials
+
+// One loss term of a call, planned before the first launch (plan_terms).
+struct PlannedTerm {
+    TermKind kind;
+    int tap;                         // index into TilePlan::order
+    const float *target, *mask;      // content map / Gram / MU then SD / null (dream); the mask map or null
+    ContentWindow win;               // the tile's window of the content or mask map (with the map's size)
+    double coef;                     // of the gradient term; the loss term takes half of it
+    size_t scalars;                  // floats of the scalar arena
+    size_t scratch_off, scratch_len; // its region of the engine's term_scratch, in floats
+    size_t sgrad_off;                // its blob S in the tap's gradient buffer (stx_engine::sgrad), in floats, or kNoSlot
+};
+
+struct TilePlan {
+    std::vector<Tap> order;         // taps, deepest first
+    std::vector<char> needed;       // blobs on the path
+    std::vector<int> tap_of;        // blob -> index into order, or -1
+    std::deque<stx_tap> extra;      // taps of the layers that only a statistics target names (lw = 1);
+                                    // `order` points into it: a deque's elements stay where they are
+    // The final sums of the loss terms are collected and run as ONE launch behind the forward pass
+    // (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did); what they add up must outlive the term's
+    // own launches: its region of term_scratch.
+    bool sums_late;
+    bool interleave;                // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
+    // The terms in queueing order -- shallowest tap first; per tap the content targets in sh->contents order,
+    // the style targets in sh->styles order, the statistics term, Deep-Dream -- which is the order of
+    // PendingLoss::terms: the host adds the loss up in it.
+    std::vector<PlannedTerm> terms;
+    std::vector<size_t> first_term;     // per tap: its first record
+    std::vector<size_t> sgrad_floats;   // per tap: the size of its gradient buffer
+    size_t scratch_floats = 0, scalars = 0;     // what the call takes of term_scratch and of the scalar arena
+};
+
+// One loss term of a tapped blob, as the backward walk adds it to the blob's gradient.
+struct Term {
+    enum Kind { Gradient, Residual } kind;
+    const float *src;        // Gradient: a ready blob S;  Residual: the map F is held against (null: Deep-Dream)
+    const float *sums;       // Gradient: &sum|S|;  Residual: {sum d^2, sum |d|}
+    float coef;
+    ContentWindow win;
+};
+
+// One evaluation (sc_grad_run): what its steps share.
+struct TileRun {
+    stx_engine *e;
+    const TilePlan &plan;
+    PendingLoss &pl;
+    std::vector<std::vector<Term>> terms;     // per tap, in plan.order
+    std::vector<SumJob> sum_jobs;
+    std::vector<SumJob> *defer() { return plan.sums_late ? &sum_jobs : nullptr; }
+};
+
+// Validates the targets of the taps (shaped blobs) and lists the terms with what each takes.
+int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan);
+// Loss terms of tap k: launches them and records them for the backward walk and the host's sum.
+int queue_tap_terms(TileRun &run, size_t k);
+int inject_terms(TileRun &run, size_t k, bool &diff_written);
+bool tap_fusable(const TileRun &run, size_t k);
+ConvInject make_inject(const TileRun &run, size_t k, const Blob &bot);
 int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
                        const float *target, float *sgrad, float *sc, const std::string &name,
                        const unsigned *f_amax = nullptr, float *term_scratch = nullptr,

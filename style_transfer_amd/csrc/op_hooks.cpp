@@ -68,29 +68,65 @@ int stx_op_pool_backward(stx_engine *e, const float *dy, const float *x, int C, 
     return pool_backward_launch(e->stream, dy, x, C, H, W, mode, relu_mask_data != nullptr, dx);
 }
 
+// The window of an h x w tile at (oy, ox) of a map_h x map_w map behind a roll: the caller gives all of them in
+// the map's own pixels, so nothing is divided by a scale.
+static ContentWindow hook_window(int C, int h, int w, int map_h, int map_w, int oy, int ox, const int roll_xy[2]) {
+    ContentWindow win;
+    win.C = C;
+    win.fh = h;
+    win.fw = w;
+    win.ch = map_h;
+    win.cw = map_w;
+    win.oy = oy;
+    win.ox = ox;
+    win.sx = roll_xy ? roll_xy[0] : 0;
+    win.sy = roll_xy ? roll_xy[1] : 0;
+    return win;
+}
+
+// The scalars of one term hook: take() drains the arena and hands out n device floats of it, fetch() mirrors
+// them, waits and hands out their host copies; the arena is empty again when the hook returns.
+namespace {
+struct HookScalars {
+    stx_engine *e;
+    size_t si = 0;
+    explicit HookScalars(stx_engine *eng) : e(eng) {}
+    ~HookScalars() { e->A().used = 0; }
+    int take(size_t n, float **sc) {
+        STX_TRY(do_sync(e));
+        STX_TRY(alloc_scalars(e, n, &si));
+        *sc = e->A().scalars.f() + si;
+        return STX_OK;
+    }
+    int fetch(const float **host) {
+        STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float), hipMemcpyDeviceToHost,
+                               e->stream));
+        STX_HIP(hipStreamSynchronize(e->stream));
+        *host = e->A().host + si;
+        return STX_OK;
+    }
+};
+}  // namespace
+
 int stx_op_style_terms(stx_engine *e, const float *feat, int C, int h, int w,
                        const float *gram_target, float *s_out, float *normalized_out,
                        double *half_sumsq, double *abs_sum) {
     if (!e || !feat || !gram_target || C <= 0 || C % 4 || h <= 0 || w <= 0) return STX_ERR_ARG;
     STX_TRY(e->set_device());
-    const int HW = h * w;
-    const size_t count = (size_t)C * HW;
-    // the launches of the style branch of stx_sc_grad_tile, in the same order
+    const size_t count = (size_t)C * h * w;
     STX_TRY(e->upload.ensure(count * sizeof(float)));
     float *sgrad = s_out ? s_out : e->upload.f();
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2, &si));
-    float *sc = e->A().scalars.f() + si;
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
+    // the launches of the style branch of stx_sc_grad_tile, in the same order
     STX_TRY(launch_style_terms(e, e->stream, feat, C, h, w, gram_target, sgrad, sc, "op"));
     if (normalized_out)
         STX_TRY(inject_style_launch(e->stream, normalized_out, sgrad, count, sc + 1, 1.0f, false));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
-    if (half_sumsq) *half_sumsq = 0.5 * (double)e->A().host[si];
-    if (abs_sum) *abs_sum = (double)e->A().host[si + 1];
-    e->A().used = 0;
+    STX_TRY(scalars.fetch(&host));
+    if (half_sumsq) *half_sumsq = 0.5 * (double)host[0];
+    if (abs_sum) *abs_sum = (double)host[1];
     return STX_OK;
 }
 
@@ -104,32 +140,18 @@ int stx_op_masked_style_terms(stx_engine *e, const float *feat, int C, int h, in
         return STX_ERR_ARG;
     }
     STX_TRY(e->set_device());
-    // (the window and the roll in the map's own pixels, like stx_op_content_terms)
-    ContentWindow win;
-    win.C = C;
-    win.fh = h;
-    win.fw = w;
-    win.ch = mh;
-    win.cw = mw;
-    win.oy = oy;
-    win.ox = ox;
-    win.sx = roll_xy ? roll_xy[0] : 0;
-    win.sy = roll_xy ? roll_xy[1] : 0;
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 4, &si));
-    float *sc = e->A().scalars.f() + si;
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(4, &sc));
     STX_TRY(e->term_scratch.ensure(kMaskScratchFloats * sizeof(float)));
     // the launches of a masked style target of stx_sc_grad_tile, in the same order
-    STX_TRY(launch_masked_style_terms(e, e->stream, feat, C, h, w, mask_map, win, gram_target, sgrad_out, sc, "op",
-                                      nullptr, nullptr, e->term_scratch.f(), nullptr));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
-    out[0] = 0.5 * (double)e->A().host[si];
-    out[1] = (double)e->A().host[si + 2];
-    out[2] = (double)e->A().host[si + 3];
-    e->A().used = 0;
+    STX_TRY(launch_masked_style_terms(e, e->stream, feat, C, h, w, mask_map, hook_window(C, h, w, mh, mw, oy, ox, roll_xy),
+                                      gram_target, sgrad_out, sc, "op", nullptr, nullptr, e->term_scratch.f(), nullptr));
+    STX_TRY(scalars.fetch(&host));
+    out[0] = 0.5 * (double)host[0];
+    out[1] = (double)host[2];
+    out[2] = (double)host[3];
     return STX_OK;
 }
 
@@ -137,19 +159,16 @@ int stx_op_stat_terms(stx_engine *e, const float *feat, int C, int h, int w, con
                       float *s_out, double out[2]) {
     if (!e || !feat || !MU || !SD || !s_out || !out || C <= 0 || h <= 0 || w <= 0) return STX_ERR_ARG;
     STX_TRY(e->set_device());
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2, &si));
-    float *sc = e->A().scalars.f() + si;
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
     STX_TRY(e->stat_scratch.ensure(stat_scratch_floats(C, h * w) * sizeof(float)));
     // the launches of a statistics target of stx_sc_grad_tile, in the same order
     STX_TRY(launch_stat_terms(e, e->stream, feat, C, h, w, MU, SD, s_out, sc, "op", e->stat_scratch.f(), nullptr));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
-    out[0] = 0.5 * (double)e->A().host[si];
-    out[1] = (double)e->A().host[si + 1];
-    e->A().used = 0;
+    STX_TRY(scalars.fetch(&host));
+    out[0] = 0.5 * (double)host[0];
+    out[1] = (double)host[1];
     return STX_OK;
 }
 
@@ -162,32 +181,19 @@ int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, 
         return STX_ERR_ARG;
     }
     STX_TRY(e->set_device());
-    // (the window and the roll in the maps' own pixels, like stx_op_content_terms)
-    ContentWindow win;
-    win.C = C;
-    win.fh = h;
-    win.fw = w;
-    win.ch = content_h;
-    win.cw = content_w;
-    win.oy = oy;
-    win.ox = ox;
-    win.sx = roll_xy ? roll_xy[0] : 0;
-    win.sy = roll_xy ? roll_xy[1] : 0;
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 4, &si));
-    float *sc = e->A().scalars.f() + si;
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(4, &sc));
     STX_TRY(e->term_scratch.ensure(kContentMaskScratchFloats * sizeof(float)));
     // the launches of a masked content target of stx_sc_grad_tile, in the same order
-    STX_TRY(launch_masked_content_terms(e, e->stream, feat, content, mask_map, win, sgrad_out, sc, "op",
+    STX_TRY(launch_masked_content_terms(e, e->stream, feat, content, mask_map,
+                                        hook_window(C, h, w, content_h, content_w, oy, ox, roll_xy), sgrad_out, sc, "op",
                                         e->term_scratch.f(), nullptr));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
-    out[0] = 0.5 * (double)e->A().host[si];
-    out[1] = (double)e->A().host[si + 1];
-    out[2] = (double)e->A().host[si + 2];
-    e->A().used = 0;
+    STX_TRY(scalars.fetch(&host));
+    out[0] = 0.5 * (double)host[0];
+    out[1] = (double)host[1];
+    out[2] = (double)host[2];
     return STX_OK;
 }
 
@@ -200,32 +206,19 @@ int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,
         return STX_ERR_ARG;
     }
     STX_TRY(e->set_device());
-    // (the caller gives the window and the roll in the map's own pixels: nothing to divide by a scale)
-    ContentWindow win;
-    win.C = C;
-    win.fh = h;
-    win.fw = w;
-    win.ch = content_h;
-    win.cw = content_w;
-    win.oy = oy;
-    win.ox = ox;
-    win.sx = roll_xy ? roll_xy[0] : 0;
-    win.sy = roll_xy ? roll_xy[1] : 0;
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2 + 2 * 1024, &si));
-    float *s = e->A().scalars.f() + si;
+    const ContentWindow win = hook_window(C, h, w, content_h, content_w, oy, ox, roll_xy);
+    HookScalars scalars(e);
+    float *s;
+    const float *host;
+    STX_TRY(scalars.take(kResidualScalars, &s));
     STX_TRY(content_sums_launch(e->stream, feat, content, win, s));
     if (normalized_out)
         STX_TRY(inject_content_launch(e->stream, normalized_out, feat, content, win, s, 1.0f, false));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, (si + 2) * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
+    STX_TRY(scalars.fetch(&host));
     if (sums) {
-        sums[0] = (double)e->A().host[si];
-        sums[1] = (double)e->A().host[si + 1];
+        sums[0] = (double)host[0];
+        sums[1] = (double)host[1];
     }
-    e->A().used = 0;
     return STX_OK;
 }
 

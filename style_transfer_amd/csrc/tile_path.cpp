@@ -1,11 +1,10 @@
 // libstx host side: the tile evaluation -- stx_features_tile and stx_sc_grad_tile (the reference's
 // CaffeModel.eval_features_tile / eval_sc_grad_tile, style_transfer.py:421-427,556-612): the forward pass
-// over the blobs on the path, the loss terms of the tapped blobs, the backward walk to the image.
+// over the blobs on the path, the backward walk to the image; the loss terms of the tapped blobs are tile_terms.cpp's.
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <deque>
 
 #include "engine.h"
 
@@ -374,163 +373,6 @@ static int run_conv_backward(stx_engine *e, int li, const ConvInject *inj, bool 
     return launch_conv(e, cfg, p);
 }
 
-// Floats of the engine's term_scratch that one style term of a C-channel, HW-pixel blob takes when its
-// final sums are deferred: 2 x gram_finish's blocks + the SYMM kernel's workgroups, which outlive the call.
-static size_t style_term_scratch_floats(int C, int HW) {
-    return 2 * (size_t)ceil_div(C * C, 64) + (size_t)symm_num_workgroups(C, HW) + 64;
-}
-
-// Style terms of one tapped blob, the launches of style_transfer.py:584-593 in order: Gram of
-// `feat` -> D = G - target (fp32 + bf16 pieces) -> S = sym(D) feat into `sgrad`;
-// sc[0] = sum of squares of tril(D), sc[1] = sum |S| (one small launch for both).
-// f_amax (or null): the kAmaxSlots words bounding |feat| that its producer left -- the fp16 two-piece
-// Gram and SYMM kernels (f16x2.h) scale by them; without them a pass over `feat` comes first.
-// term_scratch + defer (or null: sc[0], sc[1] are final when this returns): style_term_scratch_floats
-// floats, and the list that receives the two final sums for ONE launch behind the forward pass
-// (sum_jobs_launch).
-int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
-                       const float *target, float *sgrad, float *sc, const std::string &name,
-                       const unsigned *f_amax, float *term_scratch, std::vector<SumJob> *defer) {
-    const int HW = h * w;
-    // the first layer's kernel may have left this blob's Gram partials already (conv_first.hip)
-    const bool fused = e->first_gram_valid && e->first_gram_blob >= 0 &&
-                       feat == e->blobs[e->first_gram_blob].data.f() && C == 64;
-    GramPlan plan = gram_plan(C, HW);
-    if (fused) {
-        plan.splits = e->first_gram_parts;
-        plan.tiles = 1;
-        plan.parts = 1;
-        plan.partial_floats = (size_t)plan.splits * 64 * 64;
-    }
-    const int fin_blocks = gram_finish_blocks(plan);
-    float *const partials = fused ? e->first_gram.f() : nullptr;
-    // (behind the partial tiles: gram_finish's per-block sums of squares and maxima)
-    if (!fused) STX_TRY(e->gram_partials.ensure((plan.partial_floats + 2 * fin_blocks) * sizeof(float)));
-    STX_TRY(e->dsym.ensure((size_t)C * C * sizeof(float)));
-    const bool gram_h2 = !fused && gram_h2_usable(feat, C, HW);
-    const bool symm_h2 = symm_h2_usable(feat, sgrad, C, HW);
-    const bool bf3 = !symm_h2 && symm_bf3_usable(feat, sgrad, C, HW);
-    if ((gram_h2 || symm_h2) && !f_amax) {
-        unsigned *scratch;
-        STX_TRY(amax_scratch(e, &scratch));
-        ProfScope scope(e, "absmax " + name, 0.0, stream);
-        STX_TRY(absmax_launch(stream, feat, (size_t)C * HW, scratch));
-        f_amax = scratch;
-    }
-    if (bf3) STX_TRY(e->dsym_pieces.ensure(symm_pieces_elems(C) * sizeof(unsigned short)));
-    unsigned short *pieces = bf3 && C % 64 == 0 ? static_cast<unsigned short *>(e->dsym_pieces.ptr) : nullptr;
-    {
-        ProfScope scope(e, "gram " + name, 2.0 * C * C * (double)HW, stream);
-        if (!fused) STX_TRY(gram_partials_launch(stream, feat, plan, e->gram_partials.f(), gram_h2 ? f_amax : nullptr));
-        STX_TRY(gram_finish_launch(stream, fused ? partials : e->gram_partials.f(), plan, nullptr, target,
-                                   e->dsym.f(), nullptr, pieces, gram_h2 ? f_amax : nullptr,
-                                   defer ? term_scratch : nullptr));
-    }
-    ProfScope scope(e, "symm " + name, 2.0 * C * C * (double)HW, stream);
-    const float *block_sumsq = defer ? term_scratch : (fused ? partials : e->gram_partials.f()) + plan.partial_floats;
-    // the two final sums: now, or as two jobs of the caller's one launch
-    auto finish = [&](float *symm_partials, int n_wg) -> int {
-        if (!defer) return sum_partials2_launch(stream, block_sumsq, fin_blocks, sc, symm_partials, n_wg, sc + 1);
-        defer->push_back(SumJob{block_sumsq, fin_blocks, sc});
-        defer->push_back(SumJob{symm_partials, n_wg, sc + 1});
-        return STX_OK;
-    };
-    if (symm_h2 || bf3) {
-        const int n_wg = symm_num_workgroups(C, HW);
-        float *symm_partials = defer ? term_scratch + 2 * fin_blocks : nullptr;
-        if (!defer) {
-            STX_TRY(e->symm_partials.ensure((size_t)n_wg * sizeof(float)));
-            symm_partials = e->symm_partials.f();
-        }
-        if (symm_h2)
-            STX_TRY(symm_h2_launch(stream, feat, e->dsym.f(), reinterpret_cast<const unsigned *>(block_sumsq + fin_blocks),
-                                   fin_blocks, f_amax, sgrad, symm_partials, C, HW));
-        else
-            STX_TRY(symm_bf3_launch(stream, feat, e->dsym.f(), static_cast<unsigned short *>(e->dsym_pieces.ptr),
-                                    pieces != nullptr, sgrad, symm_partials, C, HW));
-        return finish(symm_partials, n_wg);
-    }
-    const ConvConfig cfg = conv_pick_config(1, C, C, h, w);
-    const int n_wg = conv_num_workgroups(cfg, C, h, w);
-    STX_TRY(e->symm_partials.ensure((size_t)n_wg * sizeof(float)));
-    ConvProblem p{};
-    p.x = feat;
-    p.w = e->dsym.f();
-    p.y = sgrad;
-    p.partials = e->symm_partials.f();
-    p.K = C;
-    p.M = C;
-    p.H = h;
-    p.W = w;
-    p.ksize = 1;
-    p.epilogue = kEpiSymm;
-    STX_TRY(conv_launch(stream, cfg, p, false));
-    // (this path keeps its SYMM partials in the engine's shared buffer: its two sums are launched here)
-    return sum_partials2_launch(stream, block_sumsq, fin_blocks, sc, e->symm_partials.f(), n_wg, sc + 1);
-}
-
-// The style term of a masked style (style_mask.hip), around launch_style_terms as it stands:
-//   Fm = feat . m with the partials of sum m^2  ->  T' = a target, a = sum m^2 / HW  ->  Gram / SYMM on (Fm, T')
-//   ->  S <- a m . S with the partials of sum |m . S|, whose final sum joins `defer` or is launched here.
-// |Fm| <= |feat|: the producer's f_amax stays a valid bound for the fp16-split kernels.  Fm is not the
-// first layer's blob, so that layer's fused Gram partials are never taken for it.
-int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
-                              const float *mask_map, const ContentWindow &win, const float *target,
-                              float *sgrad, float *sc, const std::string &name, const unsigned *f_amax,
-                              float *term_scratch, float *mask_scratch, std::vector<SumJob> *defer) {
-    STX_TRY(e->masked_feat.ensure((size_t)C * h * w * sizeof(float)));
-    STX_TRY(e->masked_target.ensure((size_t)C * C * sizeof(float)));
-    float *const m2_partials = mask_scratch, *const ms_partials = mask_scratch + kMaskParts;
-    {
-        ProfScope scope(e, "mask " + name, 0.0, stream);
-        int n_m2 = 0;
-        STX_TRY(mask_apply_launch(stream, feat, mask_map, win, e->masked_feat.f(), m2_partials, &n_m2));
-        STX_TRY(mask_target_launch(stream, target, C, m2_partials, n_m2, h * w, e->masked_target.f(), sc + 3));
-    }
-    STX_TRY(launch_style_terms(e, stream, e->masked_feat.f(), C, h, w, e->masked_target.f(), sgrad, sc, name,
-                               f_amax, term_scratch, defer));
-    ProfScope scope(e, "smask " + name, 0.0, stream);
-    int n_ms = 0;
-    STX_TRY(mask_sgrad_launch(stream, sgrad, mask_map, win, sc + 3, ms_partials, &n_ms));
-    if (!defer) return sum_partials_launch(stream, ms_partials, n_ms, sc + 2);
-    defer->push_back(SumJob{ms_partials, n_ms, sc + 2});
-    return STX_OK;
-}
-
-// The mean / std term of one tapped blob (stat.hip): the slices' partials, their merge against the targets
-// (table and E), S with the partials of sum |S|.  Everything in stat_scratch outlives the call.
-int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *MU,
-                      const float *SD, float *sgrad, float *sc, const std::string &name, float *stat_scratch,
-                      std::vector<SumJob> *defer) {
-    const int HW = h * w;
-    float *const partials = stat_scratch;
-    float *const table = partials + 4 * (size_t)C * stat_slices(HW);
-    float *const abs_partials = table + 4 * (size_t)C;
-    ProfScope scope(e, "stat " + name, 0.0, stream);
-    STX_TRY(stat_partials_launch(stream, feat, C, HW, partials));
-    STX_TRY(stat_finish_launch(stream, partials, C, HW, MU, SD, table, sc, nullptr, nullptr));
-    int n_parts = 0;
-    STX_TRY(stat_grad_launch(stream, feat, C, HW, table, sgrad, abs_partials, &n_parts));
-    if (!defer) return sum_partials_launch(stream, abs_partials, n_parts, sc + 1);
-    defer->push_back(SumJob{abs_partials, n_parts, sc + 1});
-    return STX_OK;
-}
-
-// A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
-// S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
-int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
-                                const float *mask_map, const ContentWindow &win, float *sgrad, float *sc,
-                                const std::string &name, float *partials, std::vector<SumJob> *defer) {
-    ProfScope scope(e, "cmask " + name, 0.0, stream);
-    STX_TRY(content_mask_mean_launch(stream, mask_map, win, sc + 2));
-    int n = 0;
-    STX_TRY(content_mask_term_launch(stream, feat, content, mask_map, win, sc + 2, sgrad, partials, &n));
-    if (!defer) return sum_partials2_launch(stream, partials, n, sc, partials + n, n, sc + 1);
-    defer->push_back(SumJob{partials, n, sc});
-    defer->push_back(SumJob{partials + n, n, sc + 1});
-    return STX_OK;
-}
-
 static int begin_timing(stx_engine *e) {
     e->ev_cur = (e->ev_cur + 1) % stx_engine::kTimed;
     STX_HIP(hipEventRecord(e->ev_start[e->ev_cur], e->stream));
@@ -545,72 +387,19 @@ static int end_timing(stx_engine *e) {
     return STX_OK;
 }
 
-namespace {
-
-struct Tap {
-    int blob;
-    const stx_tap *t;
-};
-
-// One stx_sc_grad_tile call.
-struct TileCall {
-    const float *img;
-    int img_mem, th, tw, rx, ry, start[2];
-    const stx_tap *taps;
-    int n_taps;
-    float *grad_out;
-    int grad_mem;
-};
-
-struct TilePlan {
-    std::vector<Tap> order;         // taps, deepest first
-    std::vector<char> needed;       // blobs on the path
-    std::vector<int> tap_of;        // blob -> index into order, or -1
-    std::deque<stx_tap> extra;      // taps of the layers that only a statistics target names (lw = 1);
-                                    // `order` points into it: a deque's elements stay where they are
-};
-
-// One loss term of a tapped blob, as the backward walk adds it to the blob's gradient.
-struct Term {
-    bool style;
-    const float *src;        // style: S = sym(tril(G - Gs)) F;  content: the content map
-    const float *sums;       // style: &sum|S|;  content: {sum c^2, sum |c|}
-    float coef;
-    ContentWindow win;
-};
-
-// One evaluation (sc_grad_run): what its steps share.
-struct TileRun {
-    stx_engine *e;
-    const TileCall &c;
-    const TilePlan &plan;
-    PendingLoss &pl;
-    // The final sums of the loss terms (two per style term, two per content term) are collected and run
-    // as ONE launch behind the forward pass (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did);
-    // what they add up must outlive the term's own launches: one scratch region per style term.
-    bool sums_late;
-    bool interleave;         // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
-    std::vector<std::vector<Term>> terms;     // per tap, in plan.order
-    std::vector<SumJob> sum_jobs;
-    size_t scratch_used;     // floats of the engine's term_scratch that style terms have taken
-    std::vector<SumJob> *defer() { return sums_late ? &sum_jobs : nullptr; }
-};
-
-}  // namespace
-
-// The mean / std target of `blob` (stx_set_stat_targets), or null.
-static const StatTarget *stat_target_of(const stx_engine *e, int blob) {
-    for (const StatTarget &t : e->sh->stats)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// Validates the taps against the graph and the targets, orders them and shapes the blobs.
+// Validates the taps against the graph and the targets, orders them, shapes the blobs and plans the loss
+// terms (plan_terms): a call that cannot be evaluated fails here, before its first launch.
 static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
     // ---- taps in deep -> shallow order (style_transfer.py:231-233)
     std::vector<Tap> &order = plan.order;
     const stx_tap *taps = c.taps;
     const int n_taps = c.n_taps;
+    const auto tapped = [&](int blob) {
+        return std::any_of(order.begin(), order.end(), [=](const Tap &o) { return o.blob == blob; });
+    };
+    const auto has_statistics = [&](int blob) {
+        return std::any_of(e->sh->stats.begin(), e->sh->stats.end(), [=](const StatTarget &t) { return t.blob == blob; });
+    };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
         if (blob <= 0) {
@@ -618,19 +407,16 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
                       taps[i].layer ? taps[i].layer : "(null)");
             return STX_ERR_ARG;
         }
-        for (const Tap &o : order)
-            if (o.blob == blob) {
-                set_error("stx_sc_grad_tile: layer '%s' is tapped twice", taps[i].layer);
-                return STX_ERR_ARG;
-            }
-        if (!taps[i].is_content && !taps[i].is_style && !taps[i].is_dd && !stat_target_of(e, blob)) continue;
+        if (tapped(blob)) {
+            set_error("stx_sc_grad_tile: layer '%s' is tapped twice", taps[i].layer);
+            return STX_ERR_ARG;
+        }
+        if (!taps[i].is_content && !taps[i].is_style && !taps[i].is_dd && !has_statistics(blob)) continue;
         order.push_back(Tap{blob, &taps[i]});
     }
     // a layer with a statistics target is part of every evaluation, tapped or not
     for (const StatTarget &st : e->sh->stats) {
-        bool tapped = false;
-        for (const Tap &o : order) tapped |= o.blob == st.blob;
-        if (tapped) continue;
+        if (tapped(st.blob)) continue;
         stx_tap t{};
         t.layer_weight = 1.0;
         plan.extra.push_back(t);
@@ -665,241 +451,10 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
             return STX_ERR_STATE;
         }
     }
-
-    return shape_blobs(e, c.th, c.tw, needed, true);
-}
-
-// The window of blob b's tile in a ch x cw content map: start_ = start // scale (style_transfer.py:572);
-// roll // scale per layer (:647-655)
-static ContentWindow content_window(const Blob &b, int ch, int cw, const int start[2], int rx, int ry) {
-    ContentWindow win;
-    win.C = b.channels;
-    win.fh = b.h;
-    win.fw = b.w;
-    win.ch = ch;
-    win.cw = cw;
-    win.oy = (int)std::floor((double)start[0] / b.scale);
-    win.ox = (int)std::floor((double)start[1] / b.scale);
-    win.sx = (int)std::floor((double)rx / b.scale);
-    win.sy = (int)std::floor((double)ry / b.scale);
-    return win;
-}
-
-// ... and its Deep-Dream form: a map of the blob's own size, nothing shifted.
-static ContentWindow dream_window(const Blob &b) {
-    const int origin[2] = {0, 0};
-    return content_window(b, b.h, b.w, origin, 0, 0);
-}
-
-// The sums of tap k's residual against `target` (null: a zero map) under `label`, as a loss term of
-// weight / 2 and a gradient term of weight.
-static int queue_residual_term(TileRun &run, size_t k, const char *label, const float *target,
-                               const ContentWindow &win, double weight) {
-    stx_engine *e = run.e;
-    const Blob &b = e->blobs[run.plan.order[k].blob];
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2 + 2 * 1024, &si));
-    float *sums = e->A().scalars.f() + si;
-    {
-        ProfScope scope(e, label + b.name, 0.0, e->stream);
-        STX_TRY(content_sums_launch(e->stream, b.data.f(), target, win, sums, run.defer()));
-    }
-    run.pl.terms.push_back(LossTerm{si, weight * 0.5});
-    run.terms[k].push_back(Term{false, target, sums, (float)weight, win});
-    return STX_OK;
-}
-
-// The content mask map at `blob` (stx_set_content_mask), or null.
-static const ContentMask *content_mask_of(const stx_engine *e, int blob) {
-    for (const ContentMask &m : e->sh->cmasks)
-        if (m.blob == blob) return &m;
-    return nullptr;
-}
-
-// The term of content target `ct` of tap k through the mask map (its size is the content map's: `win` is the
-// window of both): launch_masked_content_terms into `sgrad`, which then rides as a gradient blob.
-static int queue_masked_content_term(TileRun &run, size_t k, const ContentTarget &ct, const ContentMask &mk,
-                                     const ContentWindow &win, float *sgrad) {
-    stx_engine *e = run.e;
-    const Tap &tp = run.plan.order[k];
-    const Blob &b = e->blobs[tp.blob];
-    if (win.oy < 0 || win.ox < 0) {
-        set_error("content mask window [%d+%d, %d+%d] exceeds the %dx%d mask map of layer %s",
-                  win.oy, win.fh, win.ox, win.fw, win.ch, win.cw, b.name.c_str());
-        return STX_ERR_ARG;
-    }
-    size_t si;
-    STX_TRY(alloc_scalars(e, 4, &si));
-    float *sc = e->A().scalars.f() + si;   // [0] = sum m d^2, [1] = sum |m d|, [2] = a
-    float *partials = e->term_scratch.f() + run.scratch_used;
-    run.scratch_used += kContentMaskScratchFloats;
-    STX_TRY(launch_masked_content_terms(e, e->stream, b.data.f(), ct.feat->f(), mk.map->f(), win, sgrad, sc,
-                                        b.name, partials, run.defer()));
-    const double weight = tp.t->layer_weight * tp.t->content_weight;
-    run.pl.terms.push_back(LossTerm{si, weight * 0.5});
-    run.terms[k].push_back(Term{true, sgrad, sc + 1, (float)weight, ContentWindow{}});
-    return STX_OK;
-}
-
-static int queue_content_terms(TileRun &run, size_t k) {
-    stx_engine *e = run.e;
-    const Tap &tp = run.plan.order[k];
-    const Blob &b = e->blobs[tp.blob];
-    bool any = false;
-    const ContentMask *mk = e->sh->cmasks.empty() ? nullptr : content_mask_of(e, tp.blob);
-    int slot = 0;
-    if (mk) {
-        int n_here = 0;
-        for (const ContentTarget &ct : e->sh->contents) n_here += ct.blob == tp.blob;
-        STX_TRY(e->sgrad_content[k]->ensure((size_t)n_here * b.count() * sizeof(float)));
-    }
-    for (const ContentTarget &ct : e->sh->contents) {
-        if (ct.blob != tp.blob) continue;
-        any = true;
-        const ContentWindow win = content_window(b, ct.h, ct.w, run.c.start, run.c.rx, run.c.ry);
-        if (win.oy + win.fh > win.ch || win.ox + win.fw > win.cw) {
-            set_error("content window [%d+%d, %d+%d] exceeds the %dx%d map of layer %s",
-                      win.oy, win.fh, win.ox, win.fw, win.ch, win.cw, b.name.c_str());
-            return STX_ERR_ARG;
-        }
-        if (mk) {
-            STX_TRY(queue_masked_content_term(run, k, ct, *mk, win,
-                                              e->sgrad_content[k]->f() + (size_t)slot++ * b.count()));
-            continue;
-        }
-        STX_TRY(queue_residual_term(run, k, "content ", ct.feat->f(), win, tp.t->layer_weight * tp.t->content_weight));
-    }
-    if (!any) {
-        set_error("no content target for layer %s", b.name.c_str());
-        return STX_ERR_STATE;
-    }
-    return STX_OK;
-}
-
-// The mask map of style `index` at `blob` (stx_set_style_masks), or null.
-static const StyleMask *style_mask_of(const stx_engine *e, int index, int blob) {
-    for (const StyleMask &m : e->sh->masks)
-        if (m.index == index && m.blob == blob) return &m;
-    return nullptr;
-}
-
-// The term of a masked style target of tap k: the tile's window of the mask map, taken as a content
-// map's is, then launch_masked_style_terms.
-static int queue_masked_style_term(TileRun &run, size_t k, const StyleTarget &st, const StyleMask &mk, float *sgrad) {
-    stx_engine *e = run.e;
-    const Tap &tp = run.plan.order[k];
-    const Blob &b = e->blobs[tp.blob];
-    const ContentWindow win = content_window(b, mk.h, mk.w, run.c.start, run.c.rx, run.c.ry);
-    if (win.oy < 0 || win.ox < 0 || win.oy + win.fh > win.ch || win.ox + win.fw > win.cw) {
-        set_error("style mask window [%d+%d, %d+%d] exceeds the %dx%d mask map of layer %s",
-                  win.oy, win.fh, win.ox, win.fw, win.ch, win.cw, b.name.c_str());
-        return STX_ERR_ARG;
-    }
-    size_t si;
-    STX_TRY(alloc_scalars(e, 4, &si));
-    float *sc = e->A().scalars.f() + si;   // [0] = sum tril(D)^2, [2] = sum |m . S|, [3] = a
-    const unsigned *f_amax = b.amax_data >= 0 ? e->amax_slots(b.amax_data, false) : nullptr;
-    float *scratch = nullptr;
-    if (run.sums_late) {
-        scratch = e->term_scratch.f() + run.scratch_used;
-        run.scratch_used += style_term_scratch_floats(b.channels, b.h * b.w);
-    }
-    float *mask_scratch = e->term_scratch.f() + run.scratch_used;
-    run.scratch_used += kMaskScratchFloats;
-    STX_TRY(launch_masked_style_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, mk.map->f(), win,
-                                      st.gram->f(), sgrad, sc, b.name, f_amax, scratch, mask_scratch, run.defer()));
-    const double lw = tp.t->layer_weight;
-    run.pl.terms.push_back(LossTerm{si, lw * tp.t->style_weight * 0.5 / e->sh->n_styles});
-    run.terms[k].push_back(Term{true, sgrad, sc + 2, (float)(lw * tp.t->style_weight / e->sh->n_styles),
-                                ContentWindow{}});
-    return STX_OK;
-}
-
-// Gram -> G - Gs -> SYMM against every style target of tap k (launch_style_terms).
-static int queue_style_terms(TileRun &run, size_t k) {
-    stx_engine *e = run.e;
-    const Tap &tp = run.plan.order[k];
-    const Blob &b = e->blobs[tp.blob];
-    const double lw = tp.t->layer_weight;
-    int n_here = 0;
-    for (const StyleTarget &st : e->sh->styles) n_here += st.blob == tp.blob;
-    if (!n_here) {
-        set_error("no style target for layer %s", b.name.c_str());
-        return STX_ERR_STATE;
-    }
-    STX_TRY(e->sgrad_tap[k]->ensure((size_t)n_here * b.count() * sizeof(float)));
-    int slot = 0;
-    for (const StyleTarget &st : e->sh->styles) {
-        if (st.blob != tp.blob) continue;
-        const int C = b.channels, HW = b.h * b.w;
-        if (C % 4 != 0) {
-            set_error("style layer %s: channel count %d is not a multiple of 4", b.name.c_str(),
-                      C);
-            return STX_ERR_UNSUPPORTED;
-        }
-        float *sgrad = e->sgrad_tap[k]->f() + (size_t)slot++ * b.count();
-        if (const StyleMask *mk = style_mask_of(e, st.index, tp.blob)) {
-            STX_TRY(queue_masked_style_term(run, k, st, *mk, sgrad));
-            continue;
-        }
-        size_t si;
-        STX_TRY(alloc_scalars(e, 2, &si));
-        float *sc = e->A().scalars.f() + si;   // [0] = sum tril(D)^2, [1] = sum |S|
-        // (the maximum the blob's producer left, if it left one: the fp16-split kernels' scale)
-        const unsigned *f_amax = b.amax_data >= 0 ? e->amax_slots(b.amax_data, false) : nullptr;
-        float *scratch = nullptr;
-        if (run.sums_late) {
-            scratch = e->term_scratch.f() + run.scratch_used;
-            run.scratch_used += style_term_scratch_floats(C, HW);
-        }
-        STX_TRY(launch_style_terms(e, e->stream, b.data.f(), C, b.h, b.w, st.gram->f(), sgrad, sc,
-                                   b.name, f_amax, scratch, run.defer()));
-        run.pl.terms.push_back(LossTerm{si, lw * tp.t->style_weight * 0.5 / e->sh->n_styles});
-        run.terms[k].push_back(Term{true, sgrad, sc + 1,
-                                    (float)(lw * tp.t->style_weight / e->sh->n_styles), ContentWindow{}});
-    }
-    return STX_OK;
-}
-
-// The mean / std term of tap k against the blob's statistics target (launch_stat_terms).
-static int queue_stat_term(TileRun &run, size_t k, const StatTarget &st) {
-    stx_engine *e = run.e;
-    const Tap &tp = run.plan.order[k];
-    const Blob &b = e->blobs[tp.blob];
-    STX_TRY(e->sgrad_stat[k]->ensure(b.count() * sizeof(float)));
-    float *sgrad = e->sgrad_stat[k]->f();
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2, &si));
-    float *sc = e->A().scalars.f() + si;   // [0] = E, [1] = sum |S|
-    float *scratch = e->term_scratch.f() + run.scratch_used;
-    run.scratch_used += stat_scratch_floats(b.channels, b.h * b.w);
-    STX_TRY(launch_stat_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, st.ms->f(), st.ms->f() + st.C,
-                              sgrad, sc, b.name, scratch, run.defer()));
-    const double coef = tp.t->layer_weight * st.weight;
-    run.pl.terms.push_back(LossTerm{si, coef * 0.5});
-    run.terms[k].push_back(Term{true, sgrad, sc + 1, (float)coef, ContentWindow{}});
-    return STX_OK;
-}
-
-// Deep-Dream term (style_transfer.py:602-604): the content term against a zero map with a negative
-// weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
-static int queue_dream_term(TileRun &run, size_t k) {
-    const Tap &tp = run.plan.order[k];
-    return queue_residual_term(run, k, "dream ", nullptr, dream_window(run.e->blobs[tp.blob]),
-                               -tp.t->layer_weight * tp.t->dd_weight);
-}
-
-// Loss terms of tap k (Gram -> G - Gs -> SYMM, content residual sums).  They are queued the
-// moment the tapped blob is complete, in the middle of the forward pass, while the blob is
-// still in the L2 / Infinity Cache the convolution just wrote it through (the shallow blobs
-// were re-fetched from HBM when all taps ran after the forward pass: 1.1 GB per tile by PMC).
-static int queue_tap_terms(TileRun &run, size_t k) {
-    const stx_tap *t = run.plan.order[k].t;
-    if (t->is_content) STX_TRY(queue_content_terms(run, k));
-    if (t->is_style) STX_TRY(queue_style_terms(run, k));
-    if (const StatTarget *st = stat_target_of(run.e, run.plan.order[k].blob)) STX_TRY(queue_stat_term(run, k, *st));
-    if (t->is_dd) STX_TRY(queue_dream_term(run, k));
-    return STX_OK;
+    STX_TRY(shape_blobs(e, c.th, c.tw, needed, true));
+    plan.sums_late = !(sw_env("STX_SUMS_LATE") && !atoi(sw_env("STX_SUMS_LATE")));
+    plan.interleave = !(sw_env("STX_TERMS_LATE") && atoi(sw_env("STX_TERMS_LATE")));
+    return plan_terms(e, c, plan);
 }
 
 // `blob` is complete: the loss terms of its tap, for a run that wants them inside the forward pass.
@@ -959,65 +514,6 @@ static int forward(stx_engine *e, const std::vector<char> &needed, int relu_blob
         }
     }
     return STX_OK;
-}
-
-// Adds the terms of tap k to its blob's diff with stand-alone kernels (used for the deepest
-// tap, for blobs produced by a pooling backward, and when a tap has more than one content or
-// style term; otherwise the terms ride in the epilogue of the convolution backward above).
-static int inject_terms(TileRun &run, size_t k, bool &diff_written) {
-    stx_engine *e = run.e;
-    const int blob = run.plan.order[k].blob;
-    const std::vector<Term> &terms = run.terms[k];
-    Blob &b = e->blobs[blob];
-    ProfScope scope(e, "inject " + b.name, 0.0);
-    b.amax_diff = -1;
-    for (size_t ti = 0; ti < terms.size(); ++ti) {       // content terms come first, like the reference
-        const Term &t = terms[ti];
-        // the last term's kernel writes the blob's final gradient: it leaves its maximum for the
-        // fp16-split convolution that reads it next (the slots were zeroed when the walk began)
-        unsigned *amax = nullptr;
-        if (ti + 1 == terms.size() && conv_h2_enabled()) {
-            amax = e->amax_slots(blob, true);
-            b.amax_diff = blob;
-        }
-        if (t.style)
-            STX_TRY(inject_style_launch(e->stream, b.diff.f(), t.src, b.count(), t.sums, t.coef,
-                                        diff_written, amax));
-        else
-            STX_TRY(inject_content_launch(e->stream, b.diff.f(), b.data.f(), t.src, t.win,
-                                          t.sums, t.coef, diff_written, amax));
-        diff_written = true;
-    }
-    return STX_OK;
-}
-
-// Can the terms of tap k ride in the epilogue of the convolution backward that produces its blob's gradient?
-static bool tap_fusable(const TileRun &run, size_t k) {
-    int ns = 0, nc = 0;
-    for (const Term &t : run.terms[k]) {
-        if (!t.style && !t.src) return false;      // Deep-Dream terms take the stand-alone path
-        (t.style ? ns : nc)++;
-    }
-    return ns <= 1 && nc <= 1;
-}
-
-// ... and what that epilogue needs of them (`bot`: the tapped blob).
-static ConvInject make_inject(const TileRun &run, size_t k, const Blob &bot) {
-    ConvInject inj{};
-    for (const Term &t : run.terms[k]) {
-        if (t.style) {
-            inj.sgrad = t.src;
-            inj.s_abs_sum = t.sums;
-            inj.s_coef = t.coef;
-        } else {
-            inj.content = t.src;
-            inj.c_sums = t.sums;
-            inj.c_coef = t.coef;
-            inj.win = t.win;
-            inj.feat = bot.data.f();
-        }
-    }
-    return inj;
 }
 
 // The backward walk from the deepest tap to the image (style_transfer.py:569-610).
@@ -1081,62 +577,35 @@ static int backward_walk(TileRun &run) {
     return STX_OK;
 }
 
-// A style tap on the first layer's blob: that layer's kernel leaves its Gram partials.
+// An unmasked style term on the first layer's blob: that layer's kernel leaves its Gram partials.
+// (A masked style takes the Gram of F . m: the partials are for the unmasked targets of the blob.)
 static void first_gram_setup(stx_engine *e, const TilePlan &plan) {
     const int data_blob = e->layers[0].top_blob;
     e->first_gram_blob = -1;
     e->first_gram_valid = false;
-    for (const Tap &tp : plan.order) {
-        const int pl = e->blobs[tp.blob].producer;
-        // (a masked style takes the Gram of F . m: the partials are for the unmasked targets of the blob)
-        bool unmasked = e->sh->masks.empty();
-        for (const StyleTarget &st : e->sh->styles)
-            unmasked |= st.blob == tp.blob && !style_mask_of(e, st.index, tp.blob);
-        if (tp.t->is_style && unmasked && pl > 0 && e->layers[pl].type == STX_LAYER_CONV &&
-            e->layers[pl].bottom_blob == data_blob && e->blobs[tp.blob].channels == 64)
-            e->first_gram_blob = tp.blob;
+    for (const PlannedTerm &t : plan.terms) {
+        const int blob = plan.order[t.tap].blob, pl = e->blobs[blob].producer;
+        if (t.kind == TermKind::Style && e->first_gram_blob < 0 && pl > 0 && e->layers[pl].type == STX_LAYER_CONV &&
+            e->layers[pl].bottom_blob == data_blob && e->blobs[blob].channels == 64)
+            e->first_gram_blob = blob;
     }
 }
 
 // Enqueues the evaluation proper: forward pass with the loss terms of the tapped blobs, backward
 // walk, the mirror copy of the loss scalars.  The tile is already in the input blob; the gradient
 // is left in its diff.
-static int sc_grad_run(stx_engine *e, const TileCall &c, const TilePlan &plan, PendingLoss &pl) {
+static int sc_grad_run(stx_engine *e, const TilePlan &plan, PendingLoss &pl) {
     const std::vector<Tap> &order = plan.order;
-    TileRun run{e, c, plan, pl, !(sw_env("STX_SUMS_LATE") && !atoi(sw_env("STX_SUMS_LATE"))),
-                !(sw_env("STX_TERMS_LATE") && atoi(sw_env("STX_TERMS_LATE"))),
-                std::vector<std::vector<Term>>(order.size()), {}, 0};
-    while (e->sgrad_tap.size() < order.size()) e->sgrad_tap.emplace_back(new DevBuf);
-    if (!e->sh->stats.empty())
-        while (e->sgrad_stat.size() < order.size()) e->sgrad_stat.emplace_back(new DevBuf);
-    if (!e->sh->cmasks.empty())
-        while (e->sgrad_content.size() < order.size()) e->sgrad_content.emplace_back(new DevBuf);
-    {
-        size_t need = 0;
-        for (const Tap &tp : order) {
-            const Blob &b = e->blobs[tp.blob];
-            // (a statistics term's partials and table live there, with or without the late sums)
-            if (stat_target_of(e, tp.blob)) need += stat_scratch_floats(b.channels, b.h * b.w);
-            // (and a masked content term's partials)
-            if (tp.t->is_content && !e->sh->cmasks.empty() && content_mask_of(e, tp.blob))
-                for (const ContentTarget &ct : e->sh->contents)
-                    if (ct.blob == tp.blob) need += kContentMaskScratchFloats;
-            if (!tp.t->is_style) continue;
-            for (const StyleTarget &st : e->sh->styles) {
-                if (st.blob != tp.blob) continue;
-                if (run.sums_late) need += style_term_scratch_floats(b.channels, b.h * b.w);
-                // (a masked term's partials live there too, with or without the late sums)
-                if (style_mask_of(e, st.index, tp.blob)) need += kMaskScratchFloats;
-            }
-        }
-        STX_TRY(e->term_scratch.ensure(need * sizeof(float)));
-    }
+    TileRun run{e, plan, pl, std::vector<std::vector<Term>>(order.size()), {}};
+    while (e->sgrad.size() < order.size()) e->sgrad.emplace_back(new DevBuf);
+    for (size_t k = 0; k < order.size(); ++k) STX_TRY(e->sgrad[k]->ensure(plan.sgrad_floats[k] * sizeof(float)));
+    STX_TRY(e->term_scratch.ensure(plan.scratch_floats * sizeof(float)));
     STX_TRY(begin_timing(e));
     std::vector<char> observed(e->blobs.size(), 0);
     for (const Tap &tp : order) observed[tp.blob] = 1;
     first_gram_setup(e, plan);
-    STX_TRY(forward(e, plan.needed, order[0].blob, run.interleave ? &run : nullptr, true, observed));
-    if (!run.interleave) {
+    STX_TRY(forward(e, plan.needed, order[0].blob, plan.interleave ? &run : nullptr, true, observed));
+    if (!plan.interleave) {
         // (shallowest tap first, the order the interleaved schedule queues them in: the host adds
         // the loss terms up in queueing order, in double precision, and must get the same bits)
         for (size_t k = order.size(); k-- > 0;) STX_TRY(queue_tap_terms(run, k));
@@ -1154,25 +623,21 @@ static int sc_grad_run(stx_engine *e, const TileCall &c, const TilePlan &plan, P
 }
 
 static int sc_grad_eager(stx_engine *e, const TileCall &c, double *loss_out) {
-    // the scalar arena holds the reductions of every call queued since the last stx_sync; drain
-    // it (publishing the pending losses) before it could overflow
-    {
-        const size_t per_call = ((size_t)c.n_taps + e->sh->stats.size()) * 2100 *
-                                (size_t)std::max(1, e->sh->n_contents + e->sh->n_styles);
-        if (e->A().used + per_call > e->scalars_cap) STX_TRY(do_sync(e));
-        if (per_call > e->scalars_cap) {
-            set_error("stx_sc_grad_tile: %d taps need more scalar space than the arena holds", c.n_taps);
-            return STX_ERR_NOMEM;
-        }
-    }
     TilePlan plan;
     STX_TRY(sc_grad_prepare(e, c, plan));
+    // the scalar arena holds the reductions of every call queued since the last stx_sync; drain
+    // it (publishing the pending losses) before this call's terms could overflow it
+    if (e->A().used + plan.scalars > e->scalars_cap) STX_TRY(do_sync(e));
+    if (plan.scalars > e->scalars_cap) {
+        set_error("stx_sc_grad_tile: %d taps need more scalar space than the arena holds", c.n_taps);
+        return STX_ERR_NOMEM;
+    }
     Blob &in = e->blobs[e->layers[0].top_blob];
     // (a tile handed over in the engine's own buffers, stx_tile_buffers, needs no copies)
     if (c.img != in.data.ptr) STX_TRY(copy_in(e, in.data.ptr, c.img, c.img_mem, in.count() * sizeof(float)));
     PendingLoss pl;
     pl.out = loss_out;
-    STX_TRY(sc_grad_run(e, c, plan, pl));
+    STX_TRY(sc_grad_run(e, plan, pl));
     if (c.grad_out != in.diff.ptr)
         STX_TRY(copy_out(e, c.grad_out, c.grad_mem, in.diff.ptr, in.count() * sizeof(float)));
     e->A().pending.push_back(std::move(pl));
