@@ -559,6 +559,22 @@ int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, 
 int stx_profile_enable(stx_engine *e, int on);
 int stx_profile_read(stx_engine *e, char *buf, size_t buf_len, size_t *needed);
 
+/* An audit of the maxima that the fp16-split kernels take over from earlier kernels (for the tests; off by
+ * default, and then nothing is enqueued or allocated).  Those kernels -- the fp16-split convolution, Gram and
+ * SYMM -- scale their operand by a power of two taken from 64 words of float bits that the kernel which wrote
+ * the operand left behind, or that a pooling layer, a mask or a routed gradient passed on as a bound.  While
+ * the audit is on, every such hand-off of a tile evaluation enqueues, in front of the consumer and on its
+ * stream, a copy of the recorded words and a pass that measures max |x| over exactly the array the consumer
+ * is about to read, both into storage of the audit's own: the slots the consumers read are not touched.
+ * stx_amax_audit_read synchronises, writes one line per hand-off
+ * "consumer<TAB>blob<TAB>data|diff<TAB>blob whose slots were read<TAB>recorded<TAB>measured" into buf (like
+ * stx_profile_read; recorded = the largest slot, measured = the pass's result, both as float bits in
+ * hexadecimal) and clears the record.  consumer: "fwd conv3_2", "bwd conv2_1", "style conv4_1", or "masked
+ * style conv4_1" where the array is the masked feature map.  At most 2048 hand-offs are kept between two reads;
+ * the evaluation that would exceed them fails. */
+int stx_amax_audit(stx_engine *e, int on);
+int stx_amax_audit_read(stx_engine *e, char *buf, size_t buf_len, size_t *needed);
+
 /* Timing: ms spent by the GPU between the first and last kernel of the most recent FINISHED
  * stx_sc_grad_tile / stx_features_tile on this engine (HIP events on the engine stream; after
  * stx_sync that is the last call; while the host runs ahead it is the newest of the last four

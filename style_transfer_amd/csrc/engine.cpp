@@ -394,6 +394,7 @@ void stx_engine_destroy(stx_engine *e) {
     for (auto &b : e->sgrad) b->release();
     e->marks_buf.release();
     e->amax.release();
+    e->audit_buf.release();
     for (Blob &b : e->blobs) {
         b.data.release();
         b.diff.release();
@@ -867,6 +868,48 @@ int stx_profile_read(stx_engine *e, char *buf, size_t buf_len, size_t *needed) {
         e->event_pool.push_back(pe.stop);
     }
     e->prof.clear();
+    if (needed) *needed = out.size() + 1;
+    if (buf_len) {
+        const size_t n = std::min(buf_len - 1, out.size());
+        memcpy(buf, out.data(), n);
+        buf[n] = 0;
+    }
+    return STX_OK;
+}
+
+int stx_amax_audit(stx_engine *e, int on) {
+    if (!e) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    STX_HIP(hipStreamSynchronize(e->stream));
+    e->audit.clear();
+    e->amax_audit = false;
+    if (on)
+        STX_TRY(e->audit_buf.ensure(kMaxAmaxAudit * 2 * kAmaxSlots * sizeof(unsigned)));
+    else
+        e->audit_buf.release();
+    e->amax_audit = on != 0;
+    return STX_OK;
+}
+
+int stx_amax_audit_read(stx_engine *e, char *buf, size_t buf_len, size_t *needed) {
+    if (!e || (!buf && buf_len)) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    STX_HIP(hipStreamSynchronize(e->stream));
+    std::string out;
+    std::vector<unsigned> words(e->audit.size() * 2 * kAmaxSlots);
+    if (!words.empty())
+        STX_HIP(hipMemcpy(words.data(), e->audit_buf.ptr, words.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < e->audit.size(); ++i) {
+        const stx_engine::AuditEntry &a = e->audit[i];
+        const unsigned *rec = words.data() + 2 * i * kAmaxSlots, *meas = rec + kAmaxSlots;
+        const unsigned recorded = *std::max_element(rec, rec + kAmaxSlots);
+        const unsigned measured = *std::max_element(meas, meas + kAmaxSlots);
+        char line[256];
+        snprintf(line, sizeof line, "%s\t%s\t%s\t%s\t%08x\t%08x\n", a.consumer.c_str(), a.blob.c_str(),
+                 a.diff ? "diff" : "data", a.source.c_str(), recorded, measured);
+        out += line;
+    }
+    e->audit.clear();
     if (needed) *needed = out.size() + 1;
     if (buf_len) {
         const size_t n = std::min(buf_len - 1, out.size());

@@ -233,6 +233,16 @@ struct stx_engine {
     std::vector<ProfEntry> prof;
     std::vector<hipEvent_t> event_pool;
 
+    // optional audit of the maxima handed from kernel to kernel (stx_amax_audit): per hand-off the recorded
+    // slots and a measured maximum, kAmaxSlots words each, in audit_buf
+    bool amax_audit = false;
+    struct AuditEntry {
+        std::string consumer, blob, source;
+        bool diff;
+    };
+    std::vector<AuditEntry> audit;
+    DevBuf audit_buf;
+
     int set_device() {
         STX_HIP(hipSetDevice(device));
         return STX_OK;
@@ -296,6 +306,11 @@ ConvProblem conv_bwd_problem(const float *dy, float *dx, const float *mask, int 
 int attach_splitk(stx_engine *e, const ConvConfig &cfg, ConvProblem &p);
 int launch_conv(stx_engine *e, const ConvConfig &cfg, const ConvProblem &problem);
 int amax_scratch(stx_engine *e, unsigned **out);
+constexpr size_t kMaxAmaxAudit = 2048;   // stx_amax_audit: hand-offs kept between two reads
+// With the audit on: records that `consumer` is about to read the n floats at x scaled by `slots` (a group of
+// the engine's table) -- a copy of the slots and a measured max |x| into the audit's storage, on `stream`.
+int amax_audit_note(stx_engine *e, hipStream_t stream, const std::string &consumer, const std::string &blob,
+                    bool diff, const unsigned *slots, const float *x, size_t n);
 // ---- tile_terms.cpp: the loss terms of one tile evaluation
 struct Tap {
     int blob;

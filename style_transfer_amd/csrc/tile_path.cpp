@@ -140,15 +140,37 @@ int launch_conv(stx_engine *e, const ConvConfig &cfg, const ConvProblem &problem
 
 // The slots with max |x| of a blob's data / diff for a kernel that is about to read it: what its
 // producer left (Blob::amax_data / amax_diff), else a pass over the array now.
-static int amax_for(stx_engine *e, int blob, bool diff, const unsigned **out) {
+// `consumer`: the launch group that will read it (stx_amax_audit).
+static int amax_for(stx_engine *e, int blob, bool diff, const std::string &consumer, const unsigned **out) {
     Blob &b = e->blobs[blob];
     int &src = diff ? b.amax_diff : b.amax_data;
     if (src < 0) {
         ProfScope scope(e, std::string("absmax ") + b.name, 0.0);
         STX_TRY(absmax_launch(e->stream, diff ? b.diff.f() : b.data.f(), b.count(), e->amax_slots(blob, diff)));
         src = blob;
+    } else if (e->amax_audit) {
+        STX_TRY(amax_audit_note(e, e->stream, consumer, b.name, diff, e->amax_slots(src, diff),
+                                diff ? b.diff.f() : b.data.f(), b.count()));
     }
     *out = e->amax_slots(src, diff);
+    return STX_OK;
+}
+
+int amax_audit_note(stx_engine *e, hipStream_t stream, const std::string &consumer, const std::string &blob,
+                    bool diff, const unsigned *slots, const float *x, size_t n) {
+    if (!e->amax_audit) return STX_OK;
+    if (e->audit.size() >= kMaxAmaxAudit) {
+        set_error("stx_amax_audit: more than %zu hand-offs since the last stx_amax_audit_read", kMaxAmaxAudit);
+        return STX_ERR_STATE;
+    }
+    // whose slots: a group of the engine's table (data groups, diff groups, then the scratch groups)
+    const size_t group = (size_t)(slots - static_cast<const unsigned *>(e->amax.ptr)) / kAmaxSlots;
+    const size_t nb = e->blobs.size();
+    const std::string source = group < 2 * nb ? e->blobs[group % nb].name : "(scratch)";
+    unsigned *const rec = static_cast<unsigned *>(e->audit_buf.ptr) + 2 * e->audit.size() * kAmaxSlots;
+    STX_HIP(hipMemcpyAsync(rec, slots, kAmaxSlots * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+    STX_TRY(absmax_launch(stream, x, n, rec + kAmaxSlots));
+    e->audit.push_back(stx_engine::AuditEntry{consumer, blob, source, diff});
     return STX_OK;
 }
 
@@ -238,7 +260,7 @@ static int run_conv_forward(stx_engine *e, int li, const FwdConvPlan &plan, bool
     b.relu_codes_wanted = !conv_reads_x_amax(cfg) && !b.relu_codes_valid && plan.relu_codes && b.relu && b.channels <= 128;  // (see below)
     p.wants_codes = b.relu_codes_wanted;
     t.amax_data = -1;
-    if (conv_reads_x_amax(cfg)) STX_TRY(amax_for(e, L.bottom_blob, false, &p.x_amax));
+    if (conv_reads_x_amax(cfg)) STX_TRY(amax_for(e, L.bottom_blob, false, "fwd " + L.name, &p.x_amax));
     if (conv_leaves_y_amax(cfg)) {
         p.y_amax = e->amax_slots(L.top_blob, false);
         t.amax_data = L.top_blob;          // (a K-sliced launch leaves it through its reduce pass)
@@ -359,9 +381,9 @@ static int run_conv_backward(stx_engine *e, int li, const ConvInject *inj, bool 
         p.pin_codes = static_cast<const unsigned char *>(pt.codes.ptr);
         p.pin_mode = pooled->pool_mode;
         p.pin_mask = t.relu;
-        STX_TRY(amax_for(e, pooled->top_blob, true, &p.x_amax));    // (routing / averaging never raises the maximum)
+        STX_TRY(amax_for(e, pooled->top_blob, true, "bwd " + L.name, &p.x_amax));    // (routing / averaging never raises the maximum)
     } else if (conv_reads_x_amax(cfg)) {
-        STX_TRY(amax_for(e, L.top_blob, true, &p.x_amax));
+        STX_TRY(amax_for(e, L.top_blob, true, "bwd " + L.name, &p.x_amax));
     }
     if (conv_leaves_y_amax(cfg)) {
         p.y_amax = e->amax_slots(L.bottom_blob, true);

@@ -52,6 +52,9 @@ int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int
         ProfScope scope(e, "absmax " + name, 0.0, stream);
         STX_TRY(absmax_launch(stream, feat, (size_t)C * HW, scratch));
         f_amax = scratch;
+    } else if ((gram_h2 || symm_h2) && e->amax_audit) {    // (a maximum somebody else left: stx_amax_audit)
+        STX_TRY(amax_audit_note(e, stream, (feat == e->masked_feat.f() ? "masked style " : "style ") + name, name,
+                                false, f_amax, feat, (size_t)C * HW));
     }
     if (bf3) STX_TRY(e->dsym_pieces.ensure(symm_pieces_elems(C) * sizeof(unsigned short)));
     unsigned short *pieces = bf3 && C % 64 == 0 ? static_cast<unsigned short *>(e->dsym_pieces.ptr) : nullptr;

@@ -491,6 +491,23 @@ class TileEngine:
                         (label, float(ms), float(flops)))
         return rows
 
+    def amax_audit(self, on=True):
+        """Turns the audit of the maxima handed from kernel to kernel on or off (stx_amax_audit; clears the
+        record).  For the tests: while on, every hand-off costs a copy and a pass over the consumer's input."""
+        lib.call('stx_amax_audit', self.handle, int(on))
+
+    def amax_audit_read(self):
+        """[(consumer, blob, 'data' | 'diff', blob whose slots were read, recorded, measured)] of the hand-offs
+        since the last read, the two maxima as float32 bit patterns (ints): recorded >= measured is what the
+        fp16-split kernels rely on.  Empty while the audit is off."""
+        buf = ctypes.create_string_buffer(1 << 20)
+        lib.call('stx_amax_audit_read', self.handle, buf, len(buf), None)
+        rows = []
+        for line in buf.value.decode().splitlines():
+            consumer, blob, kind, source, recorded, measured = line.split('\t')
+            rows.append((consumer, blob, kind, source, int(recorded, 16), int(measured, 16)))
+        return rows
+
     def last_tile_flops(self):
         """(algorithmic, issued) matrix-core FLOP of the convolutions of the last tile call."""
         a, b = ctypes.c_double(0), ctypes.c_double(0)

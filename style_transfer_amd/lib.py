@@ -143,6 +143,8 @@ SIGNATURES = {
     'stx_clock_marks_read': [_vp, c_double_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
     'stx_profile_enable': [_vp, _i],
     'stx_profile_read': [_vp, ctypes.c_char_p, _sz, ctypes.POINTER(_sz)],
+    'stx_amax_audit': [_vp, _i],
+    'stx_amax_audit_read': [_vp, ctypes.c_char_p, _sz, ctypes.POINTER(_sz)],
 }
 NON_STATUS = {'stx_version': (ctypes.c_char_p, []), 'stx_last_error': (ctypes.c_char_p, []),
               'stx_engine_destroy': (None, [_vp]),

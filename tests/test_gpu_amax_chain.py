@@ -1,0 +1,384 @@
+"""The scale chain of the fp16-split kernels: the maxima that one kernel leaves for the next.
+
+conv_h2.hip and the two-piece Gram / SYMM kernels scale their operand by a power of two taken from 64 words
+that the operand's producer recorded (conv_first, the conv_h2 / conv_wino2 epilogues, the split-K reduce
+pass, the inject kernels, absmax_launch), or that the host passed on as a bound (a pooling layer forward or
+backward, a mask, a routed pooled gradient).  The split leaves a factor of four of headroom, and with the
+He-style synthetic weights every blob's maximum lies within a small factor of its neighbours': a consumer
+that reads the wrong words computes the same numbers there.  Three pieces, none of which it passes:
+
+  1. the audit (stx_amax_audit): at every hand-off the recorded words against a measured maximum of exactly
+     what the consumer reads -- recorded >= measured everywhere (a condition, not a tolerance), recorded ==
+     measured where the array's own writer recorded it;
+  2. nets whose neighbouring blobs differ by 2^12 (exactly rescaled weights): against the oracle at the
+     project's 1e-5, and bit-for-bit against the plain net's blobs times the power of two -- which holds if
+     and only if every scale follows the true maximum;
+  3. absmax_launch at its head, tail and block cap through the operator hooks.
+
+Bound-only sites, from the code (not reachable with VGG channel counts, so named here and not tested): the
+kEpiDgradInject epilogues of conv_h2.hip and conv_wino2.hip add the content term of channel 0 in lanes whose
+channel lies past M; they store nothing, but their value enters the recorded maximum, which for a channel
+count that is no multiple of the kernel's channel block is therefore an upper bound, never too small."""
+
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from tests import amax_chain as ac
+from tests.gpu_helpers import check_tile, gpu_engine, max_rel
+from tests.helpers import DEFAULT_STYLE_LAYERS, normalized_weights
+
+pytestmark = pytest.mark.gpu
+
+# ------------------------------------------------------------------------------------------ 1. the audit
+AUDIT_TILES = [(37, 53),       # every deep layer is K-sliced: the reduce pass records
+               (131, 77),      # odd planes, ceil-mode pooling edges
+               (203, 331)]     # the fused-pool and pooled-gradient (PIN) paths of test_gpu_tile_path.py
+# switches -> the kinds of line (amax_chain.line_kinds) the case must contain, beyond which nothing is vacuous.
+# 'pin' is asked for on the large tile only (small planes split their reduction and keep the pooling kernel)
+# and not with the tap set that taps every blob under a pooling layer.
+H2 = {'fwd', 'bwd', 'style', 'own', 'inherited'}
+SWITCH_SETS = {
+    'default': ({}, H2 | {'pin'}),
+    'pool-fwd-unfused': ({'STX_POOL_FWD_FUSE': '0'}, H2 | {'pin'}),
+    'pool-bwd-unfused': ({'STX_POOL_BWD_FUSE': '0'}, H2),
+    'h2a': ({'STX_CONV_ALGO': 'h2a'}, H2 | {'pin'}),
+    # a forced fp32 family switches the chain off as a whole (conv_h2_enabled): nobody records, Gram / SYMM
+    # measure for themselves, and the audit has nothing to report -- which is asserted
+    'wino2a': ({'STX_CONV_ALGO': 'wino2a'}, None),
+    'direct': ({'STX_CONV_ALGO': 'direct'}, None),
+    # ... so the mixtures in which ANOTHER family produces what the split kernels consume are these two:
+    # fp32 Winograd forward (its epilogue and conv_first record for Gram / SYMM), fp16-split backward;
+    'wino2-fwd+h2-bwd': ({'STX_CONV_H2': '0', 'STX_CONV_H2_BWD': '64'}, {'bwd', 'style', 'own', 'pin'}),
+    # fp16-split forward, fp32 Winograd backward (records gradients nobody reads)
+    'h2-fwd+wino2-bwd': ({'STX_CONV_H2_BWD': '0'}, {'fwd', 'style', 'own', 'inherited'}),
+}
+MIN_LINES = 10
+
+
+def _record_ratios(case, lines, kinds):
+    """STX_AMAX_AUDIT_STATS=<file>: recorded / measured of every inherited hand-off, appended (profiles/)."""
+    path = os.environ.get('STX_AMAX_AUDIT_STATS')
+    if not path:
+        return
+    with open(path, 'a') as f:
+        for line, k in zip(lines, kinds):
+            if 'inherited' in k:
+                rec, meas = ac.bits_to_float(line[4]), ac.bits_to_float(line[5])
+                f.write('%s: %s reads %s %s under the slots of %s: recorded %.6g measured %.6g ratio %.4f\n'
+                        % (case, line[0], line[1], line[2], line[3], rec, meas, rec / meas if meas else np.inf))
+
+
+@pytest.mark.parametrize('switches', sorted(SWITCH_SETS))
+@pytest.mark.parametrize('taps', sorted(ac.TAP_SETS))
+@pytest.mark.parametrize('th,tw', AUDIT_TILES)
+@pytest.mark.parametrize('model', ac.MODELS)
+def test_every_recorded_maximum_bounds_what_its_consumer_reads(model, th, tw, taps, switches, monkeypatch):
+    env, expect = SWITCH_SETS[switches]
+    for name in ('STX_CONV_ALGO', 'STX_CONV_H2', 'STX_CONV_H2_BWD', 'STX_POOL_FWD_FUSE', 'STX_POOL_BWD_FUSE'):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    eng = gpu_engine(model)
+    tap = ac.TAP_SETS[taps]
+    tile = ac.spiked_tile(th, tw, th + tw)
+    ac.arm(eng, tap, th, tw)
+    try:
+        # ---- audit off: nothing is recorded; audit on: the same bits
+        off = ac.evaluate(eng, tap, tile)
+        assert eng.amax_audit_read() == []
+        eng.amax_audit(True)
+        on = ac.evaluate(eng, tap, tile)
+        lines = eng.amax_audit_read()
+        assert eng.amax_audit_read() == []             # (a read clears the record)
+        eng.amax_audit(False)
+        again = ac.evaluate(eng, tap, tile)
+        assert eng.amax_audit_read() == []
+        assert np.isfinite(off[0]) and np.isfinite(off[1]).all()
+        assert on[0] == off[0] and np.array_equal(on[1], off[1])
+        assert again[0] == off[0] and np.array_equal(again[1], off[1])
+        # ---- what absmax_launch measured is the blob's maximum (every data line but the masked copies)
+        blobs = sorted({l[1] for l in lines if l[2] == 'data'})
+        feats = eng.features_tile(tile, blobs) if blobs else {}
+    finally:
+        eng.amax_audit(False)
+        eng.set_style_masks([])
+    kinds = [ac.line_kinds(l, eng.net) for l in lines]
+    case = '%s %dx%d %s %s' % (model, th, tw, taps, switches)
+    for l in lines:
+        print(case, l[:4], '%08x %08x' % l[4:])
+    _record_ratios(case, lines, kinds)
+    if expect is None:
+        assert lines == []
+        return
+    for line, k in zip(lines, kinds):
+        consumer, blob, kind, source, recorded, measured = line
+        # (non-negative floats order like their bit patterns)
+        assert recorded >= measured, (line, 'the recorded maximum is too small: the split can overflow')
+        if 'own' in k:
+            assert recorded == measured, (line, 'the kernel that wrote the array recorded another maximum')
+        if kind == 'data' and 'masked' not in k:
+            assert measured == int(np.abs(feats[blob]).max().view(np.uint32)), line
+    # ---- the case reaches what it is meant to reach
+    seen = set().union(*kinds) if kinds else set()
+    if 'pin' in expect and ((th, tw) != (203, 331) or taps == 'pool+2styles+dream'):
+        expect = expect - {'pin'}
+    if switches == 'pool-bwd-unfused':
+        assert 'pin' not in seen
+    if switches == 'pool-bwd-unfused' and taps != 'pool+2styles+dream':      # (that set taps the blobs under the pools)
+        # the pooling kernel ran and passed the bound down: some gradient is read under another blob's slots
+        assert any('bwd' in k and 'inherited' in k for k in kinds), lines
+    if tap['masked'] and 'style' in expect:
+        assert 'masked' in seen
+    assert expect <= seen, (expect - seen, lines)
+    assert len(lines) >= MIN_LINES, lines
+
+
+@pytest.mark.parametrize('model,layer', [('vgg19', 'conv3_3'), ('vgg16_avgpool', 'conv3_2')])
+def test_terms_added_behind_a_backward_convolution_leave_the_new_maximum(model, layer):
+    """A tap whose gradient a backward convolution wrote (and recorded) and whose terms are then added by the
+    stand-alone kernels: the slot is zeroed in between (backward_walk), else it would keep the larger of the two
+    maxima.  Two content targets on `layer` (two terms: not fusable) against maps of +-1e6 everywhere: each
+    term is then -+coef all over the blob, a uniform shift of the gradient by a thousandth -- which lowers
+    max |.| for one of the two signs (whichever side the maximum sits on) and raises it for the other.  With
+    a zero weight the terms add nothing and the maximum is the upstream gradient's own.  All three are the
+    blob's own maxima: recorded == measured; the seeded mistake (no zeroing) keeps the upstream maximum where
+    the shift lowered it."""
+    th, tw = 131, 77
+    eng = gpu_engine(model)
+    tile = ac.spiked_tile(th, tw, 5)
+    r = np.random.RandomState(4)
+    deep = (50 * np.abs(r.standard_normal(eng.feature_shape('conv4_2', th, tw)))).astype(np.float32)
+    measured = {}
+    eng.amax_audit(True)
+    try:
+        for sign, weight in ((0, 0.0), (1, 1e-3), (-1, 1e-3)):
+            flat = np.full(eng.feature_shape(layer, th, tw), (sign or 1) * 1e6, np.float32)
+            eng.set_contents_and_styles([{layer: flat, 'conv4_2': deep}, {layer: flat}], [])
+            loss, grad = eng.sc_grad_tile(tile, (0, 0), (0, 0), [layer, 'conv4_2'], [], {},
+                                          {layer: weight, 'conv4_2': 1.0}, {})
+            assert np.isfinite(loss) and np.isfinite(grad).all()
+            lines = [l for l in eng.amax_audit_read() if l[:3] == ('bwd ' + layer, layer, 'diff')]
+            assert len(lines) == 1, lines
+            consumer, blob, kind, source, rec, meas = lines[0]
+            print(model, layer, sign, source, ac.bits_to_float(rec), ac.bits_to_float(meas))
+            assert source == layer
+            assert rec == meas, (sign, lines[0])
+            measured[sign] = meas
+    finally:
+        eng.amax_audit(False)
+    # the case has teeth: one of the shifts lowered the maximum below the upstream gradient's
+    assert min(measured[1], measured[-1]) < measured[0] < max(measured[1], measured[-1]), measured
+
+
+def test_audit_storage_is_bounded_and_reported():
+    """More hand-offs than the audit keeps between two reads: the evaluation fails with a status, and a read
+    clears the way."""
+    from style_transfer_amd.lib import StxError
+    eng = gpu_engine('vgg19')
+    tap = ac.TAP_SETS['defaults']
+    tile = ac.spiked_tile(16, 16, 0)
+    ac.arm(eng, tap, 16, 16)
+    eng.amax_audit(True)
+    try:
+        per_call = None
+        with pytest.raises(StxError, match='stx_amax_audit'):
+            for _ in range(2048):
+                ac.evaluate(eng, tap, tile)
+                if per_call is None:
+                    per_call = len(eng.amax_audit_read())
+                    assert per_call >= MIN_LINES
+        assert len(eng.amax_audit_read()) == 2048
+        ac.evaluate(eng, tap, tile)
+        assert len(eng.amax_audit_read()) == per_call
+    finally:
+        eng.amax_audit(False)
+        eng.sync()
+
+
+# ------------------------------------------------------------------ 2. nets with 2^12 between neighbours
+STEPS = [12, -12]       # K_l = 0, +12, 0, +12, ... and 0, -12, 0, -12, ...
+RESCALED_TILES = [(37, 53), (131, 77)]
+_OWN_ENGINES = {}
+
+
+@pytest.fixture(scope='module')
+def own_engines():
+    """TileEngines of this module's own (plain and rescaled weights; not the suite's cache), closed at the end."""
+    from style_transfer_amd.engine import TileEngine
+
+    def get(model, step):
+        if (model, step) not in _OWN_ENGINES:
+            net, plain = ac.plain_weights(model)
+            _OWN_ENGINES[model, step] = TileEngine(net, 0, ac.rescaled_weights(model, step) if step else plain)
+        return _OWN_ENGINES[model, step]
+    yield get
+    for eng in _OWN_ENGINES.values():
+        eng.close()
+    _OWN_ENGINES.clear()
+
+
+@functools.lru_cache(maxsize=None)
+def _range_checked(model, step, th, tw):
+    """The CPU precondition, with the oracle alone: every activation, Gram, gradient blob and the loss of the
+    rescaled case is finite and no non-zero value lies below 2^-100 (2^12 passes on both nets and both
+    patterns: magnitudes 2e-14 .. 3e18), so the scaling is exact and the oracle decides as on the plain net."""
+    om, _, tile, start, _ = ac.rescaled_scene(model, step, th, tw)
+    cl, cw = normalized_weights(['conv4_2'], 0.05)
+    sl, sw = normalized_weights(DEFAULT_STYLE_LAYERS, 1)
+    return ac.oracle_range_check(om, tile, start, cl, cw, sl, sw)
+
+
+@functools.lru_cache(maxsize=None)
+def _plain_features(model, th, tw):
+    """The oracle's blobs of the plain net on the tile of the rescaled cases."""
+    om, _, tile, _, _ = ac.rescaled_scene(model, 0, th, tw)
+    return om.features_tile(tile, om.blob_names)
+
+
+@pytest.mark.parametrize('step', STEPS)
+@pytest.mark.parametrize('th,tw', RESCALED_TILES)
+@pytest.mark.parametrize('model', ac.MODELS)
+def test_rescaled_net_against_the_oracle(model, th, tw, step, own_engines):
+    """check_tile as it stands (1e-5) on a net whose blobs alternate between 2^0 and 2^+-12 times the plain
+    net's: a consumer that scales by a neighbour's maximum overflows fp16 (inf / NaN) or drops twelve bits."""
+    print(model, th, tw, step, 'oracle magnitudes', _range_checked(model, step, th, tw))
+    om, _, tile, start, roll = ac.rescaled_scene(model, step, th, tw)
+    eng = own_engines(model, step)
+    cl, cw = normalized_weights(['conv4_2'], 0.05)
+    sl, sw = normalized_weights(DEFAULT_STYLE_LAYERS, 1)
+    eng.set_contents_and_styles(om.contents, om.styles)
+    loss, grad, stats = check_tile(eng, om, tile, start, roll, cl, cw, sl, sw, {})
+    print(stats)
+    assert np.isfinite(loss) and np.isfinite(grad).all()
+
+
+# Both engines must choose the same kernels.  choose_conv / conv_choose decide by shape, epilogue and the
+# switches only (h2_choice, wino_choice; h2_pick_config is a cost model of the shape); timing enters in
+# direct_tune alone, among direct variants that accumulate in the same order and give the same bits.  So the
+# default choice is deterministic too; h2a / h2b / h2c force one tiling of the split kernel everywhere.
+@pytest.mark.parametrize('algo', [None, 'h2a', 'h2b', 'h2c'])
+@pytest.mark.parametrize('step', STEPS)
+@pytest.mark.parametrize('model', ac.MODELS)
+def test_rescaled_forward_pass_is_the_plain_one_times_a_power_of_two(model, step, algo, own_engines, monkeypatch):
+    """Every blob of the rescaled net equals the plain net's times 2^K_l BIT FOR BIT: the fp32 kernels scale
+    exactly, and the split kernels do if and only if their scale follows the operand's true maximum (or the
+    same bound of it).  A maximum that is too large costs bits silently -- no tolerance sees it, this does."""
+    if algo:
+        monkeypatch.setenv('STX_CONV_ALGO', algo)
+    else:
+        monkeypatch.delenv('STX_CONV_ALGO', raising=False)
+    net, _ = ac.plain_weights(model)
+    K = ac.blob_exponents(net, step)
+    blobs = [l.top for l in net.layers[1:] if l.type != 'ReLU']
+    for th, tw in RESCALED_TILES:
+        _range_checked(model, step, th, tw)
+        tile = ac.rescaled_scene(model, step, th, tw)[2]
+        plain = own_engines(model, 0).features_tile(tile, blobs)
+        scaled = own_engines(model, step).features_tile(tile, blobs)
+        ref = _plain_features(model, th, tw)
+        for b in blobs:
+            # (the plain side is the net the oracle knows: two engines that are wrong alike do not pass)
+            assert max_rel(plain[b], ref[b]) < 1e-5, b
+            assert np.isfinite(scaled[b]).all(), b
+            assert np.array_equal(scaled[b], np.ldexp(plain[b], K[b])), (b, K[b], max_rel(
+                scaled[b], np.ldexp(plain[b], K[b])))
+
+
+@pytest.mark.parametrize('model', ac.MODELS)
+def test_a_brighter_tile_leaves_nothing_behind(model, own_engines):
+    """An evaluation of the tile times 64, then the tile itself: the second result is bit-identical to the
+    tile's on an engine that never saw the bright one.  The slots are cleared once per call (forward());
+    a slot that survived a call would hold a maximum 64 times too large for the next."""
+    from style_transfer_amd.engine import TileEngine
+    th, tw = 131, 77
+    om, _, tile, start, roll = ac.rescaled_scene(model, 0, th, tw)
+    cl, cw = normalized_weights(['conv4_2'], 0.05)
+    sl, sw = normalized_weights(DEFAULT_STYLE_LAYERS, 1)
+    blobs = om.blob_names
+    run = lambda e, t: e.sc_grad_tile(t, start, roll, cl, sl, {}, cw, sw)
+    net, plain = ac.plain_weights(model)
+    fresh = TileEngine(net, 0, plain)
+    try:
+        fresh.set_contents_and_styles(om.contents, om.styles)
+        want = run(fresh, tile)
+        want_feats = fresh.features_tile(tile, blobs)
+    finally:
+        fresh.close()
+    eng = own_engines(model, 0)
+    eng.set_contents_and_styles(om.contents, om.styles)
+    bright = run(eng, tile * np.float32(64))
+    assert np.isfinite(bright[0]) and np.isfinite(bright[1]).all()
+    got = run(eng, tile)
+    assert got[0] == want[0] and np.array_equal(got[1], want[1])
+    eng.features_tile(tile * np.float32(64), blobs)
+    feats = eng.features_tile(tile, blobs)
+    for b in blobs:
+        assert np.array_equal(feats[b], want_feats[b]), b
+
+
+# ------------------------------------------------------------------------- 3. absmax_launch at its edges
+def _conv64(x, w, b=None):
+    """float64 3x3 convolution (pad 1), [Cin,H,W] -> [Cout,H,W]."""
+    import torch
+    as64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64))
+    y = torch.nn.functional.conv2d(as64(x)[None], as64(w), None if b is None else as64(b), padding=1)
+    return y[0].numpy()
+
+
+def _spiked_conv_case(eng, cin, cout, h, w, offset, spike, seed):
+    """stx_op_conv_forward and stx_op_conv_backward_data (STX_CONV_ALGO=h2a: hook_conv measures the input with
+    absmax_launch) on standard normal data with element `spike` times 1e6, the operand starting `offset`
+    floats into a larger device array.  Against float64 at the 2e-5 of tests/test_gpu_kernels.py."""
+    from style_transfer_amd import lib
+    from style_transfer_amd.engine import DeviceArray
+    rng = np.random.RandomState(seed)
+    n = cin * h * w
+    x = rng.standard_normal(n).astype(np.float32)
+    x[spike % n] *= np.float32(1e6)
+    x = x.reshape(cin, h, w)
+    wt = (rng.standard_normal((cout, cin, 3, 3)) * np.sqrt(2 / (9 * cin))).astype(np.float32)
+    b = (0.1 * rng.standard_normal(cout)).astype(np.float32)
+    wt2 = (rng.standard_normal((cin, cout, 3, 3)) * np.sqrt(2 / (9 * cin))).astype(np.float32)
+    # (the operand lies inside the allocation: `offset` floats in front of it, 4 - offset behind)
+    room = np.full(n + 4, 1e12, np.float32)         # (a maximum taken past the operand costs twenty bits)
+    room[offset:offset + n] = x.ravel()
+    d_room = eng.to_device(room)
+    d_x = DeviceArray.from_pointer(eng, d_room.ptr + 4 * offset, x.shape, owner=d_room)
+    d_w, d_b, d_w2 = eng.to_device(wt), eng.to_device(b), eng.to_device(wt2)
+    y, gx = eng.empty((cout, h, w)), eng.empty((cout, h, w))
+    try:
+        lib.call('stx_op_conv_forward', eng.handle, d_x.ptr, cin, h, w, d_w.ptr, d_b.ptr, cout, 3, 0, y.ptr)
+        got = y.get()
+        assert np.isfinite(got).all()
+        err_f = max_rel(got, _conv64(x, wt, b))
+        # the same array as the upstream gradient of the transposed layer
+        lib.call('stx_op_conv_backward_data', eng.handle, d_x.ptr, cin, h, w, d_w2.ptr, cout, 3, None, gx.ptr)
+        got = gx.get()
+        assert np.isfinite(got).all()
+        ref = _conv64(x, np.flip(wt2, (2, 3)).transpose(1, 0, 2, 3))
+        err_b = max_rel(got, ref)
+    finally:
+        for a in (d_room, d_w, d_b, d_w2, y, gx):
+            a.free()
+    print('offset %d spike %d: forward %.2e backward %.2e' % (offset, spike, err_f, err_b))
+    assert err_f < 2e-5 and err_b < 2e-5, (err_f, err_b)
+
+
+@pytest.mark.parametrize('spike', [0, 1, -2, -1])
+@pytest.mark.parametrize('offset', [0, 1, 2, 3])
+def test_absmax_sees_a_spike_in_its_head_and_tail(offset, spike, monkeypatch):
+    """absmax_kernel takes 16-byte loads over the aligned middle and the (at most three) floats in front of it
+    and behind it one by one: a spike of 1e6 in standard normal data at the first two and the last two
+    elements, the array 0 .. 3 floats off a 16-byte boundary.  A missed spike overflows the fp16 split."""
+    monkeypatch.setenv('STX_CONV_ALGO', 'h2a')
+    _spiked_conv_case(gpu_engine(), 64, 64, 9, 11, offset, spike, 7 + offset)
+
+
+@pytest.mark.parametrize('h,w', [(192, 192),      # 289 blocks
+                                 (362, 363)])     # 64 * 362 * 363 floats: past 1023 * 8192, the 1024-block cap
+def test_absmax_sees_the_last_element_of_a_large_array(h, w, monkeypatch):
+    monkeypatch.setenv('STX_CONV_ALGO', 'h2a')
+    _spiked_conv_case(gpu_engine(), 64, 64, h, w, 0, -1, h)
