@@ -506,6 +506,26 @@ int stx_image_lap(stx_engine *e, const float *img, float *grad, int H, int W, in
                   const int *pools, const double *weights, const float *target, double scale,
                   double *loss_out);
 
+/* The photorealism regulariser (Luan, Paris, Shechtman, Bala, "Deep Photo Style Transfer", 2017): the
+ * quadratic form of the matting Laplacian (Levin, Lischinski, Weiss) of a content picture, matrix-free.
+ * It is zero where the iterate is locally an affine function of the content picture's colours.
+ * Pictures are [3][H][W] float32 STX_DEVICE arrays, un-rolled; the term ignores the iteration's shift.
+ * With I = content / 255 (a 3-vector per pixel), v = a plane of img / 255 and the 3 x 3 windows w_k
+ * centred on the interior pixels (1 <= y <= H - 2, 1 <= x <= W - 2):
+ *   mu_k = mean_w I,  m_k = mean_w v,  S_k = mean_w (I - mu_k)(I - mu_k)^T,  q_k = mean_w (I - mu_k)(v - m_k)
+ *   a_k  = (S_k + (eps / 9) Id)^-1 q_k
+ *   r_ki = (v_i - m_k) - a_k . (I_i - mu_k)                     for the nine pixels i of w_k
+ *   loss = scale * sum over planes and windows of [ sum_i r_ki^2 + eps |a_k|^2 ]
+ *   grad[c][i] += scale * 2 * (sum over the windows k that hold i of r_ki) / 255
+ * A corner pixel is in one window, an interior pixel in nine.  Everything between the float32 pictures
+ * and the float32 gradient is float64 on the device; the sum of a pixel is formed first, rounded to
+ * float32 and added once: grad is read and written once.  Nothing is kept between calls.  No atomics:
+ * the same inputs give the same bits.  A null pointer, H < 3, W < 3 or an eps that is not finite and
+ * positive is STX_ERR_ARG.  *loss_out (host) is written at the next stx_sync; asynchronous like
+ * stx_image_lap. */
+int stx_image_photo(stx_engine *e, const float *img, const float *content, float *grad, int H, int W,
+                    double eps, double scale, double *loss_out);
+
 /* ------------------------------------------------------------- single-kernel test hooks */
 /* Direct entry points to the individual kernels, used by tests/ to check each against the
  * oracle (x, w, b, y: STX_DEVICE).  w is the Caffe layout [Cout][Cin][k][k]. */

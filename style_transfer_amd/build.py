@@ -34,6 +34,7 @@ SOURCES = {
     'style_mask.hip': ['-ffp-contract=off'],
     'lap.hip': ['-ffp-contract=off'],
     'stat.hip': ['-ffp-contract=off'],
+    'photo.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'tile_path.cpp': [],

@@ -137,6 +137,15 @@ _EXTENSIONS = [
                                    'scale; with --style-multiscale the layers themselves stay those of the '
                                    "first scale, whose targets are kept (default: the --style-layers' names "
                                    'with weight 1 each; its built-in list when --style-layers is empty)')),
+    (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
+                               help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
+                                    "result that is not locally an affine function of the content picture's "
+                                    'colours, the quadratic form of the matting Laplacian; keeps straight edges '
+                                    'and flat regions when the style is a photograph; 0 or absent: off '
+                                    '(default: 0)')),
+    (('--photo-eps',), dict(metavar='EPS', type=ffloat,
+                            help='regularisation of the matting Laplacian\'s 3 x 3 window covariances, finite '
+                                 'and positive (default: 1e-7)')),
 ]
 
 
@@ -249,6 +258,26 @@ def check_lap_pools(args):
     return pools
 
 
+PHOTO_EPS_DEFAULT = 1e-7
+
+
+def check_photo_options(args):
+    """--photo-eps regularises 3 x 3 covariances that are singular wherever a window's colours lie on a line:
+    a value that is not finite and positive is refused before any GPU work.  (A value bound to the run state
+    reads as a placeholder until the run exists and is checked at every evaluation instead.)  Returns
+    the eps in force."""
+    eps = getattr(args, 'photo_eps', PHOTO_EPS_DEFAULT)
+    if isinstance(eps, ValuePlaceholder):
+        return eps
+    try:
+        ok = math.isfinite(float(eps)) and float(eps) > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('--photo-eps %s: a finite positive value is needed' % (eps,))
+    return float(eps)
+
+
 # the built-in --style-layers list (read from its entry above: one statement of it)
 STYLE_LAYERS_DEFAULT = tuple(next(kw['default'] for flags, kw in _OPTIONS if flags[0] == '--style-layers'))
 
@@ -322,4 +351,5 @@ def parse_args(state=None, argv=None, config_py=None):
     check_content_mask(args)
     check_lap_pools(args)
     check_stat_options(args)
+    check_photo_options(args)
     return args

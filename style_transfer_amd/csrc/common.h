@@ -547,6 +547,13 @@ int lap_launch(hipStream_t s, const float *img, float *grad, int H, int W, const
                size_t map_floats, const float *coefs, const float *target, double *loss_terms,
                float *scratch);
 
+// photo.hip: the photorealism regulariser (the matting Laplacian's quadratic form, matrix-free).
+// grad += 2 scale (L v_c) / 255 per plane, *loss_term = sum over planes and windows of
+// [sum r^2 + eps |a|^2] (without scale); scratch holds photo_blocks(H, W) <= kBlocks floats.
+int photo_blocks(int H, int W);
+int photo_launch(hipStream_t s, const float *img, const float *content, float *grad, int H, int W,
+                 double eps, double scale, double *loss_term, float *scratch);
+
 // image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,
                 float *avg, size_t n, double lr, double b1, double b2, double bp1, double c1,

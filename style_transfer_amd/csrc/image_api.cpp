@@ -1,6 +1,6 @@
 // libstx host side: the entries that work on whole images, feature maps and parameter vectors
 // (stx_image_*, stx_map_*, stx_vec_*, stx_adam_step) -- thin wrappers that check their arguments and
-// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip on the engine's stream.
+// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip / photo.hip on the engine's stream.
 
 #include <cmath>
 #include <cstdint>
@@ -310,6 +310,30 @@ int stx_image_lap(stx_engine *e, const float *img, float *grad, int H, int W, in
     }
     return queue_dterms(e, coefs, (size_t)n_pools, loss_out, [&](double *terms) {
         return lap_launch(e->stream, img, grad, H, W, lv, floats, cell_coefs, target, terms, scratch);
+    });
+}
+
+// ---- the photorealism regulariser (photo.hip) ----
+
+int stx_image_photo(stx_engine *e, const float *img, const float *content, float *grad, int H, int W,
+                    double eps, double scale, double *loss_out) {
+    if (!e || !img || !content || !grad || !loss_out) {
+        set_error("stx_image_photo: %s is null", !e ? "the engine" : !img ? "img" : !content ? "content" :
+                  !grad ? "grad" : "loss_out");
+        return STX_ERR_ARG;
+    }
+    if (H < 3 || W < 3) {
+        set_error("stx_image_photo: a %d x %d picture holds no 3 x 3 window", H, W);
+        return STX_ERR_ARG;
+    }
+    if (!std::isfinite(eps) || !(eps > 0.0)) {
+        set_error("stx_image_photo: eps = %g, but a finite positive value is needed", eps);
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    // (the engine's reduction scratch holds kBlocks floats and more: one partial per workgroup)
+    return queue_dterms(e, {scale}, loss_out, [&](double *term) {
+        return photo_launch(e->stream, img, content, grad, H, W, eps, scale, term, e->red_scratch.f());
     });
 }
 

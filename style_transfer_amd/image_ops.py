@@ -164,6 +164,22 @@ def lap_loss(engine, img, grad, target, pools, weights, scale):
     return out
 
 
+# ---------------------------------------------------------------------- --photo-weight
+def photo_loss(engine, img, grad, content, eps, scale):
+    """grad += the gradient of scale * sum_c v_c^T L v_c, the photorealism regulariser: L is the matting
+    Laplacian of ``content`` / 255 over 3 x 3 windows with regularisation ``eps``, v_c a plane of ``img`` / 255
+    (include/stx.h has the definition).  ``img``, ``grad``, ``content``: DeviceArrays [3,H,W] with H, W >= 3.
+    Returns a PendingScalar with the loss (valid after sync)."""
+    _, H, W = img.shape
+    if content.shape != img.shape:
+        raise ValueError('photo_loss: a content picture of %dx%d for an image of %dx%d'
+                         % (content.shape[2], content.shape[1], W, H))
+    out = engine.keep_until_sync(PendingScalar())
+    lib.call('stx_image_photo', engine.handle, img.ptr, content.ptr, grad.ptr, H, W, float(eps), float(scale),
+             ctypes.byref(out._v))
+    return out
+
+
 def adam_step(engine, params, grad, g1, g2, p1, avg, lr, b1, b2, bp1, corr1, corr2, corrp):
     lib.call('stx_adam_step', engine.handle, params.ptr, grad.ptr, g1.ptr, g2.ptr, p1.ptr, avg.ptr,
              params.size, float(lr), float(b1), float(b2), float(bp1), float(corr1), float(corr2),

@@ -110,6 +110,7 @@ SIGNATURES = {
     'stx_image_swt_daub_levels': [_vp, _vp, _vp, _i, _i, _i, _i, c_int_p, _d, _d, c_double_p],
     'stx_image_lap_target': [_vp, _vp, _i, _i, _i, c_int_p, _vp],
     'stx_image_lap': [_vp, _vp, _vp, _i, _i, _i, c_int_p, c_double_p, _vp, _d, c_double_p],
+    'stx_image_photo': [_vp, _vp, _vp, _vp, _i, _i, _d, _d, c_double_p],
     'stx_adam_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _d, _d, _d, _d, _d, _d, _d],
     'stx_vec_dot': [_vp, _vp, _vp, _sz, c_double_p],
     'stx_vec_axpy': [_vp, _d, _vp, _vp, _sz],

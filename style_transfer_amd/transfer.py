@@ -23,7 +23,8 @@ import numpy as np
 from PIL import Image
 
 from . import image_ops, lib
-from .config_system import LAP_POOLS_DEFAULT, check_lap_pools, check_stat_options, ffloat, stat_layer_args
+from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_photo_options,
+                            check_stat_options, ffloat, stat_layer_args)
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
 
@@ -197,6 +198,13 @@ class StyleTransfer:
         self._lap_pools = check_lap_pools(args) if self._lap_on else []
         self._lap_target = None
         self._lap_weights_key = self._lap_weights_now = None    # the last (--lap-pools, lap_weight) parsed
+        # --photo-weight / --photo-eps (the photorealism regulariser; not options of the reference): the first
+        # content picture of the scale being optimised stays on the master GPU -- the very array that
+        # --preserve-color luma keeps, when it keeps one.  Without --photo-weight nothing here runs.
+        raw = getattr(getattr(args, 'ns', args), 'photo_weight', 0)
+        self._photo_on = bool(callable(raw) or raw)
+        self._photo_content = None  # DeviceArray [3,H,W]
+        self._photo_shared = False  # it is self._luma_content, which is freed where it is made
         # --stat-weight / --stat-layers (the mean / std style term; not options of the reference): per-channel
         # mean and sd of the style pictures' feature maps, averaged like the Grams and kept where they are
         # kept; sent to the engines behind the targets.  Without the options nothing here runs.
@@ -398,6 +406,14 @@ class StyleTransfer:
             lap = image_ops.lap_loss(self.engine, params, self.grad, self._lap_target, self._lap_pools,
                                      self._lap_weights(args, lap_weight), lw)
             loss.add(lap, self.engine)
+        photo_weight = getattr(args, 'photo_weight', 0) if self._photo_content is not None else 0
+        if photo_weight:
+            eps = check_photo_options(args)
+            if isinstance(eps, ValuePlaceholder):
+                raise ValueError('--photo-eps is bound to run state that does not exist at an evaluation')
+            photo = image_ops.photo_loss(self.engine, params, self.grad, self._photo_content, eps,
+                                         lw * photo_weight)
+            loss.add(photo, self.engine)
         return loss, self.grad
 
     def _lap_weights(self, args, lap_weight):
@@ -460,6 +476,16 @@ class StyleTransfer:
             self._lap_target = target
             if picture is not self._luma_content:
                 picture.free()
+        if self._photo_on:
+            if min(self.img.shape[1:]) < 3:
+                raise ValueError('--photo-weight: a %d x %d image holds no 3 x 3 window (raise --min-size)'
+                                 % (self.img.shape[2], self.img.shape[1]))
+            if self._photo_content is not None and not self._photo_shared:
+                self._photo_content.free()
+            self._photo_shared = self._luma_content is not None
+            self._photo_content = self._luma_content
+            if not self._photo_shared:
+                self._photo_content = self.engine.to_device(self.pil_to_image(content_images[0]))
         self.preprocess_images([] if jitter else content_images, style_images,
                                [] if jitter else content_layers, style_layers,
                                color_from=content_images[0] if self.preserve_color == 'match' else None,
