@@ -244,6 +244,39 @@ typedef struct stx_stat_target {
  * every call. */
 int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n);
 
+/* The nearest-neighbour feature matching term (NNFM; not in the reference): the per-pixel style loss of ARF,
+ * NNST and STROTSS-style tools.  Every column f_i of a tapped blob F [C][h][w] -- the array the Gram term
+ * reads, n = h w columns -- is pulled towards the most similar row of a fixed bank B [rows][C] whose rows b_j
+ * have unit length or are all zero:
+ *   r_i  = |f_i|,  x_i = f_i / r_i           (a column with r_i = 0: x_i = 0, c_i = 0, j_i = 0, S_i = 0)
+ *   j_i  = argmax_j x_i . b_j                (the LOWEST j among equal scores)
+ *   c_i  = x_i . b_{j_i}
+ *   E    = (2/n) sum_i (1 - c_i)             ( = mean |x_i - b_{j_i}|^2 for unit rows; E / 2 is ARF's loss )
+ *   S_i  = -(b_{j_i} - c_i x_i) / r_i        ( = n d(E/2)/d f_i with j_i held fixed )
+ *   loss        += lw weight E / 2
+ *   diff[layer] += lw weight S / (sum|S| / (C n) + EPS)
+ * The last line is the reference's normalize, exactly as for the Gram term.  The search runs on the fp16
+ * matrix pipe with two-piece operands (three products, fp32 accumulation): j_i is the float64 argmax up to
+ * scores closer than about 1e-6.  c_i, E and S are recomputed in float32 from (F, B, j_i) alone.  The term is
+ * per pixel: a tile's term is the tile's own and tiles exchange nothing.  No atomics; the same inputs give
+ * the same bits.  channels must be a multiple of 64 and rows x channels, n x channels stay below 2^31
+ * (STX_ERR_UNSUPPORTED otherwise). */
+typedef struct stx_nnfm_target {
+    const char *layer;
+    int channels;
+    int rows;
+    const float *bank;      /* [rows][channels] */
+    int mem;
+    double weight;
+} stx_nnfm_target;
+/* Replaces all NNFM banks of the engine's group (n = 0: none); one per layer at most.  The bank is copied and
+ * its fp16 pieces are built once, here; the source may be freed when the call returns.  The banks are shared
+ * like the style targets (stx_engine_create_shared) and stx_set_contents_and_styles clears them: call this
+ * behind it.  A layer with a bank is part of every stx_sc_grad_tile evaluation under the rules of
+ * stx_set_stat_targets: the layer_weight of its tap if the tap list names it, lw = 1 otherwise, and all
+ * layers on one path.  The term follows the blob's statistics term in the loss and in the gradient. */
+int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -298,6 +331,13 @@ int stx_gram_matrix(stx_engine *e, const float *feat, int feat_mem, int channels
  * what stx_set_stat_targets takes, by the launches the term itself runs on a tile's blob. */
 int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channels, int hw,
                       float *mean_out, float *sd_out, int out_mem);
+
+/* The NNFM bank of a feature map [channels][h][w]: its unit-normalised columns at (y, x) with y % stride == 0
+ * and x % stride == 0, in raster order, as float32 rows [rows][channels], rows = ceil(h / stride) *
+ * ceil(w / stride).  A zero column stays as a zero row.  Banks of several pictures are concatenated by the
+ * caller.  By the pass that prepares a tile's blob for the search. */
+int stx_nnfm_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int stride,
+                  float *bank_out, int out_mem);
 
 /* ------------------------------------------------- full-image ops (device-resident state) */
 /* All pointers in this group are STX_DEVICE memory on the engine's GPU, images are [3][H][W].
@@ -566,6 +606,11 @@ int stx_op_masked_content_terms(stx_engine *e, const float *feat, int channels, 
  * out = {E / 2, sum |S|}; s_out = S. */
 int stx_op_stat_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *MU,
                       const float *SD, float *s_out, double out[2]);
+/* The launches of an NNFM target (stx_set_nnfm_targets) on given arrays (all STX_DEVICE; bank [rows][channels]):
+ * out = {E, sum |S|}; s_out = S [channels][h][w]; index_out = j [h w].  An argument error leaves the outputs
+ * alone: STX_ERR_ARG for a null pointer or rows <= 0, STX_ERR_UNSUPPORTED for channels % 64 != 0. */
+int stx_op_nnfm_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *bank, int rows,
+                      float *s_out, int *index_out, double out[2]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

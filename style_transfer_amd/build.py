@@ -35,6 +35,7 @@ SOURCES = {
     'lap.hip': ['-ffp-contract=off'],
     'stat.hip': ['-ffp-contract=off'],
     'photo.hip': ['-ffp-contract=off'],
+    'nnfm.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'tile_path.cpp': [],

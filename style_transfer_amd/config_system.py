@@ -137,6 +137,20 @@ _EXTENSIONS = [
                                    'scale; with --style-multiscale the layers themselves stay those of the '
                                    "first scale, whose targets are kept (default: the --style-layers' names "
                                    'with weight 1 each; its built-in list when --style-layers is empty)')),
+    (('--nnfm-weight',), dict(metavar='WEIGHT', type=ffloat,
+                              help='nearest-neighbour feature matching factor (ARF, NNST): pulls every feature '
+                                   'vector of the result at the --nnfm-layers towards the most similar feature '
+                                   'vector of the style picture(s), by cosine -- keeps small motifs that the '
+                                   'global statistics average away; read once per scale; 0 or absent: off '
+                                   '(default: 0)')),
+    (('--nnfm-layers',), dict(nargs='+', metavar='LAYER',
+                              help='layers of the nearest-neighbour term as name or name:weight; the weights are '
+                                   'normalised to --nnfm-weight like those of a layer list and read once per '
+                                   'scale; with --style-multiscale the layers themselves stay those of the '
+                                   'first scale, whose banks are kept (default: conv3_1 conv4_1)')),
+    (('--nnfm-stride',), dict(metavar='S', type=int,
+                              help="keeps every S-th row and column of the style picture's feature maps in the "
+                                   'bank of the nearest-neighbour term, an integer >= 1 (default: 1)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -324,6 +338,57 @@ def check_stat_options(args, known_layers=None):
     return names
 
 
+NNFM_LAYERS_DEFAULT = ('conv3_1', 'conv4_1')
+
+
+def nnfm_layer_args(args):
+    """The layer list of the nearest-neighbour term (``name`` or ``name:weight`` each): --nnfm-layers, or
+    conv3_1 conv4_1.  [] when the term is off (no --nnfm-weight, or 0)."""
+    raw = getattr(getattr(args, 'ns', args), 'nnfm_weight', 0)
+    if not (callable(raw) or raw):
+        return []
+    given = getattr(args, 'nnfm_layers', None) or NNFM_LAYERS_DEFAULT
+    return [given] if isinstance(given, str) else list(given)
+
+
+def nnfm_stride(args):
+    """--nnfm-stride as an integer >= 1 (default 1); anything else is a ValueError."""
+    raw = getattr(getattr(args, 'ns', args), 'nnfm_stride', 1)
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or raw < 1:
+        raise ValueError('--nnfm-stride %r: an integer >= 1 is expected' % (raw,))
+    return int(raw)
+
+
+def check_nnfm_options(args, known_layers=None):
+    """--nnfm-weight / --nnfm-layers / --nnfm-stride: refused before any GPU work together with --style-masks
+    (there is one bank and, with masks, one style set per picture), with a malformed entry, with a layer named
+    twice, with weights that are all 0, with a stride below 1 or -- when the network's layers are known -- with
+    a layer it does not have.  Returns the layer names."""
+    items = nnfm_layer_args(args)
+    if not items:
+        return []
+    if getattr(args, 'style_masks', None):
+        raise ValueError('--nnfm-weight cannot be combined with --style-masks: there is one bank of style '
+                         'features, and masks make every style picture a style set of its own')
+    nnfm_stride(args)
+    names, total = [], 0.0
+    for item in items:
+        name, _, weight = str(item).partition(':')
+        try:
+            total += abs(ffloat(weight)) if weight else 1.0
+        except (ValueError, ZeroDivisionError):
+            raise ValueError('--nnfm-layers %s: LAYER or LAYER:weight is expected' % item) from None
+        if not name or name in names:
+            raise ValueError('--nnfm-layers %s: a layer name, given once, is expected' % item)
+        if known_layers is not None and (name not in known_layers or name == 'data'):
+            raise ValueError("--nnfm-layers %s: the network has no layer '%s'" % (item, name))
+        names.append(name)
+    if not total:
+        raise ValueError('--nnfm-layers %s: at least one layer weight must not be 0 (they are normalised '
+                         'to --nnfm-weight)' % ' '.join(map(str, items)))
+    return names
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -351,5 +416,6 @@ def parse_args(state=None, argv=None, config_py=None):
     check_content_mask(args)
     check_lap_pools(args)
     check_stat_options(args)
+    check_nnfm_options(args)
     check_photo_options(args)
     return args

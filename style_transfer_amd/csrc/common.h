@@ -489,6 +489,41 @@ int stat_finish_launch(hipStream_t s, const float *partials, int C, int HW, cons
 int stat_grad_launch(hipStream_t s, const float *feat, int C, int HW, const float *table, float *sgrad,
                      float *abs_partials, int *n_parts);
 
+// nnfm.hip: the nearest-neighbour feature matching term of a blob [C][n] against a bank [M][C] of unit rows
+// (include/stx.h, stx_set_nnfm_targets).  The search multiplies kNnfmQ query columns by kNnfmB bank rows per
+// workgroup, kNnfmK channels per LDS stage; with few query blocks the bank is cut into slices.
+constexpr int kNnfmQ = 128, kNnfmB = 128, kNnfmK = 32, kNnfmMaxSlices = 64;
+struct NnfmPlan {
+    int q_blocks, b_blocks, slices, blocks_per_slice;
+};
+NnfmPlan nnfm_plan(int n, int M);
+// floats that hold the fp16 hi / lo pieces of `rows` rows of C channels ([rows][C] hi, then [rows][C] lo)
+size_t nnfm_pieces_floats(int rows, int C);
+// floats of the caller's that one term takes, and their division (from the next 256-byte boundary)
+size_t nnfm_scratch_floats(int C, int n, int M);
+struct NnfmScratch {
+    unsigned short *xhi, *xlo;      // pieces of x_i 2^13, [n][C] each
+    float *inv_r;                   // [n]
+    int *idx;                       // [n]
+    float *part_score;              // [slices][n], or null with one slice
+    int *part_idx;
+    float *partials;                // ceil(n / 64) of (2/n) sum (1 - c_i), then as many of sum |S|
+};
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M);
+// One pass over feat [C][h][w]: per picked column (y % stride == 0 and x % stride == 0, raster order) 1 / |f|
+// (0 for a zero column) into inv_r, the pieces of f / |f| 2^13 into hi / lo, f / |f| as float32 rows into
+// rows_out -- each output optional (hi and lo together).
+int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, float *inv_r,
+                        unsigned short *hi, unsigned short *lo, float *rows_out);
+// the pieces of bank 2^13, bank [M][C] given as rows
+int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsigned short *hi, unsigned short *lo);
+// idx_out[i] = argmax_j x_i . b_j, the lowest j among equal scores
+int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigned short *bhi, const unsigned short *blo,
+                       int M, int C, int *idx_out);
+// sgrad = S [C][n]; *n_parts partials of E, then as many of sum |S|
+int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int n, const float *inv_r, const float *bank, int M,
+                     const int *idx, float *sgrad, float *partials, int *n_parts);
+
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,
                     int th, int tw, float *tile);

@@ -420,8 +420,12 @@ void stx_engine_destroy(stx_engine *e) {
         for (auto &m : e->sh->masks) m.map->release();
         for (auto &t : e->sh->stats) t.ms->release();
         for (auto &m : e->sh->cmasks) m.map->release();
+        for (auto &t : e->sh->nnfms) {
+            t.bank->release();
+            t.pieces->release();
+        }
     }
-    DevBuf *bufs[] = {&e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
+    DevBuf *bufs[] = {&e->nnfm_scratch, &e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
@@ -618,11 +622,16 @@ int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *content
     for (auto &m : e->sh->masks) m.map->release();
     for (auto &t : e->sh->stats) t.ms->release();
     for (auto &m : e->sh->cmasks) m.map->release();
+    for (auto &t : e->sh->nnfms) {
+        t.bank->release();
+        t.pieces->release();
+    }
     e->sh->contents.clear();
     e->sh->styles.clear();
     e->sh->masks.clear();
     e->sh->stats.clear();
     e->sh->cmasks.clear();
+    e->sh->nnfms.clear();
     e->sh->n_contents = e->sh->n_styles = 0;
     bool host_src = false;
     for (int i = 0; i < n_contents; ++i) {
@@ -829,6 +838,66 @@ int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
             set_error("stx_set_stat_targets: %s", hipGetErrorString(err));
             rc = STX_ERR_HIP;
         }
+    }
+    if (rc != STX_OK) clear();
+    return rc;
+}
+
+int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    std::lock_guard<std::mutex> lock(e->sh->mutex);
+    // the previous banks may still be in use by queued kernels (of any engine that shares them)
+    STX_TRY(quiesce_members(e));
+    auto clear = [&]() {
+        for (auto &t : e->sh->nnfms) {
+            t.bank->release();
+            t.pieces->release();
+        }
+        e->sh->nnfms.clear();
+    };
+    clear();
+    int rc = STX_OK;
+    for (int i = 0; i < n && rc == STX_OK; ++i) {
+        const stx_nnfm_target &nt = targets[i];
+        const int blob = e->find_blob(nt.layer);
+        bool twice = false;
+        for (const NnfmTarget &t : e->sh->nnfms) twice |= t.blob == blob;
+        if (blob <= 0 || !nt.bank || nt.rows <= 0 || twice) {
+            set_error("NNFM target %d: bad layer '%s' (unknown, the input, or given twice) or no bank", i,
+                      nt.layer ? nt.layer : "(null)");
+            rc = STX_ERR_ARG;
+            break;
+        }
+        if (nt.channels != e->blobs[blob].channels) {
+            set_error("NNFM target %d: layer %s has %d channels, not %d", i, nt.layer, e->blobs[blob].channels,
+                      nt.channels);
+            rc = STX_ERR_ARG;
+            break;
+        }
+        if (nt.channels % 64 != 0 || nt.rows >= (1ll << 31) / nt.channels) {
+            set_error("NNFM target %d: %d rows of %d channels (a multiple of 64 and rows x channels below 2^31 "
+                      "are expected)", i, nt.rows, nt.channels);
+            rc = STX_ERR_UNSUPPORTED;
+            break;
+        }
+        NnfmTarget t{blob, nt.channels, nt.rows, nt.weight, std::unique_ptr<DevBuf>(new DevBuf),
+                     std::unique_ptr<DevBuf>(new DevBuf)};
+        const size_t bytes = (size_t)t.rows * t.C * sizeof(float);
+        if ((rc = t.bank->ensure(bytes)) == STX_OK) rc = t.pieces->ensure(nnfm_pieces_floats(t.rows, t.C) * sizeof(float));
+        if (rc == STX_OK) rc = copy_in(e, t.bank->ptr, nt.bank, nt.mem, bytes);
+        // the fp16 pieces the search reads, once
+        if (rc == STX_OK)
+            rc = nnfm_split_rows_launch(e->stream, t.bank->f(), t.rows, t.C, static_cast<unsigned short *>(t.pieces->ptr),
+                                        static_cast<unsigned short *>(t.pieces->ptr) + (size_t)t.rows * t.C);
+        e->sh->nnfms.push_back(std::move(t));
+    }
+    // (a source on either side may be reused or freed right away, and the sharing engines read the banks from
+    // their own streams: the copies and the split have finished when this returns)
+    const hipError_t err = hipStreamSynchronize(e->stream);
+    if (rc == STX_OK && err != hipSuccess) {
+        set_error("stx_set_nnfm_targets: %s", hipGetErrorString(err));
+        rc = STX_ERR_HIP;
     }
     if (rc != STX_OK) clear();
     return rc;

@@ -111,6 +111,16 @@ struct StatTarget {
     std::unique_ptr<DevBuf> ms;
 };
 
+// The bank of one tapped blob's nearest-neighbour term (stx_set_nnfm_targets): float32 rows [rows][C] on the
+// device and, built once when the targets are set, their fp16 hi / lo pieces for the search (nnfm.hip).
+struct NnfmTarget {
+    int blob, C, rows;
+    double weight;
+    std::unique_ptr<DevBuf> bank, pieces;
+    const unsigned short *hi() const { return static_cast<const unsigned short *>(pieces->ptr); }
+    const unsigned short *lo() const { return hi() + (size_t)rows * C; }
+};
+
 struct LossTerm {
     size_t scalar_index;   // float in the host mirror of the scalar buffer
     double coef;
@@ -133,6 +143,7 @@ struct SharedState {
     std::vector<StyleMask> masks;      // (cleared with the targets)
     std::vector<StatTarget> stats;     // (cleared with the targets)
     std::vector<ContentMask> cmasks;   // (cleared with the targets)
+    std::vector<NnfmTarget> nnfms;     // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -182,6 +193,7 @@ struct stx_engine {
     DevBuf term_scratch;               // per term of a tile call: what its launches leave for the sum jobs (TilePlan)
     DevBuf masked_feat, masked_target; // a masked style term's F . m and a Gs (style_mask.hip), one term at a time
     DevBuf stat_scratch;               // stx_feature_stats / stx_op_stat_terms: partials, table, outputs
+    DevBuf nnfm_scratch;               // stx_nnfm_bank / stx_op_nnfm_terms: rows, bank pieces, the term's scratch
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
     // reductions), each with a pinned host mirror, and the losses that will be published from
     // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
@@ -327,7 +339,7 @@ struct TileCall {
     int grad_mem;
 };
 
-enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Dream };
+enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, Dream };
 constexpr size_t kNoSlot = ~(size_t)0;
 constexpr size_t kResidualScalars = 2 + 2 * 1024;   // content_sums_launch: two sums and their partials
 
@@ -341,13 +353,14 @@ struct PlannedTerm {
     size_t scalars;                  // floats of the scalar arena
     size_t scratch_off, scratch_len; // its region of the engine's term_scratch, in floats
     size_t sgrad_off;                // its blob S in the tap's gradient buffer (stx_engine::sgrad), in floats, or kNoSlot
+    const NnfmTarget *nnfm = nullptr; // TermKind::Nnfm: the bank with its pieces
 };
 
 struct TilePlan {
     std::vector<Tap> order;         // taps, deepest first
     std::vector<char> needed;       // blobs on the path
     std::vector<int> tap_of;        // blob -> index into order, or -1
-    std::deque<stx_tap> extra;      // taps of the layers that only a statistics target names (lw = 1);
+    std::deque<stx_tap> extra;      // taps of the layers that only a statistics or NNFM target names (lw = 1);
                                     // `order` points into it: a deque's elements stay where they are
     // The final sums of the loss terms are collected and run as ONE launch behind the forward pass
     // (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did); what they add up must outlive the term's
@@ -355,7 +368,7 @@ struct TilePlan {
     bool sums_late;
     bool interleave;                // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
     // The terms in queueing order -- shallowest tap first; per tap the content targets in sh->contents order,
-    // the style targets in sh->styles order, the statistics term, Deep-Dream -- which is the order of
+    // the style targets in sh->styles order, the statistics term, the NNFM term, Deep-Dream -- which is the order of
     // PendingLoss::terms: the host adds the loss up in it.
     std::vector<PlannedTerm> terms;
     std::vector<size_t> first_term;     // per tap: its first record
@@ -407,6 +420,13 @@ int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *fe
 int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *MU,
                       const float *SD, float *sgrad, float *sc, const std::string &name, float *stat_scratch,
                       std::vector<SumJob> *defer);
+// The nearest-neighbour term of a blob (nnfm.hip): prepare -> search (-> merge) -> S into sgrad.
+// sc[2] = {E, sum |S|}, both from partials whose final sums join `defer` or are launched here.  scratch:
+// nnfm_scratch_floats(C, h * w, rows) floats that outlive the call like term_scratch.  idx_out (or null): the
+// winning rows [h * w].
+int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *bank,
+                      const unsigned short *bank_hi, const unsigned short *bank_lo, int rows, float *sgrad,
+                      int *idx_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

@@ -1,0 +1,412 @@
+// The nearest-neighbour feature matching term (NNFM; ARF, NNST): every column f_i of a tapped blob F [C][n]
+// is pulled towards the most similar row of a fixed bank B [M][C] of unit (or zero) rows --
+//   r_i = |f_i|,  x_i = f_i / r_i,  j_i = argmax_j x_i . b_j (lowest j among equals),  c_i = x_i . b_{j_i}
+//   E   = (2/n) sum_i (1 - c_i)
+//   S_i = -(b_{j_i} - c_i x_i) / r_i                                   ( = n d(E/2)/d f_i with j_i held fixed )
+// Four launches, no atomics, every sum in a fixed order:
+//   1. nnfm_prepare_kernel   one pass over F: r_i in double, 1/r_i as a float, x_i 2^13 as fp16 hi / lo pieces
+//                            (f16x2.h) transposed to [n][C].  With a stride and a float32 output it builds a
+//                            bank from a feature map instead (stx_nnfm_bank).  nnfm_split_rows_kernel makes the
+//                            pieces of a bank that is given as rows.
+//   2. nnfm_search_kernel    the n x M x C product fused with its row-wise argmax: the score matrix never
+//                            exists in memory.  A workgroup owns kNnfmQ query columns and walks kNnfmB-row
+//                            blocks of (its slice of) the bank; both operands' pieces are staged through LDS
+//                            kNnfmK channels at a time, the next stage's loads in flight while the current
+//                            one multiplies (v_mfma_f32_32x32x16_f16, three products, smallest first).  The
+//                            bank is the A operand and the queries the B operand, so a lane's 16 accumulators
+//                            are 16 bank rows of ONE query: the running (score, index) is lane-local.
+//                            Unit vectors need no tracked maximum: both sides are scaled by 2^13.
+//   3. nnfm_merge_kernel     only when the bank was cut into slices (few query blocks): the slices'
+//                            (score, index) pairs by the same rule, "greater score, else lower index".
+//   4. nnfm_grad_kernel      per column: gathers the float32 row j_i, recomputes c_i with float32 fma in
+//                            channel order (NOT the search's score: E and S are functions of (F, B, j)),
+//                            writes S in [C][n] layout and leaves the partials of sum (1 - c_i) and sum |S|.
+
+#include <algorithm>
+#include <climits>
+
+#include "common.h"
+#include "f16x2.h"
+
+namespace stx {
+
+namespace {
+
+constexpr float kNnfmScale = 8192.f;        // 2^13: |x_i| = |b_j| = 1, so every piece fits fp16 with room
+constexpr int kLdsRow = 2 * kNnfmK + 16;    // bytes of a staged row: 64 of data + 16 of padding (conflict-free b128 reads)
+
+// ------------------------------------------------------------------------------------------- prepare
+// A workgroup owns 64 output columns: output column o is the pixel (oy stride, ox stride) of the h x w map,
+// o = oy ow + ox in raster order.
+__global__ __launch_bounds__(256) void nnfm_prepare_kernel(const float *__restrict__ F, int C, int h, int w,
+                                                           int stride, int ow, int n_out,
+                                                           float *__restrict__ inv_r, _Float16 *__restrict__ hi,
+                                                           _Float16 *__restrict__ lo, float *__restrict__ rows_out) {
+    __shared__ double red[4][64];
+    __shared__ float sinv[64];
+    __shared__ float tile[64][65];
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const size_t HW = (size_t)h * w;
+    const int o = min(blockIdx.x * 64 + col, n_out - 1);        // (columns past the end re-read the last one)
+    const size_t src = (size_t)(o / ow) * stride * w + (size_t)(o % ow) * stride;
+    double acc = 0.0;
+    for (int c = g; c < C; c += 4) {
+        const double v = (double)F[(size_t)c * HW + src];
+        acc += v * v;
+    }
+    red[g][col] = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const double ss = ((red[0][col] + red[1][col]) + red[2][col]) + red[3][col];
+        const float inv = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;
+        sinv[col] = inv;
+        if (inv_r && blockIdx.x * 64 + col < n_out) inv_r[o] = inv;
+    }
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        __syncthreads();        // (sinv is written; the tile of the round before is read)
+        for (int cc = g; cc < 64; cc += 4) tile[cc][col] = F[(size_t)(c0 + cc) * HW + src];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int item = threadIdx.x + 256 * u, col2 = item >> 3, oct = item & 7;
+            const int o2 = blockIdx.x * 64 + col2;
+            if (o2 >= n_out) continue;
+            float x[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = tile[oct * 8 + j][col2];
+            const float inv = sinv[col2];
+            const size_t at = (size_t)o2 * C + c0 + oct * 8;
+            if (hi) {
+                f16x8h ph, pl;
+                split2_f16(x, inv * kNnfmScale, ph, pl);
+                *reinterpret_cast<f16x8h *>(hi + at) = ph;
+                *reinterpret_cast<f16x8h *>(lo + at) = pl;
+            }
+            if (rows_out) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) rows_out[at + j] = x[j] * inv;
+            }
+        }
+    }
+}
+
+// The pieces of a bank given as float32 rows [M][C]: eight channels of one row per thread.
+__global__ __launch_bounds__(256) void nnfm_split_rows_kernel(const float *__restrict__ bank, size_t octets, int vec,
+                                                              _Float16 *__restrict__ hi, _Float16 *__restrict__ lo) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= octets) return;
+    float x[8];
+    if (vec) {
+        const float4 a = reinterpret_cast<const float4 *>(bank)[2 * t], b = reinterpret_cast<const float4 *>(bank)[2 * t + 1];
+        x[0] = a.x, x[1] = a.y, x[2] = a.z, x[3] = a.w, x[4] = b.x, x[5] = b.y, x[6] = b.z, x[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = bank[8 * t + j];
+    }
+    f16x8h ph, pl;
+    split2_f16(x, kNnfmScale, ph, pl);
+    reinterpret_cast<f16x8h *>(hi)[t] = ph;
+    reinterpret_cast<f16x8h *>(lo)[t] = pl;
+}
+
+// -------------------------------------------------------------------------------------------- search
+// "greater score, else lower index": associative and commutative, so no merge order can change the result
+__device__ __forceinline__ void take_better(float s, int j, float &best_s, int &best_j) {
+    if (s > best_s || (s == best_s && j < best_j)) {
+        best_s = s;
+        best_j = j;
+    }
+}
+
+typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
+
+// grid (query blocks, slices).  One slice: idx_out [n].  Several: part_score / part_idx [slices][n].
+__global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__restrict__ xhi, const _Float16 *__restrict__ xlo,
+                                                          int n, const _Float16 *__restrict__ bhi,
+                                                          const _Float16 *__restrict__ blo, int M, int C, int b_blocks,
+                                                          int blocks_per_slice, int *__restrict__ idx_out,
+                                                          float *__restrict__ part_score, int *__restrict__ part_idx) {
+    // [X hi | X lo | B hi | B lo][row][kNnfmK halves + padding]; reused for the workgroup's final merge
+    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 128 * kLdsRow];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wq = wave & 1, wb = wave >> 1;        // the wave's 64 queries x 64 bank rows of the 128 x 128 block
+    const int r = lane & 31, half = lane >> 5;
+    const int q0 = blockIdx.x * kNnfmQ;
+    const int bb0 = blockIdx.y * blocks_per_slice, bb1 = min(bb0 + blocks_per_slice, b_blocks);
+    const int KC = C / kNnfmK, T = (bb1 - bb0) * KC;
+
+    // what this thread stages: two 16-byte chunks of each of the four arrays
+    const _Float16 *const arr[4] = {xhi, xlo, bhi, blo};
+    u32x4n pre[4][2];
+    const auto prefetch = [&](int t) {
+        const int bb = bb0 + t / KC, k0 = (t % KC) * kNnfmK;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
+            const size_t q = (size_t)min(q0 + row, n - 1), j = (size_t)min(bb * kNnfmB + row, M - 1);    // padding re-reads the last row
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+                pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + (a < 2 ? q : j) * C + k0 + ch * 8);
+        }
+    };
+    const auto stage = [&]() {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+                *reinterpret_cast<u32x4n *>(lds + (a * 128 + row) * kLdsRow + ch * 16) = pre[a][u];
+        }
+    };
+    const auto frag = [&](int a, int row, int ks) {
+        return *reinterpret_cast<const f16x8h *>(lds + (a * 128 + row) * kLdsRow + ks * 32 + half * 16);
+    };
+
+    f32x16h acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[i][k][v] = 0.f;
+    float best_s[2] = {-INFINITY, -INFINITY};
+    int best_j[2] = {INT_MAX, INT_MAX};
+
+    prefetch(0);
+    for (int t = 0; t < T; ++t) {
+        __syncthreads();        // every wave has read the stage before
+        stage();
+        __syncthreads();
+        if (t + 1 < T) prefetch(t + 1);
+#pragma unroll
+        for (int ks = 0; ks < kNnfmK / 16; ++ks) {
+            f16x8h a_hi[2], a_lo[2], b_hi[2], b_lo[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                b_hi[i] = frag(0, 64 * wq + 32 * i + r, ks);
+                b_lo[i] = frag(1, 64 * wq + 32 * i + r, ks);
+                a_hi[i] = frag(2, 64 * wb + 32 * i + r, ks);
+                a_lo[i] = frag(3, 64 * wb + 32 * i + r, ks);
+            }
+#pragma unroll
+            for (int tq = 0; tq < 2; ++tq)
+#pragma unroll
+                for (int tb = 0; tb < 2; ++tb)
+                    acc[tq][tb] = mfma_split3(a_hi[tb], a_lo[tb], b_hi[tq], b_lo[tq], acc[tq][tb]);
+        }
+        if (t % KC == KC - 1) {     // the block's scores are complete: D[row = bank][col = query]
+            const int j0 = (bb0 + t / KC) * kNnfmB + 64 * wb + 4 * half;
+#pragma unroll
+            for (int tq = 0; tq < 2; ++tq)
+#pragma unroll
+                for (int tb = 0; tb < 2; ++tb)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        const int j = j0 + 32 * tb + (v & 3) + 8 * (v >> 2);
+                        if (j < M) take_better(acc[tq][tb][v], j, best_s[tq], best_j[tq]);     // padding never wins
+                        acc[tq][tb][v] = 0.f;
+                    }
+        }
+    }
+    // a query's four candidates: two lane halves x the two waves that split the bank rows
+    __syncthreads();
+    float *const cand_s = reinterpret_cast<float *>(lds);
+    int *const cand_j = reinterpret_cast<int *>(lds + kNnfmQ * 4 * sizeof(float));
+#pragma unroll
+    for (int tq = 0; tq < 2; ++tq) {
+        const int q = 64 * wq + 32 * tq + r;
+        cand_s[q * 4 + wb * 2 + half] = best_s[tq];
+        cand_j[q * 4 + wb * 2 + half] = best_j[tq];
+    }
+    __syncthreads();
+    if (threadIdx.x < kNnfmQ && q0 + (int)threadIdx.x < n) {
+        float s = cand_s[threadIdx.x * 4];
+        int j = cand_j[threadIdx.x * 4];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) take_better(cand_s[threadIdx.x * 4 + k], cand_j[threadIdx.x * 4 + k], s, j);
+        if (j == INT_MAX) j = 0;        // (scores that are not numbers: nothing was taken)
+        if (gridDim.y == 1) {
+            idx_out[q0 + threadIdx.x] = j;
+        } else {
+            part_score[(size_t)blockIdx.y * n + q0 + threadIdx.x] = s;
+            part_idx[(size_t)blockIdx.y * n + q0 + threadIdx.x] = j;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void nnfm_merge_kernel(const float *__restrict__ part_score,
+                                                         const int *__restrict__ part_idx, int n, int slices,
+                                                         int *__restrict__ idx_out) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    float s = part_score[q];
+    int j = part_idx[q];
+    for (int k = 1; k < slices; ++k) take_better(part_score[(size_t)k * n + q], part_idx[(size_t)k * n + q], s, j);
+    idx_out[q] = j;
+}
+
+// ---------------------------------------------------------------------------------------------- grad
+// One column per lane, one wave per workgroup.  partials [0 .. blocks) = (2/n) sum (1 - c_i),
+// [blocks .. 2 blocks) = sum |S| of the workgroup's columns.
+__global__ __launch_bounds__(64) void nnfm_grad_kernel(const float *__restrict__ F, int C, int n,
+                                                       const float *__restrict__ inv_r, const float *__restrict__ bank,
+                                                       int M, int vec, const int *__restrict__ idx, float *__restrict__ S,
+                                                       float *__restrict__ partials) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < n;
+    const int ii = valid ? i : n - 1;
+    const unsigned ju = (unsigned)idx[ii];
+    const float *__restrict__ row = bank + (size_t)(ju < (unsigned)M ? ju : 0u) * C;
+    const float inv = inv_r[ii];
+    const float *__restrict__ f = F + ii;
+    float c = 0.f;
+    if (vec) {
+#pragma unroll 4
+        for (int ch = 0; ch < C; ch += 4) {
+            const float4 b = *reinterpret_cast<const float4 *>(row + ch);
+            c = fmaf(f[(size_t)ch * n] * inv, b.x, c);
+            c = fmaf(f[(size_t)(ch + 1) * n] * inv, b.y, c);
+            c = fmaf(f[(size_t)(ch + 2) * n] * inv, b.z, c);
+            c = fmaf(f[(size_t)(ch + 3) * n] * inv, b.w, c);
+        }
+    } else {
+#pragma unroll 4
+        for (int ch = 0; ch < C; ++ch) c = fmaf(f[(size_t)ch * n] * inv, row[ch], c);
+    }
+    float sum_abs = 0.f;
+    if (valid) {
+        float *__restrict__ out = S + i;
+#pragma unroll 4
+        for (int ch = 0; ch < C; ++ch) {
+            const float x = f[(size_t)ch * n] * inv;
+            const float s = -((row[ch] - c * x) * inv);
+            out[(size_t)ch * n] = s;
+            sum_abs += fabsf(s);
+        }
+    }
+    const float one_minus = wave_sum_f(valid ? 1.f - c : 0.f);
+    sum_abs = wave_sum_f(sum_abs);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = one_minus * (2.f / (float)n);
+        partials[gridDim.x + blockIdx.x] = sum_abs;
+    }
+}
+
+int check_shape(const char *who, int C, long long n, long long M) {
+    if (C <= 0 || n <= 0 || M <= 0) {
+        set_error("%s: %d channels, %lld columns, %lld bank rows", who, C, n, M);
+        return STX_ERR_ARG;
+    }
+    if (C % 64 != 0) {
+        set_error("%s: the channel count %d is not a multiple of 64", who, C);
+        return STX_ERR_UNSUPPORTED;
+    }
+    if (n >= (1ll << 31) / C || M >= (1ll << 31) / C) {
+        set_error("%s: %lld columns against %lld bank rows of %d channels exceed 32-bit offsets", who, n, M, C);
+        return STX_ERR_UNSUPPORTED;
+    }
+    return STX_OK;
+}
+
+size_t round64(size_t floats) { return (floats + 63) & ~(size_t)63; }
+
+}  // namespace
+
+NnfmPlan nnfm_plan(int n, int M) {
+    NnfmPlan p;
+    p.q_blocks = ceil_div(n, kNnfmQ);
+    p.b_blocks = ceil_div(M, kNnfmB);
+    // few query blocks (a small tile's deep layers): cut the bank across workgroups, about two per CU
+    int slices = 1;
+    if (p.q_blocks < 256) slices = std::min(p.b_blocks, std::min(kNnfmMaxSlices, ceil_div(512, p.q_blocks)));
+    p.blocks_per_slice = ceil_div(p.b_blocks, slices);
+    p.slices = ceil_div(p.b_blocks, p.blocks_per_slice);
+    return p;
+}
+
+size_t nnfm_pieces_floats(int rows, int C) { return round64((size_t)rows * C); }
+
+size_t nnfm_scratch_floats(int C, int n, int M) {
+    const NnfmPlan p = nnfm_plan(n, M);
+    return 64 + nnfm_pieces_floats(n, C) + 2 * round64(n) + (p.slices > 1 ? 2 * round64((size_t)p.slices * n) : 0) +
+           round64(2 * (size_t)ceil_div(n, 64));
+}
+
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M) {
+    const NnfmPlan p = nnfm_plan(n, M);
+    NnfmScratch s;
+    float *at = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+    s.xhi = reinterpret_cast<unsigned short *>(at);
+    s.xlo = s.xhi + (size_t)n * C;
+    at += nnfm_pieces_floats(n, C);
+    s.inv_r = at;
+    at += round64(n);
+    s.idx = reinterpret_cast<int *>(at);
+    at += round64(n);
+    s.part_score = nullptr;
+    s.part_idx = nullptr;
+    if (p.slices > 1) {
+        s.part_score = at;
+        at += round64((size_t)p.slices * n);
+        s.part_idx = reinterpret_cast<int *>(at);
+        at += round64((size_t)p.slices * n);
+    }
+    s.partials = at;
+    return s;
+}
+
+int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, float *inv_r,
+                        unsigned short *hi, unsigned short *lo, float *rows_out) {
+    if (stride < 1 || h <= 0 || w <= 0) {
+        set_error("nnfm_prepare_launch: a %dx%d map with stride %d", h, w, stride);
+        return STX_ERR_ARG;
+    }
+    const int oh = ceil_div(h, stride), ow = ceil_div(w, stride);
+    STX_TRY(check_shape("nnfm_prepare_launch", C, (long long)h * w, (long long)oh * ow));
+    const int n_out = oh * ow;
+    nnfm_prepare_kernel<<<ceil_div(n_out, 64), 256, 0, s>>>(feat, C, h, w, stride, ow, n_out, inv_r,
+                                                           reinterpret_cast<_Float16 *>(hi),
+                                                           reinterpret_cast<_Float16 *>(lo), rows_out);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsigned short *hi, unsigned short *lo) {
+    STX_TRY(check_shape("nnfm_split_rows_launch", C, 1, M));
+    const size_t octets = (size_t)M * C / 8;
+    const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
+    nnfm_split_rows_kernel<<<(unsigned)((octets + 255) / 256), 256, 0, s>>>(bank, octets, vec,
+                                                                            reinterpret_cast<_Float16 *>(hi),
+                                                                            reinterpret_cast<_Float16 *>(lo));
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigned short *bhi, const unsigned short *blo,
+                       int M, int C, int *idx_out) {
+    STX_TRY(check_shape("nnfm_search_launch", C, n, M));
+    const NnfmPlan p = nnfm_plan(n, M);
+    nnfm_search_kernel<<<dim3(p.q_blocks, p.slices), 256, 0, s>>>(
+        reinterpret_cast<const _Float16 *>(x.xhi), reinterpret_cast<const _Float16 *>(x.xlo), n,
+        reinterpret_cast<const _Float16 *>(bhi), reinterpret_cast<const _Float16 *>(blo), M, C, p.b_blocks,
+        p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+    STX_CHECK_LAUNCH();
+    if (p.slices > 1) {
+        nnfm_merge_kernel<<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
+        STX_CHECK_LAUNCH();
+    }
+    return STX_OK;
+}
+
+int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int n, const float *inv_r, const float *bank, int M,
+                     const int *idx, float *sgrad, float *partials, int *n_parts) {
+    STX_TRY(check_shape("nnfm_grad_launch", C, n, M));
+    const int blocks = ceil_div(n, 64);
+    const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
+    nnfm_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, n, inv_r, bank, M, vec, idx, sgrad, partials);
+    STX_CHECK_LAUNCH();
+    *n_parts = blocks;
+    return STX_OK;
+}
+
+}  // namespace stx

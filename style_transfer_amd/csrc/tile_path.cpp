@@ -419,8 +419,9 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
     const auto tapped = [&](int blob) {
         return std::any_of(order.begin(), order.end(), [=](const Tap &o) { return o.blob == blob; });
     };
-    const auto has_statistics = [&](int blob) {
-        return std::any_of(e->sh->stats.begin(), e->sh->stats.end(), [=](const StatTarget &t) { return t.blob == blob; });
+    const auto has_statistics = [&](int blob) {     // ... or an NNFM bank: a target that makes the layer part of the call
+        return std::any_of(e->sh->stats.begin(), e->sh->stats.end(), [=](const StatTarget &t) { return t.blob == blob; }) ||
+               std::any_of(e->sh->nnfms.begin(), e->sh->nnfms.end(), [=](const NnfmTarget &t) { return t.blob == blob; });
     };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
@@ -443,6 +444,13 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
         t.layer_weight = 1.0;
         plan.extra.push_back(t);
         order.push_back(Tap{st.blob, &plan.extra.back()});
+    }
+    for (const NnfmTarget &nt : e->sh->nnfms) {     // ... and a layer with an NNFM bank
+        if (tapped(nt.blob)) continue;
+        stx_tap t{};
+        t.layer_weight = 1.0;
+        plan.extra.push_back(t);
+        order.push_back(Tap{nt.blob, &plan.extra.back()});
     }
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");
@@ -781,6 +789,30 @@ int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channe
     STX_TRY(stat_finish_launch(e->stream, e->stat_scratch.f(), channels, hw, nullptr, nullptr, nullptr, nullptr, mu, sd));
     STX_TRY(copy_out(e, mean_out, out_mem, mu, (size_t)channels * sizeof(float)));
     STX_TRY(copy_out(e, sd_out, out_mem, sd, (size_t)channels * sizeof(float)));
+    if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_nnfm_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int stride,
+                  float *bank_out, int out_mem) {
+    if (!e || !feat || !bank_out || channels <= 0 || h <= 0 || w <= 0 || stride < 1) return STX_ERR_ARG;
+    STX_TRY(e->set_device());
+    const size_t in_bytes = (size_t)channels * h * w * sizeof(float);
+    const size_t out_bytes = (size_t)ceil_div(h, stride) * ceil_div(w, stride) * channels * sizeof(float);
+    const float *src = feat;
+    if (feat_mem == STX_HOST) {
+        STX_TRY(e->upload.ensure(in_bytes));
+        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, in_bytes));
+        src = e->upload.f();
+    }
+    // the pass that prepares a tile's blob for the search (nnfm.hip), with the float32 rows as its output
+    float *dst = bank_out;
+    if (out_mem == STX_HOST) {
+        STX_TRY(e->nnfm_scratch.ensure(out_bytes));
+        dst = e->nnfm_scratch.f();
+    }
+    STX_TRY(nnfm_prepare_launch(e->stream, src, channels, h, w, stride, nullptr, nullptr, nullptr, dst));
+    if (out_mem == STX_HOST) STX_TRY(copy_out(e, bank_out, STX_HOST, dst, out_bytes));
     if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
     return STX_OK;
 }

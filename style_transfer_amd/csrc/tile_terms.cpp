@@ -155,6 +155,32 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
     return STX_OK;
 }
 
+// The nearest-neighbour term of one tapped blob (nnfm.hip): 1 / |f_i| and the pieces of the unit columns, the
+// search over the bank (with the slices' merge when the bank was cut), S with the partials of E and sum |S|.
+int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *bank,
+                      const unsigned short *bank_hi, const unsigned short *bank_lo, int rows, float *sgrad,
+                      int *idx_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer) {
+    const int n = h * w;
+    const NnfmScratch x = nnfm_carve(scratch, C, n, rows);
+    const NnfmPlan plan = nnfm_plan(n, rows);
+    int *const idx = idx_out ? idx_out : x.idx;
+    {
+        ProfScope scope(e, "nnfm prepare " + name, 0.0, stream);
+        STX_TRY(nnfm_prepare_launch(stream, feat, C, h, w, 1, x.inv_r, x.xhi, x.xlo, nullptr));
+    }
+    {
+        ProfScope scope(e, "nnfm search " + name + " x" + std::to_string(plan.slices), 6.0 * n * (double)rows * C, stream);
+        STX_TRY(nnfm_search_launch(stream, x, n, bank_hi, bank_lo, rows, C, idx));
+    }
+    ProfScope scope(e, "nnfm grad " + name, 0.0, stream);
+    int n_parts = 0;
+    STX_TRY(nnfm_grad_launch(stream, feat, C, n, x.inv_r, bank, rows, idx, sgrad, x.partials, &n_parts));
+    if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
+    defer->push_back(SumJob{x.partials, n_parts, sc});
+    defer->push_back(SumJob{x.partials + n_parts, n_parts, sc + 1});
+    return STX_OK;
+}
+
 // A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
 // S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
 int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
@@ -173,6 +199,13 @@ int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *
 // The mean / std target of `blob` (stx_set_stat_targets), or null.
 static const StatTarget *stat_target_of(const stx_engine *e, int blob) {
     for (const StatTarget &t : e->sh->stats)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
+
+// The NNFM bank of `blob` (stx_set_nnfm_targets), or null.
+static const NnfmTarget *nnfm_target_of(const stx_engine *e, int blob) {
+    for (const NnfmTarget &t : e->sh->nnfms)
         if (t.blob == blob) return &t;
     return nullptr;
 }
@@ -233,7 +266,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         const double lw = tp.t->layer_weight;
         plan.first_term[k] = plan.terms.size();
         // The tap's gradient buffer: the style slots, then (each group from a 256-byte boundary) the masked
-        // content slots and the statistics slot.
+        // content slots, the statistics slot and the NNFM slot.
         size_t styles_here = 0;
         for (const StyleTarget &st : sh.styles) styles_here += tp.t->is_style && st.blob == tp.blob;
         size_t style_slot = 0, content_slot = align(styles_here * b.count());
@@ -294,9 +327,17 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 style_slot += b.count();
             }
         }
-        if (const StatTarget *st = stat_target_of(e, tp.blob))
+        size_t nnfm_slot = align(content_slot);
+        if (const StatTarget *st = stat_target_of(e, tp.blob)) {
             add(TermKind::Stat, st->ms->f(), nullptr, ContentWindow{}, lw * st->weight, 2,
                 stat_scratch_floats(b.channels, b.h * b.w), align(content_slot));
+            nnfm_slot = align(nnfm_slot + b.count());
+        }
+        if (const NnfmTarget *nt = nnfm_target_of(e, tp.blob)) {
+            add(TermKind::Nnfm, nt->bank->f(), nullptr, ContentWindow{}, lw * nt->weight, 2,
+                nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows), nnfm_slot);
+            plan.terms.back().nnfm = nt;
+        }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
         // weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
         if (tp.t->is_dd)
@@ -349,6 +390,10 @@ int queue_tap_terms(TileRun &run, size_t k) {
         case TermKind::Stat:          // sc[0] = E, sc[1] = sum |S|
             STX_TRY(launch_stat_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.target, t.target + b.channels,
                                       sgrad, sc, b.name, scratch, run.defer()));
+            break;
+        case TermKind::Nnfm:          // sc[0] = E, sc[1] = sum |S|
+            STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.target, t.nnfm->hi(),
+                                      t.nnfm->lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch, run.defer()));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

@@ -207,6 +207,16 @@ def refuse_stat_weight(args):
                                   'ranks; run the single-process tile farm (--devices) instead')
 
 
+def refuse_nnfm_weight(args):
+    """--nnfm-weight with one process per GPU: the banks would have to travel to every rank with the other
+    targets, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
+    raw = getattr(getattr(args, 'ns', args), 'nnfm_weight', 0)
+    if callable(raw) or raw:
+        raise NotImplementedError('--nnfm-weight is not implemented for the one-process-per-GPU layout '
+                                  '(style_transfer_amd.dist): the banks of style features are not broadcast to '
+                                  'the ranks; run the single-process tile farm (--devices) instead')
+
+
 def _wire_device(device, group):
     if torch.device(device).type == 'cuda' and dist.get_backend(group) == 'gloo':
         return torch.device('cpu')          # host-staged debug path, see DistributedTiles
@@ -253,12 +263,13 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks, --content-mask or --stat-weight is refused here (refuse_style_masks,
-    refuse_content_mask, refuse_stat_weight)."""
+    a run with --style-masks, --content-mask, --stat-weight or --nnfm-weight is refused here (refuse_style_masks,
+    refuse_content_mask, refuse_stat_weight, refuse_nnfm_weight)."""
     if args is not None:
         refuse_style_masks(args)
         refuse_content_mask(args)
         refuse_stat_weight(args)
+        refuse_nnfm_weight(args)
     rank = dist.get_rank(group)
     wire = _wire_device(device, group)
     meta = [None]

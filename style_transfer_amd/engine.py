@@ -157,6 +157,7 @@ class TileEngine:
         self._info = {b: net.layer_info(b) for b in net.blob_names()}
         self.n_styles = 0
         self.stat_layers = []       # (of the primary: the layers of the group's statistics targets)
+        self.nnfm_layers = []       # (of the primary: the layers of the group's NNFM banks)
         if weights and share is None:
             for name, (w, b) in weights.items():
                 self.set_weights(name, w, b)
@@ -299,6 +300,7 @@ class TileEngine:
         lib.call('stx_set_contents_and_styles', self.handle, ctargets, n_c, starget, n_s)
         self.n_styles = len(styles)
         self.primary.stat_layers = []           # (the library clears the statistics targets with these)
+        self.primary.nnfm_layers = []           # (... and the NNFM banks)
 
     def set_stat_targets(self, targets, weights=None):
         """targets: {layer: (mean [C], sd [C])} -- what ``feature_stats`` gives for a style picture's
@@ -318,6 +320,51 @@ class TileEngine:
         lib.call('stx_set_stat_targets', self.handle, table, n)
         self.primary.stat_layers = list(targets)
         del keep
+
+    def set_nnfm_targets(self, banks, weights=None):
+        """banks: {layer: B [rows, C]} -- unit rows, what ``nnfm_bank`` gives for a style picture's feature map
+        (banks of several pictures concatenated) -- and weights: {layer: factor} (default 1 each); an empty
+        dict: none (stx_set_nnfm_targets).  The library copies a bank and builds its fp16 pieces once, here.
+        Call it after ``set_contents_and_styles``, which clears the banks.  A layer with a bank is part of
+        every tile evaluation of the group from then on."""
+        keep, n = [], len(banks)
+        table = (lib.NnfmTarget * max(1, n))()
+        for t, (layer, bank) in zip(table, banks.items()):
+            ptr, mem, obj = _as_arg(bank)
+            if len(obj.shape) != 2:
+                raise ValueError('NNFM bank %s: a [rows, C] array is expected' % layer)
+            keep.append(obj)
+            t.layer, t.channels, t.rows, t.bank, t.mem = self._cstr(layer), int(obj.shape[1]), int(obj.shape[0]), ptr, mem
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_nnfm_targets', self.handle, table, n)
+        self.primary.nnfm_layers = list(banks)
+        del keep
+
+    def nnfm_bank(self, feat, stride=1):
+        """The bank of a [C,h,w] feature map as a DeviceArray [rows, C]: its unit-normalised columns at every
+        ``stride``-th row and column, raster order (stx_nnfm_bank).  Nothing travels through the host when
+        ``feat`` is on the device."""
+        ptr, mem, keep = _as_arg(feat)
+        c, h, w = (int(v) for v in keep.shape)
+        rows = -(-h // stride) * -(-w // stride)
+        out = DeviceArray(self, (rows, c))
+        lib.call('stx_nnfm_bank', self.handle, ptr, mem, c, h, w, int(stride), out.ptr, lib.DEVICE)
+        return out
+
+    def concat_rows(self, parts):
+        """One DeviceArray [sum of rows, C] of the DeviceArrays ``parts`` ([rows_k, C] each), in their order,
+        copied on the device; the parts are freed."""
+        if len(parts) == 1:
+            return parts[0]
+        out = DeviceArray(self, (sum(p.shape[0] for p in parts), parts[0].shape[1]))
+        at = 0
+        for p in parts:
+            lib.call('stx_memcpy_async', self.handle, out.ptr + at, lib.DEVICE, p.ptr, lib.DEVICE, p.nbytes)
+            at += p.nbytes
+        self.sync()
+        for p in parts:
+            p.free()
+        return out
 
     def feature_stats(self, feat):
         """(mean [C], sd [C]) of a [C,h,w] feature map, sd = sqrt(population variance + 1e-5), as float32
@@ -413,7 +460,7 @@ class TileEngine:
               dd_layers=(), dd_weight=None):
         # (a layer that only a statistics target names is tapped for nothing: the tap carries its layer weight)
         names = list(dict.fromkeys(list(content_layers) + list(style_layers) + list(dd_layers) +
-                                   list(self.primary.stat_layers)))
+                                   list(self.primary.stat_layers) + list(self.primary.nnfm_layers)))
         taps = (lib.Tap * len(names))()
         for t, name in zip(taps, names):
             t.layer = self._cstr(name)

@@ -24,7 +24,8 @@ from PIL import Image
 
 from . import image_ops, lib
 from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_photo_options,
-                            check_stat_options, ffloat, stat_layer_args)
+                            check_nnfm_options, check_stat_options, ffloat, nnfm_layer_args, nnfm_stride,
+                            stat_layer_args)
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
 
@@ -211,6 +212,13 @@ class StyleTransfer:
         self._stat_on = bool(check_stat_options(args, farm.layers()))
         self.stat_targets = None    # {layer: (mean [C], sd [C])}
         self._stat_weights = None   # {layer: weight} of the scale being optimised
+        # --nnfm-weight / --nnfm-layers / --nnfm-stride (the nearest-neighbour feature matching term; not options
+        # of the reference): per layer one bank of the style pictures' unit feature vectors, built and
+        # concatenated on the master GPU, kept where the Grams are kept; sent to the engines behind the targets.
+        # Without the options nothing here runs.
+        self._nnfm_on = bool(check_nnfm_options(args, farm.layers()))
+        self.nnfm_banks = None      # {layer: DeviceArray [rows, C]}
+        self._nnfm_weights = None   # {layer: weight} of the scale being optimised
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
         # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
@@ -308,8 +316,26 @@ class StyleTransfer:
         self.farm.set_stat_targets({layer: self.stat_targets[layer] for layer in self._stat_weights},
                                    self._stat_weights)
 
+    def _send_nnfm(self):
+        """The banks of the scale's --nnfm-layers to the engines, behind the targets (which clear them).  With
+        --style-multiscale the banks are the first scale's: a layer that a later reading of the list drops
+        gets no term, and one that it adds has no bank and is refused."""
+        if not self._nnfm_weights:
+            return
+        missing = [layer for layer in self._nnfm_weights if layer not in self.nnfm_banks]
+        if missing:
+            raise ValueError('--nnfm-layers %s: no bank was taken there; with --style-multiscale the layers are '
+                             'those of the first scale' % ' '.join(missing))
+        self.farm.set_nnfm_targets({layer: self.nnfm_banks[layer] for layer in self._nnfm_weights},
+                                   self._nnfm_weights)
+
+    def _drop_nnfm(self):
+        for bank in (self.nnfm_banks or {}).values():
+            bank.free()
+        self.nnfm_banks = None
+
     def preprocess_images(self, content_images, style_images, content_layers, style_layers,
-                          roll=None, color_from=None, stat_layers=()):
+                          roll=None, color_from=None, stat_layers=(), nnfm_layers=(), nnfm_stride=1):
         """Targets of one scale: the style Grams, averaged with equal weight over every style
         image and ladder size (with --style-masks: over the ladder sizes of each style image, one
         style set per image), and the tiling-averaged content features
@@ -318,14 +344,18 @@ class StyleTransfer:
         ``color_from`` (--preserve-color match): every style variant is recoloured on the GPU to the
         colour mean and covariance of this picture before its features are taken.  ``stat_layers``
         (--stat-weight): the per-channel mean and sd of the same feature maps at these layers, averaged the
-        same way, into ``self.stat_targets``; the features are taken at the union of both lists, once."""
+        same way, into ``self.stat_targets``.  ``nnfm_layers`` (--nnfm-weight): the banks of the same feature
+        maps at these layers (every ``nnfm_stride``-th row and column), built on the device and concatenated
+        over the variants in this order, into ``self.nnfm_banks``.  The features are taken at the union of the
+        three lists, once."""
         farm, tile = self.farm, self.args.tile_size
         if roll is None:
             print('Preprocessing the style image(s)...')
         if not self.styles:
             total, count = {}, 0
             stat_total = {}
-            feature_layers = list(style_layers) + [l for l in stat_layers if l not in style_layers]
+            feature_layers = list(dict.fromkeys(list(style_layers) + list(stat_layers) + list(nnfm_layers)))
+            bank_parts = {layer: [] for layer in nnfm_layers}
             target = None
             if color_from is not None and style_images:
                 kept = self.engine.to_device(self.pil_to_image(color_from))
@@ -344,6 +374,8 @@ class StyleTransfer:
                         if layer in stat_layers:
                             stats = np.stack(farm.feature_stats(feat))
                             stat_total[layer] = stats if layer not in stat_total else stat_total[layer] + stats
+                        if layer in bank_parts:
+                            bank_parts[layer].append(farm.nnfm_bank(feat, nnfm_stride))
                         if layer not in style_layers:
                             feat.free()
                             continue
@@ -358,6 +390,11 @@ class StyleTransfer:
                 self.styles.append({layer: gram / count for layer, gram in total.items()})
             if stat_layers:
                 self.stat_targets = {layer: tuple(stats / np.float32(count)) for layer, stats in stat_total.items()}
+            if nnfm_layers:
+                self.nnfm_banks = {layer: self.engine.concat_rows(parts) for layer, parts in bank_parts.items()}
+                if roll is None:
+                    print('NNFM bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0])
+                                                         for layer, bank in self.nnfm_banks.items()))
         if roll is None:
             print('Preprocessing the content image(s)...')
         self.contents += [farm.prepare_features_device(self.pil_to_image(image), content_layers,
@@ -457,9 +494,13 @@ class StyleTransfer:
         stat_layers, self._stat_weights = [], None
         if self._stat_on:       # (read once per scale, like the layer lists above)
             stat_layers, self._stat_weights = parse_weights(stat_layer_args(args), args.stat_weight)
+        nnfm_layers, self._nnfm_weights = [], None
+        if self._nnfm_on:       # (read once per scale, like the layer lists above)
+            nnfm_layers, self._nnfm_weights = parse_weights(nnfm_layer_args(args), args.nnfm_weight)
         if not args.style_multiscale:
             self.styles = []
             self.stat_targets = None
+            self._drop_nnfm()
         # --jitter: the content maps are recomputed every iteration from the shifted picture
         # (style_transfer.py:757-763,789-794), only the style targets are fixed per scale
         if self.preserve_color == 'luma':
@@ -489,9 +530,11 @@ class StyleTransfer:
         self.preprocess_images([] if jitter else content_images, style_images,
                                [] if jitter else content_layers, style_layers,
                                color_from=content_images[0] if self.preserve_color == 'match' else None,
-                               stat_layers=stat_layers)
+                               stat_layers=stat_layers, nnfm_layers=nnfm_layers,
+                               nnfm_stride=nnfm_stride(args) if self._nnfm_on else 1)
         self.farm.set_contents_and_styles(self.contents, self.styles)
         self._send_stats()
+        self._send_nnfm()
         if self.style_masks is not None:
             if len(self.styles) != len(self.style_masks):
                 raise ValueError('--style-masks: %d mask(s) for %d style set(s)'
@@ -593,6 +636,7 @@ class StyleTransfer:
                 self.farm.set_contents_and_styles(self.contents, self.styles)
                 self._send_masks(roll=roll)
                 self._send_stats()
+                self._send_nnfm()
                 content_roll = (0, 0)
             sc_args = (roll, content_layers, style_layers, content_weight, style_weight,
                        dd_layers, dd_weight, content_roll)

@@ -1,0 +1,109 @@
+"""Device time of the nearest-neighbour feature matching term (nnfm.hip) on given arrays.
+
+    python tools/bench_nnfm.py [--out profiles/nnfm_times.txt]
+
+stx_op_nnfm_terms at the blob shapes of a 1024^2 tile -- conv3_1 (256 x 256^2) and conv4_1 (512 x 128^2) --
+against the banks of a 512^2 and of a 1024^2 style picture at --nnfm-stride 1 and 2, and at the shapes of a
+256^2 tile (conv3_1 256 x 64^2, conv4_1 512 x 32^2), where the bank is cut into slices.  The engine's
+per-group event timing is on: `prepare` (1 / |f_i| and the fp16 pieces of the unit columns), `search` (the
+n x M x C product with its argmax, and the slices' merge when there is one), `grad` (S with the partials, and
+the one-workgroup final sums the stand-alone call launches behind it).  Median of --reps calls after two
+warm-up calls.  The pieces of the bank are made once when the targets are set (stx_set_nnfm_targets) and are
+not part of a tile's term: their pass is outside the three groups.
+
+The search is priced against the matrix floor 3 x 2 n M C flop (three fp16 products per fp32-class product)
+at 2.5 PFLOP/s, the dense fp16 rate of the MI355X.
+"""
+
+import argparse
+import ctypes
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch                                                              # noqa: E402
+from style_transfer_amd import lib                                        # noqa: E402
+from style_transfer_amd.engine import TileEngine                          # noqa: E402
+from style_transfer_amd.netspec import builtin_net                        # noqa: E402
+from style_transfer_amd.weights import synthetic_weights                  # noqa: E402
+
+FP16_FLOPS = 2.5e15
+# (blob, C, side of the blob's map, side of the style picture's map at that layer)
+TILE_1024 = [('conv3_1', 256, 256, s) for s in (128, 256)] + [('conv4_1', 512, 128, s) for s in (64, 128)]
+TILE_256 = [('conv3_1', 256, 64, s) for s in (128, 256)] + [('conv4_1', 512, 32, s) for s in (64, 128)]
+
+
+def unit_rows(rng, m, c):
+    b = rng.standard_normal((m, c)).astype(np.float32)
+    return b / np.linalg.norm(b, axis=1, keepdims=True)
+
+
+def measure(eng, rng, c, side, rows, reps):
+    feat = eng.to_device(np.maximum(rng.standard_normal((c, side, side)), 0).astype(np.float32) + np.float32(1e-3))
+    bank = eng.to_device(unit_rows(rng, rows, c))
+    s_out = eng.empty((c, side, side))
+    idx = eng.empty((side * side,), np.int32)
+    out = (ctypes.c_double * 2)()
+    call = lambda: lib.call('stx_op_nnfm_terms', eng.handle, feat.ptr, c, side, side, bank.ptr, rows, s_out.ptr,
+                            idx.ptr, out)
+    for _ in range(2):
+        call()
+    times = {'prepare': [], 'search': [], 'grad': []}
+    slices = 1
+    eng.profile(True)
+    for _ in range(reps):
+        call()
+        for label, ms, _ in eng.profile_read():
+            words = label.split()
+            if words[0] == 'nnfm' and words[1] in times:
+                times[words[1]].append(ms)
+                if words[1] == 'search':
+                    slices = int(words[-1][1:])
+    eng.profile(False)
+    for buf in (feat, bank, s_out, idx):
+        buf.free()
+    return {k: float(np.median(v)) for k, v in times.items()}, slices
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--reps', type=int, default=20)
+    opts = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('bench_nnfm: no GPU')
+    net = builtin_net('vgg19')
+    eng = TileEngine(net, 0, synthetic_weights(net, 0))
+    rng = np.random.RandomState(0)
+    lines = ['# --nnfm-weight: stx_op_nnfm_terms, device-event ms per group (median of %d after 2 warm-up calls)'
+             % opts.reps,
+             '# device: %s' % torch.cuda.get_device_name(0),
+             '# floor = 3 x 2 n M C flop at 2.5 PFLOP/s; of floor = floor / search',
+             '%6s %8s %4s %7s %7s %6s %6s %9s %9s %9s %9s %9s %8s' % ('tile', 'blob', 'C', 'n', 'M', 'stride',
+                                                                      'slices', 'prepare', 'search', 'grad', 'total',
+                                                                      'floor ms', 'of floor')]
+    for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
+        for blob, c, side, style_side in shapes:
+            for stride in (1, 2):
+                rows = (-(-style_side // stride)) ** 2
+                t, slices = measure(eng, rng, c, side, rows, opts.reps)
+                n = side * side
+                floor_ms = 6.0 * n * rows * c / FP16_FLOPS * 1e3
+                lines.append('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f'
+                             % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
+                                sum(t.values()), floor_ms, floor_ms / t['search']))
+                print(lines[-1], flush=True)
+    text = '\n'.join(lines) + '\n'
+    if opts.out:
+        os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
+        with open(opts.out, 'w') as f:
+            f.write(text)
+    else:
+        print(text)
+    eng.close()
+
+
+if __name__ == '__main__':
+    main()
