@@ -340,6 +340,13 @@ static bool conv_backward_takes_pooled(stx_engine *e, int li) {
            conv_takes_pooled_input(cfg, p);
 }
 
+// Will the backward pass of convolution li scale its incoming gradient by a recorded maximum (run_conv_backward)?
+static bool conv_backward_reads_amax(stx_engine *e, int li) {
+    const ConvProblem p = conv_backward_shape(e, li);
+    ConvConfig cfg;
+    return !(p.ksize == 3 && p.M <= 4) && conv_choose(p, e->winograd, nullptr, &cfg) == STX_OK && conv_reads_x_amax(cfg);
+}
+
 // `pooled` (or null): the pooling layer behind this convolution whose backward pass the caller skipped
 // (conv_backward_takes_pooled): the incoming gradient is that of the pooled blob.
 static int run_conv_backward(stx_engine *e, int li, const ConvInject *inj, bool *fused, const Layer *pooled) {
@@ -585,6 +592,16 @@ static int backward_walk(TileRun &run) {
             STX_TRY(run_conv_backward(e, li, fused ? &inj : nullptr, &fused, pooled));
             pooled = nullptr;
         } else {
+            // Nobody recorded the pooled gradient's maximum (a 1x1 or few-channel layer wrote it: the direct family
+            // leaves none) and the fp16-split convolution under the pooling layer will ask for one: take it from the
+            // pooled gradient, a quarter of the elements -- the bound the pooled-gradient route scales by, so that
+            // the two routes split their operand alike and stay bit-identical (AVE spreads a window's gradient
+            // over its elements: the un-pooled array's own maximum is up to four times smaller).
+            if (top.amax_diff < 0 && e->layers[bot.producer].type == STX_LAYER_CONV &&
+                conv_backward_reads_amax(e, bot.producer)) {
+                const unsigned *unused;
+                STX_TRY(amax_for(e, cur, true, "bwd " + L.name, &unused));
+            }
             ProfScope scope(e, "bwd " + L.name, 0.0);
             if (top.codes_valid)
                 STX_TRY(pool_backward_codes_launch(

@@ -15,7 +15,8 @@ that reads the wrong words computes the same numbers there.  Three pieces, none 
      and only if every scale follows the true maximum;
   3. absmax_launch at its head, tail and block cap through the operator hooks.
 
-Bound-only sites, from the code (not reachable with VGG channel counts, so named here and not tested): the
+Bound-only sites, from the code (not reachable with VGG channel counts: the audit of tests/test_gpu_odd_nets.py,
+test_recorded_maxima_bound_what_their_consumers_read, runs them on graphs whose channel blocks are partial): the
 kEpiDgradInject epilogues of conv_h2.hip and conv_wino2.hip add the content term of channel 0 in lanes whose
 channel lies past M; they store nothing, but their value enters the recorded maximum, which for a channel
 count that is no multiple of the kernel's channel block is therefore an upper bound, never too small."""

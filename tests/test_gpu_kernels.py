@@ -60,6 +60,72 @@ def test_conv_forward_and_backward_data(cin, cout, h, w, algo, monkeypatch):
     assert max_rel(gx.get(), ref * (below > 0)) < 2e-5
 
 
+# 1x1 / pad 0 layers: the packed forward and backward-data forms of conv_mfma.hip's 1x1 variants, which
+# conv_pick_config(ksize == 1) chooses by plane size and channel count (the unpacked style-gradient product of
+# the same variants is what the SYMM tests run).  (Cin, Cout, H, W) -> the variant forward / backward take:
+CONV1X1_CASES = [
+    (64, 64, 17, 23), (20, 36, 19, 31), (130, 66, 31, 33), (8, 33, 1, 1), (64, 3, 37, 50),     # <= 128 x 128: 12 / 12
+    (64, 128, 130, 131),          # above 128 x 128, M >= 128 forward: 6 / 7
+    (128, 64, 129, 131),          # ... and M >= 128 backward: 7 / 6
+    (72, 40, 129, 130)]           # M < 128 both ways, partial channel tile and partial chunk: 7 / 7
+# STX_CONV_SYMM: the variants no shape selects, on two of the small shapes
+CONV1X1_FORCED = [('13', (64, 64, 17, 23)), ('13', (130, 66, 31, 33)), ('14', (64, 64, 17, 23)), ('14', (130, 66, 31, 33))]
+
+
+def _conv1x1_case(eng, cin, cout, h, w):
+    """Forward with and without ReLU, backward-data with and without mask -> the four device results and
+    their float64 references (oracle.layers on float64 operands)."""
+    rng = np.random.RandomState(cin * 7 + cout + h)
+    x = rng.standard_normal((cin, h, w)).astype(np.float32)
+    wt = (rng.standard_normal((cout, cin, 1, 1)) * np.sqrt(2 / cin)).astype(np.float32)
+    b = (0.1 * rng.standard_normal(cout)).astype(np.float32)
+    dy = rng.standard_normal((cout, h, w)).astype(np.float32)
+    below = np.maximum(x, 0)
+    arrays = [eng.to_device(a) for a in (x, wt, b, dy, below)]
+    dx_, dw, db, ddy, dbelow = arrays
+    y, gx = eng.empty((cout, h, w)), eng.empty((cin, h, w))
+    got = []
+    for relu in (1, 0):
+        lib.call('stx_op_conv_forward', eng.handle, dx_.ptr, cin, h, w, dw.ptr, db.ptr, cout, 1, relu, y.ptr)
+        got.append(y.get())
+    for mask in (None, dbelow.ptr):
+        lib.call('stx_op_conv_backward_data', eng.handle, ddy.ptr, cout, h, w, dw.ptr, cin, 1, mask, gx.ptr)
+        got.append(gx.get())
+    for a in arrays + [y, gx]:
+        a.free()
+    f64 = lambda a: a.astype(np.float64)
+    fwd = L.conv_forward(f64(x), f64(wt), f64(b), pad=0)
+    bwd = L.conv_backward_data(f64(dy), f64(wt), pad=0)
+    return got, [np.maximum(fwd, 0), fwd, bwd, bwd * (below > 0)]
+
+
+@pytest.mark.parametrize('cin,cout,h,w', CONV1X1_CASES)
+def test_conv_1x1_forward_and_backward_data(cin, cout, h, w, monkeypatch):
+    for name in ('STX_CONV_ALGO', 'STX_CONV_SYMM'):
+        monkeypatch.delenv(name, raising=False)
+    eng = gpu_engine()
+    got, ref = _conv1x1_case(eng, cin, cout, h, w)
+    for what, g, r in zip(('forward + ReLU', 'forward', 'backward', 'backward + mask'), got, ref):
+        assert g.shape == r.shape and np.isfinite(g).all(), what
+        assert max_rel(g, r) < 2e-5, what
+    assert np.count_nonzero(got[0]) < got[0].size and np.count_nonzero(got[3]) < got[3].size     # (ReLU and mask bit)
+    # a forced 3x3 family leaves 1x1 problems on the direct kernel: the same bits
+    for algo in ('h2a', 'wino2a'):
+        monkeypatch.setenv('STX_CONV_ALGO', algo)
+        forced, _ = _conv1x1_case(eng, cin, cout, h, w)
+        for what, g, f in zip(('forward + ReLU', 'forward', 'backward', 'backward + mask'), got, forced):
+            assert np.array_equal(g, f), (algo, what)
+
+
+@pytest.mark.parametrize('variant,shape', CONV1X1_FORCED)
+def test_conv_1x1_variants_no_shape_selects(variant, shape, monkeypatch):
+    monkeypatch.delenv('STX_CONV_ALGO', raising=False)
+    monkeypatch.setenv('STX_CONV_SYMM', variant)
+    got, ref = _conv1x1_case(gpu_engine(), *shape)
+    for what, g, r in zip(('forward + ReLU', 'forward', 'backward', 'backward + mask'), got, ref):
+        assert max_rel(g, r) < 2e-5, what
+
+
 # The fp16-split kernel (conv_h2.hip: two fp16 pieces per operand, three products on the fp16 matrix
 # cores) scales its input by a power of two taken from the blob's own maximum, so no range may
 # overflow or lose more than the float32 kernels do: activations up to 2e4 and far beyond, gradients

@@ -54,6 +54,105 @@ def test_pool_ceil_mode(h, w, mode):
             assert aux[c, i, j] == (k // win.shape[1]) * 2 + (k % win.shape[1])
 
 
+@pytest.mark.parametrize('cin,cout,h,w', [(64, 64, 17, 23), (20, 36, 19, 31), (130, 66, 31, 33), (8, 33, 1, 1),
+                                          (64, 3, 37, 50)])
+def test_conv_1x1_fwd_dgrad(cin, cout, h, w):
+    """1x1 / pad 0: the plane keeps its size, backward-to-data is W^T dy per pixel.  Against torch in float64
+    at 2e-6 of max: float32 sums of at most 130 products (130 * 2^-24 = 8e-6 is the worst case of a sum of
+    like-signed terms; random signs stay far below)."""
+    rng = np.random.RandomState(cin + h)
+    x = rng.standard_normal((cin, h, w)).astype(np.float32)
+    wt = (rng.standard_normal((cout, cin, 1, 1)) * np.sqrt(2 / cin)).astype(np.float32)
+    b = (0.01 * rng.standard_normal(cout)).astype(np.float32)
+    dy = rng.standard_normal((cout, h, w)).astype(np.float32)
+    xt = torch.tensor(x[None].astype(np.float64), requires_grad=True)
+    yt = F.conv2d(xt, torch.tensor(wt.astype(np.float64)), torch.tensor(b.astype(np.float64)), padding=0)
+    yt.backward(torch.tensor(dy[None].astype(np.float64)))
+    y = L.conv_forward(x, wt, b, pad=0)
+    assert y.shape == (cout, h, w) and y.dtype == np.float32
+    assert np.abs(y - yt[0].detach().numpy()).max() < 2e-6 * np.abs(y).max()
+    dx = L.conv_backward_data(dy, wt, pad=0)
+    assert dx.shape == (cin, h, w)
+    assert np.abs(dx - xt.grad[0].numpy()).max() < 2e-6 * np.abs(dx).max()
+
+
+def _torch_forward(net, params, tile):
+    """The graph in torch, float64: ({blob: [1,C,h,w]} with the in-place ReLUs applied, {blob: what its ReLU read})."""
+    p = {k: (torch.tensor(w.astype(np.float64)), torch.tensor(b.astype(np.float64))) for k, (w, b) in params.items()}
+    acts, pre = {'data': torch.tensor(np.asarray(tile, np.float64)[None], requires_grad=True)}, {}
+    for lay in net.layers[1:]:
+        x = acts[lay.bottom]
+        if lay.type == 'Convolution':
+            acts[lay.top] = F.conv2d(x, *p[lay.name], padding=lay.pad)
+        elif lay.type == 'ReLU':
+            pre[lay.top] = x
+            acts[lay.top] = F.relu(x)
+        elif lay.pool == 'MAX':
+            acts[lay.top] = F.max_pool2d(x, 2, 2, ceil_mode=True)
+        else:       # Caffe's AVE divides by the window clipped to the blob (pad 0)
+            acts[lay.top] = F.avg_pool2d(x, 2, 2, ceil_mode=True, count_include_pad=False)
+    return acts, pre
+
+
+@pytest.mark.parametrize('th,tw', [(37, 53), (9, 13)])
+@pytest.mark.parametrize('graph', ['ragged-max', 'ragged-ave', 'mixed-max', 'mixed-ave', 'narrow'])
+def test_odd_graphs_forward_and_backward(graph, th, tw):
+    """The graphs of tests/odd_nets.py through the oracle (float32) against torch autograd in float64: 1x1
+    layers, un-rectified blobs into pooling layers, a ReLU on a pooled blob, pool after pool, a pool on the
+    image, ceil-mode AVE windows cut by the border (odd planes at every stage of these tiles).  Every blob to
+    5e-6 of its maximum -- half of what the GPU tests allow the GPU against this oracle; the gradient of a
+    random linear functional of the last blob likewise, where no ReLU / MAX decision sits within the oracle's
+    own error of a tie (else torch and the oracle may legitimately route differently: counted, not compared)."""
+    from tests import odd_nets
+    om, net = odd_nets.make_oracle(graph)
+    rng = np.random.RandomState(th)
+    tile = rng.uniform(-110, 120, (3, th, tw)).astype(np.float32)
+    ref, pre = _torch_forward(net, om.net.params, tile)
+    last = om.last_layer
+    got = om.features_tile(tile, om.blob_names)
+    for b in om.blob_names:
+        want = ref[b][0].detach().numpy()
+        if b == last:
+            want = np.maximum(want, 0)          # (features_tile rectifies the net's last blob)
+        assert got[b].shape == want.shape, b
+        assert np.abs(got[b] - want).max() < 5e-6 * np.abs(want).max(), b
+    # the clipped divisor really occurs: an AVE layer of this case reads an odd plane
+    planes = {'data': tile.shape, **{b: got[b].shape for b in om.blob_names}}
+    clipped = [l.name for l in net.layers if l.type == 'Pooling' and l.pool == 'AVE' and
+               (planes[l.bottom][-2] % 2 or planes[l.bottom][-1] % 2)]
+    assert clipped or graph == 'ragged-max', planes
+    # backward: d <g, last blob> / d image
+    g = rng.standard_normal(got[last].shape).astype(np.float32)
+    (ref[last][0] * torch.tensor(g.astype(np.float64))).sum().backward()
+    want = ref['data'].grad[0].numpy()
+    onet = om.net
+    onet.blobs['data'].reshape(1, 3, th, tw)
+    onet.blobs['data'].data[0] = tile
+    onet.forward(end=last)
+    for blob in onet.blobs.values():
+        blob.diff[...] = 0
+    onet.blobs[last].diff[0] = g
+    onet.backward(start=net.layers[-1].name)
+    mine = onet.blobs['data'].diff[0]
+    assert np.abs(want).max() > 0
+    # near-ties: a value about to be rectified, or a MAX window's margin, within 1e-5 of the blob's maximum of
+    # a decision (windows of exact zeros behind a ReLU tie on both sides alike and pass no gradient on)
+    ties = 0
+    for lay in net.layers[1:]:
+        if lay.type == 'ReLU':
+            a = pre[lay.top][0].detach().numpy()
+            ties += int(np.count_nonzero(np.abs(a) < 1e-5 * np.abs(a).max()))
+        elif lay.type == 'Pooling' and lay.pool == 'MAX':
+            x = ref[lay.bottom][0].detach().numpy()
+            stack, valid = L._windows(x.astype(np.float32))
+            s = np.sort(np.where(valid[:, None], stack, -np.inf), axis=0)
+            ties += int(np.count_nonzero((s[-1] - s[-2] < 1e-5 * np.abs(x).max()) & (s[-1] != 0)))
+    if ties == 0:
+        assert np.abs(mine - want).max() < 5e-6 * np.abs(want).max()
+    else:
+        assert np.linalg.norm(mine - want) < 1e-2 * np.linalg.norm(want), ties
+
+
 def test_blob_with_two_consumers_adds_their_gradients():
     """Caffe puts a Split layer behind a blob that feeds two layers (net.cpp: InsertSplits); the
     reference's *_big prototxts have one (conv1_2 -> pool1, a dead end, and -> conv2_1:
