@@ -277,6 +277,33 @@ typedef struct stx_nnfm_target {
  * layers on one path.  The term follows the blob's statistics term in the loss and in the gradient. */
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n);
 
+/* The same term over 3 x 3 patches (CNNMRF, NNST): pixel p = (y, x) of the blob has the patch
+ *   P_p[t, c] = F[c][y + dy][x + dx]         t = (dy, dx), dy and dx in {-1, 0, 1}; 0 outside the map
+ * a 9 C vector in tap-major order: dy outer, dx inner, (-1, -1) first, then the channel.  Every pixel has a
+ * patch (n of them) and a bank row is a unit or all-zero 9 C vector in the same order:
+ *   R_p  = |P_p|,  X_p = P_p / R_p           (R_p = 0: c_p = 0, j_p = 0, no gradient from this patch)
+ *   j_p  = argmax_j P_p . b_j                (the LOWEST j among equal scores)
+ *   c_p  = X_p . b_{j_p}
+ *   E    = (2/n) sum_p (1 - c_p)
+ *   G_p  = -(b_{j_p} - c_p X_p) / R_p        (9 C: n d(E/2)/dP_p with j_p held fixed)
+ *   S[c][p] = sum_t G_{p - t}[t, c]          over the taps whose centre p - t lies in the map
+ * and loss, diff as above.  A tile's border patches are padded with zeros: tiles stay independent.
+ * patch: 1 (the term above, byte for byte what stx_set_nnfm_targets does) or 3; anything else is STX_ERR_ARG.
+ * channels must be a multiple of 64, and rows x patch^2 x channels, n x channels stay below 2^31
+ * (STX_ERR_UNSUPPORTED otherwise). */
+typedef struct stx_nnfm_patch_target {
+    const char *layer;
+    int channels;
+    int patch;
+    int rows;
+    const float *bank;      /* [rows][patch * patch * channels] */
+    int mem;
+    double weight;
+} stx_nnfm_patch_target;
+/* stx_set_nnfm_targets for banks of either kind: a layer has ONE bank, patch or plain, and either call
+ * replaces the whole set. */
+int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -338,6 +365,11 @@ int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channe
  * caller.  By the pass that prepares a tile's blob for the search. */
 int stx_nnfm_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int stride,
                   float *bank_out, int out_mem);
+/* patch 3: the unit patches (stx_set_nnfm_patch_targets) centred at those (y, x), [rows][9 channels]; an
+ * all-zero patch stays a zero row.  The stride thins the centres only: a patch takes its eight neighbours at
+ * distance one in the full map.  patch 1: stx_nnfm_bank. */
+int stx_nnfm_patch_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int patch,
+                        int stride, float *bank_out, int out_mem);
 
 /* ------------------------------------------------- full-image ops (device-resident state) */
 /* All pointers in this group are STX_DEVICE memory on the engine's GPU, images are [3][H][W].
@@ -611,6 +643,10 @@ int stx_op_stat_terms(stx_engine *e, const float *feat, int channels, int h, int
  * alone: STX_ERR_ARG for a null pointer or rows <= 0, STX_ERR_UNSUPPORTED for channels % 64 != 0. */
 int stx_op_nnfm_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *bank, int rows,
                       float *s_out, int *index_out, double out[2]);
+/* ... and of a patch target (stx_set_nnfm_patch_targets): bank [rows][patch * patch * channels], 16-byte aligned.
+ * patch 1 is stx_op_nnfm_terms; a patch other than 1 or 3 is STX_ERR_ARG.  Errors leave the outputs alone. */
+int stx_op_nnfm_patch_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch,
+                            const float *bank, int rows, float *s_out, int *index_out, double out[2]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

@@ -151,6 +151,11 @@ _EXTENSIONS = [
     (('--nnfm-stride',), dict(metavar='S', type=int,
                               help="keeps every S-th row and column of the style picture's feature maps in the "
                                    'bank of the nearest-neighbour term, an integer >= 1 (default: 1)')),
+    (('--nnfm-patch',), dict(metavar='P', type=int,
+                             help='matches P x P patches of feature vectors in the nearest-neighbour term instead '
+                                  'of single vectors (CNNMRF, NNST), 1 or 3: a 3 x 3 patch carries the local '
+                                  'arrangement -- strokes, hatching, small motifs -- and makes the search nine '
+                                  'times as long; read once per scale (default: 1)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -359,11 +364,32 @@ def nnfm_stride(args):
     return int(raw)
 
 
+def nnfm_patch(args):
+    """--nnfm-patch as the integer 1 or 3 (default 1); anything else, bools and floats included, is a
+    ValueError."""
+    raw = getattr(getattr(args, 'ns', args), 'nnfm_patch', 1)
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or raw not in (1, 3):
+        raise ValueError('--nnfm-patch %r: 1 or 3 is expected' % (raw,))
+    return int(raw)
+
+
+def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
+    """Rows that a [channels, h, w] feature map adds to a bank at this stride.  With ``patch`` 3 a bank that
+    would reach the library's limit -- (rows_before + rows) x 9 x channels below 2^31 -- is a ValueError, raised
+    before anything is allocated."""
+    rows = -(-h // stride) * -(-w // stride)
+    if patch != 1 and (rows_before + rows) * patch * patch * channels >= 2 ** 31:
+        raise ValueError('the NNFM bank of %d x %d x %d-channel patches would have %d rows of %d values, past the '
+                         "library's 2^31 offsets: raise --nnfm-stride (now %d), or use --nnfm-patch 1"
+                         % (patch, patch, channels, rows_before + rows, patch * patch * channels, stride))
+    return rows
+
+
 def check_nnfm_options(args, known_layers=None):
-    """--nnfm-weight / --nnfm-layers / --nnfm-stride: refused before any GPU work together with --style-masks
-    (there is one bank and, with masks, one style set per picture), with a malformed entry, with a layer named
-    twice, with weights that are all 0, with a stride below 1 or -- when the network's layers are known -- with
-    a layer it does not have.  Returns the layer names."""
+    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch: refused before any GPU work together with
+    --style-masks (there is one bank and, with masks, one style set per picture), with a malformed entry, with a
+    layer named twice, with weights that are all 0, with a stride below 1, with a patch that is not 1 or 3 or --
+    when the network's layers are known -- with a layer it does not have.  Returns the layer names."""
     items = nnfm_layer_args(args)
     if not items:
         return []
@@ -371,6 +397,7 @@ def check_nnfm_options(args, known_layers=None):
         raise ValueError('--nnfm-weight cannot be combined with --style-masks: there is one bank of style '
                          'features, and masks make every style picture a style set of its own')
     nnfm_stride(args)
+    nnfm_patch(args)
     names, total = [], 0.0
     for item in items:
         name, _, weight = str(item).partition(':')

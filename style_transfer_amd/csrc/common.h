@@ -500,16 +500,19 @@ NnfmPlan nnfm_plan(int n, int M);
 // floats that hold the fp16 hi / lo pieces of `rows` rows of C channels ([rows][C] hi, then [rows][C] lo)
 size_t nnfm_pieces_floats(int rows, int C);
 // floats of the caller's that one term takes, and their division (from the next 256-byte boundary)
-size_t nnfm_scratch_floats(int C, int n, int M);
+// (patch 3: the 3 x 3 patch term, whose bank rows have 9 C channels -- O(n) floats more)
+size_t nnfm_scratch_floats(int C, int n, int M, int patch = 1);
 struct NnfmScratch {
-    unsigned short *xhi, *xlo;      // pieces of x_i 2^13, [n][C] each
+    unsigned short *xhi, *xlo;      // pieces of x_i 2^13 (patch 3: of f_i under the blob's common scale), [n][C] each
     float *inv_r;                   // [n]
     int *idx;                       // [n]
     float *part_score;              // [slices][n], or null with one slice
     int *part_idx;
     float *partials;                // ceil(n / 64) of (2/n) sum (1 - c_i), then as many of sum |S|
+    double *work;                   // patch 3: nnfm_patch_work_floats(n) floats of nnfm_patch_prepare_launch, else null
+    float *cosv;                    // patch 3: c_p [n], else null
 };
-NnfmScratch nnfm_carve(float *scratch, int C, int n, int M);
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch = 1);
 // One pass over feat [C][h][w]: per picked column (y % stride == 0 and x % stride == 0, raster order) 1 / |f|
 // (0 for a zero column) into inv_r, the pieces of f / |f| 2^13 into hi / lo, f / |f| as float32 rows into
 // rows_out -- each output optional (hi and lo together).
@@ -523,6 +526,22 @@ int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigne
 // sgrad = S [C][n]; *n_parts partials of E, then as many of sum |S|
 int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int n, const float *inv_r, const float *bank, int M,
                      const int *idx, float *sgrad, float *partials, int *n_parts);
+// The 3 x 3 patch form (stx_set_nnfm_patch_targets): pixel p's patch is the 9 C vector of the columns at p + tap,
+// tap-major (dy outer, dx inner, (-1, -1) first), zero outside the map; bank [M][9 C] of unit or zero rows.
+// floats (8-byte aligned) that nnfm_patch_prepare_launch works in: the column norms^2 and their block maxima
+size_t nnfm_patch_work_floats(int n);
+// feat [C][h][w].  hi / lo (stride 1 only): 1 / |P_p| into inv_R and the pieces of the COLUMNS [n][C] under one
+// power of two for the whole blob.  rows_out: the unit patches centred at y % stride == 0 and x % stride == 0,
+// raster order, as float32 rows [rows][9 C] (a zero patch stays a zero row).  One of the two.
+int nnfm_patch_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, double *work,
+                              float *inv_R, unsigned short *hi, unsigned short *lo, float *rows_out);
+// idx_out[p] = argmax_j P_p . b_j, the lowest j among equal scores: the search above with 9 C / kNnfmK stages per
+// bank block and the query operand gathered from x's [n][C] pieces (bhi / blo: nnfm_split_rows_launch at 9 C)
+int nnfm_patch_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, const unsigned short *bhi,
+                             const unsigned short *blo, int M, int C, int *idx_out);
+// cosv [n] = c_p, then sgrad = S [C][n] in the gather form; partials as nnfm_grad_launch leaves them
+int nnfm_patch_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, const float *inv_R, const float *bank,
+                           int M, const int *idx, float *cosv, float *sgrad, float *partials, int *n_parts);
 
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,

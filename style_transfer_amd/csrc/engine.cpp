@@ -843,8 +843,14 @@ int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
     return rc;
 }
 
-int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
+// The banks of both setters: a plain bank is a patch target with patch 1.
+static int set_nnfm_banks(stx_engine *e, const stx_nnfm_patch_target *targets, int n, const char *who) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (targets[i].patch != 1 && targets[i].patch != 3) {
+            set_error("NNFM target %d: patch %d (1 or 3 is expected)", i, targets[i].patch);
+            return STX_ERR_ARG;
+        }
     STX_TRY(e->set_device());
     std::lock_guard<std::mutex> lock(e->sh->mutex);
     // the previous banks may still be in use by queued kernels (of any engine that shares them)
@@ -859,7 +865,7 @@ int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
     clear();
     int rc = STX_OK;
     for (int i = 0; i < n && rc == STX_OK; ++i) {
-        const stx_nnfm_target &nt = targets[i];
+        const stx_nnfm_patch_target &nt = targets[i];
         const int blob = e->find_blob(nt.layer);
         bool twice = false;
         for (const NnfmTarget &t : e->sh->nnfms) twice |= t.blob == blob;
@@ -875,32 +881,47 @@ int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
             rc = STX_ERR_ARG;
             break;
         }
-        if (nt.channels % 64 != 0 || nt.rows >= (1ll << 31) / nt.channels) {
+        const int width = nt.patch * nt.patch * nt.channels;
+        if (nt.channels % 64 != 0 || nt.rows >= (1ll << 31) / width) {
             set_error("NNFM target %d: %d rows of %d channels (a multiple of 64 and rows x channels below 2^31 "
-                      "are expected)", i, nt.rows, nt.channels);
+                      "are expected)", i, nt.rows, width);
             rc = STX_ERR_UNSUPPORTED;
             break;
         }
         NnfmTarget t{blob, nt.channels, nt.rows, nt.weight, std::unique_ptr<DevBuf>(new DevBuf),
-                     std::unique_ptr<DevBuf>(new DevBuf)};
-        const size_t bytes = (size_t)t.rows * t.C * sizeof(float);
-        if ((rc = t.bank->ensure(bytes)) == STX_OK) rc = t.pieces->ensure(nnfm_pieces_floats(t.rows, t.C) * sizeof(float));
+                     std::unique_ptr<DevBuf>(new DevBuf), nt.patch};
+        const size_t bytes = (size_t)t.rows * width * sizeof(float);
+        if ((rc = t.bank->ensure(bytes)) == STX_OK) rc = t.pieces->ensure(nnfm_pieces_floats(t.rows, width) * sizeof(float));
         if (rc == STX_OK) rc = copy_in(e, t.bank->ptr, nt.bank, nt.mem, bytes);
         // the fp16 pieces the search reads, once
         if (rc == STX_OK)
-            rc = nnfm_split_rows_launch(e->stream, t.bank->f(), t.rows, t.C, static_cast<unsigned short *>(t.pieces->ptr),
-                                        static_cast<unsigned short *>(t.pieces->ptr) + (size_t)t.rows * t.C);
+            rc = nnfm_split_rows_launch(e->stream, t.bank->f(), t.rows, width, static_cast<unsigned short *>(t.pieces->ptr),
+                                        static_cast<unsigned short *>(t.pieces->ptr) + (size_t)t.rows * width);
         e->sh->nnfms.push_back(std::move(t));
     }
     // (a source on either side may be reused or freed right away, and the sharing engines read the banks from
     // their own streams: the copies and the split have finished when this returns)
     const hipError_t err = hipStreamSynchronize(e->stream);
     if (rc == STX_OK && err != hipSuccess) {
-        set_error("stx_set_nnfm_targets: %s", hipGetErrorString(err));
+        set_error("%s: %s", who, hipGetErrorString(err));
         rc = STX_ERR_HIP;
     }
     if (rc != STX_OK) clear();
     return rc;
+}
+
+int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    std::vector<stx_nnfm_patch_target> as_patch;
+    for (int i = 0; i < n; ++i) {
+        const stx_nnfm_target &t = targets[i];
+        as_patch.push_back(stx_nnfm_patch_target{t.layer, t.channels, 1, t.rows, t.bank, t.mem, t.weight});
+    }
+    return set_nnfm_banks(e, as_patch.data(), n, "stx_set_nnfm_targets");
+}
+
+int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n) {
+    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_patch_targets");
 }
 
 int stx_profile_enable(stx_engine *e, int on) {

@@ -113,12 +113,15 @@ struct StatTarget {
 
 // The bank of one tapped blob's nearest-neighbour term (stx_set_nnfm_targets): float32 rows [rows][C] on the
 // device and, built once when the targets are set, their fp16 hi / lo pieces for the search (nnfm.hip).
+// patch 3 (stx_set_nnfm_patch_targets): rows of 3 x 3 patches, 9 C channels each.
 struct NnfmTarget {
     int blob, C, rows;
     double weight;
     std::unique_ptr<DevBuf> bank, pieces;
+    int patch = 1;
+    int width() const { return patch * patch * C; }
     const unsigned short *hi() const { return static_cast<const unsigned short *>(pieces->ptr); }
-    const unsigned short *lo() const { return hi() + (size_t)rows * C; }
+    const unsigned short *lo() const { return hi() + (size_t)rows * width(); }
 };
 
 struct LossTerm {
@@ -422,11 +425,12 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
                       std::vector<SumJob> *defer);
 // The nearest-neighbour term of a blob (nnfm.hip): prepare -> search (-> merge) -> S into sgrad.
 // sc[2] = {E, sum |S|}, both from partials whose final sums join `defer` or are launched here.  scratch:
-// nnfm_scratch_floats(C, h * w, rows) floats that outlive the call like term_scratch.  idx_out (or null): the
-// winning rows [h * w].
+// nnfm_scratch_floats(C, h * w, rows, patch) floats that outlive the call like term_scratch.  idx_out (or null):
+// the winning rows [h * w].  patch 3: the 3 x 3 patch form, bank rows of 9 C channels.
 int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *bank,
                       const unsigned short *bank_hi, const unsigned short *bank_lo, int rows, float *sgrad,
-                      int *idx_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer);
+                      int *idx_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer,
+                      int patch = 1);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

@@ -21,6 +21,9 @@
 //   4. nnfm_grad_kernel      per column: gathers the float32 row j_i, recomputes c_i with float32 fma in
 //                            channel order (NOT the search's score: E and S are functions of (F, B, j)),
 //                            writes S in [C][n] layout and leaves the partials of sum (1 - c_i) and sum |S|.
+// The 3 x 3 patch form (stx_set_nnfm_patch_targets; the nnfm_patch_* kernels below) is the same search with
+// K = 9 C and a gathered query operand: no [n][9 C] array is written anywhere.  Its prepare pass splits the
+// columns under one scale for the whole blob, its gradient gathers the nine patches a pixel belongs to.
 
 #include <algorithm>
 #include <climits>
@@ -109,6 +112,113 @@ __global__ __launch_bounds__(256) void nnfm_split_rows_kernel(const float *__res
     reinterpret_cast<f16x8h *>(lo)[t] = pl;
 }
 
+// ------------------------------------------------------------------------------------- patch prepare
+// 3 x 3 patches (stx_set_nnfm_patch_targets): pixel p's patch P_p is the 9 C vector of its columns at
+// p + tap, tap = (dy, dx) with dy outer, dx inner, (-1, -1) first, zero outside the map.  |P_p|^2 is the box
+// sum of the column norms^2, and the search needs no per-patch normalisation (argmax_j P_p . b_j is that of
+// P_p / |P_p|), so the columns are split once, [n][C], under ONE power of two for the whole blob: the one that
+// puts the largest column norm into (2^12, 2^13].  Every piece fits fp16 and a score stays below 3 2^26.
+//
+// First launch: the column norms^2 in double (the order of nnfm_prepare_kernel) and each workgroup's largest.
+__global__ __launch_bounds__(256) void nnfm_patch_norms_kernel(const float *__restrict__ F, int C, int n,
+                                                               double *__restrict__ norm2, double *__restrict__ bmax) {
+    __shared__ double red[4][64];
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int p = min(blockIdx.x * 64 + col, n - 1);            // (columns past the end re-read the last one)
+    double acc = 0.0;
+    for (int c = g; c < C; c += 4) {
+        const double v = (double)F[(size_t)c * n + p];
+        acc += v * v;
+    }
+    red[g][col] = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const double ss = ((red[0][col] + red[1][col]) + red[2][col]) + red[3][col];
+        if (blockIdx.x * 64 + col < n) norm2[p] = ss;
+        double m = ss;          // (a maximum: no order can change it)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+        if (col == 0) bmax[blockIdx.x] = m;
+    }
+}
+
+// 2^k with max_norm 2^k in (2^12, 2^13] (a zero or denormal blob: the largest power of two, harmless)
+__device__ __forceinline__ float patch_scale(double max_norm) {
+    const long long bits = __double_as_longlong(max_norm);
+    const int e = (int)((bits >> 52) & 0x7ff) - 1023;
+    const bool pow2 = (bits & ((1ll << 52) - 1)) == 0;
+    return pow2f((pow2 ? 13 : 12) - e);
+}
+
+// Second launch, grid (64-column groups, taps).  Output column o is the patch centred at (oy stride, ox stride),
+// o = oy ow + ox.  One tap (the tile's blob, stride 1): 1 / |P_o| into inv_R and the pieces of the column itself
+// under the common scale into hi / lo [n][C].  Nine taps (a bank): rows_out [n_out][9 C], the unit patches.
+__global__ __launch_bounds__(256) void nnfm_patch_rows_kernel(const float *__restrict__ F, int C, int h, int w, int stride,
+                                                              int ow, int n_out, const double *__restrict__ norm2,
+                                                              const double *__restrict__ bmax, int n_bmax,
+                                                              float *__restrict__ inv_R, _Float16 *__restrict__ hi,
+                                                              _Float16 *__restrict__ lo, float *__restrict__ rows_out) {
+    __shared__ double smax[4];
+    __shared__ float sinv[64];
+    __shared__ float tile[64][65];
+    const int col = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const size_t HW = (size_t)h * w;
+    const int o = min(blockIdx.x * 64 + col, n_out - 1);
+    const int y = (o / ow) * stride, x = (o % ow) * stride;
+    const int tap = gridDim.y == 1 ? 4 : (int)blockIdx.y;
+    const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
+    const bool inside = (unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w;
+    const size_t src = inside ? (size_t)yy * w + xx : 0;
+    float scale = 0.f;
+    if (hi) {
+        double m = 0.0;
+        for (int i = threadIdx.x; i < n_bmax; i += 256) m = fmax(m, bmax[i]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+        if (col == 0) smax[g] = m;
+        __syncthreads();
+        scale = patch_scale(sqrt(fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]))));
+    }
+    if (threadIdx.x < 64) {
+        double ss = 0.0;        // the box sum, taps in order
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int ty = y + t / 3 - 1, tx = x + t % 3 - 1;
+            if ((unsigned)ty < (unsigned)h && (unsigned)tx < (unsigned)w) ss += norm2[(size_t)ty * w + tx];
+        }
+        const float inv = ss > 0.0 ? (float)(1.0 / sqrt(ss)) : 0.f;
+        sinv[col] = inv;
+        if (inv_R && blockIdx.x * 64 + col < n_out) inv_R[o] = inv;
+    }
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        __syncthreads();        // (sinv is written; the tile of the round before is read)
+        for (int cc = g; cc < 64; cc += 4) tile[cc][col] = inside ? F[(size_t)(c0 + cc) * HW + src] : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int item = threadIdx.x + 256 * u, col2 = item >> 3, oct = item & 7;
+            const int o2 = blockIdx.x * 64 + col2;
+            if (o2 >= n_out) continue;
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = tile[oct * 8 + j][col2];
+            if (hi) {
+                const size_t at = (size_t)o2 * C + c0 + oct * 8;
+                f16x8h ph, pl;
+                split2_f16(v, scale, ph, pl);
+                *reinterpret_cast<f16x8h *>(hi + at) = ph;
+                *reinterpret_cast<f16x8h *>(lo + at) = pl;
+            }
+            if (rows_out) {
+                const float inv = sinv[col2];
+                const size_t at = ((size_t)o2 * 9 + tap) * C + c0 + oct * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) rows_out[at + j] = v[j] * inv;
+            }
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------------------- search
 // "greater score, else lower index": associative and commutative, so no merge order can change the result
 __device__ __forceinline__ void take_better(float s, int j, float &best_s, int &best_j) {
@@ -147,6 +257,142 @@ __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__rest
 #pragma unroll
             for (int a = 0; a < 4; ++a)
                 pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + (a < 2 ? q : j) * C + k0 + ch * 8);
+        }
+    };
+    const auto stage = [&]() {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+                *reinterpret_cast<u32x4n *>(lds + (a * 128 + row) * kLdsRow + ch * 16) = pre[a][u];
+        }
+    };
+    const auto frag = [&](int a, int row, int ks) {
+        return *reinterpret_cast<const f16x8h *>(lds + (a * 128 + row) * kLdsRow + ks * 32 + half * 16);
+    };
+
+    f32x16h acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[i][k][v] = 0.f;
+    float best_s[2] = {-INFINITY, -INFINITY};
+    int best_j[2] = {INT_MAX, INT_MAX};
+
+    prefetch(0);
+    for (int t = 0; t < T; ++t) {
+        __syncthreads();        // every wave has read the stage before
+        stage();
+        __syncthreads();
+        if (t + 1 < T) prefetch(t + 1);
+#pragma unroll
+        for (int ks = 0; ks < kNnfmK / 16; ++ks) {
+            f16x8h a_hi[2], a_lo[2], b_hi[2], b_lo[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                b_hi[i] = frag(0, 64 * wq + 32 * i + r, ks);
+                b_lo[i] = frag(1, 64 * wq + 32 * i + r, ks);
+                a_hi[i] = frag(2, 64 * wb + 32 * i + r, ks);
+                a_lo[i] = frag(3, 64 * wb + 32 * i + r, ks);
+            }
+#pragma unroll
+            for (int tq = 0; tq < 2; ++tq)
+#pragma unroll
+                for (int tb = 0; tb < 2; ++tb)
+                    acc[tq][tb] = mfma_split3(a_hi[tb], a_lo[tb], b_hi[tq], b_lo[tq], acc[tq][tb]);
+        }
+        if (t % KC == KC - 1) {     // the block's scores are complete: D[row = bank][col = query]
+            const int j0 = (bb0 + t / KC) * kNnfmB + 64 * wb + 4 * half;
+#pragma unroll
+            for (int tq = 0; tq < 2; ++tq)
+#pragma unroll
+                for (int tb = 0; tb < 2; ++tb)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        const int j = j0 + 32 * tb + (v & 3) + 8 * (v >> 2);
+                        if (j < M) take_better(acc[tq][tb][v], j, best_s[tq], best_j[tq]);     // padding never wins
+                        acc[tq][tb][v] = 0.f;
+                    }
+        }
+    }
+    // a query's four candidates: two lane halves x the two waves that split the bank rows
+    __syncthreads();
+    float *const cand_s = reinterpret_cast<float *>(lds);
+    int *const cand_j = reinterpret_cast<int *>(lds + kNnfmQ * 4 * sizeof(float));
+#pragma unroll
+    for (int tq = 0; tq < 2; ++tq) {
+        const int q = 64 * wq + 32 * tq + r;
+        cand_s[q * 4 + wb * 2 + half] = best_s[tq];
+        cand_j[q * 4 + wb * 2 + half] = best_j[tq];
+    }
+    __syncthreads();
+    if (threadIdx.x < kNnfmQ && q0 + (int)threadIdx.x < n) {
+        float s = cand_s[threadIdx.x * 4];
+        int j = cand_j[threadIdx.x * 4];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) take_better(cand_s[threadIdx.x * 4 + k], cand_j[threadIdx.x * 4 + k], s, j);
+        if (j == INT_MAX) j = 0;        // (scores that are not numbers: nothing was taken)
+        if (gridDim.y == 1) {
+            idx_out[q0 + threadIdx.x] = j;
+        } else {
+            part_score[(size_t)blockIdx.y * n + q0 + threadIdx.x] = s;
+            part_idx[(size_t)blockIdx.y * n + q0 + threadIdx.x] = j;
+        }
+    }
+}
+
+// The 3 x 3 patch search: nnfm_search_kernel with 9 C / kNnfmK stages per bank block (kept as a sibling so that
+// the kernel above stays instruction for instruction what it was).  A bank row has 9 C channels, tap-major; the
+// query operand is gathered from the [n][C] pieces of the w-wide map: stage t of a row reads 32 channels of
+// pixel p + tap(t), found from p's (y, x) -- the right neighbour of a row's last pixel is padding -- and zeros
+// outside the map.  Staging layout, products, argmax rule, clamps and the final merge are the kernel's above.
+__global__ __launch_bounds__(256) void nnfm_patch_search_kernel(const _Float16 *__restrict__ xhi,
+                                                                const _Float16 *__restrict__ xlo, int n, int w,
+                                                                const _Float16 *__restrict__ bhi,
+                                                                const _Float16 *__restrict__ blo, int M, int C,
+                                                                int b_blocks, int blocks_per_slice,
+                                                                int *__restrict__ idx_out, float *__restrict__ part_score,
+                                                                int *__restrict__ part_idx) {
+    // [X hi | X lo | B hi | B lo][row][kNnfmK halves + padding]; reused for the workgroup's final merge
+    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 128 * kLdsRow];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wq = wave & 1, wb = wave >> 1;        // the wave's 64 queries x 64 bank rows of the 128 x 128 block
+    const int r = lane & 31, half = lane >> 5;
+    const int q0 = blockIdx.x * kNnfmQ;
+    const int bb0 = blockIdx.y * blocks_per_slice, bb1 = min(bb0 + blocks_per_slice, b_blocks);
+    const int CB = 9 * C;       // channels of a bank row
+    const int KC = CB / kNnfmK, T = (bb1 - bb0) * KC;
+
+    // what this thread stages: two 16-byte chunks of each of the four arrays
+    const _Float16 *const arr[4] = {xhi, xlo, bhi, blo};
+    u32x4n pre[4][2];
+    int qy[2], qx[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int q = min(q0 + (int)((threadIdx.x + 256 * u) >> 2), n - 1);     // padding re-reads the last patch
+        qy[u] = q / w;
+        qx[u] = q - qy[u] * w;
+    }
+    const auto prefetch = [&](int t) {
+        const int bb = bb0 + t / KC, k0 = (t % KC) * kNnfmK;
+        const int tap = k0 / C, c0 = k0 - tap * C;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
+            const size_t j = (size_t)min(bb * kNnfmB + row, M - 1);             // ... and the last row
+            const int yy = qy[u] + tap / 3 - 1, xx = qx[u] + tap % 3 - 1;
+            const bool inside = (unsigned)xx < (unsigned)w && yy >= 0 && (size_t)yy * w + xx < (size_t)n;
+            const size_t at = inside ? ((size_t)yy * w + xx) * C + c0 + ch * 8 : 0;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + at);
+                if (!inside) pre[a][u] = u32x4n{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int a = 2; a < 4; ++a) pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + j * CB + k0 + ch * 8);
         }
     };
     const auto stage = [&]() {
@@ -292,6 +538,92 @@ __global__ __launch_bounds__(64) void nnfm_grad_kernel(const float *__restrict__
     }
 }
 
+// --------------------------------------------------------------------------------------- patch grad
+// First step, one patch per lane: the float32 row j_p and c_p = X_p . b_{j_p}, float32 fma in the order tap,
+// then channel (a tap outside the map adds nothing and is skipped), into cos_out [n].
+__global__ __launch_bounds__(64) void nnfm_patch_cos_kernel(const float *__restrict__ F, int C, int h, int w,
+                                                            const float *__restrict__ inv_R,
+                                                            const float *__restrict__ bank, int M,
+                                                            const int *__restrict__ idx, float *__restrict__ cos_out) {
+    const int n = h * w, i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int y = i / w, x = i - y * w;
+    const unsigned ju = (unsigned)idx[i];
+    const float *__restrict__ row = bank + (size_t)(ju < (unsigned)M ? ju : 0u) * 9 * C;
+    const float inv = inv_R[i];
+    float c = 0.f;
+    for (int t = 0; t < 9; ++t) {
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        if ((unsigned)yy >= (unsigned)h || (unsigned)xx >= (unsigned)w) continue;
+        const float *__restrict__ f = F + (size_t)yy * w + xx;
+        const float *__restrict__ b = row + (size_t)t * C;
+#pragma unroll 2
+        for (int ch = 0; ch < C; ch += 4) {         // (a row starts at a multiple of 16 bytes: C % 64 == 0)
+            const float4 b4 = *reinterpret_cast<const float4 *>(b + ch);
+            c = fmaf(f[(size_t)ch * n] * inv, b4.x, c);
+            c = fmaf(f[(size_t)(ch + 1) * n] * inv, b4.y, c);
+            c = fmaf(f[(size_t)(ch + 2) * n] * inv, b4.z, c);
+            c = fmaf(f[(size_t)(ch + 3) * n] * inv, b4.w, c);
+        }
+    }
+    cos_out[i] = c;
+}
+
+// Second step, one pixel per lane, one wave per workgroup: the gather form
+//   S[c][p] = -sum_tap b_{j_q}[tap, c] / R_q  +  F[c][p] sum_tap c_q / R_q^2,   q = p - tap inside the map,
+// taps in order.  partials as nnfm_grad_kernel leaves them.
+__global__ __launch_bounds__(64) void nnfm_patch_grad_kernel(const float *__restrict__ F, int C, int h, int w,
+                                                             const float *__restrict__ inv_R,
+                                                             const float *__restrict__ bank, int M,
+                                                             const int *__restrict__ idx, const float *__restrict__ cosv,
+                                                             float *__restrict__ S, float *__restrict__ partials) {
+    const int n = h * w, i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < n;
+    const int ii = valid ? i : n - 1;
+    const int y = ii / w, x = ii - y * w;
+    const float *rows[9];
+    float invq[9];
+    float a = 0.f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int qy = y - (t / 3 - 1), qx = x - (t % 3 - 1);
+        const bool inside = (unsigned)qy < (unsigned)h && (unsigned)qx < (unsigned)w;
+        const int q = inside ? qy * w + qx : ii;
+        const unsigned ju = (unsigned)idx[q];
+        rows[t] = bank + (size_t)(ju < (unsigned)M ? ju : 0u) * 9 * C + (size_t)t * C;
+        invq[t] = inside ? inv_R[q] : 0.f;
+        a = fmaf(cosv[q] * invq[t], invq[t], a);
+    }
+    float sum_abs = 0.f;
+    if (valid) {
+        const float *__restrict__ f = F + i;
+        float *__restrict__ out = S + i;
+        for (int ch = 0; ch < C; ch += 4) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const float4 b4 = *reinterpret_cast<const float4 *>(rows[t] + ch);
+                acc[0] = fmaf(b4.x, invq[t], acc[0]);
+                acc[1] = fmaf(b4.y, invq[t], acc[1]);
+                acc[2] = fmaf(b4.z, invq[t], acc[2]);
+                acc[3] = fmaf(b4.w, invq[t], acc[3]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float s = fmaf(f[(size_t)(ch + k) * n], a, -acc[k]);
+                out[(size_t)(ch + k) * n] = s;
+                sum_abs += fabsf(s);
+            }
+        }
+    }
+    const float one_minus = wave_sum_f(valid ? 1.f - cosv[ii] : 0.f);
+    sum_abs = wave_sum_f(sum_abs);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = one_minus * (2.f / (float)n);
+        partials[gridDim.x + blockIdx.x] = sum_abs;
+    }
+}
+
 int check_shape(const char *who, int C, long long n, long long M) {
     if (C <= 0 || n <= 0 || M <= 0) {
         set_error("%s: %d channels, %lld columns, %lld bank rows", who, C, n, M);
@@ -326,13 +658,15 @@ NnfmPlan nnfm_plan(int n, int M) {
 
 size_t nnfm_pieces_floats(int rows, int C) { return round64((size_t)rows * C); }
 
-size_t nnfm_scratch_floats(int C, int n, int M) {
+size_t nnfm_patch_work_floats(int n) { return 2 * round64(n) + 2 * round64(ceil_div(n, 64)); }
+
+size_t nnfm_scratch_floats(int C, int n, int M, int patch) {
     const NnfmPlan p = nnfm_plan(n, M);
     return 64 + nnfm_pieces_floats(n, C) + 2 * round64(n) + (p.slices > 1 ? 2 * round64((size_t)p.slices * n) : 0) +
-           round64(2 * (size_t)ceil_div(n, 64));
+           round64(2 * (size_t)ceil_div(n, 64)) + (patch == 3 ? nnfm_patch_work_floats(n) + round64(n) : 0);
 }
 
-NnfmScratch nnfm_carve(float *scratch, int C, int n, int M) {
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch) {
     const NnfmPlan p = nnfm_plan(n, M);
     NnfmScratch s;
     float *at = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
@@ -352,6 +686,14 @@ NnfmScratch nnfm_carve(float *scratch, int C, int n, int M) {
         at += round64((size_t)p.slices * n);
     }
     s.partials = at;
+    at += round64(2 * (size_t)ceil_div(n, 64));
+    s.work = nullptr;
+    s.cosv = nullptr;
+    if (patch == 3) {
+        s.work = reinterpret_cast<double *>(at);
+        at += nnfm_patch_work_floats(n);
+        s.cosv = at;
+    }
     return s;
 }
 
@@ -404,6 +746,76 @@ int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int n, const float
     const int blocks = ceil_div(n, 64);
     const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
     nnfm_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, n, inv_r, bank, M, vec, idx, sgrad, partials);
+    STX_CHECK_LAUNCH();
+    *n_parts = blocks;
+    return STX_OK;
+}
+
+// ------------------------------------------------------------------------------------ 3 x 3 patches
+static int check_patch_shape(const char *who, int C, long long n, long long M) {
+    if (C <= 0 || n <= 0 || M <= 0) {
+        set_error("%s: %d channels, %lld patches, %lld bank rows", who, C, n, M);
+        return STX_ERR_ARG;
+    }
+    if (C % 64 != 0) {
+        set_error("%s: the channel count %d is not a multiple of 64", who, C);
+        return STX_ERR_UNSUPPORTED;
+    }
+    if (n >= (1ll << 31) / C || M >= (1ll << 31) / (9ll * C)) {
+        set_error("%s: %lld patches against %lld bank rows of 9 x %d channels exceed 32-bit offsets", who, n, M, C);
+        return STX_ERR_UNSUPPORTED;
+    }
+    return STX_OK;
+}
+
+int nnfm_patch_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, double *work,
+                              float *inv_R, unsigned short *hi, unsigned short *lo, float *rows_out) {
+    if (stride < 1 || h <= 0 || w <= 0 || (rows_out && hi) || (hi && stride != 1)) {
+        set_error("nnfm_patch_prepare_launch: a %dx%d map with stride %d", h, w, stride);
+        return STX_ERR_ARG;
+    }
+    const int oh = ceil_div(h, stride), ow = ceil_div(w, stride);
+    STX_TRY(check_patch_shape("nnfm_patch_prepare_launch", C, (long long)h * w, (long long)oh * ow));
+    const int n = h * w, n_out = oh * ow, blocks = ceil_div(n, 64);
+    double *const norm2 = work, *const bmax = work + round64(n);
+    nnfm_patch_norms_kernel<<<blocks, 256, 0, s>>>(feat, C, n, norm2, bmax);
+    STX_CHECK_LAUNCH();
+    nnfm_patch_rows_kernel<<<dim3(ceil_div(n_out, 64), rows_out ? 9 : 1), 256, 0, s>>>(
+        feat, C, h, w, stride, ow, n_out, norm2, bmax, blocks, inv_R, reinterpret_cast<_Float16 *>(hi),
+        reinterpret_cast<_Float16 *>(lo), rows_out);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+int nnfm_patch_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, const unsigned short *bhi,
+                             const unsigned short *blo, int M, int C, int *idx_out) {
+    const int n = h * w;
+    STX_TRY(check_patch_shape("nnfm_patch_search_launch", C, n, M));
+    const NnfmPlan p = nnfm_plan(n, M);
+    nnfm_patch_search_kernel<<<dim3(p.q_blocks, p.slices), 256, 0, s>>>(
+        reinterpret_cast<const _Float16 *>(x.xhi), reinterpret_cast<const _Float16 *>(x.xlo), n, w,
+        reinterpret_cast<const _Float16 *>(bhi), reinterpret_cast<const _Float16 *>(blo), M, C, p.b_blocks,
+        p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+    STX_CHECK_LAUNCH();
+    if (p.slices > 1) {
+        nnfm_merge_kernel<<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
+        STX_CHECK_LAUNCH();
+    }
+    return STX_OK;
+}
+
+int nnfm_patch_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, const float *inv_R, const float *bank,
+                           int M, const int *idx, float *cosv, float *sgrad, float *partials, int *n_parts) {
+    const int n = h * w;
+    STX_TRY(check_patch_shape("nnfm_patch_grad_launch", C, n, M));
+    if (reinterpret_cast<uintptr_t>(bank) % 16 != 0) {
+        set_error("nnfm_patch_grad_launch: the bank is not aligned to 16 bytes");
+        return STX_ERR_UNSUPPORTED;
+    }
+    const int blocks = ceil_div(n, 64);
+    nnfm_patch_cos_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, inv_R, bank, M, idx, cosv);
+    STX_CHECK_LAUNCH();
+    nnfm_patch_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, inv_R, bank, M, idx, cosv, sgrad, partials);
     STX_CHECK_LAUNCH();
     *n_parts = blocks;
     return STX_OK;

@@ -834,4 +834,39 @@ int stx_nnfm_bank(stx_engine *e, const float *feat, int feat_mem, int channels, 
     return STX_OK;
 }
 
+int stx_nnfm_patch_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int patch,
+                        int stride, float *bank_out, int out_mem) {
+    if (patch == 1) return stx_nnfm_bank(e, feat, feat_mem, channels, h, w, stride, bank_out, out_mem);
+    if (patch != 3 || !e || !feat || !bank_out || channels <= 0 || h <= 0 || w <= 0 || stride < 1) {
+        set_error("stx_nnfm_patch_bank: bad arguments (patch %d; 1 or 3 is expected)", patch);
+        return STX_ERR_ARG;
+    }
+    const long long rows = (long long)ceil_div(h, stride) * ceil_div(w, stride);
+    if (channels % 64 != 0 || (long long)h * w >= (1ll << 31) / channels || rows >= (1ll << 31) / (9ll * channels)) {
+        set_error("stx_nnfm_patch_bank: %lld rows of 9 x %d channels from a %dx%d map (a multiple of 64 and rows x 9 "
+                  "channels below 2^31 are expected)", rows, channels, h, w);
+        return STX_ERR_UNSUPPORTED;
+    }
+    STX_TRY(e->set_device());
+    const size_t in_bytes = (size_t)channels * h * w * sizeof(float);
+    const size_t out_floats = (size_t)rows * 9 * channels, out_bytes = out_floats * sizeof(float);
+    const float *src = feat;
+    if (feat_mem == STX_HOST) {
+        STX_TRY(e->upload.ensure(in_bytes));
+        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, in_bytes));
+        src = e->upload.f();
+    }
+    // the passes that prepare a tile's blob for the patch search (nnfm.hip), with the float32 rows as their output
+    const size_t staged = out_mem == STX_HOST ? (out_floats + 63) & ~(size_t)63 : 0;
+    STX_TRY(e->nnfm_scratch.ensure((staged + nnfm_patch_work_floats(h * w)) * sizeof(float)));
+    float *dst = out_mem == STX_HOST ? e->nnfm_scratch.f() : bank_out;
+    STX_TRY(nnfm_patch_prepare_launch(e->stream, src, channels, h, w, stride,
+                                      reinterpret_cast<double *>(e->nnfm_scratch.f() + staged), nullptr, nullptr,
+                                      nullptr, dst));
+    if (out_mem == STX_HOST) STX_TRY(copy_out(e, bank_out, STX_HOST, dst, out_bytes));
+    // (the work area is the engine's: the rows are complete before another call may reuse it)
+    STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
 }  // extern "C"

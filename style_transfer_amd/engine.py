@@ -20,6 +20,7 @@ import ctypes
 import numpy as np
 
 from . import lib
+from .config_system import nnfm_bank_rows
 from .netspec import NetSpec
 
 _TYPE_CODES = {'Input': lib.LAYER_INPUT, 'Convolution': lib.LAYER_CONV, 'ReLU': lib.LAYER_RELU,
@@ -321,12 +322,31 @@ class TileEngine:
         self.primary.stat_layers = list(targets)
         del keep
 
-    def set_nnfm_targets(self, banks, weights=None):
+    def set_nnfm_targets(self, banks, weights=None, patch=1):
         """banks: {layer: B [rows, C]} -- unit rows, what ``nnfm_bank`` gives for a style picture's feature map
         (banks of several pictures concatenated) -- and weights: {layer: factor} (default 1 each); an empty
         dict: none (stx_set_nnfm_targets).  The library copies a bank and builds its fp16 pieces once, here.
         Call it after ``set_contents_and_styles``, which clears the banks.  A layer with a bank is part of
-        every tile evaluation of the group from then on."""
+        every tile evaluation of the group from then on.  ``patch`` 3: banks of 3 x 3 patches, [rows, 9 C] as
+        ``nnfm_bank(feat, stride, 3)`` gives them (stx_set_nnfm_patch_targets)."""
+        if patch == 1:
+            return self._set_nnfm_plain(banks, weights)
+        keep, n = [], len(banks)
+        table = (lib.NnfmPatchTarget * max(1, n))()
+        for t, (layer, bank) in zip(table, banks.items()):
+            ptr, mem, obj = _as_arg(bank)
+            if len(obj.shape) != 2 or isinstance(patch, bool) or patch != 3 or obj.shape[1] % 9:
+                raise ValueError('NNFM bank %s, patch %r: a [rows, patch * patch * C] array and patch 1 or 3 are '
+                                 'expected' % (layer, patch))
+            keep.append(obj)
+            t.layer, t.channels, t.patch, t.rows = self._cstr(layer), int(obj.shape[1]) // 9, 3, int(obj.shape[0])
+            t.bank, t.mem = ptr, mem
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_nnfm_patch_targets', self.handle, table, n)
+        self.primary.nnfm_layers = list(banks)
+        del keep
+
+    def _set_nnfm_plain(self, banks, weights):
         keep, n = [], len(banks)
         table = (lib.NnfmTarget * max(1, n))()
         for t, (layer, bank) in zip(table, banks.items()):
@@ -340,15 +360,20 @@ class TileEngine:
         self.primary.nnfm_layers = list(banks)
         del keep
 
-    def nnfm_bank(self, feat, stride=1):
+    def nnfm_bank(self, feat, stride=1, patch=1):
         """The bank of a [C,h,w] feature map as a DeviceArray [rows, C]: its unit-normalised columns at every
         ``stride``-th row and column, raster order (stx_nnfm_bank).  Nothing travels through the host when
-        ``feat`` is on the device."""
+        ``feat`` is on the device.  ``patch`` 3: the unit 3 x 3 patches centred there, [rows, 9 C]
+        (stx_nnfm_patch_bank); a bank past the library's 2^31 offsets is refused before it is allocated."""
         ptr, mem, keep = _as_arg(feat)
         c, h, w = (int(v) for v in keep.shape)
-        rows = -(-h // stride) * -(-w // stride)
-        out = DeviceArray(self, (rows, c))
-        lib.call('stx_nnfm_bank', self.handle, ptr, mem, c, h, w, int(stride), out.ptr, lib.DEVICE)
+        rows = nnfm_bank_rows(c, h, w, stride, patch)
+        if patch == 1:
+            out = DeviceArray(self, (rows, c))
+            lib.call('stx_nnfm_bank', self.handle, ptr, mem, c, h, w, int(stride), out.ptr, lib.DEVICE)
+            return out
+        out = DeviceArray(self, (rows, 9 * c))
+        lib.call('stx_nnfm_patch_bank', self.handle, ptr, mem, c, h, w, 3, int(stride), out.ptr, lib.DEVICE)
         return out
 
     def concat_rows(self, parts):

@@ -195,16 +195,16 @@ class TileFarm:
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)
 
-    def set_nnfm_targets(self, banks, weights=None):
+    def set_nnfm_targets(self, banks, weights=None, patch=1):
         """Hands the NNFM banks (TileEngine.set_nnfm_targets) to every GPU, once each; call it behind
         ``set_contents_and_styles``."""
         for e in self.engines:
             e.sync()
         for e in self.primaries():
-            e.set_nnfm_targets(banks, weights)
+            e.set_nnfm_targets(banks, weights, patch)
 
-    def nnfm_bank(self, feat, stride=1):
-        return self.master.nnfm_bank(feat, stride)
+    def nnfm_bank(self, feat, stride=1, patch=1):
+        return self.master.nnfm_bank(feat, stride, patch)
 
     def _engines_for(self, n_tiles):
         """The engines that share a step of n_tiles tiles, creating extra per-GPU engines on

@@ -62,6 +62,12 @@ class NnfmTarget(ctypes.Structure):
                 ('bank', ctypes.c_void_p), ('mem', ctypes.c_int), ('weight', ctypes.c_double)]
 
 
+class NnfmPatchTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('patch', ctypes.c_int),
+                ('rows', ctypes.c_int), ('bank', ctypes.c_void_p), ('mem', ctypes.c_int),
+                ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -94,6 +100,7 @@ SIGNATURES = {
     'stx_set_style_masks': [_vp, ctypes.POINTER(StyleMask), _i],
     'stx_set_stat_targets': [_vp, ctypes.POINTER(StatTarget), _i],
     'stx_set_nnfm_targets': [_vp, ctypes.POINTER(NnfmTarget), _i],
+    'stx_set_nnfm_patch_targets': [_vp, ctypes.POINTER(NnfmPatchTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -103,6 +110,7 @@ SIGNATURES = {
     'stx_gram_matrix': [_vp, _vp, _i, _i, _i, _vp, _i],
     'stx_feature_stats': [_vp, _vp, _i, _i, _i, _vp, _vp, _i],
     'stx_nnfm_bank': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i],
+    'stx_nnfm_patch_bank': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i],
     'stx_image_cut_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
     'stx_image_put_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
     'stx_image_mask_map': [_vp, _vp, _i, _i, _i, _vp],
@@ -145,6 +153,7 @@ SIGNATURES = {
     'stx_op_masked_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, c_int_p, _vp, c_double_p],
     'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
+    'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],
     'stx_last_tile_flops': [_vp, c_double_p, c_double_p],

@@ -24,7 +24,8 @@ from PIL import Image
 
 from . import image_ops, lib
 from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_photo_options,
-                            check_nnfm_options, check_stat_options, ffloat, nnfm_layer_args, nnfm_stride,
+                            check_nnfm_options, check_stat_options, ffloat, nnfm_bank_rows, nnfm_layer_args,
+                            nnfm_patch, nnfm_stride,
                             stat_layer_args)
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
@@ -212,13 +213,15 @@ class StyleTransfer:
         self._stat_on = bool(check_stat_options(args, farm.layers()))
         self.stat_targets = None    # {layer: (mean [C], sd [C])}
         self._stat_weights = None   # {layer: weight} of the scale being optimised
-        # --nnfm-weight / --nnfm-layers / --nnfm-stride (the nearest-neighbour feature matching term; not options
-        # of the reference): per layer one bank of the style pictures' unit feature vectors, built and
+        # --nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch (the nearest-neighbour feature matching term;
+        # not options of the reference): per layer one bank of the style pictures' unit feature vectors (unit
+        # 3 x 3 patches of them with --nnfm-patch 3), built and
         # concatenated on the master GPU, kept where the Grams are kept; sent to the engines behind the targets.
         # Without the options nothing here runs.
         self._nnfm_on = bool(check_nnfm_options(args, farm.layers()))
         self.nnfm_banks = None      # {layer: DeviceArray [rows, C]}
         self._nnfm_weights = None   # {layer: weight} of the scale being optimised
+        self._nnfm_patch = 1        # --nnfm-patch of the banks in ``nnfm_banks``
         # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
         # reference tree; its transform is restated for the Haar wavelet only, at any level count
         raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
@@ -327,7 +330,7 @@ class StyleTransfer:
             raise ValueError('--nnfm-layers %s: no bank was taken there; with --style-multiscale the layers are '
                              'those of the first scale' % ' '.join(missing))
         self.farm.set_nnfm_targets({layer: self.nnfm_banks[layer] for layer in self._nnfm_weights},
-                                   self._nnfm_weights)
+                                   self._nnfm_weights, self._nnfm_patch)
 
     def _drop_nnfm(self):
         for bank in (self.nnfm_banks or {}).values():
@@ -335,7 +338,8 @@ class StyleTransfer:
         self.nnfm_banks = None
 
     def preprocess_images(self, content_images, style_images, content_layers, style_layers,
-                          roll=None, color_from=None, stat_layers=(), nnfm_layers=(), nnfm_stride=1):
+                          roll=None, color_from=None, stat_layers=(), nnfm_layers=(), nnfm_stride=1,
+                          nnfm_patch=1):
         """Targets of one scale: the style Grams, averaged with equal weight over every style
         image and ladder size (with --style-masks: over the ladder sizes of each style image, one
         style set per image), and the tiling-averaged content features
@@ -345,8 +349,9 @@ class StyleTransfer:
         colour mean and covariance of this picture before its features are taken.  ``stat_layers``
         (--stat-weight): the per-channel mean and sd of the same feature maps at these layers, averaged the
         same way, into ``self.stat_targets``.  ``nnfm_layers`` (--nnfm-weight): the banks of the same feature
-        maps at these layers (every ``nnfm_stride``-th row and column), built on the device and concatenated
-        over the variants in this order, into ``self.nnfm_banks``.  The features are taken at the union of the
+        maps at these layers (every ``nnfm_stride``-th row and column; with ``nnfm_patch`` 3 the 3 x 3 patches
+        centred there), built on the device and concatenated over the variants in this order, into
+        ``self.nnfm_banks``.  The features are taken at the union of the
         three lists, once."""
         farm, tile = self.farm, self.args.tile_size
         if roll is None:
@@ -375,7 +380,10 @@ class StyleTransfer:
                             stats = np.stack(farm.feature_stats(feat))
                             stat_total[layer] = stats if layer not in stat_total else stat_total[layer] + stats
                         if layer in bank_parts:
-                            bank_parts[layer].append(farm.nnfm_bank(feat, nnfm_stride))
+                            # (a bank past the library's offsets is refused before this part is allocated)
+                            nnfm_bank_rows(*feat.shape, nnfm_stride, nnfm_patch,
+                                           sum(part.shape[0] for part in bank_parts[layer]))
+                            bank_parts[layer].append(farm.nnfm_bank(feat, nnfm_stride, nnfm_patch))
                         if layer not in style_layers:
                             feat.free()
                             continue
@@ -392,9 +400,11 @@ class StyleTransfer:
                 self.stat_targets = {layer: tuple(stats / np.float32(count)) for layer, stats in stat_total.items()}
             if nnfm_layers:
                 self.nnfm_banks = {layer: self.engine.concat_rows(parts) for layer, parts in bank_parts.items()}
+                self._nnfm_patch = nnfm_patch
                 if roll is None:
                     print('NNFM bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0])
-                                                         for layer, bank in self.nnfm_banks.items()))
+                                                         for layer, bank in self.nnfm_banks.items()) +
+                          ('; patch %d' % nnfm_patch if nnfm_patch != 1 else ''))
         if roll is None:
             print('Preprocessing the content image(s)...')
         self.contents += [farm.prepare_features_device(self.pil_to_image(image), content_layers,
@@ -531,7 +541,8 @@ class StyleTransfer:
                                [] if jitter else content_layers, style_layers,
                                color_from=content_images[0] if self.preserve_color == 'match' else None,
                                stat_layers=stat_layers, nnfm_layers=nnfm_layers,
-                               nnfm_stride=nnfm_stride(args) if self._nnfm_on else 1)
+                               nnfm_stride=nnfm_stride(args) if self._nnfm_on else 1,
+                               nnfm_patch=nnfm_patch(args) if self._nnfm_on else 1)
         self.farm.set_contents_and_styles(self.contents, self.styles)
         self._send_stats()
         self._send_nnfm()

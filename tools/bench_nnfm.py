@@ -1,6 +1,7 @@
 """Device time of the nearest-neighbour feature matching term (nnfm.hip) on given arrays.
 
     python tools/bench_nnfm.py [--out profiles/nnfm_times.txt]
+    python tools/bench_nnfm.py --patch 3 [--out profiles/nnfm_patch_times.txt]
 
 stx_op_nnfm_terms at the blob shapes of a 1024^2 tile -- conv3_1 (256 x 256^2) and conv4_1 (512 x 128^2) --
 against the banks of a 512^2 and of a 1024^2 style picture at --nnfm-stride 1 and 2, and at the shapes of a
@@ -13,6 +14,10 @@ not part of a tile's term: their pass is outside the three groups.
 
 The search is priced against the matrix floor 3 x 2 n M C flop (three fp16 products per fp32-class product)
 at 2.5 PFLOP/s, the dense fp16 rate of the MI355X.
+
+--patch 3: stx_op_nnfm_patch_terms (--nnfm-patch 3) at the same shapes, K = 9 C.  Its yardstick is the plain
+search run in the same call on a synthetic blob of 9 C channels with the same n and M: the same flops, and what
+a materialised [n][9 C] query array would cost the search (`plain 9C`, with the ratio patch / plain).
 """
 
 import argparse
@@ -40,14 +45,19 @@ def unit_rows(rng, m, c):
     return b / np.linalg.norm(b, axis=1, keepdims=True)
 
 
-def measure(eng, rng, c, side, rows, reps):
+def measure(eng, rng, c, side, rows, reps, patch=1):
+    """Median ms of the term's three groups; ``patch`` 3: the patch term of a c-channel blob (bank rows of 9 c)."""
     feat = eng.to_device(np.maximum(rng.standard_normal((c, side, side)), 0).astype(np.float32) + np.float32(1e-3))
-    bank = eng.to_device(unit_rows(rng, rows, c))
+    bank = eng.to_device(unit_rows(rng, rows, patch * patch * c))
     s_out = eng.empty((c, side, side))
     idx = eng.empty((side * side,), np.int32)
     out = (ctypes.c_double * 2)()
-    call = lambda: lib.call('stx_op_nnfm_terms', eng.handle, feat.ptr, c, side, side, bank.ptr, rows, s_out.ptr,
-                            idx.ptr, out)
+    if patch == 1:
+        call = lambda: lib.call('stx_op_nnfm_terms', eng.handle, feat.ptr, c, side, side, bank.ptr, rows, s_out.ptr,
+                                idx.ptr, out)
+    else:
+        call = lambda: lib.call('stx_op_nnfm_patch_terms', eng.handle, feat.ptr, c, side, side, patch, bank.ptr, rows,
+                                s_out.ptr, idx.ptr, out)
     for _ in range(2):
         call()
     times = {'prepare': [], 'search': [], 'grad': []}
@@ -56,7 +66,7 @@ def measure(eng, rng, c, side, rows, reps):
     for _ in range(reps):
         call()
         for label, ms, _ in eng.profile_read():
-            words = label.split()
+            words = [word for word in label.split() if word != 'patch']
             if words[0] == 'nnfm' and words[1] in times:
                 times[words[1]].append(ms)
                 if words[1] == 'search':
@@ -67,16 +77,50 @@ def measure(eng, rng, c, side, rows, reps):
     return {k: float(np.median(v)) for k, v in times.items()}, slices
 
 
+def patch_lines(eng, rng, opts):
+    lines = ['# --nnfm-patch 3: stx_op_nnfm_patch_terms, device-event ms per group (median of %d after 2 warm-up calls)'
+             % opts.reps,
+             '# device: %s' % torch.cuda.get_device_name(0),
+             '# floor = 3 x 2 n M 9C flop at 2.5 PFLOP/s; of floor = floor / search',
+             '# plain 9C = the search of stx_op_nnfm_terms on a blob of 9 C channels, same n and M; ratio = search / plain 9C',
+             '%6s %8s %4s %7s %7s %6s %6s %9s %9s %9s %9s %9s %8s %9s %6s'
+             % ('tile', 'blob', 'C', 'n', 'M', 'stride', 'slices', 'prepare', 'search', 'grad', 'total', 'floor ms',
+                'of floor', 'plain 9C', 'ratio')]
+    for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
+        for blob, c, side, style_side in shapes:
+            for stride in (1, 2):
+                rows = (-(-style_side // stride)) ** 2
+                t, slices = measure(eng, rng, c, side, rows, opts.reps, 3)
+                plain, _ = measure(eng, rng, 9 * c, side, rows, opts.reps)
+                n = side * side
+                floor_ms = 6.0 * n * rows * 9 * c / FP16_FLOPS * 1e3
+                lines.append('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f %9.4f %6.3f'
+                             % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
+                                sum(t.values()), floor_ms, floor_ms / t['search'], plain['search'],
+                                t['search'] / plain['search']))
+                print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--patch', type=int, default=1, choices=(1, 3))
     opts = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_nnfm: no GPU')
     net = builtin_net('vgg19')
     eng = TileEngine(net, 0, synthetic_weights(net, 0))
     rng = np.random.RandomState(0)
+    if opts.patch == 3:
+        text = '\n'.join(patch_lines(eng, rng, opts)) + '\n'
+        if opts.out:
+            os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
+            with open(opts.out, 'w') as f:
+                f.write(text)
+        eng.close()
+        return
     lines = ['# --nnfm-weight: stx_op_nnfm_terms, device-event ms per group (median of %d after 2 warm-up calls)'
              % opts.reps,
              '# device: %s' % torch.cuda.get_device_name(0),
