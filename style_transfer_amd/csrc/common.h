@@ -509,39 +509,33 @@ struct NnfmScratch {
     float *part_score;              // [slices][n], or null with one slice
     int *part_idx;
     float *partials;                // ceil(n / 64) of (2/n) sum (1 - c_i), then as many of sum |S|
-    double *work;                   // patch 3: nnfm_patch_work_floats(n) floats of nnfm_patch_prepare_launch, else null
+    double *work;                   // patch 3: nnfm_patch_work_floats(n) floats of nnfm_prepare_launch, else null
     float *cosv;                    // patch 3: c_p [n], else null
 };
 NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch = 1);
-// One pass over feat [C][h][w]: per picked column (y % stride == 0 and x % stride == 0, raster order) 1 / |f|
-// (0 for a zero column) into inv_r, the pieces of f / |f| 2^13 into hi / lo, f / |f| as float32 rows into
-// rows_out -- each output optional (hi and lo together).
-int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, float *inv_r,
-                        unsigned short *hi, unsigned short *lo, float *rows_out);
-// the pieces of bank 2^13, bank [M][C] given as rows
-int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsigned short *hi, unsigned short *lo);
-// idx_out[i] = argmax_j x_i . b_j, the lowest j among equal scores
-int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigned short *bhi, const unsigned short *blo,
-                       int M, int C, int *idx_out);
-// sgrad = S [C][n]; *n_parts partials of E, then as many of sum |S|
-int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int n, const float *inv_r, const float *bank, int M,
-                     const int *idx, float *sgrad, float *partials, int *n_parts);
-// The 3 x 3 patch form (stx_set_nnfm_patch_targets): pixel p's patch is the 9 C vector of the columns at p + tap,
-// tap-major (dy outer, dx inner, (-1, -1) first), zero outside the map; bank [M][9 C] of unit or zero rows.
-// floats (8-byte aligned) that nnfm_patch_prepare_launch works in: the column norms^2 and their block maxima
+// The term's three steps, for both forms.  patch 1: columns of C channels against bank rows of C.  patch 3
+// (stx_set_nnfm_patch_targets): pixel p's patch is the 9 C vector of the columns at p + tap, tap-major (dy outer,
+// dx inner, (-1, -1) first), zero outside the map, against bank rows [M][9 C] of unit or zero rows.
+// floats (8-byte aligned) that nnfm_prepare_launch works in at patch 3: the column norms^2 and their block maxima
 size_t nnfm_patch_work_floats(int n);
-// feat [C][h][w].  hi / lo (stride 1 only): 1 / |P_p| into inv_R and the pieces of the COLUMNS [n][C] under one
-// power of two for the whole blob.  rows_out: the unit patches centred at y % stride == 0 and x % stride == 0,
-// raster order, as float32 rows [rows][9 C] (a zero patch stays a zero row).  One of the two.
-int nnfm_patch_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, double *work,
-                              float *inv_R, unsigned short *hi, unsigned short *lo, float *rows_out);
-// idx_out[p] = argmax_j P_p . b_j, the lowest j among equal scores: the search above with 9 C / kNnfmK stages per
-// bank block and the query operand gathered from x's [n][C] pieces (bhi / blo: nnfm_split_rows_launch at 9 C)
-int nnfm_patch_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, const unsigned short *bhi,
-                             const unsigned short *blo, int M, int C, int *idx_out);
-// cosv [n] = c_p, then sgrad = S [C][n] in the gather form; partials as nnfm_grad_launch leaves them
-int nnfm_patch_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, const float *inv_R, const float *bank,
-                           int M, const int *idx, float *cosv, float *sgrad, float *partials, int *n_parts);
+// feat [C][h][w], outputs per picked position (y % stride == 0 and x % stride == 0, raster order).
+// patch 1, one pass, each output optional (hi and lo together): 1 / |f| (0 for a zero column) into inv_r, the
+// pieces of f / |f| 2^13 into hi / lo, f / |f| as float32 rows into rows_out; work is not used.
+// patch 3, two passes through work, one of the two: hi / lo (stride 1 only) -- 1 / |P_p| into inv_r and the pieces
+// of the COLUMNS [n][C] under one power of two for the whole blob; or rows_out -- the unit patches as float32 rows
+// [rows][9 C] (a zero patch stays a zero row).
+int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, int stride, double *work,
+                        float *inv_r, unsigned short *hi, unsigned short *lo, float *rows_out);
+// the pieces of bank 2^13, bank [M][C] given as rows (C: the whole width of a row)
+int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsigned short *hi, unsigned short *lo);
+// idx_out[i] = argmax_j x_i . b_j (patch 3: P_p . b_j, the query operand gathered from x's [n][C] pieces), the
+// lowest j among equal scores.  pieces: the bank's, [M][patch^2 C] hi then lo (nnfm_split_rows_launch)
+int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int patch, const unsigned short *pieces,
+                       int M, int C, int *idx_out);
+// sgrad = S [C][n] (patch 3: x.cosv = c_p first, then S in the gather form; the bank aligned to 16 bytes);
+// *n_parts partials of E in x.partials, then as many of sum |S|
+int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, const NnfmScratch &x,
+                     const float *bank, int M, const int *idx, float *sgrad, int *n_parts);
 
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,

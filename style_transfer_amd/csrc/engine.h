@@ -119,9 +119,8 @@ struct NnfmTarget {
     double weight;
     std::unique_ptr<DevBuf> bank, pieces;
     int patch = 1;
-    int width() const { return patch * patch * C; }
-    const unsigned short *hi() const { return static_cast<const unsigned short *>(pieces->ptr); }
-    const unsigned short *lo() const { return hi() + (size_t)rows * width(); }
+    // [rows][patch^2 C] hi, then as many lo
+    const unsigned short *pieces_hi_lo() const { return static_cast<const unsigned short *>(pieces->ptr); }
 };
 
 struct LossTerm {
@@ -426,11 +425,11 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
 // The nearest-neighbour term of a blob (nnfm.hip): prepare -> search (-> merge) -> S into sgrad.
 // sc[2] = {E, sum |S|}, both from partials whose final sums join `defer` or are launched here.  scratch:
 // nnfm_scratch_floats(C, h * w, rows, patch) floats that outlive the call like term_scratch.  idx_out (or null):
-// the winning rows [h * w].  patch 3: the 3 x 3 patch form, bank rows of 9 C channels.
-int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *bank,
-                      const unsigned short *bank_hi, const unsigned short *bank_lo, int rows, float *sgrad,
-                      int *idx_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer,
-                      int patch = 1);
+// the winning rows [h * w].  patch 1, or 3: the 3 x 3 patch form, bank rows of 9 C channels.  pieces: the bank's
+// fp16 pieces, [rows][patch^2 C] hi then lo (nnfm_split_rows_launch).
+int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int patch,
+                      const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
+                      const std::string &name, float *scratch, std::vector<SumJob> *defer);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

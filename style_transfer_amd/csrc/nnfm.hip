@@ -21,9 +21,14 @@
 //   4. nnfm_grad_kernel      per column: gathers the float32 row j_i, recomputes c_i with float32 fma in
 //                            channel order (NOT the search's score: E and S are functions of (F, B, j)),
 //                            writes S in [C][n] layout and leaves the partials of sum (1 - c_i) and sum |S|.
-// The 3 x 3 patch form (stx_set_nnfm_patch_targets; the nnfm_patch_* kernels below) is the same search with
-// K = 9 C and a gathered query operand: no [n][9 C] array is written anywhere.  Its prepare pass splits the
-// columns under one scale for the whole blob, its gradient gathers the nine patches a pixel belongs to.
+// The 3 x 3 patch form (stx_set_nnfm_patch_targets) is the same term over the 9 C vectors of a pixel's patch.
+// There is ONE search, nnfm_search_kernel<PATCH>, with two fetchers of the query operand: a row of the [n][C]
+// pieces (plain), or 32 channels of the neighbour p + tap gathered from those pieces with zeros outside the map
+// (patch; K = 9 C, and no [n][9 C] array is written anywhere).  Staging, products, the argmax rule, the clamps
+// and the merges exist once.  The prepare and gradient passes are different algorithms and stay separate
+// kernels: the patch form splits the columns under one scale for the whole blob (nnfm_patch_norms_kernel,
+// nnfm_patch_rows_kernel) and its gradient gathers the nine patches a pixel belongs to (nnfm_patch_cos_kernel,
+// nnfm_patch_grad_kernel).  The launches below take the patch size and choose among them.
 
 #include <algorithm>
 #include <climits>
@@ -230,9 +235,28 @@ __device__ __forceinline__ void take_better(float s, int j, float &best_s, int &
 
 typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
 
+// The queries of a search: n of them, and for the patch form the width of their map.  A struct of one int or of
+// two so that each instantiation keeps the kernel-argument layout -- and with it the instruction sequence -- that
+// its form had as a kernel of its own (int n / int n, int w in this place); the plain form's w is a constant.
+template <bool PATCH>
+struct NnfmQueries {
+    int n;
+    static constexpr int w = 0;
+};
+template <>
+struct NnfmQueries<true> {
+    int n, w;
+};
+
 // grid (query blocks, slices).  One slice: idx_out [n].  Several: part_score / part_idx [slices][n].
+// A bank row has CB channels: C, and the query operand is the row of the [n][C] pieces -- or, PATCH, 9 C
+// tap-major, and the query operand is gathered from those pieces of the w-wide map: stage t of a row reads 32
+// channels of pixel p + tap(t), found from p's (y, x) -- the right neighbour of a row's last pixel is padding --
+// and zeros outside the map.
+template <bool PATCH>
 __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__restrict__ xhi, const _Float16 *__restrict__ xlo,
-                                                          int n, const _Float16 *__restrict__ bhi,
+                                                          const NnfmQueries<PATCH> queries,
+                                                          const _Float16 *__restrict__ bhi,
                                                           const _Float16 *__restrict__ blo, int M, int C, int b_blocks,
                                                           int blocks_per_slice, int *__restrict__ idx_out,
                                                           float *__restrict__ part_score, int *__restrict__ part_idx) {
@@ -241,155 +265,44 @@ __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__rest
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wq = wave & 1, wb = wave >> 1;        // the wave's 64 queries x 64 bank rows of the 128 x 128 block
     const int r = lane & 31, half = lane >> 5;
+    const int n = queries.n, w = queries.w;
     const int q0 = blockIdx.x * kNnfmQ;
     const int bb0 = blockIdx.y * blocks_per_slice, bb1 = min(bb0 + blocks_per_slice, b_blocks);
-    const int KC = C / kNnfmK, T = (bb1 - bb0) * KC;
-
-    // what this thread stages: two 16-byte chunks of each of the four arrays
-    const _Float16 *const arr[4] = {xhi, xlo, bhi, blo};
-    u32x4n pre[4][2];
-    const auto prefetch = [&](int t) {
-        const int bb = bb0 + t / KC, k0 = (t % KC) * kNnfmK;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
-            const size_t q = (size_t)min(q0 + row, n - 1), j = (size_t)min(bb * kNnfmB + row, M - 1);    // padding re-reads the last row
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-                pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + (a < 2 ? q : j) * C + k0 + ch * 8);
-        }
-    };
-    const auto stage = [&]() {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-                *reinterpret_cast<u32x4n *>(lds + (a * 128 + row) * kLdsRow + ch * 16) = pre[a][u];
-        }
-    };
-    const auto frag = [&](int a, int row, int ks) {
-        return *reinterpret_cast<const f16x8h *>(lds + (a * 128 + row) * kLdsRow + ks * 32 + half * 16);
-    };
-
-    f32x16h acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[i][k][v] = 0.f;
-    float best_s[2] = {-INFINITY, -INFINITY};
-    int best_j[2] = {INT_MAX, INT_MAX};
-
-    prefetch(0);
-    for (int t = 0; t < T; ++t) {
-        __syncthreads();        // every wave has read the stage before
-        stage();
-        __syncthreads();
-        if (t + 1 < T) prefetch(t + 1);
-#pragma unroll
-        for (int ks = 0; ks < kNnfmK / 16; ++ks) {
-            f16x8h a_hi[2], a_lo[2], b_hi[2], b_lo[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                b_hi[i] = frag(0, 64 * wq + 32 * i + r, ks);
-                b_lo[i] = frag(1, 64 * wq + 32 * i + r, ks);
-                a_hi[i] = frag(2, 64 * wb + 32 * i + r, ks);
-                a_lo[i] = frag(3, 64 * wb + 32 * i + r, ks);
-            }
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq)
-#pragma unroll
-                for (int tb = 0; tb < 2; ++tb)
-                    acc[tq][tb] = mfma_split3(a_hi[tb], a_lo[tb], b_hi[tq], b_lo[tq], acc[tq][tb]);
-        }
-        if (t % KC == KC - 1) {     // the block's scores are complete: D[row = bank][col = query]
-            const int j0 = (bb0 + t / KC) * kNnfmB + 64 * wb + 4 * half;
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq)
-#pragma unroll
-                for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-                    for (int v = 0; v < 16; ++v) {
-                        const int j = j0 + 32 * tb + (v & 3) + 8 * (v >> 2);
-                        if (j < M) take_better(acc[tq][tb][v], j, best_s[tq], best_j[tq]);     // padding never wins
-                        acc[tq][tb][v] = 0.f;
-                    }
-        }
-    }
-    // a query's four candidates: two lane halves x the two waves that split the bank rows
-    __syncthreads();
-    float *const cand_s = reinterpret_cast<float *>(lds);
-    int *const cand_j = reinterpret_cast<int *>(lds + kNnfmQ * 4 * sizeof(float));
-#pragma unroll
-    for (int tq = 0; tq < 2; ++tq) {
-        const int q = 64 * wq + 32 * tq + r;
-        cand_s[q * 4 + wb * 2 + half] = best_s[tq];
-        cand_j[q * 4 + wb * 2 + half] = best_j[tq];
-    }
-    __syncthreads();
-    if (threadIdx.x < kNnfmQ && q0 + (int)threadIdx.x < n) {
-        float s = cand_s[threadIdx.x * 4];
-        int j = cand_j[threadIdx.x * 4];
-#pragma unroll
-        for (int k = 1; k < 4; ++k) take_better(cand_s[threadIdx.x * 4 + k], cand_j[threadIdx.x * 4 + k], s, j);
-        if (j == INT_MAX) j = 0;        // (scores that are not numbers: nothing was taken)
-        if (gridDim.y == 1) {
-            idx_out[q0 + threadIdx.x] = j;
-        } else {
-            part_score[(size_t)blockIdx.y * n + q0 + threadIdx.x] = s;
-            part_idx[(size_t)blockIdx.y * n + q0 + threadIdx.x] = j;
-        }
-    }
-}
-
-// The 3 x 3 patch search: nnfm_search_kernel with 9 C / kNnfmK stages per bank block (kept as a sibling so that
-// the kernel above stays instruction for instruction what it was).  A bank row has 9 C channels, tap-major; the
-// query operand is gathered from the [n][C] pieces of the w-wide map: stage t of a row reads 32 channels of
-// pixel p + tap(t), found from p's (y, x) -- the right neighbour of a row's last pixel is padding -- and zeros
-// outside the map.  Staging layout, products, argmax rule, clamps and the final merge are the kernel's above.
-__global__ __launch_bounds__(256) void nnfm_patch_search_kernel(const _Float16 *__restrict__ xhi,
-                                                                const _Float16 *__restrict__ xlo, int n, int w,
-                                                                const _Float16 *__restrict__ bhi,
-                                                                const _Float16 *__restrict__ blo, int M, int C,
-                                                                int b_blocks, int blocks_per_slice,
-                                                                int *__restrict__ idx_out, float *__restrict__ part_score,
-                                                                int *__restrict__ part_idx) {
-    // [X hi | X lo | B hi | B lo][row][kNnfmK halves + padding]; reused for the workgroup's final merge
-    __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 128 * kLdsRow];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wq = wave & 1, wb = wave >> 1;        // the wave's 64 queries x 64 bank rows of the 128 x 128 block
-    const int r = lane & 31, half = lane >> 5;
-    const int q0 = blockIdx.x * kNnfmQ;
-    const int bb0 = blockIdx.y * blocks_per_slice, bb1 = min(bb0 + blocks_per_slice, b_blocks);
-    const int CB = 9 * C;       // channels of a bank row
+    const int CB = PATCH ? 9 * C : C;       // channels of a bank row
     const int KC = CB / kNnfmK, T = (bb1 - bb0) * KC;
 
     // what this thread stages: two 16-byte chunks of each of the four arrays
     const _Float16 *const arr[4] = {xhi, xlo, bhi, blo};
     u32x4n pre[4][2];
-    int qy[2], qx[2];
+    [[maybe_unused]] int qy[2], qx[2];      // PATCH: the pixels of this thread's two query rows
+    if constexpr (PATCH) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int q = min(q0 + (int)((threadIdx.x + 256 * u) >> 2), n - 1);     // padding re-reads the last patch
-        qy[u] = q / w;
-        qx[u] = q - qy[u] * w;
+        for (int u = 0; u < 2; ++u) {
+            const int q = min(q0 + (int)((threadIdx.x + 256 * u) >> 2), n - 1);     // padding re-reads the last patch
+            qy[u] = q / w;
+            qx[u] = q - qy[u] * w;
+        }
     }
     const auto prefetch = [&](int t) {
         const int bb = bb0 + t / KC, k0 = (t % KC) * kNnfmK;
-        const int tap = k0 / C, c0 = k0 - tap * C;
+        [[maybe_unused]] const int tap = k0 / C, c0 = k0 - tap * C;             // PATCH: the stage's neighbour
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int item = threadIdx.x + 256 * u, row = item >> 2, ch = item & 3;
-            const size_t j = (size_t)min(bb * kNnfmB + row, M - 1);             // ... and the last row
-            const int yy = qy[u] + tap / 3 - 1, xx = qx[u] + tap % 3 - 1;
-            const bool inside = (unsigned)xx < (unsigned)w && yy >= 0 && (size_t)yy * w + xx < (size_t)n;
-            const size_t at = inside ? ((size_t)yy * w + xx) * C + c0 + ch * 8 : 0;
+            const size_t j = (size_t)min(bb * kNnfmB + row, M - 1);             // padding re-reads the last row
+            if constexpr (PATCH) {
+                const int yy = qy[u] + tap / 3 - 1, xx = qx[u] + tap % 3 - 1;
+                const bool inside = (unsigned)xx < (unsigned)w && yy >= 0 && (size_t)yy * w + xx < (size_t)n;
+                const size_t at = inside ? ((size_t)yy * w + xx) * C + c0 + ch * 8 : 0;
 #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + at);
-                if (!inside) pre[a][u] = u32x4n{0u, 0u, 0u, 0u};
+                for (int a = 0; a < 2; ++a) {
+                    pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + at);
+                    if (!inside) pre[a][u] = u32x4n{0u, 0u, 0u, 0u};
+                }
+            } else {
+                const size_t q = (size_t)min(q0 + row, n - 1);                  // ... and the last query
+#pragma unroll
+                for (int a = 0; a < 2; ++a) pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + q * C + k0 + ch * 8);
             }
 #pragma unroll
             for (int a = 2; a < 4; ++a) pre[a][u] = *reinterpret_cast<const u32x4n *>(arr[a] + j * CB + k0 + ch * 8);
@@ -624,17 +537,20 @@ __global__ __launch_bounds__(64) void nnfm_patch_grad_kernel(const float *__rest
     }
 }
 
-int check_shape(const char *who, int C, long long n, long long M) {
-    if (C <= 0 || n <= 0 || M <= 0) {
-        set_error("%s: %d channels, %lld columns, %lld bank rows", who, C, n, M);
+// n columns of C channels against M bank rows of patch x patch x C
+int check_shape(const char *who, int C, long long n, long long M, int patch) {
+    const char *const what = patch == 3 ? "patches" : "columns";
+    if ((patch != 1 && patch != 3) || C <= 0 || n <= 0 || M <= 0) {
+        set_error("%s: patch %d, %d channels, %lld %s, %lld bank rows", who, patch, C, n, what, M);
         return STX_ERR_ARG;
     }
     if (C % 64 != 0) {
         set_error("%s: the channel count %d is not a multiple of 64", who, C);
         return STX_ERR_UNSUPPORTED;
     }
-    if (n >= (1ll << 31) / C || M >= (1ll << 31) / C) {
-        set_error("%s: %lld columns against %lld bank rows of %d channels exceed 32-bit offsets", who, n, M, C);
+    const long long width = (long long)patch * patch * C;
+    if (n >= (1ll << 31) / C || M >= (1ll << 31) / width) {
+        set_error("%s: %lld %s against %lld bank rows of %lld channels exceed 32-bit offsets", who, n, what, M, width);
         return STX_ERR_UNSUPPORTED;
     }
     return STX_OK;
@@ -697,24 +613,34 @@ NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch) {
     return s;
 }
 
-int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, float *inv_r,
-                        unsigned short *hi, unsigned short *lo, float *rows_out) {
-    if (stride < 1 || h <= 0 || w <= 0) {
+int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, int stride, double *work,
+                        float *inv_r, unsigned short *hi, unsigned short *lo, float *rows_out) {
+    const bool p3 = patch == 3;
+    if (stride < 1 || h <= 0 || w <= 0 || (p3 && ((rows_out && hi) || (hi && stride != 1)))) {
         set_error("nnfm_prepare_launch: a %dx%d map with stride %d", h, w, stride);
         return STX_ERR_ARG;
     }
     const int oh = ceil_div(h, stride), ow = ceil_div(w, stride);
-    STX_TRY(check_shape("nnfm_prepare_launch", C, (long long)h * w, (long long)oh * ow));
-    const int n_out = oh * ow;
-    nnfm_prepare_kernel<<<ceil_div(n_out, 64), 256, 0, s>>>(feat, C, h, w, stride, ow, n_out, inv_r,
-                                                           reinterpret_cast<_Float16 *>(hi),
-                                                           reinterpret_cast<_Float16 *>(lo), rows_out);
+    STX_TRY(check_shape("nnfm_prepare_launch", C, (long long)h * w, (long long)oh * ow, patch));
+    const int n = h * w, n_out = oh * ow;
+    _Float16 *const phi = reinterpret_cast<_Float16 *>(hi), *const plo = reinterpret_cast<_Float16 *>(lo);
+    if (p3) {
+        const int blocks = ceil_div(n, 64);
+        double *const norm2 = work, *const bmax = work + round64(n);
+        nnfm_patch_norms_kernel<<<blocks, 256, 0, s>>>(feat, C, n, norm2, bmax);
+        STX_CHECK_LAUNCH();
+        nnfm_patch_rows_kernel<<<dim3(ceil_div(n_out, 64), rows_out ? 9 : 1), 256, 0, s>>>(
+            feat, C, h, w, stride, ow, n_out, norm2, bmax, blocks, inv_r, phi, plo, rows_out);
+    } else {
+        nnfm_prepare_kernel<<<ceil_div(n_out, 64), 256, 0, s>>>(feat, C, h, w, stride, ow, n_out, inv_r, phi, plo,
+                                                               rows_out);
+    }
     STX_CHECK_LAUNCH();
     return STX_OK;
 }
 
 int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsigned short *hi, unsigned short *lo) {
-    STX_TRY(check_shape("nnfm_split_rows_launch", C, 1, M));
+    STX_TRY(check_shape("nnfm_split_rows_launch", C, 1, M, 1));
     const size_t octets = (size_t)M * C / 8;
     const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
     nnfm_split_rows_kernel<<<(unsigned)((octets + 255) / 256), 256, 0, s>>>(bank, octets, vec,
@@ -724,14 +650,21 @@ int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsig
     return STX_OK;
 }
 
-int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigned short *bhi, const unsigned short *blo,
+int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int patch, const unsigned short *pieces,
                        int M, int C, int *idx_out) {
-    STX_TRY(check_shape("nnfm_search_launch", C, n, M));
+    const int n = h * w;
+    STX_TRY(check_shape("nnfm_search_launch", C, n, M, patch));
     const NnfmPlan p = nnfm_plan(n, M);
-    nnfm_search_kernel<<<dim3(p.q_blocks, p.slices), 256, 0, s>>>(
-        reinterpret_cast<const _Float16 *>(x.xhi), reinterpret_cast<const _Float16 *>(x.xlo), n,
-        reinterpret_cast<const _Float16 *>(bhi), reinterpret_cast<const _Float16 *>(blo), M, C, p.b_blocks,
-        p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+    const dim3 grid(p.q_blocks, p.slices);
+    const _Float16 *const xhi = reinterpret_cast<const _Float16 *>(x.xhi);
+    const _Float16 *const xlo = reinterpret_cast<const _Float16 *>(x.xlo);
+    const _Float16 *const bhi = reinterpret_cast<const _Float16 *>(pieces), *const blo = bhi + (size_t)M * patch * patch * C;
+    if (patch == 3)
+        nnfm_search_kernel<true><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<true>{n, w}, bhi, blo, M, C, p.b_blocks,
+                                                      p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+    else
+        nnfm_search_kernel<false><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<false>{n}, bhi, blo, M, C, p.b_blocks,
+                                                       p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
     STX_CHECK_LAUNCH();
     if (p.slices > 1) {
         nnfm_merge_kernel<<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
@@ -740,82 +673,22 @@ int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigne
     return STX_OK;
 }
 
-int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int n, const float *inv_r, const float *bank, int M,
-                     const int *idx, float *sgrad, float *partials, int *n_parts) {
-    STX_TRY(check_shape("nnfm_grad_launch", C, n, M));
-    const int blocks = ceil_div(n, 64);
+int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, const NnfmScratch &x,
+                     const float *bank, int M, const int *idx, float *sgrad, int *n_parts) {
+    const int n = h * w, blocks = ceil_div(n, 64);
+    STX_TRY(check_shape("nnfm_grad_launch", C, n, M, patch));
     const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
-    nnfm_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, n, inv_r, bank, M, vec, idx, sgrad, partials);
-    STX_CHECK_LAUNCH();
-    *n_parts = blocks;
-    return STX_OK;
-}
-
-// ------------------------------------------------------------------------------------ 3 x 3 patches
-static int check_patch_shape(const char *who, int C, long long n, long long M) {
-    if (C <= 0 || n <= 0 || M <= 0) {
-        set_error("%s: %d channels, %lld patches, %lld bank rows", who, C, n, M);
-        return STX_ERR_ARG;
-    }
-    if (C % 64 != 0) {
-        set_error("%s: the channel count %d is not a multiple of 64", who, C);
-        return STX_ERR_UNSUPPORTED;
-    }
-    if (n >= (1ll << 31) / C || M >= (1ll << 31) / (9ll * C)) {
-        set_error("%s: %lld patches against %lld bank rows of 9 x %d channels exceed 32-bit offsets", who, n, M, C);
-        return STX_ERR_UNSUPPORTED;
-    }
-    return STX_OK;
-}
-
-int nnfm_patch_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, int stride, double *work,
-                              float *inv_R, unsigned short *hi, unsigned short *lo, float *rows_out) {
-    if (stride < 1 || h <= 0 || w <= 0 || (rows_out && hi) || (hi && stride != 1)) {
-        set_error("nnfm_patch_prepare_launch: a %dx%d map with stride %d", h, w, stride);
-        return STX_ERR_ARG;
-    }
-    const int oh = ceil_div(h, stride), ow = ceil_div(w, stride);
-    STX_TRY(check_patch_shape("nnfm_patch_prepare_launch", C, (long long)h * w, (long long)oh * ow));
-    const int n = h * w, n_out = oh * ow, blocks = ceil_div(n, 64);
-    double *const norm2 = work, *const bmax = work + round64(n);
-    nnfm_patch_norms_kernel<<<blocks, 256, 0, s>>>(feat, C, n, norm2, bmax);
-    STX_CHECK_LAUNCH();
-    nnfm_patch_rows_kernel<<<dim3(ceil_div(n_out, 64), rows_out ? 9 : 1), 256, 0, s>>>(
-        feat, C, h, w, stride, ow, n_out, norm2, bmax, blocks, inv_R, reinterpret_cast<_Float16 *>(hi),
-        reinterpret_cast<_Float16 *>(lo), rows_out);
-    STX_CHECK_LAUNCH();
-    return STX_OK;
-}
-
-int nnfm_patch_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, const unsigned short *bhi,
-                             const unsigned short *blo, int M, int C, int *idx_out) {
-    const int n = h * w;
-    STX_TRY(check_patch_shape("nnfm_patch_search_launch", C, n, M));
-    const NnfmPlan p = nnfm_plan(n, M);
-    nnfm_patch_search_kernel<<<dim3(p.q_blocks, p.slices), 256, 0, s>>>(
-        reinterpret_cast<const _Float16 *>(x.xhi), reinterpret_cast<const _Float16 *>(x.xlo), n, w,
-        reinterpret_cast<const _Float16 *>(bhi), reinterpret_cast<const _Float16 *>(blo), M, C, p.b_blocks,
-        p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
-    STX_CHECK_LAUNCH();
-    if (p.slices > 1) {
-        nnfm_merge_kernel<<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
+    if (patch == 3) {
+        if (!vec) {
+            set_error("nnfm_grad_launch: the bank is not aligned to 16 bytes");
+            return STX_ERR_UNSUPPORTED;
+        }
+        nnfm_patch_cos_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, x.inv_r, bank, M, idx, x.cosv);
         STX_CHECK_LAUNCH();
+        nnfm_patch_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, x.inv_r, bank, M, idx, x.cosv, sgrad, x.partials);
+    } else {
+        nnfm_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, n, x.inv_r, bank, M, vec, idx, sgrad, x.partials);
     }
-    return STX_OK;
-}
-
-int nnfm_patch_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, const float *inv_R, const float *bank,
-                           int M, const int *idx, float *cosv, float *sgrad, float *partials, int *n_parts) {
-    const int n = h * w;
-    STX_TRY(check_patch_shape("nnfm_patch_grad_launch", C, n, M));
-    if (reinterpret_cast<uintptr_t>(bank) % 16 != 0) {
-        set_error("nnfm_patch_grad_launch: the bank is not aligned to 16 bytes");
-        return STX_ERR_UNSUPPORTED;
-    }
-    const int blocks = ceil_div(n, 64);
-    nnfm_patch_cos_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, inv_R, bank, M, idx, cosv);
-    STX_CHECK_LAUNCH();
-    nnfm_patch_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, inv_R, bank, M, idx, cosv, sgrad, partials);
     STX_CHECK_LAUNCH();
     *n_parts = blocks;
     return STX_OK;

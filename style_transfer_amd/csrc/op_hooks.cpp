@@ -197,78 +197,61 @@ int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, 
     return STX_OK;
 }
 
-int stx_op_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *bank, int rows,
-                      float *s_out, int *index_out, double out[2]) {
-    if (!e || !feat || !bank || !s_out || !index_out || !out || C <= 0 || h <= 0 || w <= 0 || rows <= 0) {
-        set_error("stx_op_nnfm_terms: bad arguments");
+// Both NNFM hooks.  Patch 1 is the plain term and speaks as stx_op_nnfm_terms through either entry point; every
+// other patch size speaks as stx_op_nnfm_patch_terms: `plain` picks between the two entry points' messages, which
+// are the ones they had as two functions.  Nothing is written before the arguments are accepted.  (An error behind
+// take() leaves the scalar arena empty, as in the other term hooks.)
+static int hook_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, const float *bank, int rows,
+                           float *s_out, int *index_out, double out[2]) {
+    const bool plain = patch == 1;
+    const char *const who = plain ? "stx_op_nnfm_terms" : "stx_op_nnfm_patch_terms";
+    if ((!plain && patch != 3) || !e || !feat || !bank || !s_out || !index_out || !out || C <= 0 || h <= 0 || w <= 0 ||
+        rows <= 0) {
+        if (plain)
+            set_error("%s: bad arguments", who);
+        else
+            set_error("%s: bad arguments (patch %d; 1 or 3 is expected)", who, patch);
         return STX_ERR_ARG;
     }
     if (C % 64 != 0) {
-        set_error("stx_op_nnfm_terms: the channel count %d is not a multiple of 64", C);
+        set_error("%s: the channel count %d is not a multiple of 64", who, C);
         return STX_ERR_UNSUPPORTED;
     }
-    if ((long long)h * w >= (1ll << 31) / C || rows >= (1ll << 31) / C) {
-        set_error("stx_op_nnfm_terms: %lld columns against %d rows of %d channels exceed 32-bit offsets",
-                  (long long)h * w, rows, C);
+    const long long n = (long long)h * w, width = (long long)patch * patch * C;
+    if (n >= (1ll << 31) / C || rows >= (1ll << 31) / width || (!plain && reinterpret_cast<uintptr_t>(bank) % 16 != 0)) {
+        if (plain)
+            set_error("%s: %lld columns against %d rows of %d channels exceed 32-bit offsets", who, n, rows, C);
+        else
+            set_error("%s: %lld patches against %d rows of 9 x %d channels exceed 32-bit offsets, or the bank is not "
+                      "aligned to 16 bytes", who, n, rows, C);
         return STX_ERR_UNSUPPORTED;
     }
     STX_TRY(e->set_device());
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2, &si));
-    float *sc = e->A().scalars.f() + si;
-    const size_t pieces = nnfm_pieces_floats(rows, C);
-    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows)) * sizeof(float)));
-    unsigned short *bhi = static_cast<unsigned short *>(e->nnfm_scratch.ptr), *blo = bhi + (size_t)rows * C;
-    // what stx_set_nnfm_targets does once, then the launches of an NNFM target of stx_sc_grad_tile, in the same order
-    STX_TRY(nnfm_split_rows_launch(e->stream, bank, rows, C, bhi, blo));
-    STX_TRY(launch_nnfm_terms(e, e->stream, feat, C, h, w, bank, bhi, blo, rows, s_out, index_out, sc, "op",
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
+    const size_t pieces = nnfm_pieces_floats(rows, (int)width);
+    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows, patch)) * sizeof(float)));
+    unsigned short *bhi = static_cast<unsigned short *>(e->nnfm_scratch.ptr);
+    // what the targets' setter does once, then the launches of an NNFM target of stx_sc_grad_tile, in the same order
+    STX_TRY(nnfm_split_rows_launch(e->stream, bank, rows, (int)width, bhi, bhi + (size_t)rows * width));
+    STX_TRY(launch_nnfm_terms(e, e->stream, feat, C, h, w, patch, bank, bhi, rows, s_out, index_out, sc, "op",
                               e->nnfm_scratch.f() + pieces, nullptr));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
-    out[0] = (double)e->A().host[si];
-    out[1] = (double)e->A().host[si + 1];
-    e->A().used = 0;
+    STX_TRY(scalars.fetch(&host));
+    out[0] = (double)host[0];
+    out[1] = (double)host[1];
     return STX_OK;
+}
+
+int stx_op_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *bank, int rows,
+                      float *s_out, int *index_out, double out[2]) {
+    return hook_nnfm_terms(e, feat, C, h, w, 1, bank, rows, s_out, index_out, out);
 }
 
 int stx_op_nnfm_patch_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, const float *bank,
                             int rows, float *s_out, int *index_out, double out[2]) {
-    if (patch == 1) return stx_op_nnfm_terms(e, feat, C, h, w, bank, rows, s_out, index_out, out);
-    if (patch != 3 || !e || !feat || !bank || !s_out || !index_out || !out || C <= 0 || h <= 0 || w <= 0 || rows <= 0) {
-        set_error("stx_op_nnfm_patch_terms: bad arguments (patch %d; 1 or 3 is expected)", patch);
-        return STX_ERR_ARG;
-    }
-    if (C % 64 != 0) {
-        set_error("stx_op_nnfm_patch_terms: the channel count %d is not a multiple of 64", C);
-        return STX_ERR_UNSUPPORTED;
-    }
-    if ((long long)h * w >= (1ll << 31) / C || rows >= (1ll << 31) / (9ll * C) ||
-        reinterpret_cast<uintptr_t>(bank) % 16 != 0) {
-        set_error("stx_op_nnfm_patch_terms: %lld patches against %d rows of 9 x %d channels exceed 32-bit offsets, "
-                  "or the bank is not aligned to 16 bytes", (long long)h * w, rows, C);
-        return STX_ERR_UNSUPPORTED;
-    }
-    STX_TRY(e->set_device());
-    STX_TRY(do_sync(e));
-    size_t si;
-    STX_TRY(alloc_scalars(e, 2, &si));
-    float *sc = e->A().scalars.f() + si;
-    const size_t pieces = nnfm_pieces_floats(rows, 9 * C);
-    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows, 3)) * sizeof(float)));
-    unsigned short *bhi = static_cast<unsigned short *>(e->nnfm_scratch.ptr), *blo = bhi + (size_t)rows * 9 * C;
-    // what stx_set_nnfm_patch_targets does once, then the launches of a patch target of stx_sc_grad_tile
-    STX_TRY(nnfm_split_rows_launch(e->stream, bank, rows, 9 * C, bhi, blo));
-    STX_TRY(launch_nnfm_terms(e, e->stream, feat, C, h, w, bank, bhi, blo, rows, s_out, index_out, sc, "op",
-                              e->nnfm_scratch.f() + pieces, nullptr, 3));
-    STX_HIP(hipMemcpyAsync(e->A().host, e->A().scalars.ptr, e->A().used * sizeof(float),
-                           hipMemcpyDeviceToHost, e->stream));
-    STX_HIP(hipStreamSynchronize(e->stream));
-    out[0] = (double)e->A().host[si];
-    out[1] = (double)e->A().host[si + 1];
-    e->A().used = 0;
-    return STX_OK;
+    return hook_nnfm_terms(e, feat, C, h, w, patch, bank, rows, s_out, index_out, out);
 }
 
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,

@@ -810,28 +810,38 @@ int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channe
     return STX_OK;
 }
 
-int stx_nnfm_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int stride,
-                  float *bank_out, int out_mem) {
-    if (!e || !feat || !bank_out || channels <= 0 || h <= 0 || w <= 0 || stride < 1) return STX_ERR_ARG;
+// Both bank entries, their arguments accepted: the pass (patch 3: the passes) that prepares a tile's blob for the
+// search (nnfm.hip), with the float32 rows as the output.  The engine's nnfm_scratch holds the rows of a host
+// destination, then the work area of patch 3.
+static int nnfm_bank_rows(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int patch,
+                          int stride, float *bank_out, int out_mem) {
     STX_TRY(e->set_device());
     const size_t in_bytes = (size_t)channels * h * w * sizeof(float);
-    const size_t out_bytes = (size_t)ceil_div(h, stride) * ceil_div(w, stride) * channels * sizeof(float);
+    const size_t out_floats = (size_t)ceil_div(h, stride) * ceil_div(w, stride) * patch * patch * channels;
     const float *src = feat;
     if (feat_mem == STX_HOST) {
         STX_TRY(e->upload.ensure(in_bytes));
         STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, in_bytes));
         src = e->upload.f();
     }
-    // the pass that prepares a tile's blob for the search (nnfm.hip), with the float32 rows as its output
-    float *dst = bank_out;
-    if (out_mem == STX_HOST) {
-        STX_TRY(e->nnfm_scratch.ensure(out_bytes));
-        dst = e->nnfm_scratch.f();
-    }
-    STX_TRY(nnfm_prepare_launch(e->stream, src, channels, h, w, stride, nullptr, nullptr, nullptr, dst));
-    if (out_mem == STX_HOST) STX_TRY(copy_out(e, bank_out, STX_HOST, dst, out_bytes));
-    if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+    const size_t staged = out_mem == STX_HOST ? (out_floats + 63) & ~(size_t)63 : 0;
+    const size_t work = patch == 3 ? nnfm_patch_work_floats(h * w) : 0;
+    STX_TRY(e->nnfm_scratch.ensure((staged + work) * sizeof(float)));
+    float *dst = out_mem == STX_HOST ? e->nnfm_scratch.f() : bank_out;
+    STX_TRY(nnfm_prepare_launch(e->stream, src, channels, h, w, patch, stride,
+                                work ? reinterpret_cast<double *>(e->nnfm_scratch.f() + staged) : nullptr, nullptr,
+                                nullptr, nullptr, dst));
+    if (out_mem == STX_HOST) STX_TRY(copy_out(e, bank_out, STX_HOST, dst, out_floats * sizeof(float)));
+    // (a side on the host; or the work area, which is the engine's: the rows are complete before another call may
+    // reuse it)
+    if (work || feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
     return STX_OK;
+}
+
+int stx_nnfm_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int stride,
+                  float *bank_out, int out_mem) {
+    if (!e || !feat || !bank_out || channels <= 0 || h <= 0 || w <= 0 || stride < 1) return STX_ERR_ARG;
+    return nnfm_bank_rows(e, feat, feat_mem, channels, h, w, 1, stride, bank_out, out_mem);
 }
 
 int stx_nnfm_patch_bank(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int patch,
@@ -847,26 +857,7 @@ int stx_nnfm_patch_bank(stx_engine *e, const float *feat, int feat_mem, int chan
                   "channels below 2^31 are expected)", rows, channels, h, w);
         return STX_ERR_UNSUPPORTED;
     }
-    STX_TRY(e->set_device());
-    const size_t in_bytes = (size_t)channels * h * w * sizeof(float);
-    const size_t out_floats = (size_t)rows * 9 * channels, out_bytes = out_floats * sizeof(float);
-    const float *src = feat;
-    if (feat_mem == STX_HOST) {
-        STX_TRY(e->upload.ensure(in_bytes));
-        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, in_bytes));
-        src = e->upload.f();
-    }
-    // the passes that prepare a tile's blob for the patch search (nnfm.hip), with the float32 rows as their output
-    const size_t staged = out_mem == STX_HOST ? (out_floats + 63) & ~(size_t)63 : 0;
-    STX_TRY(e->nnfm_scratch.ensure((staged + nnfm_patch_work_floats(h * w)) * sizeof(float)));
-    float *dst = out_mem == STX_HOST ? e->nnfm_scratch.f() : bank_out;
-    STX_TRY(nnfm_patch_prepare_launch(e->stream, src, channels, h, w, stride,
-                                      reinterpret_cast<double *>(e->nnfm_scratch.f() + staged), nullptr, nullptr,
-                                      nullptr, dst));
-    if (out_mem == STX_HOST) STX_TRY(copy_out(e, bank_out, STX_HOST, dst, out_bytes));
-    // (the work area is the engine's: the rows are complete before another call may reuse it)
-    STX_HIP(hipStreamSynchronize(e->stream));
-    return STX_OK;
+    return nnfm_bank_rows(e, feat, feat_mem, channels, h, w, 3, stride, bank_out, out_mem);
 }
 
 }  // extern "C"

@@ -158,32 +158,26 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
 // The nearest-neighbour term of one tapped blob (nnfm.hip): 1 / |f_i| and the pieces of the unit columns, the
 // search over the bank (with the slices' merge when the bank was cut), S with the partials of E and sum |S|.
 // patch 3: 1 / |P_p| and the pieces of the columns under one scale, the gathered search, c_p and S.
-int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *bank,
-                      const unsigned short *bank_hi, const unsigned short *bank_lo, int rows, float *sgrad,
-                      int *idx_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer,
-                      int patch) {
+int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int patch,
+                      const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
+                      const std::string &name, float *scratch, std::vector<SumJob> *defer) {
     const int n = h * w;
     const NnfmScratch x = nnfm_carve(scratch, C, n, rows, patch);
     const NnfmPlan plan = nnfm_plan(n, rows);
     int *const idx = idx_out ? idx_out : x.idx;
-    const bool p3 = patch == 3;         // the same steps over 3 x 3 patches: the search's K is 9 C
-    const std::string tag = p3 ? "nnfm patch " : "nnfm ";
+    const std::string tag = patch == 3 ? "nnfm patch " : "nnfm ";
     {
         ProfScope scope(e, tag + "prepare " + name, 0.0, stream);
-        STX_TRY(p3 ? nnfm_patch_prepare_launch(stream, feat, C, h, w, 1, x.work, x.inv_r, x.xhi, x.xlo, nullptr)
-                   : nnfm_prepare_launch(stream, feat, C, h, w, 1, x.inv_r, x.xhi, x.xlo, nullptr));
+        STX_TRY(nnfm_prepare_launch(stream, feat, C, h, w, patch, 1, x.work, x.inv_r, x.xhi, x.xlo, nullptr));
     }
     {
         ProfScope scope(e, tag + "search " + name + " x" + std::to_string(plan.slices),
-                        6.0 * n * (double)rows * C * (p3 ? 9 : 1), stream);
-        STX_TRY(p3 ? nnfm_patch_search_launch(stream, x, h, w, bank_hi, bank_lo, rows, C, idx)
-                   : nnfm_search_launch(stream, x, n, bank_hi, bank_lo, rows, C, idx));
+                        6.0 * n * (double)rows * C * (patch * patch), stream);
+        STX_TRY(nnfm_search_launch(stream, x, h, w, patch, pieces, rows, C, idx));
     }
     ProfScope scope(e, tag + "grad " + name, 0.0, stream);
     int n_parts = 0;
-    STX_TRY(p3 ? nnfm_patch_grad_launch(stream, feat, C, h, w, x.inv_r, bank, rows, idx, x.cosv, sgrad, x.partials,
-                                        &n_parts)
-               : nnfm_grad_launch(stream, feat, C, n, x.inv_r, bank, rows, idx, sgrad, x.partials, &n_parts));
+    STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts));
     if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
     defer->push_back(SumJob{x.partials, n_parts, sc});
     defer->push_back(SumJob{x.partials + n_parts, n_parts, sc + 1});
@@ -401,9 +395,9 @@ int queue_tap_terms(TileRun &run, size_t k) {
                                       sgrad, sc, b.name, scratch, run.defer()));
             break;
         case TermKind::Nnfm:          // sc[0] = E, sc[1] = sum |S|
-            STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.target, t.nnfm->hi(),
-                                      t.nnfm->lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch, run.defer(),
-                                      t.nnfm->patch));
+            STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.nnfm->patch, t.target,
+                                      t.nnfm->pieces_hi_lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch,
+                                      run.defer()));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

@@ -325,55 +325,37 @@ class TileEngine:
     def set_nnfm_targets(self, banks, weights=None, patch=1):
         """banks: {layer: B [rows, C]} -- unit rows, what ``nnfm_bank`` gives for a style picture's feature map
         (banks of several pictures concatenated) -- and weights: {layer: factor} (default 1 each); an empty
-        dict: none (stx_set_nnfm_targets).  The library copies a bank and builds its fp16 pieces once, here.
-        Call it after ``set_contents_and_styles``, which clears the banks.  A layer with a bank is part of
+        dict: none.  The library copies a bank and builds its fp16 pieces once, here.  Call it after ``set_contents_and_styles``, which clears the banks.  A layer with a bank is part of
         every tile evaluation of the group from then on.  ``patch`` 3: banks of 3 x 3 patches, [rows, 9 C] as
-        ``nnfm_bank(feat, stride, 3)`` gives them (stx_set_nnfm_patch_targets)."""
-        if patch == 1:
-            return self._set_nnfm_plain(banks, weights)
+        ``nnfm_bank(feat, stride, 3)`` gives them.  Both forms are patch targets of the library
+        (stx_set_nnfm_patch_targets), the plain one with patch 1."""
         keep, n = [], len(banks)
         table = (lib.NnfmPatchTarget * max(1, n))()
         for t, (layer, bank) in zip(table, banks.items()):
             ptr, mem, obj = _as_arg(bank)
-            if len(obj.shape) != 2 or isinstance(patch, bool) or patch != 3 or obj.shape[1] % 9:
+            if patch == 1 and len(obj.shape) != 2:
+                raise ValueError('NNFM bank %s: a [rows, C] array is expected' % layer)
+            if patch != 1 and (len(obj.shape) != 2 or isinstance(patch, bool) or patch != 3 or obj.shape[1] % 9):
                 raise ValueError('NNFM bank %s, patch %r: a [rows, patch * patch * C] array and patch 1 or 3 are '
                                  'expected' % (layer, patch))
             keep.append(obj)
-            t.layer, t.channels, t.patch, t.rows = self._cstr(layer), int(obj.shape[1]) // 9, 3, int(obj.shape[0])
-            t.bank, t.mem = ptr, mem
+            t.layer, t.patch, t.rows = self._cstr(layer), int(patch), int(obj.shape[0])
+            t.channels, t.bank, t.mem = int(obj.shape[1]) // (t.patch * t.patch), ptr, mem
             t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
         lib.call('stx_set_nnfm_patch_targets', self.handle, table, n)
         self.primary.nnfm_layers = list(banks)
         del keep
 
-    def _set_nnfm_plain(self, banks, weights):
-        keep, n = [], len(banks)
-        table = (lib.NnfmTarget * max(1, n))()
-        for t, (layer, bank) in zip(table, banks.items()):
-            ptr, mem, obj = _as_arg(bank)
-            if len(obj.shape) != 2:
-                raise ValueError('NNFM bank %s: a [rows, C] array is expected' % layer)
-            keep.append(obj)
-            t.layer, t.channels, t.rows, t.bank, t.mem = self._cstr(layer), int(obj.shape[1]), int(obj.shape[0]), ptr, mem
-            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
-        lib.call('stx_set_nnfm_targets', self.handle, table, n)
-        self.primary.nnfm_layers = list(banks)
-        del keep
-
     def nnfm_bank(self, feat, stride=1, patch=1):
         """The bank of a [C,h,w] feature map as a DeviceArray [rows, C]: its unit-normalised columns at every
-        ``stride``-th row and column, raster order (stx_nnfm_bank).  Nothing travels through the host when
-        ``feat`` is on the device.  ``patch`` 3: the unit 3 x 3 patches centred there, [rows, 9 C]
-        (stx_nnfm_patch_bank); a bank past the library's 2^31 offsets is refused before it is allocated."""
+        ``stride``-th row and column, raster order.  Nothing travels through the host when ``feat`` is on the
+        device.  ``patch`` 3: the unit 3 x 3 patches centred there, [rows, 9 C]; a bank past the library's 2^31
+        offsets is refused before it is allocated.  One call for both (stx_nnfm_patch_bank, patch 1 or 3)."""
         ptr, mem, keep = _as_arg(feat)
         c, h, w = (int(v) for v in keep.shape)
         rows = nnfm_bank_rows(c, h, w, stride, patch)
-        if patch == 1:
-            out = DeviceArray(self, (rows, c))
-            lib.call('stx_nnfm_bank', self.handle, ptr, mem, c, h, w, int(stride), out.ptr, lib.DEVICE)
-            return out
-        out = DeviceArray(self, (rows, 9 * c))
-        lib.call('stx_nnfm_patch_bank', self.handle, ptr, mem, c, h, w, 3, int(stride), out.ptr, lib.DEVICE)
+        out = DeviceArray(self, (rows, patch * patch * c))
+        lib.call('stx_nnfm_patch_bank', self.handle, ptr, mem, c, h, w, int(patch), int(stride), out.ptr, lib.DEVICE)
         return out
 
     def concat_rows(self, parts):

@@ -258,8 +258,9 @@ def test_patch_1_gives_the_bytes_of_the_plain_entry_points():
     assert old[0].tobytes() == new[0].tobytes() and np.array_equal(old[1], new[1]) and old[2:] == new[2:]
     d_feat = eng.to_device(feat)
     for stride in (1, 2):
-        a, b = eng.nnfm_bank(d_feat, stride), eng.nnfm_bank(d_feat, stride, 1)
-        out = eng.empty(a.shape)
+        b = eng.nnfm_bank(d_feat, stride, 1)
+        a, out = eng.empty(b.shape), eng.empty(b.shape)
+        lib.call('stx_nnfm_bank', eng.handle, d_feat.ptr, lib.DEVICE, c, h, w, stride, a.ptr, lib.DEVICE)
         lib.call('stx_nnfm_patch_bank', eng.handle, d_feat.ptr, lib.DEVICE, c, h, w, 1, stride, out.ptr, lib.DEVICE)
         assert a.get().tobytes() == b.get().tobytes() == out.get().tobytes()
         for arr in (a, b, out):
@@ -269,10 +270,15 @@ def test_patch_1_gives_the_bytes_of_the_plain_entry_points():
     style_bank = np.ascontiguousarray(_scene()[2].reshape(-1, 9, 256)[:, 4])      # any [rows, 256] array
     eng.set_contents_and_styles(om.contents, om.styles)
     run = lambda: eng.sc_grad_tile(full, (0, 0), (0, 0), [], SL, LW, {}, SW)
-    eng.set_nnfm_targets({'conv3_1': style_bank}, NNFM_W)
+    d_bank = eng.to_device(style_bank)
+    table = (lib.NnfmTarget * 1)()          # the plain setter itself (TileEngine sets both forms as patch targets)
+    t = table[0]
+    t.layer, t.channels, t.rows, t.bank, t.mem = b'conv3_1', 256, style_bank.shape[0], d_bank.ptr, lib.DEVICE
+    t.weight = NNFM_W['conv3_1']
+    lib.call('stx_set_nnfm_targets', eng.handle, table, 1)
+    eng.primary.nnfm_layers = ['conv3_1']
     plain = run()
     table = (lib.NnfmPatchTarget * 1)()
-    d_bank = eng.to_device(style_bank)
     t = table[0]
     t.layer, t.channels, t.patch, t.rows, t.bank, t.mem = b'conv3_1', 256, 1, style_bank.shape[0], d_bank.ptr, lib.DEVICE
     t.weight = NNFM_W['conv3_1']

@@ -9,8 +9,8 @@ against the banks of a 512^2 and of a 1024^2 style picture at --nnfm-stride 1 an
 per-group event timing is on: `prepare` (1 / |f_i| and the fp16 pieces of the unit columns), `search` (the
 n x M x C product with its argmax, and the slices' merge when there is one), `grad` (S with the partials, and
 the one-workgroup final sums the stand-alone call launches behind it).  Median of --reps calls after two
-warm-up calls.  The pieces of the bank are made once when the targets are set (stx_set_nnfm_targets) and are
-not part of a tile's term: their pass is outside the three groups.
+warm-up calls.  The pieces of the bank are made once when the targets are set (stx_set_nnfm_patch_targets) and
+are not part of a tile's term: their pass is outside the three groups.
 
 The search is priced against the matrix floor 3 x 2 n M C flop (three fp16 products per fp32-class product)
 at 2.5 PFLOP/s, the dense fp16 rate of the MI355X.
@@ -77,28 +77,35 @@ def measure(eng, rng, c, side, rows, reps, patch=1):
     return {k: float(np.median(v)) for k, v in times.items()}, slices
 
 
-def patch_lines(eng, rng, opts):
-    lines = ['# --nnfm-patch 3: stx_op_nnfm_patch_terms, device-event ms per group (median of %d after 2 warm-up calls)'
-             % opts.reps,
+def table_lines(eng, rng, opts):
+    """The table of one mode: the plain columns, and for --patch 3 the plain search at 9 C and the ratio to it."""
+    p3 = opts.patch == 3
+    name, width = ('stx_op_nnfm_patch_terms', '9C') if p3 else ('stx_op_nnfm_terms', 'C')
+    lines = ['# --nnfm-%s: %s, device-event ms per group (median of %d after 2 warm-up calls)'
+             % ('patch 3' if p3 else 'weight', name, opts.reps),
              '# device: %s' % torch.cuda.get_device_name(0),
-             '# floor = 3 x 2 n M 9C flop at 2.5 PFLOP/s; of floor = floor / search',
-             '# plain 9C = the search of stx_op_nnfm_terms on a blob of 9 C channels, same n and M; ratio = search / plain 9C',
-             '%6s %8s %4s %7s %7s %6s %6s %9s %9s %9s %9s %9s %8s %9s %6s'
-             % ('tile', 'blob', 'C', 'n', 'M', 'stride', 'slices', 'prepare', 'search', 'grad', 'total', 'floor ms',
-                'of floor', 'plain 9C', 'ratio')]
+             '# floor = 3 x 2 n M %s flop at 2.5 PFLOP/s; of floor = floor / search' % width]
+    if p3:
+        lines.append('# plain 9C = the search of stx_op_nnfm_terms on a blob of 9 C channels, same n and M; '
+                     'ratio = search / plain 9C')
+    head = ('tile', 'blob', 'C', 'n', 'M', 'stride', 'slices', 'prepare', 'search', 'grad', 'total', 'floor ms', 'of floor')
+    lines.append('%6s %8s %4s %7s %7s %6s %6s %9s %9s %9s %9s %9s %8s' % head
+                 + (' %9s %6s' % ('plain 9C', 'ratio') if p3 else ''))
     for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
         for blob, c, side, style_side in shapes:
             for stride in (1, 2):
                 rows = (-(-style_side // stride)) ** 2
-                t, slices = measure(eng, rng, c, side, rows, opts.reps, 3)
-                plain, _ = measure(eng, rng, 9 * c, side, rows, opts.reps)
+                t, slices = measure(eng, rng, c, side, rows, opts.reps, opts.patch)
                 n = side * side
-                floor_ms = 6.0 * n * rows * 9 * c / FP16_FLOPS * 1e3
-                lines.append('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f %9.4f %6.3f'
-                             % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
-                                sum(t.values()), floor_ms, floor_ms / t['search'], plain['search'],
-                                t['search'] / plain['search']))
-                print(lines[-1], flush=True)
+                floor_ms = 6.0 * n * rows * opts.patch ** 2 * c / FP16_FLOPS * 1e3
+                line = ('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f'
+                        % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
+                           sum(t.values()), floor_ms, floor_ms / t['search']))
+                if p3:
+                    plain, _ = measure(eng, rng, 9 * c, side, rows, opts.reps)
+                    line += ' %9.4f %6.3f' % (plain['search'], t['search'] / plain['search'])
+                lines.append(line)
+                print(line, flush=True)
     return lines
 
 
@@ -112,34 +119,7 @@ def main():
         sys.exit('bench_nnfm: no GPU')
     net = builtin_net('vgg19')
     eng = TileEngine(net, 0, synthetic_weights(net, 0))
-    rng = np.random.RandomState(0)
-    if opts.patch == 3:
-        text = '\n'.join(patch_lines(eng, rng, opts)) + '\n'
-        if opts.out:
-            os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
-            with open(opts.out, 'w') as f:
-                f.write(text)
-        eng.close()
-        return
-    lines = ['# --nnfm-weight: stx_op_nnfm_terms, device-event ms per group (median of %d after 2 warm-up calls)'
-             % opts.reps,
-             '# device: %s' % torch.cuda.get_device_name(0),
-             '# floor = 3 x 2 n M C flop at 2.5 PFLOP/s; of floor = floor / search',
-             '%6s %8s %4s %7s %7s %6s %6s %9s %9s %9s %9s %9s %8s' % ('tile', 'blob', 'C', 'n', 'M', 'stride',
-                                                                      'slices', 'prepare', 'search', 'grad', 'total',
-                                                                      'floor ms', 'of floor')]
-    for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
-        for blob, c, side, style_side in shapes:
-            for stride in (1, 2):
-                rows = (-(-style_side // stride)) ** 2
-                t, slices = measure(eng, rng, c, side, rows, opts.reps)
-                n = side * side
-                floor_ms = 6.0 * n * rows * c / FP16_FLOPS * 1e3
-                lines.append('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f'
-                             % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
-                                sum(t.values()), floor_ms, floor_ms / t['search']))
-                print(lines[-1], flush=True)
-    text = '\n'.join(lines) + '\n'
+    text = '\n'.join(table_lines(eng, np.random.RandomState(0), opts)) + '\n'
     if opts.out:
         os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
         with open(opts.out, 'w') as f:
