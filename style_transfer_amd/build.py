@@ -38,6 +38,7 @@ SOURCES = {
     'nnfm.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
+    'targets.cpp': [],
     'tile_path.cpp': [],
     'tile_terms.cpp': [],
     'image_api.cpp': [],

@@ -227,6 +227,19 @@ def eval_config(path):
     return scope
 
 
+def raw_option(args, name, default=0):
+    """An option as it was given: a value bound to the run state stays the callable it is (reading it through a
+    LazyArgs would call it)."""
+    return getattr(getattr(args, 'ns', args), name, default)
+
+
+def option_on(args, name):
+    """Whether a weight option switches its term on: a number that is not 0, or a callable of the run state
+    (what it will return is not known before the run)."""
+    raw = raw_option(args, name)
+    return bool(callable(raw) or raw)
+
+
 def check_style_masks(args):
     """--style-masks names one mask per style image: anything else is refused before any GPU work."""
     masks = getattr(args, 'style_masks', None)
@@ -305,8 +318,7 @@ def stat_layer_args(args):
     """The layer list of the mean / std style term (``name`` or ``name:weight`` each): --stat-layers, or the
     names of the --style-layers when only --stat-weight is set (of its built-in list when it is empty: the
     Gram term can be switched off that way).  [] when the term is off (no --stat-weight, or 0)."""
-    raw = getattr(getattr(args, 'ns', args), 'stat_weight', 0)
-    if not (callable(raw) or raw):
+    if not option_on(args, 'stat_weight'):
         return []
     given = getattr(args, 'stat_layers', None)
     if not given:
@@ -314,33 +326,40 @@ def stat_layer_args(args):
     return [given] if isinstance(given, str) else list(given)
 
 
-def check_stat_options(args, known_layers=None):
-    """--stat-weight / --stat-layers: refused before any GPU work together with --style-masks (there is one
-    statistics set and, with masks, one style set per picture), with a malformed entry, with a layer named
-    twice, with weights that are all 0 or -- when the network's layers are known -- with a layer it does not
-    have.  Returns the layer names."""
-    items = stat_layer_args(args)
-    if not items:
-        return []
+def check_layer_list(args, items, weight_flag, layers_flag, one_set, known_layers=None):
+    """A ``LAYER[:weight]`` list of a style term that has one set of targets (``one_set`` says of what): refused
+    together with --style-masks, with a malformed entry, with a layer named twice, with weights that are all 0
+    or -- when the network's layers are known -- with a layer it does not have.  Returns the layer names."""
     if getattr(args, 'style_masks', None):
-        raise ValueError('--stat-weight cannot be combined with --style-masks: there is one set of statistics '
-                         'targets, and masks make every style picture a style set of its own')
+        raise ValueError('%s cannot be combined with --style-masks: there is %s, and masks make every style '
+                         'picture a style set of its own' % (weight_flag, one_set))
     names, total = [], 0.0
     for item in items:
         name, _, weight = str(item).partition(':')
         try:
             total += abs(ffloat(weight)) if weight else 1.0
         except (ValueError, ZeroDivisionError):
-            raise ValueError('--stat-layers %s: LAYER or LAYER:weight is expected' % item) from None
+            raise ValueError('%s %s: LAYER or LAYER:weight is expected' % (layers_flag, item)) from None
         if not name or name in names:
-            raise ValueError('--stat-layers %s: a layer name, given once, is expected' % item)
+            raise ValueError('%s %s: a layer name, given once, is expected' % (layers_flag, item))
         if known_layers is not None and (name not in known_layers or name == 'data'):
-            raise ValueError("--stat-layers %s: the network has no layer '%s'" % (item, name))
+            raise ValueError("%s %s: the network has no layer '%s'" % (layers_flag, item, name))
         names.append(name)
     if not total:
-        raise ValueError('--stat-layers %s: at least one layer weight must not be 0 (they are normalised '
-                         'to --stat-weight)' % ' '.join(map(str, items)))
+        raise ValueError('%s %s: at least one layer weight must not be 0 (they are normalised to %s)'
+                         % (layers_flag, ' '.join(map(str, items)), weight_flag))
     return names
+
+
+def check_stat_options(args, known_layers=None):
+    """--stat-weight / --stat-layers: refused before any GPU work together with --style-masks (there is one
+    statistics set and, with masks, one style set per picture) and with a bad layer list (check_layer_list).
+    Returns the layer names."""
+    items = stat_layer_args(args)
+    if not items:
+        return []
+    return check_layer_list(args, items, '--stat-weight', '--stat-layers', 'one set of statistics targets',
+                            known_layers)
 
 
 NNFM_LAYERS_DEFAULT = ('conv3_1', 'conv4_1')
@@ -349,8 +368,7 @@ NNFM_LAYERS_DEFAULT = ('conv3_1', 'conv4_1')
 def nnfm_layer_args(args):
     """The layer list of the nearest-neighbour term (``name`` or ``name:weight`` each): --nnfm-layers, or
     conv3_1 conv4_1.  [] when the term is off (no --nnfm-weight, or 0)."""
-    raw = getattr(getattr(args, 'ns', args), 'nnfm_weight', 0)
-    if not (callable(raw) or raw):
+    if not option_on(args, 'nnfm_weight'):
         return []
     given = getattr(args, 'nnfm_layers', None) or NNFM_LAYERS_DEFAULT
     return [given] if isinstance(given, str) else list(given)
@@ -358,7 +376,7 @@ def nnfm_layer_args(args):
 
 def nnfm_stride(args):
     """--nnfm-stride as an integer >= 1 (default 1); anything else is a ValueError."""
-    raw = getattr(getattr(args, 'ns', args), 'nnfm_stride', 1)
+    raw = raw_option(args, 'nnfm_stride', 1)
     if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or raw < 1:
         raise ValueError('--nnfm-stride %r: an integer >= 1 is expected' % (raw,))
     return int(raw)
@@ -367,7 +385,7 @@ def nnfm_stride(args):
 def nnfm_patch(args):
     """--nnfm-patch as the integer 1 or 3 (default 1); anything else, bools and floats included, is a
     ValueError."""
-    raw = getattr(getattr(args, 'ns', args), 'nnfm_patch', 1)
+    raw = raw_option(args, 'nnfm_patch', 1)
     if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or raw not in (1, 3):
         raise ValueError('--nnfm-patch %r: 1 or 3 is expected' % (raw,))
     return int(raw)
@@ -387,33 +405,16 @@ def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
 
 def check_nnfm_options(args, known_layers=None):
     """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch: refused before any GPU work together with
-    --style-masks (there is one bank and, with masks, one style set per picture), with a malformed entry, with a
-    layer named twice, with weights that are all 0, with a stride below 1, with a patch that is not 1 or 3 or --
-    when the network's layers are known -- with a layer it does not have.  Returns the layer names."""
+    --style-masks (there is one bank and, with masks, one style set per picture), with a stride below 1, with a
+    patch that is not 1 or 3 and with a bad layer list (check_layer_list).  Returns the layer names."""
     items = nnfm_layer_args(args)
     if not items:
         return []
-    if getattr(args, 'style_masks', None):
-        raise ValueError('--nnfm-weight cannot be combined with --style-masks: there is one bank of style '
-                         'features, and masks make every style picture a style set of its own')
-    nnfm_stride(args)
-    nnfm_patch(args)
-    names, total = [], 0.0
-    for item in items:
-        name, _, weight = str(item).partition(':')
-        try:
-            total += abs(ffloat(weight)) if weight else 1.0
-        except (ValueError, ZeroDivisionError):
-            raise ValueError('--nnfm-layers %s: LAYER or LAYER:weight is expected' % item) from None
-        if not name or name in names:
-            raise ValueError('--nnfm-layers %s: a layer name, given once, is expected' % item)
-        if known_layers is not None and (name not in known_layers or name == 'data'):
-            raise ValueError("--nnfm-layers %s: the network has no layer '%s'" % (item, name))
-        names.append(name)
-    if not total:
-        raise ValueError('--nnfm-layers %s: at least one layer weight must not be 0 (they are normalised '
-                         'to --nnfm-weight)' % ' '.join(map(str, items)))
-    return names
+    if not getattr(args, 'style_masks', None):      # (the refusal of --style-masks comes first)
+        nnfm_stride(args)
+        nnfm_patch(args)
+    return check_layer_list(args, items, '--nnfm-weight', '--nnfm-layers', 'one bank of style features',
+                            known_layers)
 
 
 def parse_args(state=None, argv=None, config_py=None):

@@ -7,8 +7,8 @@
 // calls that enqueue kernels asynchronously instead of pickled messages over multiprocessing
 // queues and POSIX shared memory.
 //
-// This file: the engine's life cycle, weights and targets, the scalar arenas and their fences, and the
-// profiling readers.  engine.h says which host file owns what.
+// This file: the engine's life cycle and weights, the scalar arenas and their fences, and the profiling
+// readers.  engine.h says which host file owns what.
 
 #include <algorithm>
 #include <atomic>
@@ -94,7 +94,7 @@ int do_sync(stx_engine *e) {
 
 // Waits for the streams of every engine that shares e's state (weights or targets are about to be
 // replaced under them).  Their pending results stay pending.
-static int quiesce_members(stx_engine *e) {
+int quiesce_members(stx_engine *e) {
     for (stx_engine *m : e->sh->members) STX_HIP(hipStreamSynchronize(m->stream));
     return STX_OK;
 }
@@ -415,15 +415,7 @@ void stx_engine_destroy(stx_engine *e) {
             kv.second.b.release();
             for (auto &p : kv.second.packed) p.second->release();
         }
-        for (auto &c : e->sh->contents) c.feat->release();
-        for (auto &s : e->sh->styles) s.gram->release();
-        for (auto &m : e->sh->masks) m.map->release();
-        for (auto &t : e->sh->stats) t.ms->release();
-        for (auto &m : e->sh->cmasks) m.map->release();
-        for (auto &t : e->sh->nnfms) {
-            t.bank->release();
-            t.pieces->release();
-        }
+        clear_all_targets(*e->sh);
     }
     DevBuf *bufs[] = {&e->nnfm_scratch, &e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->first_gram, &e->color_sums};
@@ -606,322 +598,6 @@ int stx_memcpy_async(stx_engine *e, void *dst, int dst_mem, const void *src, int
     if (dst_mem == STX_DEVICE && src_mem == STX_HOST) kind = hipMemcpyHostToDevice;
     STX_HIP(hipMemcpyAsync(dst, src, bytes, kind, e->stream));
     return STX_OK;
-}
-
-int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *contents, int n_contents,
-                                const stx_style_target *styles, int n_styles) {
-    if (!e || (n_contents && !contents) || (n_styles && !styles)) return STX_ERR_ARG;
-    STX_TRY(e->set_device());
-    std::lock_guard<std::mutex> lock(e->sh->mutex);
-    const bool shared = e->sh->members.size() > 1;
-    // the previous targets may still be in use by queued kernels (of any engine that shares them)
-    STX_TRY(quiesce_members(e));
-    double copied = 0;
-    for (auto &c : e->sh->contents) c.feat->release();
-    for (auto &s : e->sh->styles) s.gram->release();
-    for (auto &m : e->sh->masks) m.map->release();
-    for (auto &t : e->sh->stats) t.ms->release();
-    for (auto &m : e->sh->cmasks) m.map->release();
-    for (auto &t : e->sh->nnfms) {
-        t.bank->release();
-        t.pieces->release();
-    }
-    e->sh->contents.clear();
-    e->sh->styles.clear();
-    e->sh->masks.clear();
-    e->sh->stats.clear();
-    e->sh->cmasks.clear();
-    e->sh->nnfms.clear();
-    e->sh->n_contents = e->sh->n_styles = 0;
-    bool host_src = false;
-    for (int i = 0; i < n_contents; ++i) {
-        const stx_content_target &c = contents[i];
-        const int blob = e->find_blob(c.layer);
-        if (blob < 0 || !c.features || c.channels != e->blobs[blob].channels || c.height <= 0 ||
-            c.width <= 0 || c.content_index < 0) {
-            set_error("content target %d: bad layer '%s' or shape", i, c.layer ? c.layer : "(null)");
-            return STX_ERR_ARG;
-        }
-        ContentTarget t;
-        t.index = c.content_index;
-        t.blob = blob;
-        t.C = c.channels;
-        t.h = c.height;
-        t.w = c.width;
-        t.feat.reset(new DevBuf);
-        const size_t bytes = (size_t)t.C * t.h * t.w * sizeof(float);
-        STX_TRY(t.feat->ensure(bytes));
-        STX_TRY(copy_in(e, t.feat->ptr, c.features, c.mem, bytes));
-        copied += (double)bytes;
-        host_src |= c.mem == STX_HOST;
-        e->sh->n_contents = std::max(e->sh->n_contents, t.index + 1);
-        e->sh->contents.push_back(std::move(t));
-    }
-    for (int i = 0; i < n_styles; ++i) {
-        const stx_style_target &s = styles[i];
-        const int blob = e->find_blob(s.layer);
-        if (blob < 0 || !s.gram || s.channels != e->blobs[blob].channels || s.style_index < 0) {
-            set_error("style target %d: bad layer '%s' or shape", i, s.layer ? s.layer : "(null)");
-            return STX_ERR_ARG;
-        }
-        StyleTarget t;
-        t.index = s.style_index;
-        t.blob = blob;
-        t.C = s.channels;
-        t.gram.reset(new DevBuf);
-        const size_t bytes = (size_t)t.C * t.C * sizeof(float);
-        STX_TRY(t.gram->ensure(bytes));
-        STX_TRY(copy_in(e, t.gram->ptr, s.gram, s.mem, bytes));
-        copied += (double)bytes;
-        host_src |= s.mem == STX_HOST;
-        e->sh->n_styles = std::max(e->sh->n_styles, t.index + 1);
-        e->sh->styles.push_back(std::move(t));
-    }
-    // (the sharing engines use the new targets from their own streams)
-    if (host_src || shared) STX_HIP(hipStreamSynchronize(e->stream));
-    e->sh->target_uploads += 1;
-    e->sh->target_bytes += copied;
-    return STX_OK;
-}
-
-int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n) {
-    if (!e || n < 0 || (n && !masks)) return STX_ERR_ARG;
-    STX_TRY(e->set_device());
-    std::lock_guard<std::mutex> lock(e->sh->mutex);
-    // the previous maps may still be in use by queued kernels (of any engine that shares them)
-    STX_TRY(quiesce_members(e));
-    for (auto &m : e->sh->masks) m.map->release();
-    e->sh->masks.clear();
-    DevBuf staged;      // a host mask on its way to the device
-    int rc = STX_OK;
-    for (int i = 0; i < n && rc == STX_OK; ++i) {
-        const stx_style_mask &sm = masks[i];
-        bool any = false;
-        for (const StyleTarget &st : e->sh->styles) any |= st.index == sm.style_index;
-        if (!sm.mask || sm.H <= 0 || sm.W <= 0 || !any) {
-            set_error("style mask %d: no mask, a bad size or no style target of index %d", i, sm.style_index);
-            rc = STX_ERR_ARG;
-            break;
-        }
-        const float *src = sm.mask;
-        if (sm.mem == STX_HOST) {
-            const size_t bytes = (size_t)sm.H * sm.W * sizeof(float);
-            if ((rc = staged.ensure(bytes)) != STX_OK) break;
-            if ((rc = copy_in(e, staged.ptr, sm.mask, STX_HOST, bytes)) != STX_OK) break;
-            src = staged.f();
-        }
-        for (const StyleTarget &st : e->sh->styles) {
-            if (st.index != sm.style_index) continue;
-            bool have = false;
-            for (const StyleMask &m : e->sh->masks) have |= m.index == st.index && m.blob == st.blob;
-            if (have) continue;
-            const int scale = e->blobs[st.blob].scale;
-            StyleMask m{st.index, st.blob, ceil_div(sm.H, scale), ceil_div(sm.W, scale),
-                        std::unique_ptr<DevBuf>(new DevBuf)};
-            if ((rc = m.map->ensure((size_t)m.h * m.w * sizeof(float))) != STX_OK) break;
-            rc = mask_map_launch(e->stream, src, sm.H, sm.W, scale, m.map->f());
-            e->sh->masks.push_back(std::move(m));
-            if (rc != STX_OK) break;
-        }
-    }
-    // (host sources may be reused right away; the sharing engines read the maps from their own streams)
-    const hipError_t err = hipStreamSynchronize(e->stream);
-    staged.release();
-    if (rc == STX_OK && err != hipSuccess) {
-        set_error("stx_set_style_masks: %s", hipGetErrorString(err));
-        rc = STX_ERR_HIP;
-    }
-    if (rc != STX_OK) {
-        for (auto &m : e->sh->masks) m.map->release();
-        e->sh->masks.clear();
-    }
-    return rc;
-}
-
-int stx_set_content_mask(stx_engine *e, const float *mask, int H, int W, int mem) {
-    if (!e || (mask && (H <= 0 || W <= 0))) return STX_ERR_ARG;
-    STX_TRY(e->set_device());
-    std::lock_guard<std::mutex> lock(e->sh->mutex);
-    // the previous maps may still be in use by queued kernels (of any engine that shares them)
-    STX_TRY(quiesce_members(e));
-    auto clear = [&]() {
-        for (auto &m : e->sh->cmasks) m.map->release();
-        e->sh->cmasks.clear();
-    };
-    clear();
-    if (!mask) return STX_OK;
-    if (e->sh->contents.empty()) {
-        set_error("stx_set_content_mask: no content targets set (call it after stx_set_contents_and_styles)");
-        return STX_ERR_STATE;
-    }
-    // the map of a blob has the size of the blob's content maps: the tile's window is taken from both alike
-    for (const ContentTarget &ct : e->sh->contents) {
-        const int scale = e->blobs[ct.blob].scale;
-        if (ceil_div(H, scale) != ct.h || ceil_div(W, scale) != ct.w) {
-            set_error("stx_set_content_mask: a %dx%d mask gives a %dx%d map at layer %s, whose content map is "
-                      "%dx%d; the mask must have the content picture's size", H, W, ceil_div(H, scale),
-                      ceil_div(W, scale), e->blobs[ct.blob].name.c_str(), ct.h, ct.w);
-            return STX_ERR_ARG;
-        }
-    }
-    DevBuf staged;      // a host mask on its way to the device
-    int rc = STX_OK;
-    const float *src = mask;
-    if (mem == STX_HOST) {
-        const size_t bytes = (size_t)H * W * sizeof(float);
-        if ((rc = staged.ensure(bytes)) == STX_OK) rc = copy_in(e, staged.ptr, mask, STX_HOST, bytes);
-        src = staged.f();
-    }
-    for (const ContentTarget &ct : e->sh->contents) {
-        if (rc != STX_OK) break;
-        bool have = false;
-        for (const ContentMask &m : e->sh->cmasks) have |= m.blob == ct.blob;
-        if (have) continue;
-        ContentMask m{ct.blob, ct.h, ct.w, std::unique_ptr<DevBuf>(new DevBuf)};
-        if ((rc = m.map->ensure((size_t)m.h * m.w * sizeof(float))) == STX_OK)
-            rc = mask_map_launch(e->stream, src, H, W, e->blobs[ct.blob].scale, m.map->f());
-        e->sh->cmasks.push_back(std::move(m));
-    }
-    // (a host source may be reused right away; the sharing engines read the maps from their own streams)
-    const hipError_t err = hipStreamSynchronize(e->stream);
-    staged.release();
-    if (rc == STX_OK && err != hipSuccess) {
-        set_error("stx_set_content_mask: %s", hipGetErrorString(err));
-        rc = STX_ERR_HIP;
-    }
-    if (rc != STX_OK) clear();
-    return rc;
-}
-
-int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
-    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    STX_TRY(e->set_device());
-    std::lock_guard<std::mutex> lock(e->sh->mutex);
-    const bool shared = e->sh->members.size() > 1;
-    // the previous targets may still be in use by queued kernels (of any engine that shares them)
-    STX_TRY(quiesce_members(e));
-    auto clear = [&]() {
-        for (auto &t : e->sh->stats) t.ms->release();
-        e->sh->stats.clear();
-    };
-    clear();
-    bool host_src = false;
-    int rc = STX_OK;
-    for (int i = 0; i < n && rc == STX_OK; ++i) {
-        const stx_stat_target &st = targets[i];
-        const int blob = e->find_blob(st.layer);
-        bool twice = false;
-        for (const StatTarget &t : e->sh->stats) twice |= t.blob == blob;
-        if (blob <= 0 || !st.mean || !st.sd || twice) {
-            set_error("statistics target %d: bad layer '%s' (unknown, the input, or given twice) or no data", i,
-                      st.layer ? st.layer : "(null)");
-            rc = STX_ERR_ARG;
-            break;
-        }
-        if (st.channels != e->blobs[blob].channels) {
-            set_error("statistics target %d: layer %s has %d channels, not %d", i, st.layer,
-                      e->blobs[blob].channels, st.channels);
-            rc = STX_ERR_ARG;
-            break;
-        }
-        StatTarget t{blob, st.channels, st.weight, std::unique_ptr<DevBuf>(new DevBuf)};
-        const size_t bytes = (size_t)t.C * sizeof(float);
-        if ((rc = t.ms->ensure(2 * bytes)) == STX_OK) rc = copy_in(e, t.ms->ptr, st.mean, st.mem, bytes);
-        if (rc == STX_OK) rc = copy_in(e, t.ms->f() + t.C, st.sd, st.mem, bytes);
-        host_src |= st.mem == STX_HOST;
-        e->sh->stats.push_back(std::move(t));
-    }
-    // (host sources may be reused right away; the sharing engines read the targets from their own streams)
-    if (host_src || shared || rc != STX_OK) {
-        const hipError_t err = hipStreamSynchronize(e->stream);
-        if (rc == STX_OK && err != hipSuccess) {
-            set_error("stx_set_stat_targets: %s", hipGetErrorString(err));
-            rc = STX_ERR_HIP;
-        }
-    }
-    if (rc != STX_OK) clear();
-    return rc;
-}
-
-// The banks of both setters: a plain bank is a patch target with patch 1.
-static int set_nnfm_banks(stx_engine *e, const stx_nnfm_patch_target *targets, int n, const char *who) {
-    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    for (int i = 0; i < n; ++i)
-        if (targets[i].patch != 1 && targets[i].patch != 3) {
-            set_error("NNFM target %d: patch %d (1 or 3 is expected)", i, targets[i].patch);
-            return STX_ERR_ARG;
-        }
-    STX_TRY(e->set_device());
-    std::lock_guard<std::mutex> lock(e->sh->mutex);
-    // the previous banks may still be in use by queued kernels (of any engine that shares them)
-    STX_TRY(quiesce_members(e));
-    auto clear = [&]() {
-        for (auto &t : e->sh->nnfms) {
-            t.bank->release();
-            t.pieces->release();
-        }
-        e->sh->nnfms.clear();
-    };
-    clear();
-    int rc = STX_OK;
-    for (int i = 0; i < n && rc == STX_OK; ++i) {
-        const stx_nnfm_patch_target &nt = targets[i];
-        const int blob = e->find_blob(nt.layer);
-        bool twice = false;
-        for (const NnfmTarget &t : e->sh->nnfms) twice |= t.blob == blob;
-        if (blob <= 0 || !nt.bank || nt.rows <= 0 || twice) {
-            set_error("NNFM target %d: bad layer '%s' (unknown, the input, or given twice) or no bank", i,
-                      nt.layer ? nt.layer : "(null)");
-            rc = STX_ERR_ARG;
-            break;
-        }
-        if (nt.channels != e->blobs[blob].channels) {
-            set_error("NNFM target %d: layer %s has %d channels, not %d", i, nt.layer, e->blobs[blob].channels,
-                      nt.channels);
-            rc = STX_ERR_ARG;
-            break;
-        }
-        const int width = nt.patch * nt.patch * nt.channels;
-        if (nt.channels % 64 != 0 || nt.rows >= (1ll << 31) / width) {
-            set_error("NNFM target %d: %d rows of %d channels (a multiple of 64 and rows x channels below 2^31 "
-                      "are expected)", i, nt.rows, width);
-            rc = STX_ERR_UNSUPPORTED;
-            break;
-        }
-        NnfmTarget t{blob, nt.channels, nt.rows, nt.weight, std::unique_ptr<DevBuf>(new DevBuf),
-                     std::unique_ptr<DevBuf>(new DevBuf), nt.patch};
-        const size_t bytes = (size_t)t.rows * width * sizeof(float);
-        if ((rc = t.bank->ensure(bytes)) == STX_OK) rc = t.pieces->ensure(nnfm_pieces_floats(t.rows, width) * sizeof(float));
-        if (rc == STX_OK) rc = copy_in(e, t.bank->ptr, nt.bank, nt.mem, bytes);
-        // the fp16 pieces the search reads, once
-        if (rc == STX_OK)
-            rc = nnfm_split_rows_launch(e->stream, t.bank->f(), t.rows, width, static_cast<unsigned short *>(t.pieces->ptr),
-                                        static_cast<unsigned short *>(t.pieces->ptr) + (size_t)t.rows * width);
-        e->sh->nnfms.push_back(std::move(t));
-    }
-    // (a source on either side may be reused or freed right away, and the sharing engines read the banks from
-    // their own streams: the copies and the split have finished when this returns)
-    const hipError_t err = hipStreamSynchronize(e->stream);
-    if (rc == STX_OK && err != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(err));
-        rc = STX_ERR_HIP;
-    }
-    if (rc != STX_OK) clear();
-    return rc;
-}
-
-int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
-    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    std::vector<stx_nnfm_patch_target> as_patch;
-    for (int i = 0; i < n; ++i) {
-        const stx_nnfm_target &t = targets[i];
-        as_patch.push_back(stx_nnfm_patch_target{t.layer, t.channels, 1, t.rows, t.bank, t.mem, t.weight});
-    }
-    return set_nnfm_banks(e, as_patch.data(), n, "stx_set_nnfm_targets");
-}
-
-int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n) {
-    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_patch_targets");
 }
 
 int stx_profile_enable(stx_engine *e, int on) {

@@ -1,5 +1,6 @@
 // The engine's state and the few helpers that more than one host file uses.  Internal: not installed.
-//   engine.cpp     engine life cycle, weights and targets, scalar arenas and fences, profiling readers
+//   engine.cpp     engine life cycle, weights, scalar arenas and fences, profiling readers
+//   targets.cpp    stx_set_*: the group's targets (contents, styles, masks, statistics, banks) and their swap
 //   tile_path.cpp  the tile evaluation: shaping, forward pass, backward walk
 //   tile_terms.cpp the loss terms of a tile evaluation: their plan, their launches, their injection
 //   image_api.cpp  whole-image and vector entries, the SWT regulariser's tables, the Laplacian loss
@@ -83,11 +84,13 @@ struct ConvParams {
 struct ContentTarget {
     int index, blob, C, h, w;
     std::unique_ptr<DevBuf> feat;
+    void release() { feat->release(); }
 };
 
 struct StyleTarget {
     int index, blob, C;
     std::unique_ptr<DevBuf> gram;
+    void release() { gram->release(); }
 };
 
 // The mask of style `index` at one tapped blob (stx_set_style_masks): the block means of the
@@ -95,6 +98,7 @@ struct StyleTarget {
 struct StyleMask {
     int index, blob, h, w;
     std::unique_ptr<DevBuf> map;
+    void release() { map->release(); }
 };
 
 // The content mask at one blob that has a content target (stx_set_content_mask): the block means of the
@@ -102,6 +106,7 @@ struct StyleMask {
 struct ContentMask {
     int blob, h, w;
     std::unique_ptr<DevBuf> map;
+    void release() { map->release(); }
 };
 
 // The mean / std targets of one tapped blob (stx_set_stat_targets): MU [C] then SD [C] on the device.
@@ -109,6 +114,7 @@ struct StatTarget {
     int blob, C;
     double weight;
     std::unique_ptr<DevBuf> ms;
+    void release() { ms->release(); }
 };
 
 // The bank of one tapped blob's nearest-neighbour term (stx_set_nnfm_targets): float32 rows [rows][C] on the
@@ -121,6 +127,10 @@ struct NnfmTarget {
     int patch = 1;
     // [rows][patch^2 C] hi, then as many lo
     const unsigned short *pieces_hi_lo() const { return static_cast<const unsigned short *>(pieces->ptr); }
+    void release() {
+        bank->release();
+        pieces->release();
+    }
 };
 
 struct LossTerm {
@@ -312,6 +322,26 @@ int alloc_dscalars(stx_engine *e, size_t n, size_t *index);
 int copy_in(stx_engine *e, void *dst, const void *src, int mem, size_t bytes);
 int copy_out(stx_engine *e, void *dst, int mem, const void *src, size_t bytes);
 int do_sync(stx_engine *e);
+int quiesce_members(stx_engine *e);
+// Frees the device memory of every target of one kind and forgets them: the one place that releases targets.
+// (The caller has made sure that no queued kernel still reads them: quiesce_members.)
+template <class T>
+inline void clear_targets(std::vector<T> &targets) {
+    for (T &t : targets) t.release();
+    targets.clear();
+}
+inline void clear_dependent_targets(SharedState &sh) {   // what is set behind the contents and styles, and goes with them
+    clear_targets(sh.masks);
+    clear_targets(sh.stats);
+    clear_targets(sh.cmasks);
+    clear_targets(sh.nnfms);
+}
+inline void clear_all_targets(SharedState &sh) {
+    clear_targets(sh.contents);
+    clear_targets(sh.styles);
+    sh.n_contents = sh.n_styles = 0;
+    clear_dependent_targets(sh);
+}
 // tile_path.cpp
 ConvProblem conv_fwd_problem(const float *x, float *y, const float *bias, int Cin, int Cout, int H, int W,
                              int ks, int relu);

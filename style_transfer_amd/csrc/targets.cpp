@@ -1,0 +1,267 @@
+// libstx host side: the targets of an engine group (stx_set_*).
+//
+// The engines of one GPU share their targets (SharedState): the content maps and style Grams, and behind them
+// the style masks, the content mask, the statistics targets and the NNFM banks, which go when new contents
+// and styles arrive.  Every setter is one swap (swap_targets) around a body that validates and copies.
+
+#include "engine.h"
+
+namespace {
+
+// One swap of the group's targets: nothing that any member has queued still reads the old ones when `body`
+// runs, and the copies and launches that `body` queued have finished when this returns -- a source on either
+// side may be reused or freed right away, and the sharing engines read the new targets from their own streams.
+// `body(wait)` returns a status; it may clear `wait` when nothing needs the host to wait.  On any failure
+// `rollback` runs, so that no half-made target stays behind.
+template <class Body, class Rollback>
+static int swap_targets(stx_engine *e, const char *who, Body body, Rollback rollback) {
+    STX_TRY(e->set_device());
+    std::lock_guard<std::mutex> lock(e->sh->mutex);
+    STX_TRY(quiesce_members(e));
+    bool wait = true;
+    int rc = body(wait);
+    if (wait || rc != STX_OK) {
+        const hipError_t err = hipStreamSynchronize(e->stream);
+        if (rc == STX_OK && err != hipSuccess) {
+            set_error("%s: %s", who, hipGetErrorString(err));
+            rc = STX_ERR_HIP;
+        }
+    }
+    if (rc != STX_OK) rollback();
+    return rc;
+}
+
+// A caller's image-resolution mask [H][W] for the two mask setters: a host mask is staged on the device (in a
+// buffer that goes with this object, behind the swap's wait), and map_at makes the block means at one scale.
+struct MaskSource {
+    DevBuf staged;
+    const float *src = nullptr;
+    int H = 0, W = 0;
+    ~MaskSource() { staged.release(); }
+    int stage(stx_engine *e, const float *mask, int h, int w, int mem) {
+        src = mask, H = h, W = w;
+        if (mem != STX_HOST) return STX_OK;
+        const size_t bytes = (size_t)H * W * sizeof(float);
+        STX_TRY(staged.ensure(bytes));
+        src = staged.f();
+        return copy_in(e, staged.ptr, mask, STX_HOST, bytes);
+    }
+    // (the map is allocated even when the launch fails: the caller keeps it where its rollback finds it)
+    int map_at(stx_engine *e, int scale, int h, int w, std::unique_ptr<DevBuf> &map) const {
+        map.reset(new DevBuf);
+        STX_TRY(map->ensure((size_t)h * w * sizeof(float)));
+        return mask_map_launch(e->stream, src, H, W, scale, map->f());
+    }
+};
+
+// The banks of both NNFM setters: a plain bank is a patch target with patch 1.
+static int set_nnfm_banks(stx_engine *e, const stx_nnfm_patch_target *targets, int n, const char *who) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (targets[i].patch != 1 && targets[i].patch != 3) {
+            set_error("NNFM target %d: patch %d (1 or 3 is expected)", i, targets[i].patch);
+            return STX_ERR_ARG;
+        }
+    auto &nnfms = e->sh->nnfms;
+    return swap_targets(e, who, [&](bool &) -> int {
+        clear_targets(nnfms);
+        for (int i = 0; i < n; ++i) {
+            const stx_nnfm_patch_target &nt = targets[i];
+            const int blob = e->find_blob(nt.layer);
+            bool twice = false;
+            for (const NnfmTarget &t : nnfms) twice |= t.blob == blob;
+            if (blob <= 0 || !nt.bank || nt.rows <= 0 || twice) {
+                set_error("NNFM target %d: bad layer '%s' (unknown, the input, or given twice) or no bank", i,
+                          nt.layer ? nt.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            if (nt.channels != e->blobs[blob].channels) {
+                set_error("NNFM target %d: layer %s has %d channels, not %d", i, nt.layer, e->blobs[blob].channels,
+                          nt.channels);
+                return STX_ERR_ARG;
+            }
+            const int width = nt.patch * nt.patch * nt.channels;
+            if (nt.channels % 64 != 0 || nt.rows >= (1ll << 31) / width) {
+                set_error("NNFM target %d: %d rows of %d channels (a multiple of 64 and rows x channels below 2^31 "
+                          "are expected)", i, nt.rows, width);
+                return STX_ERR_UNSUPPORTED;
+            }
+            nnfms.push_back(NnfmTarget{blob, nt.channels, nt.rows, nt.weight, std::unique_ptr<DevBuf>(new DevBuf),
+                                       std::unique_ptr<DevBuf>(new DevBuf), nt.patch});
+            NnfmTarget &t = nnfms.back();
+            const size_t bytes = (size_t)t.rows * width * sizeof(float);
+            STX_TRY(t.bank->ensure(bytes));
+            STX_TRY(t.pieces->ensure(nnfm_pieces_floats(t.rows, width) * sizeof(float)));
+            STX_TRY(copy_in(e, t.bank->ptr, nt.bank, nt.mem, bytes));
+            // the fp16 pieces the search reads, once
+            unsigned short *hi = static_cast<unsigned short *>(t.pieces->ptr);
+            STX_TRY(nnfm_split_rows_launch(e->stream, t.bank->f(), t.rows, width, hi, hi + (size_t)t.rows * width));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(nnfms); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int stx_set_contents_and_styles(stx_engine *e, const stx_content_target *contents, int n_contents,
+                                const stx_style_target *styles, int n_styles) {
+    if (!e || (n_contents && !contents) || (n_styles && !styles)) return STX_ERR_ARG;
+    SharedState &sh = *e->sh;
+    return swap_targets(e, "stx_set_contents_and_styles", [&](bool &wait) -> int {
+        clear_all_targets(sh);     // (with the masks, statistics and banks that were set behind the old ones)
+        double copied = 0;
+        bool host_src = false;
+        for (int i = 0; i < n_contents; ++i) {
+            const stx_content_target &c = contents[i];
+            const int blob = e->find_blob(c.layer);
+            if (blob < 0 || !c.features || c.channels != e->blobs[blob].channels || c.height <= 0 ||
+                c.width <= 0 || c.content_index < 0) {
+                set_error("content target %d: bad layer '%s' or shape", i, c.layer ? c.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            sh.contents.push_back(ContentTarget{c.content_index, blob, c.channels, c.height, c.width,
+                                                std::unique_ptr<DevBuf>(new DevBuf)});
+            ContentTarget &t = sh.contents.back();
+            const size_t bytes = (size_t)t.C * t.h * t.w * sizeof(float);
+            STX_TRY(t.feat->ensure(bytes));
+            STX_TRY(copy_in(e, t.feat->ptr, c.features, c.mem, bytes));
+            copied += (double)bytes;
+            host_src |= c.mem == STX_HOST;
+            sh.n_contents = std::max(sh.n_contents, t.index + 1);
+        }
+        for (int i = 0; i < n_styles; ++i) {
+            const stx_style_target &s = styles[i];
+            const int blob = e->find_blob(s.layer);
+            if (blob < 0 || !s.gram || s.channels != e->blobs[blob].channels || s.style_index < 0) {
+                set_error("style target %d: bad layer '%s' or shape", i, s.layer ? s.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            sh.styles.push_back(StyleTarget{s.style_index, blob, s.channels, std::unique_ptr<DevBuf>(new DevBuf)});
+            StyleTarget &t = sh.styles.back();
+            const size_t bytes = (size_t)t.C * t.C * sizeof(float);
+            STX_TRY(t.gram->ensure(bytes));
+            STX_TRY(copy_in(e, t.gram->ptr, s.gram, s.mem, bytes));
+            copied += (double)bytes;
+            host_src |= s.mem == STX_HOST;
+            sh.n_styles = std::max(sh.n_styles, t.index + 1);
+        }
+        // (device sources of an engine that shares with nobody: its own stream orders the copies before the
+        // next tile, and a --jitter step sets targets without a host wait)
+        wait = host_src || sh.members.size() > 1;
+        sh.target_uploads += 1;
+        sh.target_bytes += copied;
+        return STX_OK;
+    }, [&]() { clear_all_targets(sh); });
+}
+
+int stx_set_style_masks(stx_engine *e, const stx_style_mask *masks, int n) {
+    if (!e || n < 0 || (n && !masks)) return STX_ERR_ARG;
+    SharedState &sh = *e->sh;
+    MaskSource source;
+    return swap_targets(e, "stx_set_style_masks", [&](bool &) -> int {
+        clear_targets(sh.masks);
+        for (int i = 0; i < n; ++i) {
+            const stx_style_mask &sm = masks[i];
+            bool any = false;
+            for (const StyleTarget &st : sh.styles) any |= st.index == sm.style_index;
+            if (!sm.mask || sm.H <= 0 || sm.W <= 0 || !any) {
+                set_error("style mask %d: no mask, a bad size or no style target of index %d", i, sm.style_index);
+                return STX_ERR_ARG;
+            }
+            STX_TRY(source.stage(e, sm.mask, sm.H, sm.W, sm.mem));
+            for (const StyleTarget &st : sh.styles) {
+                if (st.index != sm.style_index) continue;
+                bool have = false;
+                for (const StyleMask &m : sh.masks) have |= m.index == st.index && m.blob == st.blob;
+                if (have) continue;
+                const int scale = e->blobs[st.blob].scale;
+                sh.masks.push_back(StyleMask{st.index, st.blob, ceil_div(sm.H, scale), ceil_div(sm.W, scale), nullptr});
+                StyleMask &m = sh.masks.back();
+                STX_TRY(source.map_at(e, scale, m.h, m.w, m.map));
+            }
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(sh.masks); });
+}
+
+int stx_set_content_mask(stx_engine *e, const float *mask, int H, int W, int mem) {
+    if (!e || (mask && (H <= 0 || W <= 0))) return STX_ERR_ARG;
+    SharedState &sh = *e->sh;
+    MaskSource source;
+    return swap_targets(e, "stx_set_content_mask", [&](bool &) -> int {
+        clear_targets(sh.cmasks);
+        if (!mask) return STX_OK;
+        if (sh.contents.empty()) {
+            set_error("stx_set_content_mask: no content targets set (call it after stx_set_contents_and_styles)");
+            return STX_ERR_STATE;
+        }
+        // the map of a blob has the size of the blob's content maps: the tile's window is taken from both alike
+        for (const ContentTarget &ct : sh.contents) {
+            const int scale = e->blobs[ct.blob].scale;
+            if (ceil_div(H, scale) != ct.h || ceil_div(W, scale) != ct.w) {
+                set_error("stx_set_content_mask: a %dx%d mask gives a %dx%d map at layer %s, whose content map is "
+                          "%dx%d; the mask must have the content picture's size", H, W, ceil_div(H, scale),
+                          ceil_div(W, scale), e->blobs[ct.blob].name.c_str(), ct.h, ct.w);
+                return STX_ERR_ARG;
+            }
+        }
+        STX_TRY(source.stage(e, mask, H, W, mem));
+        for (const ContentTarget &ct : sh.contents) {
+            bool have = false;
+            for (const ContentMask &m : sh.cmasks) have |= m.blob == ct.blob;
+            if (have) continue;
+            sh.cmasks.push_back(ContentMask{ct.blob, ct.h, ct.w, nullptr});
+            STX_TRY(source.map_at(e, e->blobs[ct.blob].scale, ct.h, ct.w, sh.cmasks.back().map));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(sh.cmasks); });
+}
+
+int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    auto &stats = e->sh->stats;
+    return swap_targets(e, "stx_set_stat_targets", [&](bool &) -> int {
+        clear_targets(stats);
+        for (int i = 0; i < n; ++i) {
+            const stx_stat_target &st = targets[i];
+            const int blob = e->find_blob(st.layer);
+            bool twice = false;
+            for (const StatTarget &t : stats) twice |= t.blob == blob;
+            if (blob <= 0 || !st.mean || !st.sd || twice) {
+                set_error("statistics target %d: bad layer '%s' (unknown, the input, or given twice) or no data", i,
+                          st.layer ? st.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            if (st.channels != e->blobs[blob].channels) {
+                set_error("statistics target %d: layer %s has %d channels, not %d", i, st.layer,
+                          e->blobs[blob].channels, st.channels);
+                return STX_ERR_ARG;
+            }
+            stats.push_back(StatTarget{blob, st.channels, st.weight, std::unique_ptr<DevBuf>(new DevBuf)});
+            StatTarget &t = stats.back();
+            const size_t bytes = (size_t)t.C * sizeof(float);
+            STX_TRY(t.ms->ensure(2 * bytes));
+            STX_TRY(copy_in(e, t.ms->ptr, st.mean, st.mem, bytes));
+            STX_TRY(copy_in(e, t.ms->f() + t.C, st.sd, st.mem, bytes));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(stats); });
+}
+
+int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    std::vector<stx_nnfm_patch_target> as_patch;
+    for (int i = 0; i < n; ++i) {
+        const stx_nnfm_target &t = targets[i];
+        as_patch.push_back(stx_nnfm_patch_target{t.layer, t.channels, 1, t.rows, t.bank, t.mem, t.weight});
+    }
+    return set_nnfm_banks(e, as_patch.data(), n, "stx_set_nnfm_targets");
+}
+
+int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n) {
+    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_patch_targets");
+}
+
+}  // extern "C"

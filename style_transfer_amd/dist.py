@@ -31,6 +31,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .config_system import option_on
+
 
 class DistributedTiles:
     """cut(rect, roll) -> tensor[3,th,tw] on rank 0; evaluate(jobs, roll) with
@@ -179,42 +181,25 @@ class DistributedTiles:
         return None
 
 
-def refuse_style_masks(args):
-    """--style-masks with one process per GPU: the masks would have to travel to every rank with the
-    targets, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
-    if getattr(args, 'style_masks', None):
-        raise NotImplementedError('--style-masks is not implemented for the one-process-per-GPU layout '
-                                  '(style_transfer_amd.dist): the masks are not broadcast to the ranks; '
-                                  'run the single-process tile farm (--devices) instead')
+# Options whose targets would have to travel to every rank with the contents and styles, which broadcast_targets
+# does not do: (option, whether it is a weight that may be bound to the run state, what is not broadcast).
+UNBROADCAST_OPTIONS = (
+    ('style_masks', False, 'the masks are'),
+    ('content_mask', False, 'the mask is'),
+    ('stat_weight', True, 'the statistics targets are'),
+    ('nnfm_weight', True, 'the banks of style features are'),
+)
 
 
-def refuse_content_mask(args):
-    """--content-mask with one process per GPU: the mask would have to travel to every rank with the
-    targets, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
-    if getattr(args, 'content_mask', None):
-        raise NotImplementedError('--content-mask is not implemented for the one-process-per-GPU layout '
-                                  '(style_transfer_amd.dist): the mask is not broadcast to the ranks; '
-                                  'run the single-process tile farm (--devices) instead')
-
-
-def refuse_stat_weight(args):
-    """--stat-weight with one process per GPU: the statistics targets would have to travel to every rank
-    with the others, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
-    raw = getattr(getattr(args, 'ns', args), 'stat_weight', 0)
-    if callable(raw) or raw:
-        raise NotImplementedError('--stat-weight is not implemented for the one-process-per-GPU layout '
-                                  '(style_transfer_amd.dist): the statistics targets are not broadcast to the '
-                                  'ranks; run the single-process tile farm (--devices) instead')
-
-
-def refuse_nnfm_weight(args):
-    """--nnfm-weight with one process per GPU: the banks would have to travel to every rank with the other
-    targets, which broadcast_targets does not do.  The single-process farm drives several GPUs."""
-    raw = getattr(getattr(args, 'ns', args), 'nnfm_weight', 0)
-    if callable(raw) or raw:
-        raise NotImplementedError('--nnfm-weight is not implemented for the one-process-per-GPU layout '
-                                  '(style_transfer_amd.dist): the banks of style features are not broadcast to '
-                                  'the ranks; run the single-process tile farm (--devices) instead')
+def refuse_unbroadcast_options(args):
+    """A run with one of UNBROADCAST_OPTIONS set is refused for the one-process-per-GPU layout: the
+    single-process farm drives several GPUs."""
+    for name, lazy_weight, what in UNBROADCAST_OPTIONS:
+        if option_on(args, name) if lazy_weight else getattr(args, name, None):
+            raise NotImplementedError('--%s is not implemented for the one-process-per-GPU layout '
+                                      '(style_transfer_amd.dist): %s not broadcast to the ranks; run the '
+                                      'single-process tile farm (--devices) instead'
+                                      % (name.replace('_', '-'), what))
 
 
 def _wire_device(device, group):
@@ -263,13 +248,10 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks, --content-mask, --stat-weight or --nnfm-weight is refused here (refuse_style_masks,
-    refuse_content_mask, refuse_stat_weight, refuse_nnfm_weight)."""
+    a run with --style-masks, --content-mask, --stat-weight or --nnfm-weight is refused here
+    (refuse_unbroadcast_options)."""
     if args is not None:
-        refuse_style_masks(args)
-        refuse_content_mask(args)
-        refuse_stat_weight(args)
-        refuse_nnfm_weight(args)
+        refuse_unbroadcast_options(args)
     rank = dist.get_rank(group)
     wire = _wire_device(device, group)
     meta = [None]

@@ -25,6 +25,7 @@ from .netspec import NetSpec
 
 _TYPE_CODES = {'Input': lib.LAYER_INPUT, 'Convolution': lib.LAYER_CONV, 'ReLU': lib.LAYER_RELU,
                'Pooling': lib.LAYER_POOL}
+EXTRA_TAP_KINDS = ('stat', 'nnfm')      # the targets that tap layers of their own, in the order of their taps
 
 
 class DeviceArray:
@@ -157,8 +158,9 @@ class TileEngine:
         self._results = []
         self._info = {b: net.layer_info(b) for b in net.blob_names()}
         self.n_styles = 0
-        self.stat_layers = []       # (of the primary: the layers of the group's statistics targets)
-        self.nnfm_layers = []       # (of the primary: the layers of the group's NNFM banks)
+        # (of the primary) the layers that the group's extra targets tap, by kind: kept like the library keeps
+        # the targets -- emptied by set_contents_and_styles, one kind replaced by its setter
+        self.extra_taps = {kind: [] for kind in EXTRA_TAP_KINDS}
         if weights and share is None:
             for name, (w, b) in weights.items():
                 self.set_weights(name, w, b)
@@ -300,8 +302,8 @@ class TileEngine:
                 i += 1
         lib.call('stx_set_contents_and_styles', self.handle, ctargets, n_c, starget, n_s)
         self.n_styles = len(styles)
-        self.primary.stat_layers = []           # (the library clears the statistics targets with these)
-        self.primary.nnfm_layers = []           # (... and the NNFM banks)
+        # (the library clears the extra targets with these)
+        self.primary.extra_taps = {kind: [] for kind in EXTRA_TAP_KINDS}
 
     def set_stat_targets(self, targets, weights=None):
         """targets: {layer: (mean [C], sd [C])} -- what ``feature_stats`` gives for a style picture's
@@ -319,7 +321,7 @@ class TileEngine:
             t.layer, t.channels, t.mean, t.sd, t.mem = self._cstr(layer), int(mobj.shape[0]), mp, sp, mmem
             t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
         lib.call('stx_set_stat_targets', self.handle, table, n)
-        self.primary.stat_layers = list(targets)
+        self.primary.extra_taps['stat'] = list(targets)
         del keep
 
     def set_nnfm_targets(self, banks, weights=None, patch=1):
@@ -343,7 +345,7 @@ class TileEngine:
             t.channels, t.bank, t.mem = int(obj.shape[1]) // (t.patch * t.patch), ptr, mem
             t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
         lib.call('stx_set_nnfm_patch_targets', self.handle, table, n)
-        self.primary.nnfm_layers = list(banks)
+        self.primary.extra_taps['nnfm'] = list(banks)
         del keep
 
     def nnfm_bank(self, feat, stride=1, patch=1):
@@ -467,7 +469,7 @@ class TileEngine:
               dd_layers=(), dd_weight=None):
         # (a layer that only a statistics target names is tapped for nothing: the tap carries its layer weight)
         names = list(dict.fromkeys(list(content_layers) + list(style_layers) + list(dd_layers) +
-                                   list(self.primary.stat_layers) + list(self.primary.nnfm_layers)))
+                                   sum(self.primary.extra_taps.values(), [])))
         taps = (lib.Tap * len(names))()
         for t, name in zip(taps, names):
             t.layer = self._cstr(name)

@@ -159,49 +159,35 @@ class TileFarm:
             for name, (w, b) in weights.items():
                 e.set_weights(name, w, b)
 
+    def _set_on_primaries(self, method, *args):
+        """Syncs every engine (nothing queued may still read what is replaced), then calls the named
+        TileEngine method on every GPU's primary: the targets go to every GPU, once each."""
+        for e in self.engines:
+            e.sync()
+        for e in self.primaries():
+            getattr(e, method)(*args)
+
     def set_contents_and_styles(self, contents, styles):
         """Hands the targets to every GPU, once each (TileWorkerPool.set_contents_and_styles,
         style_transfer.py:309-332, sends them to every worker process)."""
         self._targets = (contents, styles)
-        for e in self.engines:          # nothing of the previous scale may still be running
-            e.sync()
-        for e in self.primaries():
-            e.set_contents_and_styles(contents, styles)
+        self._set_on_primaries('set_contents_and_styles', contents, styles)
 
+    # The optional targets (TileEngine's methods of the same names): call them behind ``set_contents_and_styles``.
     def set_style_masks(self, masks):
-        """Hands the style masks (TileEngine.set_style_masks) to every GPU, once each, the way the
-        targets are handed; call it behind ``set_contents_and_styles``."""
-        for e in self.engines:
-            e.sync()
-        for e in self.primaries():
-            e.set_style_masks(masks)
+        self._set_on_primaries('set_style_masks', masks)
 
     def set_content_mask(self, mask):
-        """Hands the content mask (TileEngine.set_content_mask) to every GPU, once each, the way the
-        targets are handed; call it behind ``set_contents_and_styles``."""
-        for e in self.engines:
-            e.sync()
-        for e in self.primaries():
-            e.set_content_mask(mask)
+        self._set_on_primaries('set_content_mask', mask)
 
     def set_stat_targets(self, targets, weights=None):
-        """Hands the statistics targets (TileEngine.set_stat_targets) to every GPU, once each; call it
-        behind ``set_contents_and_styles``."""
-        for e in self.engines:
-            e.sync()
-        for e in self.primaries():
-            e.set_stat_targets(targets, weights)
+        self._set_on_primaries('set_stat_targets', targets, weights)
+
+    def set_nnfm_targets(self, banks, weights=None, patch=1):
+        self._set_on_primaries('set_nnfm_targets', banks, weights, patch)
 
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)
-
-    def set_nnfm_targets(self, banks, weights=None, patch=1):
-        """Hands the NNFM banks (TileEngine.set_nnfm_targets) to every GPU, once each; call it behind
-        ``set_contents_and_styles``."""
-        for e in self.engines:
-            e.sync()
-        for e in self.primaries():
-            e.set_nnfm_targets(banks, weights, patch)
 
     def nnfm_bank(self, feat, stride=1, patch=1):
         return self.master.nnfm_bank(feat, stride, patch)

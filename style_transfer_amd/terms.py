@@ -1,0 +1,271 @@
+"""The optional loss terms of a run (none but SWT is an option of the reference), behind two small protocols: the
+schedule in ``transfer.py`` loops over two lists built from the options and names no term.  Target terms keep targets
+in the engines beside the Grams; image terms add to the loss of the whole image.  The order of a list is the order
+of the library's calls and of the loss's sum.  ``st`` below is the StyleTransfer.
+"""
+
+import warnings
+
+import numpy as np
+from PIL import Image
+
+from . import image_ops
+from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_nnfm_options,
+                            check_photo_options, check_stat_options, ffloat, nnfm_bank_rows, nnfm_layer_args,
+                            nnfm_patch, nnfm_stride, option_on, stat_layer_args)
+
+
+def parse_weights(args, master_weight):
+    """['name', 'name:2', ...] -> (names, {name: weight normalised to sum |w| = master})
+    (style_transfer.py:684-698)."""
+    names, weights, total = [], {}, 0
+    for arg in args:
+        name, _, w = arg.partition(':')
+        names.append(name)
+        weights[name] = ffloat(w) if w else 1
+        total += abs(weights[name])
+    return names, {n: w * master_weight / total for n, w in weights.items()}
+
+
+def lap_pool_weights(pools, lap_weight):
+    """--lap-pools ['4', '16:3'] and --lap-weight 30 -> ([4, 16], [7.5, 22.5]): the pool sizes and their
+    weights, normalised to sum |w| = lap_weight exactly as a layer list's are (parse_weights)."""
+    names, weights = parse_weights(list(pools), lap_weight)
+    return [int(name) for name in names], [weights[name] for name in names]
+
+
+def mask_at_size(mask, size_hw):
+    """A greyscale PIL mask at one scale: Lanczos-resized to (H, W), as float32 in [0, 1] (clipped)."""
+    h, w = int(size_hw[0]), int(size_hw[1])
+    return np.clip(np.float32(mask.convert('L').resize((w, h), Image.LANCZOS)) / np.float32(255), 0, 1)
+
+
+def rolled_mask(mask, roll):
+    """An [H, W] mask moved with the picture by ``roll`` = (x, y) pixels (--jitter), wrapping; None: as it is."""
+    if roll is None:
+        return mask
+    return np.roll(mask, (int(roll[1]), int(roll[0])), (0, 1))
+
+
+# ---------------------------------------------------------------------------------------- target terms
+def _nothing(self, *args, **kwargs):
+    pass
+
+
+class TargetTerm:
+    """A term whose targets live in the engines.  Per scale ``read(st)`` comes first.  When the style targets are
+    made (preprocess_images) the term sees every variant's feature maps at its ``layers``: ``begin()``,
+    ``take(st, layer, feat)`` per variant and layer, ``finish(st, count, quiet)`` with the variant count.
+    ``send(st, roll)`` follows every set_contents_and_styles, which clears the engines' copy (``roll``: the
+    iteration's shift under --jitter).  ``drop()`` goes with the style targets."""
+    layers = ()
+    read = begin = take = finish = send = drop = _nothing
+
+
+class LayerTargets(TargetTerm):
+    """One target per layer of a ``LAYER[:weight]`` list, which is read once per scale like the other layer lists.
+    The targets may be older (--style-multiscale): a layer that a later reading drops gets no term, and one that
+    it adds has no target and is refused."""
+    weights = targets = None    # {layer: weight} of the scale; {layer: target}, or None while there are none
+
+    def read(self, st):
+        self.layers, self.weights = parse_weights(self.layer_args(st.args), getattr(st.args, self.WEIGHT))
+
+    def begin(self):
+        self._parts = {layer: [] for layer in self.layers}
+
+    def drop(self):
+        self.targets = None
+
+    def send(self, st, roll=None):
+        if not self.weights:
+            return
+        missing = [layer for layer in self.weights if layer not in self.targets]
+        if missing:
+            raise ValueError('%s %s: no %s was taken there; with --style-multiscale the layers are those of the '
+                             'first scale' % (self.FLAG, ' '.join(missing), self.WHAT))
+        self.set_targets(st.farm, {layer: self.targets[layer] for layer in self.weights})
+
+
+class StatTargets(LayerTargets):
+    """--stat-weight / --stat-layers (the mean / std style term): per-channel mean and sd of the style pictures'
+    feature maps, averaged like the Grams; ``targets`` = {layer: (mean [C], sd [C])}."""
+    FLAG, WEIGHT, WHAT, layer_args = '--stat-layers', 'stat_weight', 'statistics target', staticmethod(stat_layer_args)
+
+    def take(self, st, layer, feat):
+        self._parts[layer].append(np.stack(st.farm.feature_stats(feat)))
+
+    def finish(self, st, count, quiet):
+        self.targets = {layer: tuple(sum(parts[1:], parts[0]) / np.float32(count))
+                        for layer, parts in self._parts.items() if parts}
+
+    def set_targets(self, farm, targets):
+        farm.set_stat_targets(targets, self.weights)
+
+
+class NnfmBanks(LayerTargets):
+    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch (nearest-neighbour feature matching): per layer
+    one bank of the style pictures' unit feature vectors (3 x 3 patches of them with --nnfm-patch 3), built on the
+    master GPU and concatenated over the variants; ``targets`` = {layer: DeviceArray [rows, patch^2 C]}."""
+    FLAG, WEIGHT, WHAT, layer_args = '--nnfm-layers', 'nnfm_weight', 'bank', staticmethod(nnfm_layer_args)
+    targets_patch = 1       # --nnfm-patch of the banks in ``targets``
+
+    def read(self, st):
+        super().read(st)
+        self.stride, self.patch = nnfm_stride(st.args), nnfm_patch(st.args)
+
+    def take(self, st, layer, feat):
+        # (a bank past the library's offsets is refused before this part is allocated)
+        nnfm_bank_rows(*feat.shape, self.stride, self.patch, sum(part.shape[0] for part in self._parts[layer]))
+        self._parts[layer].append(st.farm.nnfm_bank(feat, self.stride, self.patch))
+
+    def finish(self, st, count, quiet):
+        self.targets = {layer: st.engine.concat_rows(parts) for layer, parts in self._parts.items()}
+        self.targets_patch = self.patch
+        if not quiet:
+            print('NNFM bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0])
+                                                 for layer, bank in self.targets.items()) +
+                  ('; patch %d' % self.patch if self.patch != 1 else ''))
+
+    def drop(self):
+        for bank in (self.targets or {}).values():
+            bank.free()
+        self.targets = None
+
+    def set_targets(self, farm, targets):
+        farm.set_nnfm_targets(targets, self.weights, self.targets_patch)
+
+
+class Masks(TargetTerm):
+    """--style-masks / --content-mask (spatial control): ``st.style_masks`` and ``st.content_mask`` resized to the
+    scale's content size.  Under --jitter the engines hold content maps of the rolled picture and shift nothing,
+    so the masks are rolled too.  Without masks nothing here runs."""
+    style = content = None      # [H, W] float32 arrays in [0, 1] of the scale being optimised
+
+    def read(self, st):
+        if st.style_masks is not None:
+            self.style = [mask_at_size(mask, st.img.shape[1:]) for mask in st.style_masks]
+        if st.content_mask is not None:
+            self.content = mask_at_size(st.content_mask, st.img.shape[1:])
+
+    def send(self, st, roll=None):
+        if self.style is not None:
+            if len(st.styles) != len(self.style):
+                raise ValueError('--style-masks: %d mask(s) for %d style set(s)' % (len(self.style), len(st.styles)))
+            st.farm.set_style_masks([rolled_mask(mask, roll) for mask in self.style])
+        # (the content mask goes with content targets only: under --jitter there are none until the first step)
+        if self.content is not None and st.contents:
+            st.farm.set_content_mask(rolled_mask(self.content, roll))
+
+
+def target_terms(args, known_layers):
+    """The target terms of a run, in the order they are sent; a bad option is refused here, before any GPU work.
+    (The masks are handed to transfer_multiscale, so their term is always listed.)"""
+    checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks))
+    return [cls() for check, cls in checked if check(args, known_layers)] + [Masks()]
+
+
+# ----------------------------------------------------------------------------------------- image terms
+class ImageTerm:
+    """A term of the whole image.  Per scale ``prepare(st, picture)``: ``picture`` is ``st.content_picture``, which
+    StyleTransfer owns -- there for a term that ``needs_content``, and still there at every ``add()`` for one that
+    ``keeps_content``; a term frees only what it made.  ``add(st, loss, params, roll)`` adds the term to ``loss``
+    and its gradient to ``st.grad``; weights are read at every evaluation (a config file may bind them)."""
+    needs_content = keeps_content = False
+    __init__ = prepare = add = _nothing
+
+
+class SwtTerm(ImageTerm):
+    """--swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the reference tree; its
+    transform is restated for the Haar wavelet only, at any level count (oracle/num_ops.py,
+    tests/swt_levels_ref.py)."""
+
+    def __init__(self, args):
+        if str(args.swt_wavelet) not in ('haar', 'db1'):
+            raise NotImplementedError('--swt-wavelet %s: only the Haar wavelet (haar / db1) is '
+                                      'implemented' % args.swt_wavelet)
+        if int(args.swt_levels) < 1:
+            raise ValueError('--swt-levels %s: at least one level is needed' % args.swt_levels)
+        warnings.warn('--swt-weight: the Haar SWT term is a restatement of PyWavelets\' '
+                      'swt2 / iswt2, which is not part of the reference tree and not '
+                      'installed here; it has never been compared with it (parity unpinned)')
+
+    def prepare(self, st, picture):
+        # pywt.swt2 refuses more levels than log2 of the padded side (num_utils.py:186-191):
+        # the reference stops at its first evaluation of such a scale
+        args, (h, w) = st.args, st.img.shape[1:]
+        side = image_ops.swt_padded_side(h, w)
+        if 2 ** int(args.swt_levels) > side:
+            raise ValueError('--swt-levels %d: a %d x %d image is padded to a square of side %d, '
+                             'which takes %d levels at most (raise --min-size or lower the level '
+                             'count)' % (args.swt_levels, w, h, side, side.bit_length() - 1))
+
+    def add(self, st, loss, params, roll):
+        args = st.args
+        if args.swt_weight:
+            loss.add(image_ops.swt_haar(st.engine, params, st.grad, st.layer_weights['data'] * args.swt_weight,
+                                        args.swt_power, roll=roll, levels=int(args.swt_levels)), st.engine)
+
+
+class LapTerm(ImageTerm):
+    """--lap-weight / --lap-pools (the Laplacian loss): ``target`` is D P_p u of the scale's first content
+    picture for every pool size, on the master GPU; the previous scale's is freed when the next one is made."""
+    needs_content = True
+
+    def __init__(self, args):
+        self.pools = check_lap_pools(args)
+        self.target = None
+        self._key = self._weights = None    # the last (--lap-pools, lap_weight) parsed
+
+    def prepare(self, st, picture):
+        target = image_ops.lap_target(st.engine, picture, self.pools)
+        if self.target is not None:
+            self.target.free()
+        self.target = target
+
+    def add(self, st, loss, params, roll):
+        lap_weight = getattr(st.args, 'lap_weight', 0)
+        if lap_weight:
+            # the pool weights carry --lap-weight (sum |w| = lap_weight), the scale the data layer's factor
+            loss.add(image_ops.lap_loss(st.engine, params, st.grad, self.target, self.pools,
+                                        self.weights(st.args, lap_weight), st.layer_weights['data']), st.engine)
+
+    def weights(self, args, lap_weight):
+        """The weights of the target's pool sizes for this evaluation.  The sizes are those the target was
+        made for: the target's layout follows from them, so an ``args.lap_pools`` that names other sizes
+        by now is refused and never reaches the kernels."""
+        spec = getattr(args, 'lap_pools', None) or LAP_POOLS_DEFAULT
+        key = (tuple([spec] if isinstance(spec, str) else spec), lap_weight)
+        if key != self._key:
+            pools, weights = lap_pool_weights(key[0], lap_weight)
+            if pools != self.pools:
+                raise ValueError('--lap-pools changed from %s to %s during the run; the pool sizes are fixed '
+                                 'when the run starts, only their weights may move' % (self.pools, pools))
+            self._key, self._weights = key, weights
+        return self._weights
+
+
+class PhotoTerm(ImageTerm):
+    """--photo-weight / --photo-eps (the photorealism regulariser): the matting Laplacian of the scale's first
+    content picture, which stays on the master GPU for it."""
+    needs_content = keeps_content = True
+
+    def prepare(self, st, picture):
+        if min(st.img.shape[1:]) < 3:
+            raise ValueError('--photo-weight: a %d x %d image holds no 3 x 3 window (raise --min-size)'
+                             % (st.img.shape[2], st.img.shape[1]))
+
+    def add(self, st, loss, params, roll):
+        photo_weight = getattr(st.args, 'photo_weight', 0)
+        if photo_weight:
+            eps = check_photo_options(st.args)
+            if isinstance(eps, ValuePlaceholder):
+                raise ValueError('--photo-eps is bound to run state that does not exist at an evaluation')
+            loss.add(image_ops.photo_loss(st.engine, params, st.grad, st.content_picture, eps,
+                                          st.layer_weights['data'] * photo_weight), st.engine)
+
+
+def image_terms(args):
+    """The image terms of a run, in the order they join the loss; a bad option is refused here."""
+    weights = (('swt_weight', SwtTerm), ('lap_weight', LapTerm), ('photo_weight', PhotoTerm))
+    return [cls(args) for name, cls in weights if option_on(args, name)]

@@ -22,13 +22,10 @@ import time
 import numpy as np
 from PIL import Image
 
-from . import image_ops, lib
-from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_photo_options,
-                            check_nnfm_options, check_stat_options, ffloat, nnfm_bank_rows, nnfm_layer_args,
-                            nnfm_patch, nnfm_stride,
-                            stat_layer_args)
+from . import image_ops, lib, terms
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
+from .terms import lap_pool_weights, mask_at_size, parse_weights, rolled_mask      # (their users import them here)
 
 
 def fit_size(wh, size, scale_up=False, div=1):
@@ -114,38 +111,6 @@ def style_pyramid(args):
 PRESERVE_COLOR = ('none', 'luma', 'match')
 
 
-def mask_at_size(mask, size_hw):
-    """A greyscale PIL mask at one scale: Lanczos-resized to (H, W), as float32 in [0, 1] (clipped)."""
-    h, w = int(size_hw[0]), int(size_hw[1])
-    return np.clip(np.float32(mask.convert('L').resize((w, h), Image.LANCZOS)) / np.float32(255), 0, 1)
-
-
-def rolled_mask(mask, roll):
-    """An [H, W] mask moved with the picture by ``roll`` = (x, y) pixels (--jitter), wrapping; None: as it is."""
-    if roll is None:
-        return mask
-    return np.roll(mask, (int(roll[1]), int(roll[0])), (0, 1))
-
-
-def parse_weights(args, master_weight):
-    """['name', 'name:2', ...] -> (names, {name: weight normalised to sum |w| = master})
-    (style_transfer.py:684-698)."""
-    names, weights, total = [], {}, 0
-    for arg in args:
-        name, _, w = arg.partition(':')
-        names.append(name)
-        weights[name] = ffloat(w) if w else 1
-        total += abs(weights[name])
-    return names, {n: w * master_weight / total for n, w in weights.items()}
-
-
-def lap_pool_weights(pools, lap_weight):
-    """--lap-pools ['4', '16:3'] and --lap-weight 30 -> ([4, 16], [7.5, 22.5]): the pool sizes and their
-    weights, normalised to sum |w| = lap_weight exactly as a layer list's are (parse_weights)."""
-    names, weights = parse_weights(list(pools), lap_weight)
-    return [int(name) for name in names], [weights[name] for name in names]
-
-
 class StyleTransfer:
     """Runs style transfer on a ``TileFarm``.  ``args`` is the option namespace of
     ``config_system.parse_args`` (any object with the same attributes works)."""
@@ -180,62 +145,16 @@ class StyleTransfer:
         if self.preserve_color not in PRESERVE_COLOR:
             raise ValueError('--preserve-color %s: one of %s' % (self.preserve_color,
                                                                  ', '.join(PRESERVE_COLOR)))
-        self._luma_content = None   # DeviceArray [3,H,W] ('luma' only)
-        # --style-masks (spatial control; not an option of the reference): one greyscale PIL picture per
-        # style image in the content picture's frame, handed to transfer_multiscale.  With masks every
-        # style picture is a style set of its own, and the masks -- resized to the scale's content size --
-        # go to the engines behind the targets.  None: no new code runs.
+        # The scale's first content picture on the master GPU, DeviceArray [3,H,W]: at most one copy, owned here,
+        # made once per scale when 'luma' or an image term reads it (transfer) and freed there at the next.
+        self.content_picture = None
+        # --style-masks / --content-mask (spatial control): greyscale PIL pictures in the content picture's frame,
+        # handed to transfer_multiscale.  With style masks every style picture is a style set of its own.
         self.style_masks = None
-        self._scale_masks = None    # [H, W] float32 arrays in [0, 1] of the scale being optimised
-        # --content-mask (spatial control of the content term; not an option of the reference): one greyscale
-        # PIL picture in the content picture's frame, handed to transfer_multiscale; resized to the scale's
-        # content size it goes to the engines behind the targets.  None: no new code runs.
         self.content_mask = None
-        self._scale_content_mask = None
-        # --lap-weight / --lap-pools (the Laplacian loss; not options of the reference): the target of the
-        # scale being optimised, D P_p u of its first content picture for every pool size, on the master
-        # GPU.  Without the options nothing here runs.
-        raw = getattr(getattr(args, 'ns', args), 'lap_weight', 0)
-        self._lap_on = bool(callable(raw) or raw)
-        self._lap_pools = check_lap_pools(args) if self._lap_on else []
-        self._lap_target = None
-        self._lap_weights_key = self._lap_weights_now = None    # the last (--lap-pools, lap_weight) parsed
-        # --photo-weight / --photo-eps (the photorealism regulariser; not options of the reference): the first
-        # content picture of the scale being optimised stays on the master GPU -- the very array that
-        # --preserve-color luma keeps, when it keeps one.  Without --photo-weight nothing here runs.
-        raw = getattr(getattr(args, 'ns', args), 'photo_weight', 0)
-        self._photo_on = bool(callable(raw) or raw)
-        self._photo_content = None  # DeviceArray [3,H,W]
-        self._photo_shared = False  # it is self._luma_content, which is freed where it is made
-        # --stat-weight / --stat-layers (the mean / std style term; not options of the reference): per-channel
-        # mean and sd of the style pictures' feature maps, averaged like the Grams and kept where they are
-        # kept; sent to the engines behind the targets.  Without the options nothing here runs.
-        self._stat_on = bool(check_stat_options(args, farm.layers()))
-        self.stat_targets = None    # {layer: (mean [C], sd [C])}
-        self._stat_weights = None   # {layer: weight} of the scale being optimised
-        # --nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch (the nearest-neighbour feature matching term;
-        # not options of the reference): per layer one bank of the style pictures' unit feature vectors (unit
-        # 3 x 3 patches of them with --nnfm-patch 3), built and
-        # concatenated on the master GPU, kept where the Grams are kept; sent to the engines behind the targets.
-        # Without the options nothing here runs.
-        self._nnfm_on = bool(check_nnfm_options(args, farm.layers()))
-        self.nnfm_banks = None      # {layer: DeviceArray [rows, C]}
-        self._nnfm_weights = None   # {layer: weight} of the scale being optimised
-        self._nnfm_patch = 1        # --nnfm-patch of the banks in ``nnfm_banks``
-        # --swt-weight (style_transfer.py:716-720) calls PyWavelets, which is not part of the
-        # reference tree; its transform is restated for the Haar wavelet only, at any level count
-        raw = getattr(getattr(args, 'ns', args), 'swt_weight', 0)
-        self._swt_on = bool(callable(raw) or raw)
-        if self._swt_on and str(args.swt_wavelet) not in ('haar', 'db1'):
-            raise NotImplementedError('--swt-wavelet %s: only the Haar wavelet (haar / db1) is '
-                                      'implemented' % args.swt_wavelet)
-        if self._swt_on and int(args.swt_levels) < 1:
-            raise ValueError('--swt-levels %s: at least one level is needed' % args.swt_levels)
-        if self._swt_on:
-            import warnings
-            warnings.warn('--swt-weight: the Haar SWT term is a restatement of PyWavelets\' '
-                          'swt2 / iswt2, which is not part of the reference tree and not '
-                          'installed here; it has never been compared with it (parity unpinned)')
+        # the optional terms of the run (terms.py), each list in the order of its library calls
+        self.target_terms = terms.target_terms(args, farm.layers())
+        self.image_terms = terms.image_terms(args)
 
     # ----------------------------------------------------------------------- image <-> params
     def pil_to_image(self, img):
@@ -257,11 +176,11 @@ class StyleTransfer:
         the run is written: under --preserve-color luma with the content picture's chroma."""
         params = self.current_raw if params is None else params
         if self.preserve_color == 'luma':
-            if self._luma_content is None or self._luma_content.shape != params.shape:
+            if self.content_picture is None or self.content_picture.shape != params.shape:
                 raise ValueError('--preserve-color luma: no content picture of size %dx%d is kept '
                                  '(pictures are written at the size of the scale being optimised)'
                                  % (params.shape[2], params.shape[1]))
-            return image_ops.to_u8_luma(self.engine, params, self._luma_content, self.mean)
+            return image_ops.to_u8_luma(self.engine, params, self.content_picture, self.mean)
         return image_ops.to_u8(self.engine, params, self.mean)
 
     @property
@@ -292,75 +211,26 @@ class StyleTransfer:
         A, b = image_ops.color_match_transform(image_ops.color_stats(self.engine, dev), target)
         return image_ops.color_affine(self.engine, dev, dev, A, b, self.mean)
 
-    def _masks_for(self, size_hw):
-        """The style masks at one scale: Lanczos-resized to the content size, clipped to [0, 1]."""
-        return [mask_at_size(mask, size_hw) for mask in self.style_masks]
-
-    def _send_masks(self, roll=None):
-        """The scale's style masks and content mask to the engines, behind the targets (which clear them).
-        ``roll`` (--jitter): the engines hold content maps of the rolled picture and shift nothing, so the
-        masks are rolled too.  The content mask goes with content targets only (under --jitter there are none
-        until the first step)."""
-        if self._scale_masks is not None:
-            self.farm.set_style_masks([rolled_mask(m, roll) for m in self._scale_masks])
-        if self._scale_content_mask is not None and self.contents:
-            self.farm.set_content_mask(rolled_mask(self._scale_content_mask, roll))
-
-    def _send_stats(self):
-        """The statistics targets of the scale's --stat-layers to the engines, behind the targets (which clear
-        them).  With --style-multiscale the targets are the first scale's: a layer that a later reading of
-        the list drops gets no term, and one that it adds has no target and is refused."""
-        if not self._stat_weights:
-            return
-        missing = [layer for layer in self._stat_weights if layer not in self.stat_targets]
-        if missing:
-            raise ValueError('--stat-layers %s: no statistics target was taken there; with --style-multiscale '
-                             'the layers are those of the first scale' % ' '.join(missing))
-        self.farm.set_stat_targets({layer: self.stat_targets[layer] for layer in self._stat_weights},
-                                   self._stat_weights)
-
-    def _send_nnfm(self):
-        """The banks of the scale's --nnfm-layers to the engines, behind the targets (which clear them).  With
-        --style-multiscale the banks are the first scale's: a layer that a later reading of the list drops
-        gets no term, and one that it adds has no bank and is refused."""
-        if not self._nnfm_weights:
-            return
-        missing = [layer for layer in self._nnfm_weights if layer not in self.nnfm_banks]
-        if missing:
-            raise ValueError('--nnfm-layers %s: no bank was taken there; with --style-multiscale the layers are '
-                             'those of the first scale' % ' '.join(missing))
-        self.farm.set_nnfm_targets({layer: self.nnfm_banks[layer] for layer in self._nnfm_weights},
-                                   self._nnfm_weights, self._nnfm_patch)
-
-    def _drop_nnfm(self):
-        for bank in (self.nnfm_banks or {}).values():
-            bank.free()
-        self.nnfm_banks = None
-
     def preprocess_images(self, content_images, style_images, content_layers, style_layers,
-                          roll=None, color_from=None, stat_layers=(), nnfm_layers=(), nnfm_stride=1,
-                          nnfm_patch=1):
+                          roll=None, color_from=None):
         """Targets of one scale: the style Grams, averaged with equal weight over every style
         image and ladder size (with --style-masks: over the ladder sizes of each style image, one
         style set per image), and the tiling-averaged content features
         (style_transfer.py:488-554).  Everything stays on the master GPU.  ``roll`` (--jitter,
         once per iteration): features of the pictures rolled by it, one pass, no messages.
         ``color_from`` (--preserve-color match): every style variant is recoloured on the GPU to the
-        colour mean and covariance of this picture before its features are taken.  ``stat_layers``
-        (--stat-weight): the per-channel mean and sd of the same feature maps at these layers, averaged the
-        same way, into ``self.stat_targets``.  ``nnfm_layers`` (--nnfm-weight): the banks of the same feature
-        maps at these layers (every ``nnfm_stride``-th row and column; with ``nnfm_patch`` 3 the 3 x 3 patches
-        centred there), built on the device and concatenated over the variants in this order, into
-        ``self.nnfm_banks``.  The features are taken at the union of the
-        three lists, once."""
+        colour mean and covariance of this picture before its features are taken.  The target terms see the
+        same feature maps at their own layers (terms.TargetTerm): the features are taken at the union of the
+        lists, once."""
         farm, tile = self.farm, self.args.tile_size
         if roll is None:
             print('Preprocessing the style image(s)...')
         if not self.styles:
-            total, count = {}, 0
-            stat_total = {}
-            feature_layers = list(dict.fromkeys(list(style_layers) + list(stat_layers) + list(nnfm_layers)))
-            bank_parts = {layer: [] for layer in nnfm_layers}
+            total, count, variants = {}, 0, 0
+            feature_layers = list(dict.fromkeys(list(style_layers) +
+                                                [layer for term in self.target_terms for layer in term.layers]))
+            for term in self.target_terms:
+                term.begin()
             target = None
             if color_from is not None and style_images:
                 kept = self.engine.to_device(self.pil_to_image(color_from))
@@ -376,41 +246,50 @@ class StyleTransfer:
                     if target is not None:
                         picture.free()
                     for layer, feat in feats.items():
-                        if layer in stat_layers:
-                            stats = np.stack(farm.feature_stats(feat))
-                            stat_total[layer] = stats if layer not in stat_total else stat_total[layer] + stats
-                        if layer in bank_parts:
-                            # (a bank past the library's offsets is refused before this part is allocated)
-                            nnfm_bank_rows(*feat.shape, nnfm_stride, nnfm_patch,
-                                           sum(part.shape[0] for part in bank_parts[layer]))
-                            bank_parts[layer].append(farm.nnfm_bank(feat, nnfm_stride, nnfm_patch))
-                        if layer not in style_layers:
-                            feat.free()
-                            continue
-                        gram = farm.gram_matrix(feat)
+                        for term in self.target_terms:
+                            if layer in term.layers:
+                                term.take(self, layer, feat)
+                        if layer in style_layers:
+                            gram = farm.gram_matrix(feat)
+                            total[layer] = gram if layer not in total else total[layer] + gram
                         feat.free()
-                        total[layer] = gram if layer not in total else total[layer] + gram
                     count += 1
+                    variants += 1
                 if self.style_masks is not None and count:     # one style set per picture
                     self.styles.append({layer: gram / count for layer, gram in total.items()})
                     total, count = {}, 0
             if self.style_masks is None:
                 self.styles.append({layer: gram / count for layer, gram in total.items()})
-            if stat_layers:
-                self.stat_targets = {layer: tuple(stats / np.float32(count)) for layer, stats in stat_total.items()}
-            if nnfm_layers:
-                self.nnfm_banks = {layer: self.engine.concat_rows(parts) for layer, parts in bank_parts.items()}
-                self._nnfm_patch = nnfm_patch
-                if roll is None:
-                    print('NNFM bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0])
-                                                         for layer, bank in self.nnfm_banks.items()) +
-                          ('; patch %d' % nnfm_patch if nnfm_patch != 1 else ''))
+            for term in self.target_terms:
+                term.finish(self, variants, quiet=roll is not None)
         if roll is None:
             print('Preprocessing the content image(s)...')
         self.contents += [farm.prepare_features_device(self.pil_to_image(image), content_layers,
                                                        tile, passes=10 if roll is None else 1,
                                                        roll=roll)
                           for image in content_images]
+
+    def _send_targets(self, roll=None):
+        """The contents and styles to the engines, then every target term's (``roll``: --jitter's shift)."""
+        self.farm.set_contents_and_styles(self.contents, self.styles)
+        for term in self.target_terms:
+            term.send(self, roll)
+
+    def _keep_content_picture(self, image):
+        """The scale's first content picture to the master GPU, once, when --preserve-color luma or an image term
+        reads it; the previous scale's is freed here.  The image terms prepare their scale from it; a copy that
+        only such preparation needed is freed again."""
+        luma = self.preserve_color == 'luma'
+        if self.content_picture is not None:
+            self.content_picture.free()
+            self.content_picture = None
+        if luma or any(term.needs_content for term in self.image_terms):
+            self.content_picture = self.engine.to_device(self.pil_to_image(image))
+        for term in self.image_terms:
+            term.prepare(self, self.content_picture)
+        if self.content_picture is not None and not (luma or any(term.keeps_content for term in self.image_terms)):
+            self.content_picture.free()
+            self.content_picture = None
 
     def _drop_contents(self):
         for content in self.contents:
@@ -441,42 +320,9 @@ class StyleTransfer:
                 lw * args.p_weight, args.p_power, self.aux_image,
                 lw * args.aux_weight if aux_on else 0.0, aux_roll=roll)
             loss.add(reg, self.engine)
-        if args.swt_weight:
-            # style_transfer.py:716-720.  Only the Haar transform is restated (oracle/num_ops.py,
-            # tests/swt_levels_ref.py): PyWavelets, which it calls, is not part of its tree.
-            swt = image_ops.swt_haar(self.engine, params, self.grad, lw * args.swt_weight,
-                                     args.swt_power, roll=roll, levels=int(args.swt_levels))
-            loss.add(swt, self.engine)
-        lap_weight = getattr(args, 'lap_weight', 0) if self._lap_target is not None else 0
-        if lap_weight:
-            # the pool weights carry --lap-weight (sum |w| = lap_weight), the scale the data layer's factor
-            lap = image_ops.lap_loss(self.engine, params, self.grad, self._lap_target, self._lap_pools,
-                                     self._lap_weights(args, lap_weight), lw)
-            loss.add(lap, self.engine)
-        photo_weight = getattr(args, 'photo_weight', 0) if self._photo_content is not None else 0
-        if photo_weight:
-            eps = check_photo_options(args)
-            if isinstance(eps, ValuePlaceholder):
-                raise ValueError('--photo-eps is bound to run state that does not exist at an evaluation')
-            photo = image_ops.photo_loss(self.engine, params, self.grad, self._photo_content, eps,
-                                         lw * photo_weight)
-            loss.add(photo, self.engine)
+        for term in self.image_terms:
+            term.add(self, loss, params, roll)
         return loss, self.grad
-
-    def _lap_weights(self, args, lap_weight):
-        """The weights of the target's pool sizes for this evaluation.  The sizes are those the target was
-        made for: the target's layout follows from them, so an ``args.lap_pools`` that names other sizes
-        by now is refused and never reaches the kernels."""
-        spec = getattr(args, 'lap_pools', None) or LAP_POOLS_DEFAULT
-        key = (tuple([spec] if isinstance(spec, str) else spec), lap_weight)
-        if key != self._lap_weights_key:
-            pools, weights = lap_pool_weights(key[0], lap_weight)
-            if pools != self._lap_pools:
-                raise ValueError('--lap-pools changed from %s to %s during the run; the pool sizes are fixed '
-                                 'when the run starts, only their weights may move'
-                                 % (self._lap_pools, pools))
-            self._lap_weights_key, self._lap_weights_now = key, weights
-        return self._lap_weights_now
 
     # --------------------------------------------------------------------------- one scale
     def transfer(self, iterations, content_images, style_images, callback=None):
@@ -486,74 +332,24 @@ class StyleTransfer:
         state.scale = state.scale + 1 if 'scale' in state else 0
         state.step, state.steps = 0, iterations
         state.img_size = self.img.shape[1:]
-        if self._swt_on:
-            # pywt.swt2 refuses more levels than log2 of the padded side (num_utils.py:186-191):
-            # the reference stops at its first evaluation of such a scale
-            side = image_ops.swt_padded_side(*self.img.shape[1:])
-            if 2 ** int(args.swt_levels) > side:
-                raise ValueError('--swt-levels %d: a %d x %d image is padded to a square of side %d, '
-                                 'which takes %d levels at most (raise --min-size or lower the level '
-                                 'count)' % (args.swt_levels, self.img.shape[2], self.img.shape[1],
-                                             side, side.bit_length() - 1))
-
         content_layers, content_weight = parse_weights(args.content_layers, args.content_weight)
         style_layers, style_weight = parse_weights(args.style_layers, 1)
         dd_layers, dd_weight = parse_weights(args.dd_layers, args.dd_weight)
         jitter = bool(args.jitter)
         self._drop_contents()                  # device-resident maps of the previous scale
-        stat_layers, self._stat_weights = [], None
-        if self._stat_on:       # (read once per scale, like the layer lists above)
-            stat_layers, self._stat_weights = parse_weights(stat_layer_args(args), args.stat_weight)
-        nnfm_layers, self._nnfm_weights = [], None
-        if self._nnfm_on:       # (read once per scale, like the layer lists above)
-            nnfm_layers, self._nnfm_weights = parse_weights(nnfm_layer_args(args), args.nnfm_weight)
-        if not args.style_multiscale:
+        for term in self.target_terms:         # (their options are read once per scale, like the layer lists above)
+            term.read(self)
+        if not args.style_multiscale:          # (with it the first scale's style targets stay)
             self.styles = []
-            self.stat_targets = None
-            self._drop_nnfm()
+            for term in self.target_terms:
+                term.drop()
+        self._keep_content_picture(content_images[0])
         # --jitter: the content maps are recomputed every iteration from the shifted picture
         # (style_transfer.py:757-763,789-794), only the style targets are fixed per scale
-        if self.preserve_color == 'luma':
-            if self._luma_content is not None:
-                self._luma_content.free()
-            self._luma_content = self.engine.to_device(self.pil_to_image(content_images[0]))
-        if self._lap_on:
-            picture = self._luma_content
-            if picture is None:
-                picture = self.engine.to_device(self.pil_to_image(content_images[0]))
-            target = image_ops.lap_target(self.engine, picture, self._lap_pools)
-            if self._lap_target is not None:
-                self._lap_target.free()
-            self._lap_target = target
-            if picture is not self._luma_content:
-                picture.free()
-        if self._photo_on:
-            if min(self.img.shape[1:]) < 3:
-                raise ValueError('--photo-weight: a %d x %d image holds no 3 x 3 window (raise --min-size)'
-                                 % (self.img.shape[2], self.img.shape[1]))
-            if self._photo_content is not None and not self._photo_shared:
-                self._photo_content.free()
-            self._photo_shared = self._luma_content is not None
-            self._photo_content = self._luma_content
-            if not self._photo_shared:
-                self._photo_content = self.engine.to_device(self.pil_to_image(content_images[0]))
         self.preprocess_images([] if jitter else content_images, style_images,
                                [] if jitter else content_layers, style_layers,
-                               color_from=content_images[0] if self.preserve_color == 'match' else None,
-                               stat_layers=stat_layers, nnfm_layers=nnfm_layers,
-                               nnfm_stride=nnfm_stride(args) if self._nnfm_on else 1,
-                               nnfm_patch=nnfm_patch(args) if self._nnfm_on else 1)
-        self.farm.set_contents_and_styles(self.contents, self.styles)
-        self._send_stats()
-        self._send_nnfm()
-        if self.style_masks is not None:
-            if len(self.styles) != len(self.style_masks):
-                raise ValueError('--style-masks: %d mask(s) for %d style set(s)'
-                                 % (len(self.style_masks), len(self.styles)))
-            self._scale_masks = self._masks_for(self.img.shape[1:])
-        if self.content_mask is not None:
-            self._scale_content_mask = mask_at_size(self.content_mask, self.img.shape[1:])
-        self._send_masks()
+                               color_from=content_images[0] if self.preserve_color == 'match' else None)
+        self._send_targets()
 
         if self.grad is None or self.grad.shape != self.img.shape:
             for buf in (self.grad, self.old_avg):
@@ -644,10 +440,7 @@ class StyleTransfer:
                 # them where they are
                 self._drop_contents()
                 self.preprocess_images(content_images, [], content_layers, [], roll=roll)
-                self.farm.set_contents_and_styles(self.contents, self.styles)
-                self._send_masks(roll=roll)
-                self._send_stats()
-                self._send_nnfm()
+                self._send_targets(roll)
                 content_roll = (0, 0)
             sc_args = (roll, content_layers, style_layers, content_weight, style_weight,
                        dd_layers, dd_weight, content_roll)

@@ -53,10 +53,10 @@ def test_refused_without_content_layers_before_any_gpu_work():
 
 
 def test_dist_refuses_content_mask():
-    from style_transfer_amd.dist import broadcast_targets, refuse_content_mask
-    refuse_content_mask(Namespace())
+    from style_transfer_amd.dist import broadcast_targets, refuse_unbroadcast_options
+    refuse_unbroadcast_options(Namespace())
     with pytest.raises(NotImplementedError, match='--content-mask is not implemented for the one-process-per-GPU'):
-        refuse_content_mask(Namespace(content_mask='m.png'))
+        refuse_unbroadcast_options(Namespace(content_mask='m.png'))
     with pytest.raises(NotImplementedError, match='content-mask'):
         broadcast_targets([], [], 'cpu', args=Namespace(content_mask='m.png'))
 

@@ -109,7 +109,7 @@ def tile_digests(eng):
         t.layer, t.channels, t.rows, t.bank, t.mem = b'conv3_1', 256, d_plain.shape[0], d_plain.ptr, lib.DEVICE
         t.weight = NNFM_W['conv3_1']
         lib.call('stx_set_nnfm_targets', eng.handle, table, 1)
-        eng.primary.nnfm_layers = ['conv3_1']
+        eng.primary.extra_taps['nnfm'] = ['conv3_1']
         out['tile alone plain'] = sha(*run())
         eng.set_nnfm_targets({'conv3_1': bank}, NNFM_W, patch=3)
         out['tile alone patch3'] = sha(*run())

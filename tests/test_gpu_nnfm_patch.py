@@ -276,14 +276,14 @@ def test_patch_1_gives_the_bytes_of_the_plain_entry_points():
     t.layer, t.channels, t.rows, t.bank, t.mem = b'conv3_1', 256, style_bank.shape[0], d_bank.ptr, lib.DEVICE
     t.weight = NNFM_W['conv3_1']
     lib.call('stx_set_nnfm_targets', eng.handle, table, 1)
-    eng.primary.nnfm_layers = ['conv3_1']
+    eng.primary.extra_taps['nnfm'] = ['conv3_1']
     plain = run()
     table = (lib.NnfmPatchTarget * 1)()
     t = table[0]
     t.layer, t.channels, t.patch, t.rows, t.bank, t.mem = b'conv3_1', 256, 1, style_bank.shape[0], d_bank.ptr, lib.DEVICE
     t.weight = NNFM_W['conv3_1']
     lib.call('stx_set_nnfm_patch_targets', eng.handle, table, 1)
-    eng.primary.nnfm_layers = ['conv3_1']
+    eng.primary.extra_taps['nnfm'] = ['conv3_1']
     try:
         through_patch = run()
     finally:

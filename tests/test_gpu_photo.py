@@ -268,7 +268,7 @@ def test_transfer_keeps_one_content_copy_per_scale_and_makes_one_call_per_evalua
         assert np.array_equal(call['picture'], want)         # the content picture at that scale's size
         assert call['eps'] == 1e-5 and call['scale'] == st.layer_weights['data'] * 1e4
         assert call['term'].value > 0
-    assert calls[0]['content'] is calls[1]['content'] and calls[2]['content'] is st._photo_content
+    assert calls[0]['content'] is calls[1]['content'] and calls[2]['content'] is st.content_picture
     assert calls[0]['content'].ptr is None                   # the previous scale's copy is freed
     farm.close()
 

@@ -221,11 +221,11 @@ def _untapped(eng, evaluate):
     """evaluate() with a tap list that names no layer for its statistics target alone (TileEngine adds a tap
     without flags for each): such a layer reaches the library through its target only, which adds it to the
     path with lw = 1."""
-    kept, eng.primary.stat_layers = eng.primary.stat_layers, []
+    kept, eng.primary.extra_taps['stat'] = eng.primary.extra_taps['stat'], []
     try:
         return evaluate()
     finally:
-        eng.primary.stat_layers = kept
+        eng.primary.extra_taps['stat'] = kept
 
 
 @pytest.mark.parametrize('case', ['pool', 'conv'])

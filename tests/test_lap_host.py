@@ -91,18 +91,18 @@ def test_the_pool_sizes_of_the_target_hold_for_the_run():
     """The target's layout follows from the pool sizes it was made for; an evaluation takes its weights
     from the options of the moment, and sizes that differ by then are refused before the call."""
     from argparse import Namespace
-    from style_transfer_amd.transfer import StyleTransfer
-    st = StyleTransfer.__new__(StyleTransfer)
-    st._lap_pools, st._lap_weights_key, st._lap_weights_now = [4, 16], None, None
-    assert st._lap_weights(Namespace(lap_pools=['4', '16:3']), 30) == [7.5, 22.5]
-    assert st._lap_weights(Namespace(lap_pools=['4', '16:3']), 10) == [2.5, 7.5]       # a weight that moves
-    assert st._lap_weights(Namespace(lap_pools=['4:3', '16']), 10) == [7.5, 2.5]
+    from style_transfer_amd.terms import LapTerm
+    st = LapTerm.__new__(LapTerm)
+    st.pools, st._key, st._weights = [4, 16], None, None
+    assert st.weights(Namespace(lap_pools=['4', '16:3']), 30) == [7.5, 22.5]
+    assert st.weights(Namespace(lap_pools=['4', '16:3']), 10) == [2.5, 7.5]       # a weight that moves
+    assert st.weights(Namespace(lap_pools=['4:3', '16']), 10) == [7.5, 2.5]
     for other in (['4'], ['16', '4'], ['4', '8'], None):
         with pytest.raises(ValueError) as err:
-            st._lap_weights(Namespace(lap_pools=other), 10)
+            st.weights(Namespace(lap_pools=other), 10)
         assert '--lap-pools' in str(err.value)
-    st._lap_pools = [4]
-    assert st._lap_weights(Namespace(), 2.0) == [2.0]        # the default pools
+    st.pools = [4]
+    assert st.weights(Namespace(), 2.0) == [2.0]        # the default pools
 
 
 def test_the_three_symbols_are_exported_with_their_signatures():

@@ -182,11 +182,11 @@ def test_refused_before_any_gpu_work():
 
 
 def test_dist_refuses_nnfm_weight():
-    from style_transfer_amd.dist import broadcast_targets, refuse_nnfm_weight
-    refuse_nnfm_weight(Namespace())
-    refuse_nnfm_weight(Namespace(nnfm_weight=0))
+    from style_transfer_amd.dist import broadcast_targets, refuse_unbroadcast_options
+    refuse_unbroadcast_options(Namespace())
+    refuse_unbroadcast_options(Namespace(nnfm_weight=0))
     with pytest.raises(NotImplementedError, match='--nnfm-weight'):
-        refuse_nnfm_weight(Namespace(nnfm_weight=1.0))
+        refuse_unbroadcast_options(Namespace(nnfm_weight=1.0))
     with pytest.raises(NotImplementedError, match='--nnfm-weight'):
         broadcast_targets([], [], 'cpu', args=Namespace(nnfm_weight=1.0))
 

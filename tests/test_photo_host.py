@@ -254,7 +254,7 @@ def test_transfer_keeps_one_content_copy_per_scale_and_makes_one_call_per_evalua
         assert call['eps'] == 1e-5 and call['scale'] == lw * 1e4
         assert losses[i].added == ['photo term %d' % (i + 1)]       # the only full-image term that is on
     assert calls[0]['content'] is calls[1]['content'] and calls[2]['content'] is calls[3]['content']
-    assert calls[0]['content'].ptr is None and calls[2]['content'] is st._photo_content    # the old one is freed
+    assert calls[0]['content'].ptr is None and calls[2]['content'] is st.content_picture    # the old one is freed
     # alive after a scale: the iterate, the gradient, the previous average and one content copy
     assert [len(a) for a in alive] == [4, 4]
 
@@ -282,7 +282,7 @@ def test_the_options_are_read_at_every_evaluation(monkeypatch, capsys):
 def test_the_copy_of_preserve_color_luma_is_shared(monkeypatch, capsys):
     st, calls, _, alive, _ = _fake_run(monkeypatch, ['--photo-weight', '1', '--preserve-color', 'luma'])
     capsys.readouterr()
-    assert st._photo_content is st._luma_content and calls[-1]['content'] is st._luma_content
+    assert st.preserve_color == 'luma' and calls[-1]['content'] is st.content_picture       # the one kept picture
     assert calls[0]['content'].ptr is None                   # freed once, by the code that made it
     assert calls[0]['eps'] == 1e-7                           # the default
     assert [len(a) for a in alive] == [4, 4]
@@ -292,7 +292,7 @@ def test_without_the_option_no_call_and_no_allocation(monkeypatch, capsys):
     for options in ([], ['--photo-weight', '0'], ['--photo-eps', '1e-5']):
         st, calls, losses, alive, _ = _fake_run(monkeypatch, options)
         capsys.readouterr()
-        assert calls == [] and st._photo_content is None
+        assert calls == [] and st.content_picture is None
         assert all(loss.added == [] for loss in losses) and len(losses) == 4
         assert [len(a) for a in alive] == [3, 3]             # the iterate, the gradient, the previous average
 

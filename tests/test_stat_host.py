@@ -11,6 +11,7 @@ from style_transfer_amd import lib
 from style_transfer_amd.config_system import (STYLE_LAYERS_DEFAULT, check_stat_options, parse_args,
                                               stat_layer_args)
 from style_transfer_amd.netspec import builtin_net
+from style_transfer_amd.terms import StatTargets
 from tests import stat_ref
 
 BASE = ['-ci', 'c.png', '-si', 's.png']
@@ -105,11 +106,11 @@ def test_refused_for_an_unknown_layer_before_any_gpu_work():
 
 
 def test_dist_refuses_stat_weight():
-    from style_transfer_amd.dist import broadcast_targets, refuse_stat_weight
-    refuse_stat_weight(Namespace())
-    refuse_stat_weight(Namespace(stat_weight=0))
+    from style_transfer_amd.dist import broadcast_targets, refuse_unbroadcast_options
+    refuse_unbroadcast_options(Namespace())
+    refuse_unbroadcast_options(Namespace(stat_weight=0))
     with pytest.raises(NotImplementedError, match='--stat-weight'):
-        refuse_stat_weight(Namespace(stat_weight=1.0))
+        refuse_unbroadcast_options(Namespace(stat_weight=1.0))
     with pytest.raises(NotImplementedError, match='--stat-weight'):
         broadcast_targets([], [], 'cpu', args=Namespace(stat_weight=1.0))
 
@@ -194,12 +195,14 @@ def test_targets_are_the_equal_weight_average_over_style_pictures_and_ladder_siz
     pictures = [Image.fromarray(np.uint8(rng.uniform(0, 255, (n, n, 3)))) for n in (64, 50)]
     variants = [st.pil_to_image(v) for i, p in enumerate(pictures) for v in st._style_variants(i, p)]
     assert sorted(v.shape[1] for v in variants) == [32, 32, 45, 45, 50, 64]
-    st.preprocess_images([], pictures, [], ['conv1_1', 'conv3_1'], stat_layers=['conv1_1', 'conv2_2'])
+    stat, = [term for term in st.target_terms if isinstance(term, StatTargets)]
+    stat.layers = ['conv1_1', 'conv2_2']
+    st.preprocess_images([], pictures, [], ['conv1_1', 'conv3_1'])
     capsys.readouterr()
     assert farm.passes == [['conv1_1', 'conv3_1', 'conv2_2']] * 6
     assert all(feat.freed for feat in farm.feats)
-    assert sorted(st.stat_targets) == ['conv1_1', 'conv2_2'] and sorted(st.styles[0]) == ['conv1_1', 'conv3_1']
-    for layer, (mean, sd) in st.stat_targets.items():
+    assert sorted(stat.targets) == ['conv1_1', 'conv2_2'] and sorted(st.styles[0]) == ['conv1_1', 'conv3_1']
+    for layer, (mean, sd) in stat.targets.items():
         each = [stat_ref.feature_stats(farm.feature(v, layer)) for v in variants]
         want_mean, want_sd = np.mean([e[0] for e in each], axis=0), np.mean([e[1] for e in each], axis=0)
         assert mean.dtype == np.float32 and mean.shape == sd.shape == (3,)
@@ -215,14 +218,15 @@ def test_only_the_layers_of_the_scale_are_sent_and_a_layer_without_a_target_is_r
     """--style-multiscale keeps the first scale's targets while the weights are read again every scale."""
     st, farm = _fake_transfer()
     one = (np.zeros(3, np.float32), np.ones(3, np.float32))
-    st.stat_targets = {'conv1_1': one, 'conv2_2': one}
-    st._stat_weights = None
-    st._send_stats()
+    stat, = [term for term in st.target_terms if isinstance(term, StatTargets)]
+    stat.targets = {'conv1_1': one, 'conv2_2': one}
+    stat.weights = None
+    stat.send(st)
     assert farm.sent == []
-    st._stat_weights = {'conv2_2': 1.0}                    # the list was re-read without conv1_1
-    st._send_stats()
+    stat.weights = {'conv2_2': 1.0}                    # the list was re-read without conv1_1
+    stat.send(st)
     assert list(farm.sent[-1][0]) == ['conv2_2'] and farm.sent[-1][1] == {'conv2_2': 1.0}
-    st._stat_weights = {'conv2_2': 0.5, 'conv3_1': 0.5}    # ... and with a layer that has no target
+    stat.weights = {'conv2_2': 0.5, 'conv3_1': 0.5}    # ... and with a layer that has no target
     with pytest.raises(ValueError, match='--stat-layers conv3_1.*--style-multiscale'):
-        st._send_stats()
+        stat.send(st)
     assert len(farm.sent) == 1
