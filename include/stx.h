@@ -304,6 +304,30 @@ typedef struct stx_nnfm_patch_target {
  * replaces the whole set. */
 int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n);
 
+/* The same term against the k best rows instead of one (patch-based synthesis, NNST): with K = min(k, rows),
+ *   J_i  = (j_i1 ... j_iK)                   the K rows with the best scores x_i . b_j, ordered by score
+ *                                            descending, and among equal scores the LOWER index first
+ *   t_i  = (1/K) sum_r b_{j_ir}              (float32, added in rank order, then scaled)
+ *   c_i  = x_i . t_i,   E = (2/n) sum_i (1 - c_i)      ( = the mean over i and r of |x_i - b_{j_ir}|^2 )
+ *   S_i  = -(t_i - c_i x_i) / r_i            (n d(E/2)/df_i with J_i held fixed)
+ * and loss, diff as above; with patch 3, x_i and r_i are X_p and R_p and G_p is folded into S as above.  A zero
+ * column takes the rows 0 .. K - 1, c = 0, S = 0.  The search's matrix work is done once whatever k is.
+ * k: 1 (stx_set_nnfm_patch_targets, byte for byte) to 4; anything else is STX_ERR_ARG.  Every other refusal is
+ * that of stx_set_nnfm_patch_targets. */
+typedef struct stx_nnfm_knn_target {
+    const char *layer;
+    int channels;
+    int patch;
+    int k;
+    int rows;
+    const float *bank;      /* [rows][patch * patch * channels] */
+    int mem;
+    double weight;
+} stx_nnfm_knn_target;
+/* stx_set_nnfm_targets for banks of any kind: a layer has ONE bank, and any of the three calls replaces the
+ * whole set. */
+int stx_set_nnfm_knn_targets(stx_engine *e, const stx_nnfm_knn_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -647,6 +671,11 @@ int stx_op_nnfm_terms(stx_engine *e, const float *feat, int channels, int h, int
  * patch 1 is stx_op_nnfm_terms; a patch other than 1 or 3 is STX_ERR_ARG.  Errors leave the outputs alone. */
 int stx_op_nnfm_patch_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch,
                             const float *bank, int rows, float *s_out, int *index_out, double out[2]);
+/* ... and of a k-nearest target (stx_set_nnfm_knn_targets): index_out = J [k][h w], rank-major, -1 from rank
+ * min(k, rows) on.  k 1 is stx_op_nnfm_patch_terms; k outside 1 .. 4 is STX_ERR_ARG.  Errors leave the outputs
+ * alone. */
+int stx_op_nnfm_knn_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch, int k,
+                          const float *bank, int rows, float *s_out, int *index_out, double out[2]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

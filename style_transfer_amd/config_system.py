@@ -156,6 +156,11 @@ _EXTENSIONS = [
                                   'of single vectors (CNNMRF, NNST), 1 or 3: a 3 x 3 patch carries the local '
                                   'arrangement -- strokes, hatching, small motifs -- and makes the search nine '
                                   'times as long; read once per scale (default: 1)')),
+    (('--nnfm-k',), dict(metavar='K', type=int,
+                         help='pulls every feature vector (or patch) of the nearest-neighbour term towards the mean '
+                              'of its K most similar bank rows instead of the single best one, an integer from 1 '
+                              'to 4: steadier targets where two rows are nearly tied and with --nnfm-stride above '
+                              '1; the search is done once whatever K is; read once per scale (default: 1)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -391,6 +396,15 @@ def nnfm_patch(args):
     return int(raw)
 
 
+def nnfm_k(args):
+    """--nnfm-k as an integer from 1 to 4 (default 1); anything else, bools and floats included, is a
+    ValueError."""
+    raw = raw_option(args, 'nnfm_k', 1)
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 1 <= raw <= 4:
+        raise ValueError('--nnfm-k %r: an integer from 1 to 4 is expected' % (raw,))
+    return int(raw)
+
+
 def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
     """Rows that a [channels, h, w] feature map adds to a bank at this stride.  With ``patch`` 3 a bank that
     would reach the library's limit -- (rows_before + rows) x 9 x channels below 2^31 -- is a ValueError, raised
@@ -404,15 +418,16 @@ def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
 
 
 def check_nnfm_options(args, known_layers=None):
-    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch: refused before any GPU work together with
-    --style-masks (there is one bank and, with masks, one style set per picture), with a stride below 1, with a
-    patch that is not 1 or 3 and with a bad layer list (check_layer_list).  Returns the layer names."""
+    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k: refused before any GPU work together
+    with --style-masks (there is one bank and, with masks, one style set per picture), with a stride below 1, with a
+    patch that is not 1 or 3, with a k outside 1 .. 4 and with a bad layer list (check_layer_list).  Returns the layer names."""
     items = nnfm_layer_args(args)
     if not items:
         return []
     if not getattr(args, 'style_masks', None):      # (the refusal of --style-masks comes first)
         nnfm_stride(args)
         nnfm_patch(args)
+        nnfm_k(args)
     return check_layer_list(args, items, '--nnfm-weight', '--nnfm-layers', 'one bank of style features',
                             known_layers)
 

@@ -493,6 +493,7 @@ int stat_grad_launch(hipStream_t s, const float *feat, int C, int HW, const floa
 // (include/stx.h, stx_set_nnfm_targets).  The search multiplies kNnfmQ query columns by kNnfmB bank rows per
 // workgroup, kNnfmK channels per LDS stage; with few query blocks the bank is cut into slices.
 constexpr int kNnfmQ = 128, kNnfmB = 128, kNnfmK = 32, kNnfmMaxSlices = 64;
+constexpr int kNnfmMaxK = 4;        // the k best rows per query (stx_set_nnfm_knn_targets): 1 .. 4
 struct NnfmPlan {
     int q_blocks, b_blocks, slices, blocks_per_slice;
 };
@@ -500,19 +501,20 @@ NnfmPlan nnfm_plan(int n, int M);
 // floats that hold the fp16 hi / lo pieces of `rows` rows of C channels ([rows][C] hi, then [rows][C] lo)
 size_t nnfm_pieces_floats(int rows, int C);
 // floats of the caller's that one term takes, and their division (from the next 256-byte boundary)
-// (patch 3: the 3 x 3 patch term, whose bank rows have 9 C channels -- O(n) floats more)
-size_t nnfm_scratch_floats(int C, int n, int M, int patch = 1);
+// (patch 3: the 3 x 3 patch term, whose bank rows have 9 C channels -- O(n) floats more; k rows per query: k - 1
+// further index planes and k-fold slice pairs)
+size_t nnfm_scratch_floats(int C, int n, int M, int patch = 1, int k = 1);
 struct NnfmScratch {
     unsigned short *xhi, *xlo;      // pieces of x_i 2^13 (patch 3: of f_i under the blob's common scale), [n][C] each
     float *inv_r;                   // [n]
-    int *idx;                       // [n]
-    float *part_score;              // [slices][n], or null with one slice
+    int *idx;                       // [k][n], rank-major
+    float *part_score;              // [slices][k][n], or null with one slice
     int *part_idx;
     float *partials;                // ceil(n / 64) of (2/n) sum (1 - c_i), then as many of sum |S|
     double *work;                   // patch 3: nnfm_patch_work_floats(n) floats of nnfm_prepare_launch, else null
     float *cosv;                    // patch 3: c_p [n], else null
 };
-NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch = 1);
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch = 1, int k = 1);
 // The term's three steps, for both forms.  patch 1: columns of C channels against bank rows of C.  patch 3
 // (stx_set_nnfm_patch_targets): pixel p's patch is the 9 C vector of the columns at p + tap, tap-major (dy outer,
 // dx inner, (-1, -1) first), zero outside the map, against bank rows [M][9 C] of unit or zero rows.
@@ -529,13 +531,15 @@ int nnfm_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, i
 // the pieces of bank 2^13, bank [M][C] given as rows (C: the whole width of a row)
 int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsigned short *hi, unsigned short *lo);
 // idx_out[i] = argmax_j x_i . b_j (patch 3: P_p . b_j, the query operand gathered from x's [n][C] pieces), the
-// lowest j among equal scores.  pieces: the bank's, [M][patch^2 C] hi then lo (nnfm_split_rows_launch)
+// lowest j among equal scores.  pieces: the bank's, [M][patch^2 C] hi then lo (nnfm_split_rows_launch).
+// k > 1: idx_out [k][n], the k best rows by (score descending, index ascending), -1 from rank min(k, M) on.
 int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int patch, const unsigned short *pieces,
-                       int M, int C, int *idx_out);
+                       int M, int C, int *idx_out, int k = 1);
 // sgrad = S [C][n] (patch 3: x.cosv = c_p first, then S in the gather form; the bank aligned to 16 bytes);
-// *n_parts partials of E in x.partials, then as many of sum |S|
+// *n_parts partials of E in x.partials, then as many of sum |S|.  k > 1: idx [k][n], and the target of a column is
+// the mean of its min(k, M) rows
 int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, const NnfmScratch &x,
-                     const float *bank, int M, const int *idx, float *sgrad, int *n_parts);
+                     const float *bank, int M, const int *idx, float *sgrad, int *n_parts, int k = 1);
 
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,

@@ -22,13 +22,13 @@
 //                            channel order (NOT the search's score: E and S are functions of (F, B, j)),
 //                            writes S in [C][n] layout and leaves the partials of sum (1 - c_i) and sum |S|.
 // The 3 x 3 patch form (stx_set_nnfm_patch_targets) is the same term over the 9 C vectors of a pixel's patch.
-// There is ONE search, nnfm_search_kernel<PATCH>, with two fetchers of the query operand: a row of the [n][C]
-// pieces (plain), or 32 channels of the neighbour p + tap gathered from those pieces with zeros outside the map
-// (patch; K = 9 C, and no [n][9 C] array is written anywhere).  Staging, products, the argmax rule, the clamps
-// and the merges exist once.  The prepare and gradient passes are different algorithms and stay separate
-// kernels: the patch form splits the columns under one scale for the whole blob (nnfm_patch_norms_kernel,
-// nnfm_patch_rows_kernel) and its gradient gathers the nine patches a pixel belongs to (nnfm_patch_cos_kernel,
-// nnfm_patch_grad_kernel).  The launches below take the patch size and choose among them.
+// There is ONE search, nnfm_search_kernel<PATCH, K>, with two fetchers of the query operand: a row of the [n][C]
+// pieces (plain), or 32 channels of p + tap gathered from those pieces with zeros outside the map (patch; 9 C deep,
+// no [n][9 C] array is written anywhere).  Staging, products, the order rule, the clamps and the merges exist once.
+// K > 1 (stx_set_nnfm_knn_targets): a sorted list of the K best rows per query takes the place of the one winner and
+// S pulls towards their mean (the *_k kernels).  Prepare and gradient are different algorithms per form and stay
+// separate kernels: nnfm_patch_norms_kernel / nnfm_patch_rows_kernel split the columns under one scale for the blob,
+// nnfm_patch_cos_kernel / nnfm_patch_grad_kernel gather the nine patches of a pixel.  The launches choose among them.
 
 #include <algorithm>
 #include <climits>
@@ -248,12 +248,33 @@ struct NnfmQueries<true> {
     int n, w;
 };
 
-// grid (query blocks, slices).  One slice: idx_out [n].  Several: part_score / part_idx [slices][n].
+// The K best of a query, K > 1 (stx_set_nnfm_knn_targets): a sorted list under the strict total order "greater
+// score, else lower index" (indices are distinct).  The candidate is carried down the list and changes places with
+// every entry it beats, so the list stays sorted and holds the K best of all that was offered: the top K of a union
+// under a strict total order, which no order of offering or merging can change.  Empty places are
+// (-inf, INT_MAX): nothing offered loses to them, and they are never offered.
+template <int K>
+__device__ __forceinline__ void take_k_better(float s, int j, float (&best_s)[K], int (&best_j)[K]) {
+    if (!(s > best_s[K - 1] || (s == best_s[K - 1] && j < best_j[K - 1]))) return;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const bool up = s > best_s[r] || (s == best_s[r] && j < best_j[r]);
+        const float ts = up ? best_s[r] : s;
+        const int tj = up ? best_j[r] : j;
+        best_s[r] = up ? s : best_s[r];
+        best_j[r] = up ? j : best_j[r];
+        s = ts;
+        j = tj;
+    }
+}
+
+// grid (query blocks, slices).  One slice: idx_out [K][n], rank-major, -1 where fewer than K rows exist.
+// Several: part_score / part_idx [slices][K][n], empty places as (-inf, INT_MAX).  K = 1 is the plain argmax.
 // A bank row has CB channels: C, and the query operand is the row of the [n][C] pieces -- or, PATCH, 9 C
 // tap-major, and the query operand is gathered from those pieces of the w-wide map: stage t of a row reads 32
 // channels of pixel p + tap(t), found from p's (y, x) -- the right neighbour of a row's last pixel is padding --
 // and zeros outside the map.
-template <bool PATCH>
+template <bool PATCH, int K>
 __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__restrict__ xhi, const _Float16 *__restrict__ xlo,
                                                           const NnfmQueries<PATCH> queries,
                                                           const _Float16 *__restrict__ bhi,
@@ -330,6 +351,14 @@ __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__rest
             for (int v = 0; v < 16; ++v) acc[i][k][v] = 0.f;
     float best_s[2] = {-INFINITY, -INFINITY};
     int best_j[2] = {INT_MAX, INT_MAX};
+    [[maybe_unused]] float top_s[2][K];     // K > 1: the sorted lists of this lane's two queries
+    [[maybe_unused]] int top_j[2][K];
+    if constexpr (K > 1) {
+#pragma unroll
+        for (int tq = 0; tq < 2; ++tq)
+#pragma unroll
+            for (int k = 0; k < K; ++k) top_s[tq][k] = -INFINITY, top_j[tq][k] = INT_MAX;
+    }
 
     prefetch(0);
     for (int t = 0; t < T; ++t) {
@@ -358,37 +387,89 @@ __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__rest
 #pragma unroll
             for (int tq = 0; tq < 2; ++tq)
 #pragma unroll
-                for (int tb = 0; tb < 2; ++tb)
+                for (int tb = 0; tb < 2; ++tb) {
+                    // K > 1: a tile whose largest score lies below the list's last place offers nothing (padding
+                    // repeats a real row's score, so it can only keep a tile from being passed over)
+                    if constexpr (K > 1) {
+                        float top = acc[tq][tb][0];
+#pragma unroll
+                        for (int v = 1; v < 16; ++v) top = fmaxf(top, acc[tq][tb][v]);
+                        if (top >= top_s[tq][K - 1]) {
+#pragma unroll
+                            for (int v = 0; v < 16; ++v) {
+                                const int j = j0 + 32 * tb + (v & 3) + 8 * (v >> 2);
+                                if (j < M) take_k_better<K>(acc[tq][tb][v], j, top_s[tq], top_j[tq]);
+                            }
+                        }
+#pragma unroll
+                        for (int v = 0; v < 16; ++v) acc[tq][tb][v] = 0.f;
+                        continue;
+                    }
 #pragma unroll
                     for (int v = 0; v < 16; ++v) {
                         const int j = j0 + 32 * tb + (v & 3) + 8 * (v >> 2);
                         if (j < M) take_better(acc[tq][tb][v], j, best_s[tq], best_j[tq]);     // padding never wins
                         acc[tq][tb][v] = 0.f;
                     }
+                }
         }
     }
     // a query's four candidates: two lane halves x the two waves that split the bank rows
     __syncthreads();
-    float *const cand_s = reinterpret_cast<float *>(lds);
-    int *const cand_j = reinterpret_cast<int *>(lds + kNnfmQ * 4 * sizeof(float));
+    if constexpr (K == 1) {
+        float *const cand_s = reinterpret_cast<float *>(lds);
+        int *const cand_j = reinterpret_cast<int *>(lds + kNnfmQ * 4 * sizeof(float));
 #pragma unroll
-    for (int tq = 0; tq < 2; ++tq) {
-        const int q = 64 * wq + 32 * tq + r;
-        cand_s[q * 4 + wb * 2 + half] = best_s[tq];
-        cand_j[q * 4 + wb * 2 + half] = best_j[tq];
-    }
-    __syncthreads();
-    if (threadIdx.x < kNnfmQ && q0 + (int)threadIdx.x < n) {
-        float s = cand_s[threadIdx.x * 4];
-        int j = cand_j[threadIdx.x * 4];
+        for (int tq = 0; tq < 2; ++tq) {
+            const int q = 64 * wq + 32 * tq + r;
+            cand_s[q * 4 + wb * 2 + half] = best_s[tq];
+            cand_j[q * 4 + wb * 2 + half] = best_j[tq];
+        }
+        __syncthreads();
+        if (threadIdx.x < kNnfmQ && q0 + (int)threadIdx.x < n) {
+            float s = cand_s[threadIdx.x * 4];
+            int j = cand_j[threadIdx.x * 4];
 #pragma unroll
-        for (int k = 1; k < 4; ++k) take_better(cand_s[threadIdx.x * 4 + k], cand_j[threadIdx.x * 4 + k], s, j);
-        if (j == INT_MAX) j = 0;        // (scores that are not numbers: nothing was taken)
-        if (gridDim.y == 1) {
-            idx_out[q0 + threadIdx.x] = j;
-        } else {
-            part_score[(size_t)blockIdx.y * n + q0 + threadIdx.x] = s;
-            part_idx[(size_t)blockIdx.y * n + q0 + threadIdx.x] = j;
+            for (int k = 1; k < 4; ++k) take_better(cand_s[threadIdx.x * 4 + k], cand_j[threadIdx.x * 4 + k], s, j);
+            if (j == INT_MAX) j = 0;        // (scores that are not numbers: nothing was taken)
+            if (gridDim.y == 1) {
+                idx_out[q0 + threadIdx.x] = j;
+            } else {
+                part_score[(size_t)blockIdx.y * n + q0 + threadIdx.x] = s;
+                part_idx[(size_t)blockIdx.y * n + q0 + threadIdx.x] = j;
+            }
+        }
+    } else {        // the same four candidate places, K entries each; the best K of the 4 K
+        float *const cand_s = reinterpret_cast<float *>(lds);
+        int *const cand_j = reinterpret_cast<int *>(lds + kNnfmQ * 4 * K * sizeof(float));
+#pragma unroll
+        for (int tq = 0; tq < 2; ++tq) {
+            const int q = 64 * wq + 32 * tq + r;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                cand_s[(q * 4 + wb * 2 + half) * K + k] = top_s[tq][k];
+                cand_j[(q * 4 + wb * 2 + half) * K + k] = top_j[tq][k];
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < kNnfmQ && q0 + (int)threadIdx.x < n) {
+            float s[K];
+            int j[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) s[k] = -INFINITY, j[k] = INT_MAX;
+#pragma unroll
+            for (int k = 0; k < 4 * K; ++k)
+                if (cand_j[threadIdx.x * 4 * K + k] != INT_MAX)
+                    take_k_better<K>(cand_s[threadIdx.x * 4 * K + k], cand_j[threadIdx.x * 4 * K + k], s, j);
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                if (gridDim.y == 1) {
+                    idx_out[(size_t)k * n + q0 + threadIdx.x] = j[k] == INT_MAX ? -1 : j[k];
+                } else {
+                    part_score[((size_t)blockIdx.y * K + k) * n + q0 + threadIdx.x] = s[k];
+                    part_idx[((size_t)blockIdx.y * K + k) * n + q0 + threadIdx.x] = j[k];
+                }
+            }
         }
     }
 }
@@ -402,6 +483,36 @@ __global__ __launch_bounds__(256) void nnfm_merge_kernel(const float *__restrict
     int j = part_idx[q];
     for (int k = 1; k < slices; ++k) take_better(part_score[(size_t)k * n + q], part_idx[(size_t)k * n + q], s, j);
     idx_out[q] = j;
+}
+
+// K > 1: the best K of the slices' K each, part [slices][K][n] -> idx_out [K][n] (-1: fewer than K rows)
+template <int K>
+__global__ __launch_bounds__(256) void nnfm_merge_k_kernel(const float *__restrict__ part_score,
+                                                           const int *__restrict__ part_idx, int n, int slices,
+                                                           int *__restrict__ idx_out) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    float s[K];
+    int j[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = -INFINITY, j[k] = INT_MAX;
+    // eight candidates' loads in flight at a time: a thread's walk is a chain of dependent selects, not of loads
+    for (int k0 = 0; k0 < slices * K; k0 += 8) {
+        float cs[8];
+        int cj[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const bool there = k0 + u < slices * K;
+            const size_t at = (size_t)(there ? k0 + u : 0) * n + q;
+            cs[u] = part_score[at];
+            cj[u] = there ? part_idx[at] : INT_MAX;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (cj[u] != INT_MAX) take_k_better<K>(cs[u], cj[u], s, j);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) idx_out[(size_t)k * n + q] = j[k] == INT_MAX ? -1 : j[k];
 }
 
 // ---------------------------------------------------------------------------------------------- grad
@@ -441,6 +552,76 @@ __global__ __launch_bounds__(64) void nnfm_grad_kernel(const float *__restrict__
             const float s = -((row[ch] - c * x) * inv);
             out[(size_t)ch * n] = s;
             sum_abs += fabsf(s);
+        }
+    }
+    const float one_minus = wave_sum_f(valid ? 1.f - c : 0.f);
+    sum_abs = wave_sum_f(sum_abs);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = one_minus * (2.f / (float)n);
+        partials[gridDim.x + blockIdx.x] = sum_abs;
+    }
+}
+
+// The K nearest rows (stx_set_nnfm_knn_targets), KK = min(K, M) > 1 of them: idx [K][n], rank-major, and the
+// target is their mean, t_i = (b_{j_i1} + ... + b_{j_iKK}) (1 / KK) -- float32, added in rank order, then scaled;
+// formed twice, the same way (knn_mean4), since C floats do not fit a lane.  All else as nnfm_grad_kernel.
+// (four channels at a time: one 16-byte load per row where the bank allows it -- the same sums either way)
+template <int KK>
+__device__ __forceinline__ float4 knn_mean4(const float *__restrict__ bank, const unsigned (&at)[KK], int ch, bool vec) {
+    float4 t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < KK; ++r) {
+        const float *__restrict__ row = bank + at[r] + ch;
+        const float4 b = vec ? *reinterpret_cast<const float4 *>(row) : float4{row[0], row[1], row[2], row[3]};
+        if (r == 0) {
+            t = b;
+        } else {
+            t.x += b.x, t.y += b.y, t.z += b.z, t.w += b.w;
+        }
+    }
+    constexpr float inv_k = 1.f / (float)KK;
+    return float4{t.x * inv_k, t.y * inv_k, t.z * inv_k, t.w * inv_k};
+}
+
+template <int KK>
+__global__ __launch_bounds__(64) void nnfm_grad_k_kernel(const float *__restrict__ F, int C, int n,
+                                                         const float *__restrict__ inv_r, const float *__restrict__ bank,
+                                                         int M, int vec, const int *__restrict__ idx,
+                                                         float *__restrict__ S, float *__restrict__ partials) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < n;
+    const int ii = valid ? i : n - 1;
+    unsigned at[KK];        // (rows x C stays below 2^31)
+#pragma unroll
+    for (int r = 0; r < KK; ++r) {
+        const unsigned ju = (unsigned)idx[(size_t)r * n + ii];
+        at[r] = (ju < (unsigned)M ? ju : 0u) * (unsigned)C;
+    }
+    const float inv = inv_r[ii];
+    const float *__restrict__ f = F + ii;
+    float c = 0.f;
+#pragma unroll 2
+    for (int ch = 0; ch < C; ch += 4) {
+        const float4 t = knn_mean4<KK>(bank, at, ch, vec);
+        c = fmaf(f[(size_t)ch * n] * inv, t.x, c);
+        c = fmaf(f[(size_t)(ch + 1) * n] * inv, t.y, c);
+        c = fmaf(f[(size_t)(ch + 2) * n] * inv, t.z, c);
+        c = fmaf(f[(size_t)(ch + 3) * n] * inv, t.w, c);
+    }
+    float sum_abs = 0.f;
+    if (valid) {
+        float *__restrict__ out = S + i;
+#pragma unroll 2
+        for (int ch = 0; ch < C; ch += 4) {
+            const float4 t4 = knn_mean4<KK>(bank, at, ch, vec);
+            const float t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float x = f[(size_t)(ch + k) * n] * inv;
+                const float s = -((t[k] - c * x) * inv);
+                out[(size_t)(ch + k) * n] = s;
+                sum_abs += fabsf(s);
+            }
         }
     }
     const float one_minus = wave_sum_f(valid ? 1.f - c : 0.f);
@@ -537,6 +718,97 @@ __global__ __launch_bounds__(64) void nnfm_patch_grad_kernel(const float *__rest
     }
 }
 
+// The two patch steps for the KK = min(K, M) > 1 nearest rows, idx [K][n]: b_{j_p} becomes the mean t_p of the
+// rows (knn_mean4: rank order, then scaled), everything else as above.
+template <int KK>
+__global__ __launch_bounds__(64) void nnfm_patch_cos_k_kernel(const float *__restrict__ F, int C, int h, int w,
+                                                              const float *__restrict__ inv_R,
+                                                              const float *__restrict__ bank, int M,
+                                                              const int *__restrict__ idx, float *__restrict__ cos_out) {
+    const int n = h * w, i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int y = i / w, x = i - y * w;
+    unsigned at[KK];        // (rows x 9 C stays below 2^31)
+#pragma unroll
+    for (int r = 0; r < KK; ++r) {
+        const unsigned ju = (unsigned)idx[(size_t)r * n + i];
+        at[r] = (ju < (unsigned)M ? ju : 0u) * 9u * (unsigned)C;
+    }
+    const float inv = inv_R[i];
+    float c = 0.f;
+    for (int t = 0; t < 9; ++t) {
+        const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+        if ((unsigned)yy >= (unsigned)h || (unsigned)xx >= (unsigned)w) continue;
+        const float *__restrict__ f = F + (size_t)yy * w + xx;
+#pragma unroll 2
+        for (int ch = 0; ch < C; ch += 4) {         // (a row starts at a multiple of 16 bytes: C % 64 == 0)
+            const float4 b4 = knn_mean4<KK>(bank, at, t * C + ch, true);
+            c = fmaf(f[(size_t)ch * n] * inv, b4.x, c);
+            c = fmaf(f[(size_t)(ch + 1) * n] * inv, b4.y, c);
+            c = fmaf(f[(size_t)(ch + 2) * n] * inv, b4.z, c);
+            c = fmaf(f[(size_t)(ch + 3) * n] * inv, b4.w, c);
+        }
+    }
+    cos_out[i] = c;
+}
+
+template <int KK>
+__global__ __launch_bounds__(64) void nnfm_patch_grad_k_kernel(const float *__restrict__ F, int C, int h, int w,
+                                                               const float *__restrict__ inv_R,
+                                                               const float *__restrict__ bank, int M,
+                                                               const int *__restrict__ idx,
+                                                               const float *__restrict__ cosv, float *__restrict__ S,
+                                                               float *__restrict__ partials) {
+    const int n = h * w, i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < n;
+    const int ii = valid ? i : n - 1;
+    const int y = ii / w, x = ii - y * w;
+    unsigned at[9][KK];     // tap t of the rows of the patch centred at p - tap
+    float invq[9];
+    float a = 0.f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int qy = y - (t / 3 - 1), qx = x - (t % 3 - 1);
+        const bool inside = (unsigned)qy < (unsigned)h && (unsigned)qx < (unsigned)w;
+        const int q = inside ? qy * w + qx : ii;
+#pragma unroll
+        for (int r = 0; r < KK; ++r) {
+            const unsigned ju = (unsigned)idx[(size_t)r * n + q];
+            at[t][r] = ((ju < (unsigned)M ? ju : 0u) * 9u + (unsigned)t) * (unsigned)C;
+        }
+        invq[t] = inside ? inv_R[q] : 0.f;
+        a = fmaf(cosv[q] * invq[t], invq[t], a);
+    }
+    float sum_abs = 0.f;
+    if (valid) {
+        const float *__restrict__ f = F + i;
+        float *__restrict__ out = S + i;
+        for (int ch = 0; ch < C; ch += 4) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const float4 b4 = knn_mean4<KK>(bank, at[t], ch, true);
+                acc[0] = fmaf(b4.x, invq[t], acc[0]);
+                acc[1] = fmaf(b4.y, invq[t], acc[1]);
+                acc[2] = fmaf(b4.z, invq[t], acc[2]);
+                acc[3] = fmaf(b4.w, invq[t], acc[3]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float s = fmaf(f[(size_t)(ch + k) * n], a, -acc[k]);
+                out[(size_t)(ch + k) * n] = s;
+                sum_abs += fabsf(s);
+            }
+        }
+    }
+    const float one_minus = wave_sum_f(valid ? 1.f - cosv[ii] : 0.f);
+    sum_abs = wave_sum_f(sum_abs);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = one_minus * (2.f / (float)n);
+        partials[gridDim.x + blockIdx.x] = sum_abs;
+    }
+}
+
 // n columns of C channels against M bank rows of patch x patch x C
 int check_shape(const char *who, int C, long long n, long long M, int patch) {
     const char *const what = patch == 3 ? "patches" : "columns";
@@ -576,13 +848,14 @@ size_t nnfm_pieces_floats(int rows, int C) { return round64((size_t)rows * C); }
 
 size_t nnfm_patch_work_floats(int n) { return 2 * round64(n) + 2 * round64(ceil_div(n, 64)); }
 
-size_t nnfm_scratch_floats(int C, int n, int M, int patch) {
+size_t nnfm_scratch_floats(int C, int n, int M, int patch, int k) {
     const NnfmPlan p = nnfm_plan(n, M);
-    return 64 + nnfm_pieces_floats(n, C) + 2 * round64(n) + (p.slices > 1 ? 2 * round64((size_t)p.slices * n) : 0) +
+    return 64 + nnfm_pieces_floats(n, C) + round64(n) + round64((size_t)k * n) +
+           (p.slices > 1 ? 2 * round64((size_t)p.slices * k * n) : 0) +
            round64(2 * (size_t)ceil_div(n, 64)) + (patch == 3 ? nnfm_patch_work_floats(n) + round64(n) : 0);
 }
 
-NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch) {
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch, int k) {
     const NnfmPlan p = nnfm_plan(n, M);
     NnfmScratch s;
     float *at = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
@@ -592,14 +865,14 @@ NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch) {
     s.inv_r = at;
     at += round64(n);
     s.idx = reinterpret_cast<int *>(at);
-    at += round64(n);
+    at += round64((size_t)k * n);
     s.part_score = nullptr;
     s.part_idx = nullptr;
     if (p.slices > 1) {
         s.part_score = at;
-        at += round64((size_t)p.slices * n);
+        at += round64((size_t)p.slices * k * n);
         s.part_idx = reinterpret_cast<int *>(at);
-        at += round64((size_t)p.slices * n);
+        at += round64((size_t)p.slices * k * n);
     }
     s.partials = at;
     at += round64(2 * (size_t)ceil_div(n, 64));
@@ -650,21 +923,74 @@ int nnfm_split_rows_launch(hipStream_t s, const float *bank, int M, int C, unsig
     return STX_OK;
 }
 
+namespace {
+
+template <bool PATCH, int K>
+void search_k_launch(hipStream_t s, const dim3 grid, const NnfmScratch &x, int n, int w, const _Float16 *bhi,
+                     const _Float16 *blo, int M, int C, const NnfmPlan &p, int *idx_out) {
+    const _Float16 *const xhi = reinterpret_cast<const _Float16 *>(x.xhi);
+    const _Float16 *const xlo = reinterpret_cast<const _Float16 *>(x.xlo);
+    NnfmQueries<PATCH> queries;
+    queries.n = n;
+    if constexpr (PATCH) queries.w = w;
+    nnfm_search_kernel<PATCH, K><<<grid, 256, 0, s>>>(xhi, xlo, queries, bhi, blo, M, C, p.b_blocks, p.blocks_per_slice,
+                                                      idx_out, x.part_score, x.part_idx);
+    if (p.slices > 1 && hipPeekAtLastError() == hipSuccess)
+        nnfm_merge_k_kernel<K><<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
+}
+
+template <int KK>
+void grad_k_launch(hipStream_t s, int blocks, const float *feat, int C, int h, int w, int patch, const NnfmScratch &x,
+                   const float *bank, int M, const int *idx, float *sgrad) {
+    if (patch == 3) {
+        nnfm_patch_cos_k_kernel<KK><<<blocks, 64, 0, s>>>(feat, C, h, w, x.inv_r, bank, M, idx, x.cosv);
+        if (hipPeekAtLastError() != hipSuccess) return;
+        nnfm_patch_grad_k_kernel<KK><<<blocks, 64, 0, s>>>(feat, C, h, w, x.inv_r, bank, M, idx, x.cosv, sgrad,
+                                                           x.partials);
+    } else {
+        const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
+        nnfm_grad_k_kernel<KK><<<blocks, 64, 0, s>>>(feat, C, h * w, x.inv_r, bank, M, vec, idx, sgrad, x.partials);
+    }
+}
+
+int check_k(const char *who, int k) {
+    if (k >= 1 && k <= kNnfmMaxK) return STX_OK;
+    set_error("%s: k %d (1 to %d is expected)", who, k, kNnfmMaxK);
+    return STX_ERR_ARG;
+}
+
+}  // namespace
+
 int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int patch, const unsigned short *pieces,
-                       int M, int C, int *idx_out) {
+                       int M, int C, int *idx_out, int k) {
     const int n = h * w;
     STX_TRY(check_shape("nnfm_search_launch", C, n, M, patch));
+    STX_TRY(check_k("nnfm_search_launch", k));
     const NnfmPlan p = nnfm_plan(n, M);
     const dim3 grid(p.q_blocks, p.slices);
     const _Float16 *const xhi = reinterpret_cast<const _Float16 *>(x.xhi);
     const _Float16 *const xlo = reinterpret_cast<const _Float16 *>(x.xlo);
     const _Float16 *const bhi = reinterpret_cast<const _Float16 *>(pieces), *const blo = bhi + (size_t)M * patch * patch * C;
+    if (k > 1) {        // the K best rows: idx_out [k][n]
+        const bool p3 = patch == 3;
+        if (k == 2)
+            p3 ? search_k_launch<true, 2>(s, grid, x, n, w, bhi, blo, M, C, p, idx_out)
+               : search_k_launch<false, 2>(s, grid, x, n, w, bhi, blo, M, C, p, idx_out);
+        else if (k == 3)
+            p3 ? search_k_launch<true, 3>(s, grid, x, n, w, bhi, blo, M, C, p, idx_out)
+               : search_k_launch<false, 3>(s, grid, x, n, w, bhi, blo, M, C, p, idx_out);
+        else
+            p3 ? search_k_launch<true, 4>(s, grid, x, n, w, bhi, blo, M, C, p, idx_out)
+               : search_k_launch<false, 4>(s, grid, x, n, w, bhi, blo, M, C, p, idx_out);
+        STX_CHECK_LAUNCH();
+        return STX_OK;
+    }
     if (patch == 3)
-        nnfm_search_kernel<true><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<true>{n, w}, bhi, blo, M, C, p.b_blocks,
-                                                      p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+        nnfm_search_kernel<true, 1><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<true>{n, w}, bhi, blo, M, C, p.b_blocks,
+                                                         p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
     else
-        nnfm_search_kernel<false><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<false>{n}, bhi, blo, M, C, p.b_blocks,
-                                                       p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+        nnfm_search_kernel<false, 1><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<false>{n}, bhi, blo, M, C, p.b_blocks,
+                                                          p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
     STX_CHECK_LAUNCH();
     if (p.slices > 1) {
         nnfm_merge_kernel<<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
@@ -674,15 +1000,23 @@ int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int pa
 }
 
 int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, const NnfmScratch &x,
-                     const float *bank, int M, const int *idx, float *sgrad, int *n_parts) {
+                     const float *bank, int M, const int *idx, float *sgrad, int *n_parts, int k) {
     const int n = h * w, blocks = ceil_div(n, 64);
     STX_TRY(check_shape("nnfm_grad_launch", C, n, M, patch));
+    STX_TRY(check_k("nnfm_grad_launch", k));
     const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
-    if (patch == 3) {
-        if (!vec) {
-            set_error("nnfm_grad_launch: the bank is not aligned to 16 bytes");
-            return STX_ERR_UNSUPPORTED;
-        }
+    if (patch == 3 && !vec) {
+        set_error("nnfm_grad_launch: the bank is not aligned to 16 bytes");
+        return STX_ERR_UNSUPPORTED;
+    }
+    const int kk = std::min(k, M);      // the rows there are; one row: the first index plane and today's kernels
+    if (kk == 2) {
+        grad_k_launch<2>(s, blocks, feat, C, h, w, patch, x, bank, M, idx, sgrad);
+    } else if (kk == 3) {
+        grad_k_launch<3>(s, blocks, feat, C, h, w, patch, x, bank, M, idx, sgrad);
+    } else if (kk == 4) {
+        grad_k_launch<4>(s, blocks, feat, C, h, w, patch, x, bank, M, idx, sgrad);
+    } else if (patch == 3) {
         nnfm_patch_cos_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, x.inv_r, bank, M, idx, x.cosv);
         STX_CHECK_LAUNCH();
         nnfm_patch_grad_kernel<<<blocks, 64, 0, s>>>(feat, C, h, w, x.inv_r, bank, M, idx, x.cosv, sgrad, x.partials);

@@ -197,14 +197,15 @@ int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, 
     return STX_OK;
 }
 
-// Both NNFM hooks.  Patch 1 is the plain term and speaks as stx_op_nnfm_terms through either entry point; every
+// The NNFM hooks.  k = 1 through stx_op_nnfm_knn_terms is the patch call; k > 1 speaks as stx_op_nnfm_knn_terms and
+// index_out holds [k][h w].  Patch 1 is the plain term and speaks as stx_op_nnfm_terms through either entry point; every
 // other patch size speaks as stx_op_nnfm_patch_terms: `plain` picks between the two entry points' messages, which
 // are the ones they had as two functions.  Nothing is written before the arguments are accepted.  (An error behind
 // take() leaves the scalar arena empty, as in the other term hooks.)
 static int hook_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, const float *bank, int rows,
-                           float *s_out, int *index_out, double out[2]) {
+                           float *s_out, int *index_out, double out[2], int k = 1) {
     const bool plain = patch == 1;
-    const char *const who = plain ? "stx_op_nnfm_terms" : "stx_op_nnfm_patch_terms";
+    const char *const who = k > 1 ? "stx_op_nnfm_knn_terms" : plain ? "stx_op_nnfm_terms" : "stx_op_nnfm_patch_terms";
     if ((!plain && patch != 3) || !e || !feat || !bank || !s_out || !index_out || !out || C <= 0 || h <= 0 || w <= 0 ||
         rows <= 0) {
         if (plain)
@@ -232,12 +233,12 @@ static int hook_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w
     const float *host;
     STX_TRY(scalars.take(2, &sc));
     const size_t pieces = nnfm_pieces_floats(rows, (int)width);
-    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows, patch)) * sizeof(float)));
+    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows, patch, k)) * sizeof(float)));
     unsigned short *bhi = static_cast<unsigned short *>(e->nnfm_scratch.ptr);
     // what the targets' setter does once, then the launches of an NNFM target of stx_sc_grad_tile, in the same order
     STX_TRY(nnfm_split_rows_launch(e->stream, bank, rows, (int)width, bhi, bhi + (size_t)rows * width));
     STX_TRY(launch_nnfm_terms(e, e->stream, feat, C, h, w, patch, bank, bhi, rows, s_out, index_out, sc, "op",
-                              e->nnfm_scratch.f() + pieces, nullptr));
+                              e->nnfm_scratch.f() + pieces, nullptr, k));
     STX_TRY(scalars.fetch(&host));
     out[0] = (double)host[0];
     out[1] = (double)host[1];
@@ -252,6 +253,15 @@ int stx_op_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w, con
 int stx_op_nnfm_patch_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, const float *bank,
                             int rows, float *s_out, int *index_out, double out[2]) {
     return hook_nnfm_terms(e, feat, C, h, w, patch, bank, rows, s_out, index_out, out);
+}
+
+int stx_op_nnfm_knn_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, int k, const float *bank,
+                          int rows, float *s_out, int *index_out, double out[2]) {
+    if (k < 1 || k > kNnfmMaxK) {
+        set_error("stx_op_nnfm_knn_terms: k %d (1 to %d is expected)", k, kNnfmMaxK);
+        return STX_ERR_ARG;
+    }
+    return hook_nnfm_terms(e, feat, C, h, w, patch, bank, rows, s_out, index_out, out, k);
 }
 
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,

@@ -54,19 +54,24 @@ struct MaskSource {
     }
 };
 
-// The banks of both NNFM setters: a plain bank is a patch target with patch 1.
-static int set_nnfm_banks(stx_engine *e, const stx_nnfm_patch_target *targets, int n, const char *who) {
+// The banks of the three NNFM setters: a plain bank is a patch target with patch 1, and both match k = 1 row.
+static int set_nnfm_banks(stx_engine *e, const stx_nnfm_knn_target *targets, int n, const char *who) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         if (targets[i].patch != 1 && targets[i].patch != 3) {
             set_error("NNFM target %d: patch %d (1 or 3 is expected)", i, targets[i].patch);
             return STX_ERR_ARG;
         }
+        if (targets[i].k < 1 || targets[i].k > kNnfmMaxK) {
+            set_error("NNFM target %d: k %d (1 to %d is expected)", i, targets[i].k, kNnfmMaxK);
+            return STX_ERR_ARG;
+        }
+    }
     auto &nnfms = e->sh->nnfms;
     return swap_targets(e, who, [&](bool &) -> int {
         clear_targets(nnfms);
         for (int i = 0; i < n; ++i) {
-            const stx_nnfm_patch_target &nt = targets[i];
+            const stx_nnfm_knn_target &nt = targets[i];
             const int blob = e->find_blob(nt.layer);
             bool twice = false;
             for (const NnfmTarget &t : nnfms) twice |= t.blob == blob;
@@ -87,7 +92,7 @@ static int set_nnfm_banks(stx_engine *e, const stx_nnfm_patch_target *targets, i
                 return STX_ERR_UNSUPPORTED;
             }
             nnfms.push_back(NnfmTarget{blob, nt.channels, nt.rows, nt.weight, std::unique_ptr<DevBuf>(new DevBuf),
-                                       std::unique_ptr<DevBuf>(new DevBuf), nt.patch});
+                                       std::unique_ptr<DevBuf>(new DevBuf), nt.patch, nt.k});
             NnfmTarget &t = nnfms.back();
             const size_t bytes = (size_t)t.rows * width * sizeof(float);
             STX_TRY(t.bank->ensure(bytes));
@@ -252,16 +257,26 @@ int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
 
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    std::vector<stx_nnfm_patch_target> as_patch;
+    std::vector<stx_nnfm_knn_target> as_knn;
     for (int i = 0; i < n; ++i) {
         const stx_nnfm_target &t = targets[i];
-        as_patch.push_back(stx_nnfm_patch_target{t.layer, t.channels, 1, t.rows, t.bank, t.mem, t.weight});
+        as_knn.push_back(stx_nnfm_knn_target{t.layer, t.channels, 1, 1, t.rows, t.bank, t.mem, t.weight});
     }
-    return set_nnfm_banks(e, as_patch.data(), n, "stx_set_nnfm_targets");
+    return set_nnfm_banks(e, as_knn.data(), n, "stx_set_nnfm_targets");
 }
 
 int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n) {
-    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_patch_targets");
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    std::vector<stx_nnfm_knn_target> as_knn;
+    for (int i = 0; i < n; ++i) {
+        const stx_nnfm_patch_target &t = targets[i];
+        as_knn.push_back(stx_nnfm_knn_target{t.layer, t.channels, t.patch, 1, t.rows, t.bank, t.mem, t.weight});
+    }
+    return set_nnfm_banks(e, as_knn.data(), n, "stx_set_nnfm_patch_targets");
+}
+
+int stx_set_nnfm_knn_targets(stx_engine *e, const stx_nnfm_knn_target *targets, int n) {
+    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_knn_targets");
 }
 
 }  // extern "C"

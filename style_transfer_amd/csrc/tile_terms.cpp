@@ -158,14 +158,15 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
 // The nearest-neighbour term of one tapped blob (nnfm.hip): 1 / |f_i| and the pieces of the unit columns, the
 // search over the bank (with the slices' merge when the bank was cut), S with the partials of E and sum |S|.
 // patch 3: 1 / |P_p| and the pieces of the columns under one scale, the gathered search, c_p and S.
+// k > 1: the search keeps the k best rows of a column and S pulls towards their mean (the profile names say so).
 int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int patch,
                       const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
-                      const std::string &name, float *scratch, std::vector<SumJob> *defer) {
+                      const std::string &name, float *scratch, std::vector<SumJob> *defer, int k) {
     const int n = h * w;
-    const NnfmScratch x = nnfm_carve(scratch, C, n, rows, patch);
+    const NnfmScratch x = nnfm_carve(scratch, C, n, rows, patch, k);
     const NnfmPlan plan = nnfm_plan(n, rows);
     int *const idx = idx_out ? idx_out : x.idx;
-    const std::string tag = patch == 3 ? "nnfm patch " : "nnfm ";
+    const std::string tag = std::string(patch == 3 ? "nnfm patch " : "nnfm ") + (k > 1 ? "k" + std::to_string(k) + " " : "");
     {
         ProfScope scope(e, tag + "prepare " + name, 0.0, stream);
         STX_TRY(nnfm_prepare_launch(stream, feat, C, h, w, patch, 1, x.work, x.inv_r, x.xhi, x.xlo, nullptr));
@@ -173,11 +174,11 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
     {
         ProfScope scope(e, tag + "search " + name + " x" + std::to_string(plan.slices),
                         6.0 * n * (double)rows * C * (patch * patch), stream);
-        STX_TRY(nnfm_search_launch(stream, x, h, w, patch, pieces, rows, C, idx));
+        STX_TRY(nnfm_search_launch(stream, x, h, w, patch, pieces, rows, C, idx, k));
     }
     ProfScope scope(e, tag + "grad " + name, 0.0, stream);
     int n_parts = 0;
-    STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts));
+    STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts, k));
     if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
     defer->push_back(SumJob{x.partials, n_parts, sc});
     defer->push_back(SumJob{x.partials + n_parts, n_parts, sc + 1});
@@ -338,7 +339,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         }
         if (const NnfmTarget *nt = nnfm_target_of(e, tp.blob)) {
             add(TermKind::Nnfm, nt->bank->f(), nullptr, ContentWindow{}, lw * nt->weight, 2,
-                nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch), nnfm_slot);
+                nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k), nnfm_slot);
             plan.terms.back().nnfm = nt;
         }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
@@ -397,7 +398,7 @@ int queue_tap_terms(TileRun &run, size_t k) {
         case TermKind::Nnfm:          // sc[0] = E, sc[1] = sum |S|
             STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.nnfm->patch, t.target,
                                       t.nnfm->pieces_hi_lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch,
-                                      run.defer()));
+                                      run.defer(), t.nnfm->k));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

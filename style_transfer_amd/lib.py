@@ -68,6 +68,12 @@ class NnfmPatchTarget(ctypes.Structure):
                 ('weight', ctypes.c_double)]
 
 
+class NnfmKnnTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('patch', ctypes.c_int),
+                ('k', ctypes.c_int), ('rows', ctypes.c_int), ('bank', ctypes.c_void_p), ('mem', ctypes.c_int),
+                ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -101,6 +107,7 @@ SIGNATURES = {
     'stx_set_stat_targets': [_vp, ctypes.POINTER(StatTarget), _i],
     'stx_set_nnfm_targets': [_vp, ctypes.POINTER(NnfmTarget), _i],
     'stx_set_nnfm_patch_targets': [_vp, ctypes.POINTER(NnfmPatchTarget), _i],
+    'stx_set_nnfm_knn_targets': [_vp, ctypes.POINTER(NnfmKnnTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -154,6 +161,7 @@ SIGNATURES = {
     'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
+    'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],
     'stx_last_tile_flops': [_vp, c_double_p, c_double_p],

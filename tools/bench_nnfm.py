@@ -2,6 +2,7 @@
 
     python tools/bench_nnfm.py [--out profiles/nnfm_times.txt]
     python tools/bench_nnfm.py --patch 3 [--out profiles/nnfm_patch_times.txt]
+    python tools/bench_nnfm.py --k 1 2 4 [--out profiles/nnfm_knn_times.txt]
 
 stx_op_nnfm_terms at the blob shapes of a 1024^2 tile -- conv3_1 (256 x 256^2) and conv4_1 (512 x 128^2) --
 against the banks of a 512^2 and of a 1024^2 style picture at --nnfm-stride 1 and 2, and at the shapes of a
@@ -18,6 +19,10 @@ at 2.5 PFLOP/s, the dense fp16 rate of the MI355X.
 --patch 3: stx_op_nnfm_patch_terms (--nnfm-patch 3) at the same shapes, K = 9 C.  Its yardstick is the plain
 search run in the same call on a synthetic blob of 9 C channels with the same n and M: the same flops, and what
 a materialised [n][9 C] query array would cost the search (`plain 9C`, with the ratio patch / plain).
+
+--k 1 2 4: the k-nearest term (--nnfm-k, stx_op_nnfm_knn_terms) at the same shapes, one row per K, every K in the
+same run as K = 1 (which is the call of the table without --k): `search x` and `grad x` are the group's time over
+that of the K = 1 row above it.
 """
 
 import argparse
@@ -45,14 +50,18 @@ def unit_rows(rng, m, c):
     return b / np.linalg.norm(b, axis=1, keepdims=True)
 
 
-def measure(eng, rng, c, side, rows, reps, patch=1):
-    """Median ms of the term's three groups; ``patch`` 3: the patch term of a c-channel blob (bank rows of 9 c)."""
+def measure(eng, rng, c, side, rows, reps, patch=1, k=1):
+    """Median ms of the term's three groups; ``patch`` 3: the patch term of a c-channel blob (bank rows of 9 c);
+    ``k`` above 1: the k-nearest term."""
     feat = eng.to_device(np.maximum(rng.standard_normal((c, side, side)), 0).astype(np.float32) + np.float32(1e-3))
     bank = eng.to_device(unit_rows(rng, rows, patch * patch * c))
     s_out = eng.empty((c, side, side))
-    idx = eng.empty((side * side,), np.int32)
+    idx = eng.empty((k * side * side,), np.int32)
     out = (ctypes.c_double * 2)()
-    if patch == 1:
+    if k > 1:
+        call = lambda: lib.call('stx_op_nnfm_knn_terms', eng.handle, feat.ptr, c, side, side, patch, k, bank.ptr, rows,
+                                s_out.ptr, idx.ptr, out)
+    elif patch == 1:
         call = lambda: lib.call('stx_op_nnfm_terms', eng.handle, feat.ptr, c, side, side, bank.ptr, rows, s_out.ptr,
                                 idx.ptr, out)
     else:
@@ -66,7 +75,7 @@ def measure(eng, rng, c, side, rows, reps, patch=1):
     for _ in range(reps):
         call()
         for label, ms, _ in eng.profile_read():
-            words = [word for word in label.split() if word != 'patch']
+            words = [word for word in label.split() if word != 'patch' and word != 'k%d' % k]
             if words[0] == 'nnfm' and words[1] in times:
                 times[words[1]].append(ms)
                 if words[1] == 'search':
@@ -88,24 +97,33 @@ def table_lines(eng, rng, opts):
     if p3:
         lines.append('# plain 9C = the search of stx_op_nnfm_terms on a blob of 9 C channels, same n and M; '
                      'ratio = search / plain 9C')
+    many = opts.k != [1]
+    if many:
+        lines.append('# --nnfm-k: one row per K (K > 1: stx_op_nnfm_knn_terms); search x, grad x = the time over the '
+                     'K = 1 row of the same shape, same run')
     head = ('tile', 'blob', 'C', 'n', 'M', 'stride', 'slices', 'prepare', 'search', 'grad', 'total', 'floor ms', 'of floor')
     lines.append('%6s %8s %4s %7s %7s %6s %6s %9s %9s %9s %9s %9s %8s' % head
-                 + (' %9s %6s' % ('plain 9C', 'ratio') if p3 else ''))
+                 + (' %9s %6s' % ('plain 9C', 'ratio') if p3 else '') + (' %2s %8s %7s' % ('K', 'search x', 'grad x') if many else ''))
     for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
         for blob, c, side, style_side in shapes:
             for stride in (1, 2):
                 rows = (-(-style_side // stride)) ** 2
-                t, slices = measure(eng, rng, c, side, rows, opts.reps, opts.patch)
                 n = side * side
                 floor_ms = 6.0 * n * rows * opts.patch ** 2 * c / FP16_FLOPS * 1e3
-                line = ('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f'
-                        % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
-                           sum(t.values()), floor_ms, floor_ms / t['search']))
-                if p3:
-                    plain, _ = measure(eng, rng, 9 * c, side, rows, opts.reps)
-                    line += ' %9.4f %6.3f' % (plain['search'], t['search'] / plain['search'])
-                lines.append(line)
-                print(line, flush=True)
+                one = None
+                for k in opts.k:
+                    t, slices = measure(eng, rng, c, side, rows, opts.reps, opts.patch, k)
+                    one = t if k == 1 else one
+                    line = ('%6d %8s %4d %7d %7d %6d %6d %9.4f %9.4f %9.4f %9.4f %9.4f %8.3f'
+                            % (tile, blob, c, n, rows, stride, slices, t['prepare'], t['search'], t['grad'],
+                               sum(t.values()), floor_ms, floor_ms / t['search']))
+                    if p3:
+                        plain, _ = measure(eng, rng, 9 * c, side, rows, opts.reps)
+                        line += ' %9.4f %6.3f' % (plain['search'], t['search'] / plain['search'])
+                    if many:
+                        line += ' %2d %8.3f %7.3f' % (k, t['search'] / one['search'], t['grad'] / one['grad'])
+                    lines.append(line)
+                    print(line, flush=True)
     return lines
 
 
@@ -114,7 +132,11 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--patch', type=int, default=1, choices=(1, 3))
+    ap.add_argument('--k', type=int, nargs='+', default=[1], choices=(1, 2, 3, 4),
+                    help='rows per query, K = 1 first: every K is set beside the K = 1 of the same run')
     opts = ap.parse_args()
+    if opts.k[0] != 1:
+        ap.error('--k: the list begins with 1, the row the others are set beside')
     if not torch.cuda.is_available():
         sys.exit('bench_nnfm: no GPU')
     net = builtin_net('vgg19')
