@@ -328,6 +328,35 @@ typedef struct stx_nnfm_knn_target {
  * whole set. */
 int stx_set_nnfm_knn_targets(stx_engine *e, const stx_nnfm_knn_target *targets, int n);
 
+/* The same term with a coverage part (the other half of STROTSS's relaxed earth mover's distance): every bank row
+ * also looks for ITS most similar column and pulls that one towards itself, so that rows no column picked still
+ * act on the result.  With lambda = cover and E_fwd, S_fwd the term above (any k):
+ *   i*_j    = argmax_i x_i . b_j             the LOWEST i among equal scores; a zero column scores 0 and may win
+ *   c'_j    = x_{i*_j} . b_j                 (float32 fma in channel order, recomputed: not the search's score)
+ *   E_cov   = (2/M) sum_j (1 - c'_j)
+ *   S_cov,i = -(n/M) sum_{j : i*_j = i} (b_j - c'_j x_i) / r_i     (0 for r_i = 0; n d(E_cov/2)/df_i, winners held;
+ *                                                                   rows added in ascending j)
+ *   E = E_fwd + lambda E_cov,  S = S_fwd + lambda S_cov
+ *   loss += lw w E / 2,  diff[layer] += lw w S / (sum|S| / (C n) + EPS)          (ONE normalisation, of the sum)
+ * Zero bank rows count in M: each adds 1 to the sum and nothing to S.  The term belongs to one tile: every tile is
+ * asked to cover the whole bank.  cover 0 is stx_set_nnfm_knn_targets, byte for byte; a cover that is negative or
+ * not finite, or one other than 0 with patch 3 (the coverage part has no patch form), is STX_ERR_ARG.  Every other
+ * refusal is that of stx_set_nnfm_knn_targets. */
+typedef struct stx_nnfm_cover_target {
+    const char *layer;
+    int channels;
+    int patch;
+    int k;
+    int rows;
+    const float *bank;      /* [rows][patch * patch * channels] */
+    int mem;
+    double weight;
+    float cover;
+} stx_nnfm_cover_target;
+/* stx_set_nnfm_targets for banks of any kind: a layer has ONE bank, and any of the four calls replaces the
+ * whole set. */
+int stx_set_nnfm_cover_targets(stx_engine *e, const stx_nnfm_cover_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -676,6 +705,12 @@ int stx_op_nnfm_patch_terms(stx_engine *e, const float *feat, int channels, int 
  * alone. */
 int stx_op_nnfm_knn_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch, int k,
                           const float *bank, int rows, float *s_out, int *index_out, double out[2]);
+/* ... and of a target with a coverage part (stx_set_nnfm_cover_targets): winner_out = i* [rows], out = {E, sum |S|,
+ * E_cov}, E and S those of the sum.  cover 0 is stx_op_nnfm_knn_terms (out[2] and winner_out untouched); a cover
+ * that is negative or not finite, or one other than 0 with patch 3, is STX_ERR_ARG.  Errors leave the outputs
+ * alone. */
+int stx_op_nnfm_cover_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch, int k, float cover,
+                            const float *bank, int rows, float *s_out, int *index_out, int *winner_out, double out[3]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

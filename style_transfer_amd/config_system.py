@@ -161,6 +161,14 @@ _EXTENSIONS = [
                               'of its K most similar bank rows instead of the single best one, an integer from 1 '
                               'to 4: steadier targets where two rows are nearly tied and with --nnfm-stride above '
                               '1; the search is done once whatever K is; read once per scale (default: 1)')),
+    (('--nnfm-cover',), dict(metavar='LAMBDA', type=ffloat,
+                             help='adds LAMBDA times the coverage part to the nearest-neighbour term (the other half '
+                                  "of STROTSS's relaxed earth mover's distance): every bank row also looks for its "
+                                  'most similar feature vector of the result and pulls that one towards itself, so '
+                                  'that the whole style bank is used and not only the rows that are easiest to '
+                                  'reach; every tile is asked to cover the whole bank, so --nnfm-stride matters '
+                                  'more; a finite number >= 0, not with --nnfm-patch 3; read once per scale; 0 or '
+                                  'absent: off (default: 0)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -405,6 +413,16 @@ def nnfm_k(args):
     return int(raw)
 
 
+def nnfm_cover(args):
+    """--nnfm-cover as a finite float >= 0 (default 0: no coverage part); anything else, bools and strings
+    included, is a ValueError."""
+    raw = raw_option(args, 'nnfm_cover', 0.0)
+    if (isinstance(raw, bool) or not isinstance(raw, (int, float, np.integer, np.floating)) or not np.isfinite(raw)
+            or raw < 0):
+        raise ValueError('--nnfm-cover %r: a finite number >= 0 is expected' % (raw,))
+    return float(raw)
+
+
 def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
     """Rows that a [channels, h, w] feature map adds to a bank at this stride.  With ``patch`` 3 a bank that
     would reach the library's limit -- (rows_before + rows) x 9 x channels below 2^31 -- is a ValueError, raised
@@ -418,9 +436,11 @@ def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
 
 
 def check_nnfm_options(args, known_layers=None):
-    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k: refused before any GPU work together
-    with --style-masks (there is one bank and, with masks, one style set per picture), with a stride below 1, with a
-    patch that is not 1 or 3, with a k outside 1 .. 4 and with a bad layer list (check_layer_list).  Returns the layer names."""
+    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k / --nnfm-cover: refused before any GPU
+    work together with --style-masks (there is one bank and, with masks, one style set per picture), with a stride
+    below 1, with a patch that is not 1 or 3, with a k outside 1 .. 4, with a cover that is not a finite number >= 0,
+    with a cover other than 0 beside patch 3 (the coverage part has no patch form) and with a bad layer list
+    (check_layer_list).  Returns the layer names."""
     items = nnfm_layer_args(args)
     if not items:
         return []
@@ -428,6 +448,9 @@ def check_nnfm_options(args, known_layers=None):
         nnfm_stride(args)
         nnfm_patch(args)
         nnfm_k(args)
+        if nnfm_cover(args) != 0 and nnfm_patch(args) != 1:
+            raise ValueError('--nnfm-cover %g cannot be combined with --nnfm-patch 3: the coverage part matches '
+                             'single feature vectors only' % nnfm_cover(args))
     return check_layer_list(args, items, '--nnfm-weight', '--nnfm-layers', 'one bank of style features',
                             known_layers)
 

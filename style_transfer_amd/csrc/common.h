@@ -502,8 +502,24 @@ NnfmPlan nnfm_plan(int n, int M);
 size_t nnfm_pieces_floats(int rows, int C);
 // floats of the caller's that one term takes, and their division (from the next 256-byte boundary)
 // (patch 3: the 3 x 3 patch term, whose bank rows have 9 C channels -- O(n) floats more; k rows per query: k - 1
-// further index planes and k-fold slice pairs)
-size_t nnfm_scratch_floats(int C, int n, int M, int patch = 1, int k = 1);
+// further index planes and k-fold slice pairs; cover: the arrays of NnfmCover behind everything else, so that a
+// term without the coverage part keeps its size and layout)
+size_t nnfm_scratch_floats(int C, int n, int M, int patch = 1, int k = 1, bool cover = false);
+// The coverage part (stx_set_nnfm_cover_targets): every bank row j looks for its best column i*_j.  All null
+// without it.
+struct NnfmCover {
+    int *winner = nullptr;          // [M]: i*_j
+    float *part_score = nullptr;    // [slices of nnfm_plan(M, n)][M], or null with one slice
+    int *part_idx = nullptr;
+    int *cursor = nullptr;          // [n]: rows per column, then each column's fill cursor
+    int *offsets = nullptr;         // [n + 1]: column i owns list[offsets[i] .. offsets[i + 1])
+    int *unordered = nullptr;       // [M]: the lists as the cursors filled them
+    int *list = nullptr;            // [M]: the lists, ascending j within a column
+    float *cprime = nullptr;        // [M]: c'_j
+    float *e_parts = nullptr;       // ceil(n / 64) partials of E_fwd, then ceil(M / 64) of cover E_cov: ONE list of E
+    float *e_cov_parts = nullptr;   // ceil(M / 64) partials of E_cov alone
+    float *abs_parts = nullptr;     // (C / 64) ceil(n / 64) partials of sum |S| of the final S
+};
 struct NnfmScratch {
     unsigned short *xhi, *xlo;      // pieces of x_i 2^13 (patch 3: of f_i under the blob's common scale), [n][C] each
     float *inv_r;                   // [n]
@@ -513,8 +529,9 @@ struct NnfmScratch {
     float *partials;                // ceil(n / 64) of (2/n) sum (1 - c_i), then as many of sum |S|
     double *work;                   // patch 3: nnfm_patch_work_floats(n) floats of nnfm_prepare_launch, else null
     float *cosv;                    // patch 3: c_p [n], else null
+    NnfmCover cov;                  // the coverage part, or nulls
 };
-NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch = 1, int k = 1);
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch = 1, int k = 1, bool cover = false);
 // The term's three steps, for both forms.  patch 1: columns of C channels against bank rows of C.  patch 3
 // (stx_set_nnfm_patch_targets): pixel p's patch is the 9 C vector of the columns at p + tap, tap-major (dy outer,
 // dx inner, (-1, -1) first), zero outside the map, against bank rows [M][9 C] of unit or zero rows.
@@ -540,6 +557,19 @@ int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int pa
 // the mean of its min(k, M) rows
 int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, int patch, const NnfmScratch &x,
                      const float *bank, int M, const int *idx, float *sgrad, int *n_parts, int k = 1);
+// The coverage part of the plain term (patch 1), behind nnfm_prepare_launch and nnfm_grad_launch, in three steps.
+// winner_out[j] = argmax_i x_i . b_j, the lowest i among equal scores: nnfm_search_kernel<false, 1> with the
+// operands exchanged -- the bank's pieces are the queries, x's pieces the bank -- under nnfm_plan(M, n).
+int nnfm_cover_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigned short *pieces, int M, int C,
+                             int *winner_out);
+// c'_j into x.cov.cprime with the partials of E_cov (and of cover E_cov behind E_fwd's place in x.cov.e_parts), then
+// the inverted index: x.cov.offsets and x.cov.list, ascending j within a column.
+int nnfm_cover_index_launch(hipStream_t s, const float *feat, int C, int n, const NnfmScratch &x, const float *bank,
+                            int M, const int *winner, float cover);
+// sgrad = S_fwd + cover S_cov in place, the lists added in their order; E_fwd's partials join x.cov.e_parts:
+// *n_e partials of E = E_fwd + cover E_cov there, *n_abs of sum |S| in x.cov.abs_parts.
+int nnfm_cover_grad_launch(hipStream_t s, const float *feat, int C, int n, const NnfmScratch &x, const float *bank,
+                           int M, float cover, float *sgrad, int *n_e, int *n_abs);
 
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,

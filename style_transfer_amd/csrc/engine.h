@@ -120,12 +120,14 @@ struct StatTarget {
 // The bank of one tapped blob's nearest-neighbour term (stx_set_nnfm_targets): float32 rows [rows][C] on the
 // device and, built once when the targets are set, their fp16 hi / lo pieces for the search (nnfm.hip).
 // patch 3 (stx_set_nnfm_patch_targets): rows of 3 x 3 patches, 9 C channels each.  k (stx_set_nnfm_knn_targets):
-// the rows a query is matched to, 1 .. kNnfmMaxK; the bank does not depend on it.
+// the rows a query is matched to, 1 .. kNnfmMaxK; the bank does not depend on it.  cover
+// (stx_set_nnfm_cover_targets): the factor of the coverage part, 0: none (patch 1 only).
 struct NnfmTarget {
     int blob, C, rows;
     double weight;
     std::unique_ptr<DevBuf> bank, pieces;
     int patch = 1, k = 1;
+    float cover = 0.f;
     // [rows][patch^2 C] hi, then as many lo
     const unsigned short *pieces_hi_lo() const { return static_cast<const unsigned short *>(pieces->ptr); }
     void release() {
@@ -458,9 +460,12 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
 // nnfm_scratch_floats(C, h * w, rows, patch, k) floats that outlive the call like term_scratch.  idx_out (or null):
 // the winning rows [k][h * w].  patch 1, or 3: the 3 x 3 patch form, bank rows of 9 C channels.  pieces: the bank's
 // fp16 pieces, [rows][patch^2 C] hi then lo (nnfm_split_rows_launch).  k: the rows per query, 1 .. kNnfmMaxK.
+// cover != 0 (patch 1 only; the scratch sized with it): E and S gain cover times the coverage part; winner_out (or
+// null): every bank row's best column [rows]; e_cov_out (or null): E_cov alone, summed here.
 int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int patch,
                       const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
-                      const std::string &name, float *scratch, std::vector<SumJob> *defer, int k = 1);
+                      const std::string &name, float *scratch, std::vector<SumJob> *defer, int k = 1, float cover = 0.f,
+                      int *winner_out = nullptr, float *e_cov_out = nullptr);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

@@ -29,6 +29,9 @@
 // S pulls towards their mean (the *_k kernels).  Prepare and gradient are different algorithms per form and stay
 // separate kernels: nnfm_patch_norms_kernel / nnfm_patch_rows_kernel split the columns under one scale for the blob,
 // nnfm_patch_cos_kernel / nnfm_patch_grad_kernel gather the nine patches of a pixel.  The launches choose among them.
+// The coverage part (stx_set_nnfm_cover_targets, patch 1): behind those, every bank row looks for ITS best column --
+// the same search with the operands exchanged -- and the nnfm_cover_* kernels turn the winners into an inverted
+// index (lists in ascending row order) and add every column's rows to S in that order.  Integer atomics only.
 
 #include <algorithm>
 #include <climits>
@@ -809,6 +812,186 @@ __global__ __launch_bounds__(64) void nnfm_patch_grad_k_kernel(const float *__re
     }
 }
 
+// -------------------------------------------------------------------------------------------- cover
+// The coverage part (stx_set_nnfm_cover_targets; STROTSS's other half): every bank row j looks for its best
+// column, i*_j = argmax_i x_i . b_j (nnfm_search_kernel<false, 1> with the operands exchanged), and pulls it
+// towards itself --
+//   c'_j = x_{i*_j} . b_j,   E_cov = (2/M) sum_j (1 - c'_j),   S_cov,i = -(n/M) sum_{j : i*_j = i} (b_j - c'_j x_i) / r_i
+// a scatter from M rows into the columns that won them, done as a gather over an inverted index: no float atomics.
+//
+// First step, one bank row per lane, one wave per workgroup: c'_j with float32 fma in channel order, the row count
+// of the winning column (an integer atomic: a count does not depend on the order of its additions) and the
+// partials of E_cov -- alone in e_cov_parts and, times the factor, in e_parts, where they follow E_fwd's.
+__global__ __launch_bounds__(64) void nnfm_cover_cos_kernel(const float *__restrict__ F, int C, int n,
+                                                            const float *__restrict__ inv_r,
+                                                            const float *__restrict__ bank, int M, int vec,
+                                                            const int *__restrict__ winner, float cover,
+                                                            float *__restrict__ cprime, int *__restrict__ counts,
+                                                            float *__restrict__ e_parts, float *__restrict__ e_cov_parts) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = j < M;
+    const int jj = valid ? j : M - 1;
+    const unsigned iu = (unsigned)winner[jj];
+    const int i = iu < (unsigned)n ? (int)iu : 0;
+    const float *__restrict__ row = bank + (size_t)jj * C;
+    const float inv = inv_r[i];
+    const float *__restrict__ f = F + i;
+    float c = 0.f;
+    if (vec) {
+#pragma unroll 4
+        for (int ch = 0; ch < C; ch += 4) {
+            const float4 b = *reinterpret_cast<const float4 *>(row + ch);
+            c = fmaf(f[(size_t)ch * n] * inv, b.x, c);
+            c = fmaf(f[(size_t)(ch + 1) * n] * inv, b.y, c);
+            c = fmaf(f[(size_t)(ch + 2) * n] * inv, b.z, c);
+            c = fmaf(f[(size_t)(ch + 3) * n] * inv, b.w, c);
+        }
+    } else {
+#pragma unroll 4
+        for (int ch = 0; ch < C; ++ch) c = fmaf(f[(size_t)ch * n] * inv, row[ch], c);
+    }
+    if (valid) {
+        cprime[j] = c;
+        atomicAdd(counts + i, 1);
+    }
+    const float one_minus = wave_sum_f(valid ? 1.f - c : 0.f);
+    if (threadIdx.x == 0) {
+        const float e = one_minus * (2.f / (float)M);
+        e_cov_parts[blockIdx.x] = e;
+        e_parts[blockIdx.x] = cover * e;
+    }
+}
+
+// Second step, ONE workgroup: offsets = the exclusive prefix sums of the counts, 1024 columns per round; the counts
+// become each column's fill cursor (its first place).  Integers: no order can change a sum.
+__global__ __launch_bounds__(256) void nnfm_cover_offsets_kernel(int *__restrict__ counts, int n,
+                                                                 int *__restrict__ offsets) {
+    __shared__ int wsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int at = base + 4 * (int)threadIdx.x;
+        int v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = at + u < n ? counts[at + u] : 0;
+        const int t = (v[0] + v[1]) + (v[2] + v[3]);
+        int inc = t;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < wave) before += wsum[k];
+            total += wsum[k];
+        }
+        int ex = carry + before + inc - t;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (at + u < n) {
+                offsets[at + u] = ex;
+                counts[at + u] = ex;
+            }
+            ex += v[u];
+        }
+        carry += total;
+        __syncthreads();        // (wsum is read; the next round writes it)
+    }
+    if (threadIdx.x == 0) offsets[n] = carry;
+}
+
+// Third step: every row takes a place of its column's through the cursor.  WHICH place depends on the order the
+// atomics retire in, so this list is only the set of a column's rows ...
+__global__ __launch_bounds__(256) void nnfm_cover_fill_kernel(const int *__restrict__ winner, int M, int n,
+                                                              int *__restrict__ cursor, int *__restrict__ unordered) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const unsigned iu = (unsigned)winner[j];
+    const int p = atomicAdd(cursor + (iu < (unsigned)n ? (int)iu : 0), 1);
+    if ((unsigned)p < (unsigned)M) unordered[p] = j;
+}
+
+// ... and the fourth puts it in order: row j's place is the number of rows of its column that are below j (rows are
+// distinct), a function of the set alone.  list[offsets[i] ...) is then ascending in j whatever the third step did.
+// A row walks its column's whole list: sum of squared list lengths comparisons, M^2 when one column owns every row.
+__global__ __launch_bounds__(256) void nnfm_cover_order_kernel(const int *__restrict__ winner, int M, int n,
+                                                               const int *__restrict__ offsets,
+                                                               const int *__restrict__ unordered, int *__restrict__ list) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    const unsigned iu = (unsigned)winner[j];
+    const int i = iu < (unsigned)n ? (int)iu : 0;
+    const int beg = offsets[i], end = min(offsets[i + 1], M);
+    int rank = 0;
+    for (int p = beg; p < end; ++p) rank += unordered[p] < j ? 1 : 0;
+    if ((unsigned)(beg + rank) < (unsigned)M) list[beg + rank] = j;
+}
+
+// The gradient, grid (64-column groups, 64-channel groups), four waves.  A wave owns 16 of the group's columns, one
+// after the other, and its lanes are the 64 channels: it walks the column's list in order and a lane adds
+// b_j[ch] - c'_j x_i[ch] row by row -- 256 contiguous bytes of a bank row per step, and the order of a column's sum
+// is the list's, whatever the grid.  The sums go through LDS so that S is read and written along i, like
+// nnfm_grad_kernel: S = S_fwd + cover S_cov in place.  A long list is one wave's work per channel group: M steps of
+// C / 64 waves when one column owns every row.
+// abs_parts [channel group][column group] = sum |S|; the channel group 0 moves E_fwd's partial into e_parts.
+__global__ __launch_bounds__(256) void nnfm_cover_grad_kernel(const float *__restrict__ F, int C, int n,
+                                                              const float *__restrict__ inv_r,
+                                                              const float *__restrict__ bank, int M,
+                                                              const int *__restrict__ offsets,
+                                                              const int *__restrict__ list,
+                                                              const float *__restrict__ cprime, float cover, float *S,
+                                                              const float *__restrict__ fwd_parts,
+                                                              float *__restrict__ e_parts, float *__restrict__ abs_parts) {
+    __shared__ float tile[64][65];
+    __shared__ float red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const int icol = min(i0 + lane, n - 1);         // (columns past the end re-read the last one)
+    for (int cc = wave; cc < 64; cc += 4) tile[cc][lane] = F[(size_t)(c0 + cc) * n + icol];
+    __syncthreads();
+    const float n_over_m = (float)n / (float)M;
+    const float *__restrict__ bch = bank + c0 + lane;
+    for (int u = 0; u < 16; ++u) {
+        const int col = wave * 16 + u, i = i0 + col;
+        float out = 0.f;
+        if (i < n) {
+            const float inv = inv_r[i];
+            const float x = tile[lane][col] * inv;
+            const int beg = offsets[i], end = min(offsets[i + 1], M);
+            float acc = 0.f;
+#pragma unroll 4
+            for (int p = beg; p < end; ++p) {
+                const unsigned ju = (unsigned)list[p];
+                const size_t j = ju < (unsigned)M ? ju : 0u;
+                acc += bch[j * C] - cprime[j] * x;
+            }
+            out = -((n_over_m * acc) * inv);
+        }
+        tile[lane][col] = out;      // (the place this lane alone has read)
+    }
+    __syncthreads();
+    float sum_abs = 0.f;
+    if (i0 + lane < n) {
+        for (int cc = wave; cc < 64; cc += 4) {
+            const size_t at = (size_t)(c0 + cc) * n + i0 + lane;
+            const float s = S[at] + cover * tile[cc][lane];
+            S[at] = s;
+            sum_abs += fabsf(s);
+        }
+    }
+    sum_abs = wave_sum_f(sum_abs);
+    if (lane == 0) red[wave] = sum_abs;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        abs_parts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+        if (blockIdx.y == 0) e_parts[blockIdx.x] = fwd_parts[blockIdx.x];
+    }
+}
+
 // n columns of C channels against M bank rows of patch x patch x C
 int check_shape(const char *who, int C, long long n, long long M, int patch) {
     const char *const what = patch == 3 ? "patches" : "columns";
@@ -848,14 +1031,27 @@ size_t nnfm_pieces_floats(int rows, int C) { return round64((size_t)rows * C); }
 
 size_t nnfm_patch_work_floats(int n) { return 2 * round64(n) + 2 * round64(ceil_div(n, 64)); }
 
-size_t nnfm_scratch_floats(int C, int n, int M, int patch, int k) {
+namespace {
+
+// the floats of NnfmCover, in its order
+size_t cover_floats(int C, int n, int M) {
+    const NnfmPlan r = nnfm_plan(M, n);
+    const size_t nb = ceil_div(n, 64), mb = ceil_div(M, 64);
+    return 4 * round64(M) + (r.slices > 1 ? 2 * round64((size_t)r.slices * M) : 0) + round64(n) +
+           round64((size_t)n + 1) + round64(nb + mb) + round64(mb) + round64((size_t)(C / 64) * nb);
+}
+
+}  // namespace
+
+size_t nnfm_scratch_floats(int C, int n, int M, int patch, int k, bool cover) {
     const NnfmPlan p = nnfm_plan(n, M);
     return 64 + nnfm_pieces_floats(n, C) + round64(n) + round64((size_t)k * n) +
            (p.slices > 1 ? 2 * round64((size_t)p.slices * k * n) : 0) +
-           round64(2 * (size_t)ceil_div(n, 64)) + (patch == 3 ? nnfm_patch_work_floats(n) + round64(n) : 0);
+           round64(2 * (size_t)ceil_div(n, 64)) + (patch == 3 ? nnfm_patch_work_floats(n) + round64(n) : 0) +
+           (cover ? cover_floats(C, n, M) : 0);
 }
 
-NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch, int k) {
+NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch, int k, bool cover) {
     const NnfmPlan p = nnfm_plan(n, M);
     NnfmScratch s;
     float *at = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
@@ -882,6 +1078,35 @@ NnfmScratch nnfm_carve(float *scratch, int C, int n, int M, int patch, int k) {
         s.work = reinterpret_cast<double *>(at);
         at += nnfm_patch_work_floats(n);
         s.cosv = at;
+        at += round64(n);
+    }
+    if (cover) {        // behind everything else: the layout without it does not move
+        const NnfmPlan r = nnfm_plan(M, n);
+        const size_t nb = ceil_div(n, 64), mb = ceil_div(M, 64);
+        NnfmCover &c = s.cov;
+        c.winner = reinterpret_cast<int *>(at);
+        at += round64(M);
+        if (r.slices > 1) {
+            c.part_score = at;
+            at += round64((size_t)r.slices * M);
+            c.part_idx = reinterpret_cast<int *>(at);
+            at += round64((size_t)r.slices * M);
+        }
+        c.cursor = reinterpret_cast<int *>(at);
+        at += round64(n);
+        c.offsets = reinterpret_cast<int *>(at);
+        at += round64((size_t)n + 1);
+        c.unordered = reinterpret_cast<int *>(at);
+        at += round64(M);
+        c.list = reinterpret_cast<int *>(at);
+        at += round64(M);
+        c.cprime = at;
+        at += round64(M);
+        c.e_parts = at;
+        at += round64(nb + mb);
+        c.e_cov_parts = at;
+        at += round64(mb);
+        c.abs_parts = at;
     }
     return s;
 }
@@ -1025,6 +1250,53 @@ int nnfm_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, int 
     }
     STX_CHECK_LAUNCH();
     *n_parts = blocks;
+    return STX_OK;
+}
+
+int nnfm_cover_search_launch(hipStream_t s, const NnfmScratch &x, int n, const unsigned short *pieces, int M, int C,
+                             int *winner_out) {
+    if (!x.cov.winner) {
+        set_error("nnfm_cover_search_launch: a scratch without the coverage part");
+        return STX_ERR_ARG;
+    }
+    // the roles exchanged: the bank's pieces are M queries (a map M x 1), and x's pieces, [n][C] hi with lo right
+    // behind them, are a bank of n rows
+    NnfmScratch r{};
+    r.xhi = const_cast<unsigned short *>(pieces);
+    r.xlo = r.xhi + (size_t)M * C;
+    r.part_score = x.cov.part_score;
+    r.part_idx = x.cov.part_idx;
+    return nnfm_search_launch(s, r, M, 1, 1, x.xhi, n, C, winner_out, 1);
+}
+
+int nnfm_cover_index_launch(hipStream_t s, const float *feat, int C, int n, const NnfmScratch &x, const float *bank,
+                            int M, const int *winner, float cover) {
+    STX_TRY(check_shape("nnfm_cover_index_launch", C, n, M, 1));
+    const NnfmCover &c = x.cov;
+    const int vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
+    STX_HIP(hipMemsetAsync(c.cursor, 0, (size_t)n * sizeof(int), s));
+    nnfm_cover_cos_kernel<<<ceil_div(M, 64), 64, 0, s>>>(feat, C, n, x.inv_r, bank, M, vec, winner, cover, c.cprime,
+                                                         c.cursor, c.e_parts + ceil_div(n, 64), c.e_cov_parts);
+    STX_CHECK_LAUNCH();
+    nnfm_cover_offsets_kernel<<<1, 256, 0, s>>>(c.cursor, n, c.offsets);
+    STX_CHECK_LAUNCH();
+    nnfm_cover_fill_kernel<<<ceil_div(M, 256), 256, 0, s>>>(winner, M, n, c.cursor, c.unordered);
+    STX_CHECK_LAUNCH();
+    nnfm_cover_order_kernel<<<ceil_div(M, 256), 256, 0, s>>>(winner, M, n, c.offsets, c.unordered, c.list);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+int nnfm_cover_grad_launch(hipStream_t s, const float *feat, int C, int n, const NnfmScratch &x, const float *bank,
+                           int M, float cover, float *sgrad, int *n_e, int *n_abs) {
+    STX_TRY(check_shape("nnfm_cover_grad_launch", C, n, M, 1));
+    const NnfmCover &c = x.cov;
+    const int nb = ceil_div(n, 64);
+    nnfm_cover_grad_kernel<<<dim3(nb, C / 64), 256, 0, s>>>(feat, C, n, x.inv_r, bank, M, c.offsets, c.list, c.cprime,
+                                                            cover, sgrad, x.partials, c.e_parts, c.abs_parts);
+    STX_CHECK_LAUNCH();
+    *n_e = nb + ceil_div(M, 64);
+    *n_abs = (C / 64) * nb;
     return STX_OK;
 }
 

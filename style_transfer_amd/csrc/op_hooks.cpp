@@ -1,6 +1,8 @@
 // libstx host side: the stx_op_* test hooks -- single operators of the tile path, launched the way the
 // tile path launches them, on caller-owned device arrays.
 
+#include <cmath>
+
 #include "engine.h"
 
 extern "C" {
@@ -203,9 +205,13 @@ int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, 
 // are the ones they had as two functions.  Nothing is written before the arguments are accepted.  (An error behind
 // take() leaves the scalar arena empty, as in the other term hooks.)
 static int hook_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, const float *bank, int rows,
-                           float *s_out, int *index_out, double out[2], int k = 1) {
-    const bool plain = patch == 1;
-    const char *const who = k > 1 ? "stx_op_nnfm_knn_terms" : plain ? "stx_op_nnfm_terms" : "stx_op_nnfm_patch_terms";
+                           float *s_out, int *index_out, double out[2], int k = 1, float cover = 0.f,
+                           int *winner_out = nullptr) {
+    const bool plain = patch == 1, covered = cover != 0.f;      // covered: out[3] = {E, sum |S|, E_cov}
+    const char *const who = covered ? "stx_op_nnfm_cover_terms"
+                            : k > 1 ? "stx_op_nnfm_knn_terms"
+                            : plain ? "stx_op_nnfm_terms"
+                                    : "stx_op_nnfm_patch_terms";
     if ((!plain && patch != 3) || !e || !feat || !bank || !s_out || !index_out || !out || C <= 0 || h <= 0 || w <= 0 ||
         rows <= 0) {
         if (plain)
@@ -231,17 +237,18 @@ static int hook_nnfm_terms(stx_engine *e, const float *feat, int C, int h, int w
     HookScalars scalars(e);
     float *sc;
     const float *host;
-    STX_TRY(scalars.take(2, &sc));
+    STX_TRY(scalars.take(covered ? 3 : 2, &sc));
     const size_t pieces = nnfm_pieces_floats(rows, (int)width);
-    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows, patch, k)) * sizeof(float)));
+    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_scratch_floats(C, h * w, rows, patch, k, covered)) * sizeof(float)));
     unsigned short *bhi = static_cast<unsigned short *>(e->nnfm_scratch.ptr);
     // what the targets' setter does once, then the launches of an NNFM target of stx_sc_grad_tile, in the same order
     STX_TRY(nnfm_split_rows_launch(e->stream, bank, rows, (int)width, bhi, bhi + (size_t)rows * width));
     STX_TRY(launch_nnfm_terms(e, e->stream, feat, C, h, w, patch, bank, bhi, rows, s_out, index_out, sc, "op",
-                              e->nnfm_scratch.f() + pieces, nullptr, k));
+                              e->nnfm_scratch.f() + pieces, nullptr, k, cover, winner_out, covered ? sc + 2 : nullptr));
     STX_TRY(scalars.fetch(&host));
     out[0] = (double)host[0];
     out[1] = (double)host[1];
+    if (covered) out[2] = (double)host[2];
     return STX_OK;
 }
 
@@ -262,6 +269,25 @@ int stx_op_nnfm_knn_terms(stx_engine *e, const float *feat, int C, int h, int w,
         return STX_ERR_ARG;
     }
     return hook_nnfm_terms(e, feat, C, h, w, patch, bank, rows, s_out, index_out, out, k);
+}
+
+int stx_op_nnfm_cover_terms(stx_engine *e, const float *feat, int C, int h, int w, int patch, int k, float cover,
+                            const float *bank, int rows, float *s_out, int *index_out, int *winner_out, double out[3]) {
+    if (!(cover >= 0.f) || !std::isfinite(cover)) {
+        set_error("stx_op_nnfm_cover_terms: cover %g (a finite factor, 0 or more, is expected)", (double)cover);
+        return STX_ERR_ARG;
+    }
+    if (cover == 0.f) return stx_op_nnfm_knn_terms(e, feat, C, h, w, patch, k, bank, rows, s_out, index_out, out);
+    if (patch != 1 || !winner_out) {
+        set_error("stx_op_nnfm_cover_terms: cover %g with patch %d%s (the coverage part has no patch form)", (double)cover,
+                  patch, winner_out ? "" : " and no place for the winners");
+        return STX_ERR_ARG;
+    }
+    if (k < 1 || k > kNnfmMaxK) {
+        set_error("stx_op_nnfm_cover_terms: k %d (1 to %d is expected)", k, kNnfmMaxK);
+        return STX_ERR_ARG;
+    }
+    return hook_nnfm_terms(e, feat, C, h, w, patch, bank, rows, s_out, index_out, out, k, cover, winner_out);
 }
 
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,

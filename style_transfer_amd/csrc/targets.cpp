@@ -4,6 +4,8 @@
 // the style masks, the content mask, the statistics targets and the NNFM banks, which go when new contents
 // and styles arrive.  Every setter is one swap (swap_targets) around a body that validates and copies.
 
+#include <cmath>
+
 #include "engine.h"
 
 namespace {
@@ -54,8 +56,9 @@ struct MaskSource {
     }
 };
 
-// The banks of the three NNFM setters: a plain bank is a patch target with patch 1, and both match k = 1 row.
-static int set_nnfm_banks(stx_engine *e, const stx_nnfm_knn_target *targets, int n, const char *who) {
+// The banks of the four NNFM setters: a plain bank is a patch target with patch 1, both match k = 1 row, and all
+// three have no coverage part (cover 0).
+static int set_nnfm_banks(stx_engine *e, const stx_nnfm_cover_target *targets, int n, const char *who) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
     for (int i = 0; i < n; ++i) {
         if (targets[i].patch != 1 && targets[i].patch != 3) {
@@ -66,12 +69,21 @@ static int set_nnfm_banks(stx_engine *e, const stx_nnfm_knn_target *targets, int
             set_error("NNFM target %d: k %d (1 to %d is expected)", i, targets[i].k, kNnfmMaxK);
             return STX_ERR_ARG;
         }
+        if (!(targets[i].cover >= 0.f) || !std::isfinite(targets[i].cover)) {
+            set_error("NNFM target %d: cover %g (a finite factor, 0 or more, is expected)", i, (double)targets[i].cover);
+            return STX_ERR_ARG;
+        }
+        if (targets[i].cover != 0.f && targets[i].patch != 1) {
+            set_error("NNFM target %d: cover %g with patch %d (the coverage part has no patch form)", i,
+                      (double)targets[i].cover, targets[i].patch);
+            return STX_ERR_ARG;
+        }
     }
     auto &nnfms = e->sh->nnfms;
     return swap_targets(e, who, [&](bool &) -> int {
         clear_targets(nnfms);
         for (int i = 0; i < n; ++i) {
-            const stx_nnfm_knn_target &nt = targets[i];
+            const stx_nnfm_cover_target &nt = targets[i];
             const int blob = e->find_blob(nt.layer);
             bool twice = false;
             for (const NnfmTarget &t : nnfms) twice |= t.blob == blob;
@@ -92,7 +104,7 @@ static int set_nnfm_banks(stx_engine *e, const stx_nnfm_knn_target *targets, int
                 return STX_ERR_UNSUPPORTED;
             }
             nnfms.push_back(NnfmTarget{blob, nt.channels, nt.rows, nt.weight, std::unique_ptr<DevBuf>(new DevBuf),
-                                       std::unique_ptr<DevBuf>(new DevBuf), nt.patch, nt.k});
+                                       std::unique_ptr<DevBuf>(new DevBuf), nt.patch, nt.k, nt.cover});
             NnfmTarget &t = nnfms.back();
             const size_t bytes = (size_t)t.rows * width * sizeof(float);
             STX_TRY(t.bank->ensure(bytes));
@@ -257,26 +269,36 @@ int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
 
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    std::vector<stx_nnfm_knn_target> as_knn;
+    std::vector<stx_nnfm_cover_target> as_knn;
     for (int i = 0; i < n; ++i) {
         const stx_nnfm_target &t = targets[i];
-        as_knn.push_back(stx_nnfm_knn_target{t.layer, t.channels, 1, 1, t.rows, t.bank, t.mem, t.weight});
+        as_knn.push_back(stx_nnfm_cover_target{t.layer, t.channels, 1, 1, t.rows, t.bank, t.mem, t.weight, 0.f});
     }
     return set_nnfm_banks(e, as_knn.data(), n, "stx_set_nnfm_targets");
 }
 
 int stx_set_nnfm_patch_targets(stx_engine *e, const stx_nnfm_patch_target *targets, int n) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
-    std::vector<stx_nnfm_knn_target> as_knn;
+    std::vector<stx_nnfm_cover_target> as_knn;
     for (int i = 0; i < n; ++i) {
         const stx_nnfm_patch_target &t = targets[i];
-        as_knn.push_back(stx_nnfm_knn_target{t.layer, t.channels, t.patch, 1, t.rows, t.bank, t.mem, t.weight});
+        as_knn.push_back(stx_nnfm_cover_target{t.layer, t.channels, t.patch, 1, t.rows, t.bank, t.mem, t.weight, 0.f});
     }
     return set_nnfm_banks(e, as_knn.data(), n, "stx_set_nnfm_patch_targets");
 }
 
 int stx_set_nnfm_knn_targets(stx_engine *e, const stx_nnfm_knn_target *targets, int n) {
-    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_knn_targets");
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    std::vector<stx_nnfm_cover_target> as_cover;
+    for (int i = 0; i < n; ++i) {
+        const stx_nnfm_knn_target &t = targets[i];
+        as_cover.push_back(stx_nnfm_cover_target{t.layer, t.channels, t.patch, t.k, t.rows, t.bank, t.mem, t.weight, 0.f});
+    }
+    return set_nnfm_banks(e, as_cover.data(), n, "stx_set_nnfm_knn_targets");
+}
+
+int stx_set_nnfm_cover_targets(stx_engine *e, const stx_nnfm_cover_target *targets, int n) {
+    return set_nnfm_banks(e, targets, n, "stx_set_nnfm_cover_targets");
 }
 
 }  // extern "C"

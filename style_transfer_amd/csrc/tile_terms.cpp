@@ -159,11 +159,20 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
 // search over the bank (with the slices' merge when the bank was cut), S with the partials of E and sum |S|.
 // patch 3: 1 / |P_p| and the pieces of the columns under one scale, the gathered search, c_p and S.
 // k > 1: the search keeps the k best rows of a column and S pulls towards their mean (the profile names say so).
+// cover != 0 (patch 1): behind those, the reverse search (bank rows look for their best column), the inverted index
+// and the pass that adds cover S_cov to S; sc[0] is then the sum of ONE list of partials, E_fwd's and cover E_cov's,
+// and sc[1] that of the final S's.
 int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int patch,
                       const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
-                      const std::string &name, float *scratch, std::vector<SumJob> *defer, int k) {
+                      const std::string &name, float *scratch, std::vector<SumJob> *defer, int k, float cover,
+                      int *winner_out, float *e_cov_out) {
     const int n = h * w;
-    const NnfmScratch x = nnfm_carve(scratch, C, n, rows, patch, k);
+    const bool covered = cover != 0.f;
+    if (covered && patch != 1) {
+        set_error("launch_nnfm_terms: the coverage part with patch %d", patch);
+        return STX_ERR_ARG;
+    }
+    const NnfmScratch x = nnfm_carve(scratch, C, n, rows, patch, k, covered);
     const NnfmPlan plan = nnfm_plan(n, rows);
     int *const idx = idx_out ? idx_out : x.idx;
     const std::string tag = std::string(patch == 3 ? "nnfm patch " : "nnfm ") + (k > 1 ? "k" + std::to_string(k) + " " : "");
@@ -176,8 +185,34 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
                         6.0 * n * (double)rows * C * (patch * patch), stream);
         STX_TRY(nnfm_search_launch(stream, x, h, w, patch, pieces, rows, C, idx, k));
     }
-    ProfScope scope(e, tag + "grad " + name, 0.0, stream);
     int n_parts = 0;
+    if (covered) {
+        int *const winner = winner_out ? winner_out : x.cov.winner;
+        int n_e = 0, n_abs = 0;
+        {
+            ProfScope scope(e, tag + "grad " + name, 0.0, stream);
+            STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts, k));
+        }
+        {
+            ProfScope scope(e, "nnfm cover search " + name + " x" + std::to_string(nnfm_plan(rows, n).slices),
+                            6.0 * n * (double)rows * C, stream);
+            STX_TRY(nnfm_cover_search_launch(stream, x, n, pieces, rows, C, winner));
+        }
+        {
+            ProfScope scope(e, "nnfm cover index " + name, 0.0, stream);
+            STX_TRY(nnfm_cover_index_launch(stream, feat, C, n, x, bank, rows, winner, cover));
+        }
+        {
+            ProfScope scope(e, "nnfm cover grad " + name, 0.0, stream);
+            STX_TRY(nnfm_cover_grad_launch(stream, feat, C, n, x, bank, rows, cover, sgrad, &n_e, &n_abs));
+        }
+        if (e_cov_out) STX_TRY(sum_partials_launch(stream, x.cov.e_cov_parts, ceil_div(rows, 64), e_cov_out));
+        if (!defer) return sum_partials2_launch(stream, x.cov.e_parts, n_e, sc, x.cov.abs_parts, n_abs, sc + 1);
+        defer->push_back(SumJob{x.cov.e_parts, n_e, sc});
+        defer->push_back(SumJob{x.cov.abs_parts, n_abs, sc + 1});
+        return STX_OK;
+    }
+    ProfScope scope(e, tag + "grad " + name, 0.0, stream);
     STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts, k));
     if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
     defer->push_back(SumJob{x.partials, n_parts, sc});
@@ -339,7 +374,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         }
         if (const NnfmTarget *nt = nnfm_target_of(e, tp.blob)) {
             add(TermKind::Nnfm, nt->bank->f(), nullptr, ContentWindow{}, lw * nt->weight, 2,
-                nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k), nnfm_slot);
+                nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k, nt->cover != 0.f), nnfm_slot);
             plan.terms.back().nnfm = nt;
         }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
@@ -398,7 +433,7 @@ int queue_tap_terms(TileRun &run, size_t k) {
         case TermKind::Nnfm:          // sc[0] = E, sc[1] = sum |S|
             STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.nnfm->patch, t.target,
                                       t.nnfm->pieces_hi_lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch,
-                                      run.defer(), t.nnfm->k));
+                                      run.defer(), t.nnfm->k, t.nnfm->cover));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

@@ -324,18 +324,29 @@ class TileEngine:
         self.primary.extra_taps['stat'] = list(targets)
         del keep
 
-    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1):
+    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0):
         """banks: {layer: B [rows, C]} -- unit rows, what ``nnfm_bank`` gives for a style picture's feature map
         (banks of several pictures concatenated) -- and weights: {layer: factor} (default 1 each); an empty
         dict: none.  The library copies a bank and builds its fp16 pieces once, here.  Call it after ``set_contents_and_styles``, which clears the banks.  A layer with a bank is part of
         every tile evaluation of the group from then on.  ``patch`` 3: banks of 3 x 3 patches, [rows, 9 C] as
         ``nnfm_bank(feat, stride, 3)`` gives them.  Both forms are patch targets of the library
         (stx_set_nnfm_patch_targets), the plain one with patch 1.  ``k`` 2 to 4: every vector is pulled towards
-        the mean of its k best rows (stx_set_nnfm_knn_targets); with k = 1 the calls are those without it."""
+        the mean of its k best rows (stx_set_nnfm_knn_targets); with k = 1 the calls are those without it.
+        ``cover`` above 0: that factor times the coverage part -- every bank row pulls its most similar vector
+        towards itself -- is added (stx_set_nnfm_cover_targets; patch 1 only); with 0 the calls are those
+        without it."""
         if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 4:
             raise ValueError('NNFM banks, k %r: an integer from 1 to 4 is expected' % (k,))
+        if isinstance(cover, bool) or not isinstance(cover, (int, float)) or not 0 <= cover < float('inf'):
+            raise ValueError('NNFM banks, cover %r: a finite number >= 0 is expected' % (cover,))
+        if cover != 0 and patch != 1:
+            raise ValueError('NNFM banks, cover %r with patch %r: the coverage part matches single vectors only'
+                             % (cover, patch))
         keep, n = [], len(banks)
-        table = ((lib.NnfmPatchTarget if k == 1 else lib.NnfmKnnTarget) * max(1, n))()
+        kind, call = ((lib.NnfmCoverTarget, 'stx_set_nnfm_cover_targets') if cover != 0 else
+                      (lib.NnfmPatchTarget, 'stx_set_nnfm_patch_targets') if k == 1 else
+                      (lib.NnfmKnnTarget, 'stx_set_nnfm_knn_targets'))
+        table = (kind * max(1, n))()
         for t, (layer, bank) in zip(table, banks.items()):
             ptr, mem, obj = _as_arg(bank)
             if patch == 1 and len(obj.shape) != 2:
@@ -347,9 +358,11 @@ class TileEngine:
             t.layer, t.patch, t.rows = self._cstr(layer), int(patch), int(obj.shape[0])
             t.channels, t.bank, t.mem = int(obj.shape[1]) // (t.patch * t.patch), ptr, mem
             t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
-            if k != 1:
+            if k != 1 or cover != 0:
                 t.k = k
-        lib.call('stx_set_nnfm_patch_targets' if k == 1 else 'stx_set_nnfm_knn_targets', self.handle, table, n)
+            if cover != 0:
+                t.cover = float(cover)
+        lib.call(call, self.handle, table, n)
         self.primary.extra_taps['nnfm'] = list(banks)
         del keep
 

@@ -183,8 +183,8 @@ class TileFarm:
     def set_stat_targets(self, targets, weights=None):
         self._set_on_primaries('set_stat_targets', targets, weights)
 
-    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1):
-        self._set_on_primaries('set_nnfm_targets', banks, weights, patch, k)
+    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0):
+        self._set_on_primaries('set_nnfm_targets', banks, weights, patch, k, *((cover,) if cover else ()))
 
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)

@@ -74,6 +74,12 @@ class NnfmKnnTarget(ctypes.Structure):
                 ('weight', ctypes.c_double)]
 
 
+class NnfmCoverTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('patch', ctypes.c_int),
+                ('k', ctypes.c_int), ('rows', ctypes.c_int), ('bank', ctypes.c_void_p), ('mem', ctypes.c_int),
+                ('weight', ctypes.c_double), ('cover', ctypes.c_float)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -108,6 +114,7 @@ SIGNATURES = {
     'stx_set_nnfm_targets': [_vp, ctypes.POINTER(NnfmTarget), _i],
     'stx_set_nnfm_patch_targets': [_vp, ctypes.POINTER(NnfmPatchTarget), _i],
     'stx_set_nnfm_knn_targets': [_vp, ctypes.POINTER(NnfmKnnTarget), _i],
+    'stx_set_nnfm_cover_targets': [_vp, ctypes.POINTER(NnfmCoverTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -162,6 +169,7 @@ SIGNATURES = {
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
+    'stx_op_nnfm_cover_terms': [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],
     'stx_last_tile_flops': [_vp, c_double_p, c_double_p],

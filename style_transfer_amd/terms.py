@@ -12,7 +12,7 @@ from PIL import Image
 from . import image_ops
 from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_nnfm_options,
                             check_photo_options, check_stat_options, ffloat, nnfm_bank_rows, nnfm_layer_args,
-                            nnfm_k, nnfm_patch, nnfm_stride, option_on, stat_layer_args)
+                            nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on, stat_layer_args)
 
 
 def parse_weights(args, master_weight):
@@ -104,16 +104,17 @@ class StatTargets(LayerTargets):
 
 
 class NnfmBanks(LayerTargets):
-    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k (nearest-neighbour feature matching):
+    """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k / --nnfm-cover (nearest-neighbour feature matching):
     per layer one bank of the style pictures' unit feature vectors (3 x 3 patches of them with --nnfm-patch 3), built
     on the master GPU and concatenated over the variants; ``targets`` = {layer: DeviceArray [rows, patch^2 C]}.  The
-    banks do not depend on --nnfm-k, which is read once per scale and goes with the targets."""
+    banks do not depend on --nnfm-k or --nnfm-cover, which are read once per scale and go with the targets."""
     FLAG, WEIGHT, WHAT, layer_args = '--nnfm-layers', 'nnfm_weight', 'bank', staticmethod(nnfm_layer_args)
     targets_patch = 1       # --nnfm-patch of the banks in ``targets``
 
     def read(self, st):
         super().read(st)
         self.stride, self.patch, self.k = nnfm_stride(st.args), nnfm_patch(st.args), nnfm_k(st.args)
+        self.cover = nnfm_cover(st.args)
 
     def take(self, st, layer, feat):
         # (a bank past the library's offsets is refused before this part is allocated)
@@ -126,7 +127,8 @@ class NnfmBanks(LayerTargets):
         if not quiet:
             print('NNFM bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0])
                                                  for layer, bank in self.targets.items()) +
-                  ('; patch %d' % self.patch if self.patch != 1 else '') + ('; k %d' % self.k if self.k != 1 else ''))
+                  ('; patch %d' % self.patch if self.patch != 1 else '') + ('; k %d' % self.k if self.k != 1 else '') +
+                  ('; cover %g' % self.cover if self.cover != 0 else ''))
 
     def drop(self):
         for bank in (self.targets or {}).values():
@@ -134,7 +136,10 @@ class NnfmBanks(LayerTargets):
         self.targets = None
 
     def set_targets(self, farm, targets):
-        farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k)
+        if self.cover != 0:
+            farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k, self.cover)
+        else:
+            farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k)
 
 
 class Masks(TargetTerm):

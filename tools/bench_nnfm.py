@@ -3,6 +3,7 @@
     python tools/bench_nnfm.py [--out profiles/nnfm_times.txt]
     python tools/bench_nnfm.py --patch 3 [--out profiles/nnfm_patch_times.txt]
     python tools/bench_nnfm.py --k 1 2 4 [--out profiles/nnfm_knn_times.txt]
+    python tools/bench_nnfm.py --cover [--out profiles/nnfm_cover_times.txt]
 
 stx_op_nnfm_terms at the blob shapes of a 1024^2 tile -- conv3_1 (256 x 256^2) and conv4_1 (512 x 128^2) --
 against the banks of a 512^2 and of a 1024^2 style picture at --nnfm-stride 1 and 2, and at the shapes of a
@@ -23,6 +24,15 @@ a materialised [n][9 C] query array would cost the search (`plain 9C`, with the 
 --k 1 2 4: the k-nearest term (--nnfm-k, stx_op_nnfm_knn_terms) at the same shapes, one row per K, every K in the
 same run as K = 1 (which is the call of the table without --k): `search x` and `grad x` are the group's time over
 that of the K = 1 row above it.
+
+--cover: the coverage part (--nnfm-cover, stx_op_nnfm_cover_terms with factor 1, K = 1) at the same shapes.  Beside
+the forward search and gradient of the same call: `rsearch` (the reverse search: the same kernel with the operands
+exchanged, the same 6 n M C flop, under nnfm_plan(M, n) -- `rslices`), `index` (c'_j with the row counts, the
+prefix sums, the cursor fill and the pass that puts every list in order) and `cgrad` (the pass that adds the
+lists' rows to S), each with its ratio to the forward group it stands beside (index and cgrad: to the forward
+gradient).  Two rows per shape: random unit rows, whose winners spread over the columns (`longest` = the longest
+list), and `one list` -- every bank row a noisy copy of column 0's direction, so that ONE column owns all M rows:
+the worst case of the index's ordering pass and of the gradient's walk (fewer repetitions).
 """
 
 import argparse
@@ -86,6 +96,69 @@ def measure(eng, rng, c, side, rows, reps, patch=1, k=1):
     return {k: float(np.median(v)) for k, v in times.items()}, slices
 
 
+def measure_cover(eng, rng, c, side, rows, reps, one_list):
+    """Median ms of the six groups of a call with a coverage part, the two slice counts and the longest list."""
+    f = np.maximum(rng.standard_normal((c, side, side)), 0).astype(np.float32) + np.float32(1e-3)
+    b = unit_rows(rng, rows, c)
+    if one_list:        # every row leans towards column 0, far more than towards any other column
+        d = unit_rows(rng, 1, c)[0]
+        f[:, 0, 0] = 5 * d
+        b = d[None, :] + np.float32(0.3) * b
+        b /= np.linalg.norm(b, axis=1, keepdims=True)
+    feat, bank = eng.to_device(f), eng.to_device(b.astype(np.float32))
+    s_out = eng.empty((c, side, side))
+    idx, win = eng.empty((side * side,), np.int32), eng.empty((rows,), np.int32)
+    out = (ctypes.c_double * 3)()
+    call = lambda: lib.call('stx_op_nnfm_cover_terms', eng.handle, feat.ptr, c, side, side, 1, 1, 1.0, bank.ptr, rows,
+                            s_out.ptr, idx.ptr, win.ptr, out)
+    for _ in range(2):
+        call()
+    names = {'nnfm prepare': 'prepare', 'nnfm search': 'search', 'nnfm grad': 'grad', 'nnfm cover search': 'rsearch',
+             'nnfm cover index': 'index', 'nnfm cover grad': 'cgrad'}
+    times = {name: [] for name in names.values()}
+    slices = {}
+    eng.profile(True)
+    for _ in range(reps):
+        call()
+        for label, ms, _ in eng.profile_read():
+            words = label.split()
+            head = ' '.join(words[:3 if words[1] == 'cover' else 2])
+            if head in names:
+                times[names[head]].append(ms)
+                if names[head].endswith('search'):
+                    slices[names[head]] = int(words[-1][1:])
+    eng.profile(False)
+    longest = int(np.bincount(win.get(), minlength=side * side).max())
+    for buf in (feat, bank, s_out, idx, win):
+        buf.free()
+    return {k: float(np.median(v)) for k, v in times.items()}, slices, longest
+
+
+def cover_lines(eng, rng, opts):
+    lines = ['# --nnfm-cover: stx_op_nnfm_cover_terms (cover 1, K = 1), device-event ms per group (median of %d, `one '
+             'list` rows of %d, after 2 warm-up calls)' % (opts.reps, min(opts.reps, 5)),
+             '# device: %s' % torch.cuda.get_device_name(0),
+             '# rsearch x = rsearch / search; index x, cgrad x = the group over the forward grad; all of one call',
+             '%6s %8s %4s %7s %7s %6s %6s %7s %8s %8s %9s %9s %9s %9s %9s %9s %9s %8s %7s  %s'
+             % ('tile', 'blob', 'C', 'n', 'M', 'stride', 'slices', 'rslices', 'longest', 'prepare', 'search', 'grad', 'rsearch',
+                'index', 'cgrad', 'rsearch x', 'index x', 'cgrad x', 'added', 'bank')]
+    for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
+        for blob, c, side, style_side in shapes:
+            for stride in (1, 2):
+                rows = (-(-style_side // stride)) ** 2
+                for one_list in (False, True):
+                    t, slices, longest = measure_cover(eng, rng, c, side, rows, min(opts.reps, 5) if one_list else opts.reps,
+                                                       one_list)
+                    added = t['rsearch'] + t['index'] + t['cgrad']
+                    line = ('%6d %8s %4d %7d %7d %6d %6d %7d %8d %8.4f %9.4f %9.4f %9.4f %9.4f %9.4f %9.3f %9.3f %8.3f %7.4f  %s'
+                            % (tile, blob, c, side * side, rows, stride, slices['search'], slices['rsearch'], longest, t['prepare'],
+                               t['search'], t['grad'], t['rsearch'], t['index'], t['cgrad'], t['rsearch'] / t['search'],
+                               t['index'] / t['grad'], t['cgrad'] / t['grad'], added, 'one list' if one_list else 'random'))
+                    lines.append(line)
+                    print(line, flush=True)
+    return lines
+
+
 def table_lines(eng, rng, opts):
     """The table of one mode: the plain columns, and for --patch 3 the plain search at 9 C and the ratio to it."""
     p3 = opts.patch == 3
@@ -134,14 +207,19 @@ def main():
     ap.add_argument('--patch', type=int, default=1, choices=(1, 3))
     ap.add_argument('--k', type=int, nargs='+', default=[1], choices=(1, 2, 3, 4),
                     help='rows per query, K = 1 first: every K is set beside the K = 1 of the same run')
+    ap.add_argument('--cover', action='store_true',
+                    help='the coverage part (--nnfm-cover): reverse search, index and gradient beside the forward groups')
     opts = ap.parse_args()
+    if opts.cover and (opts.patch != 1 or opts.k != [1]):
+        ap.error('--cover: the table is that of patch 1 and K = 1')
     if opts.k[0] != 1:
         ap.error('--k: the list begins with 1, the row the others are set beside')
     if not torch.cuda.is_available():
         sys.exit('bench_nnfm: no GPU')
     net = builtin_net('vgg19')
     eng = TileEngine(net, 0, synthetic_weights(net, 0))
-    text = '\n'.join(table_lines(eng, np.random.RandomState(0), opts)) + '\n'
+    lines = (cover_lines if opts.cover else table_lines)(eng, np.random.RandomState(0), opts)
+    text = '\n'.join(lines) + '\n'
     if opts.out:
         os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
         with open(opts.out, 'w') as f:
