@@ -118,9 +118,15 @@ typedef enum stx_query {
     STX_Q_TARGET_BYTES = 2,    /* bytes those calls copied, cumulative */
     STX_Q_WEIGHT_BYTES = 3,    /* device bytes of weights + packed banks held by this group */
     STX_Q_TILE_EVALS = 4,      /* stx_sc_grad_tile calls enqueued by this engine */
-    STX_Q_PEERS_WITHOUT_ACCESS = 5  /* GPUs of the node this engine's GPU has no direct (xGMI peer)
+    STX_Q_PEERS_WITHOUT_ACCESS = 5, /* GPUs of the node this engine's GPU has no direct (xGMI peer)
                                      * access to: copies to / from them are staged by the runtime
                                      * (reported once on stderr) */
+    STX_Q_TILE_IO_DIRECT = 6,  /* ends of this engine's stx_sc_grad_tile calls (the tile in, the gradient out:
+                                * up to two per call) that worked on the caller's buffers without a copy */
+    STX_Q_INJECT_SPECIALISED = 7,   /* backward convolutions this engine launched with a specialised body of
+                                     * the loss-injecting epilogue */
+    STX_Q_INJECT_VARIANTS = 8  /* ... and which: bit v is set once body v has run (v = 1 style term | 2 content
+                                * term, + 4 masked by ReLU nibbles | 8 by the fp32 blob) */
 } stx_query;
 int stx_engine_query(stx_engine *e, int what, double *value);
 int stx_engine_device(stx_engine *e, int *device);
@@ -388,6 +394,10 @@ typedef struct stx_tap {
  *   start_yx   tile origin in the rolled image (y, x) (style_transfer.py:571-573);
  *   loss_out   host double; written by the next stx_sync() (or immediately if sync_now != 0);
  *   grad_out   [3][th][tw], the reference's diff['data'].
+ * img is read and grad_out written in stream order on the engine's stream, where they are if they are
+ * distinct STX_DEVICE buffers of the engine's own GPU that the first and the last kernel of the graph can
+ * work on, through a copy otherwise; img is never written.  Both stay allocated until the
+ * call has run.
  */
 int stx_sc_grad_tile(stx_engine *e, const float *img, int img_mem, int th, int tw,
                      const int roll_xy[2], const int start_yx[2], const stx_tap *taps, int n_taps,

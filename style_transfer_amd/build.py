@@ -22,7 +22,8 @@ SOURCES = {
     'conv_mfma.hip': [],
     'conv_wino2.hip': [],
     'conv_first.hip': [],
-    'conv_h2.hip': [],
+    'conv_h2.hip': ['-DSTX_H2_SPLIT_UNITS'],    # (its specialised bodies: conv_h2_inject.hip)
+    'conv_h2_inject.hip': [],   # (includes conv_h2.hip: the injecting epilogue's specialised bodies, compiled beside it)
     'gram.hip': [],
     'symm.hip': [],
     'pool.hip': [],
@@ -61,6 +62,8 @@ def _compile(src, extra, force):
     path = os.path.join(CSRC, src)
     deps = [path, os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'bf16x3.h'),
             os.path.join(CSRC, 'f16x2.h'), os.path.join(CSRC, 'engine.h'), os.path.join(INCLUDE, 'stx.h')]
+    if src == 'conv_h2_inject.hip':
+        deps.append(os.path.join(CSRC, 'conv_h2.hip'))
     if force or _stale(obj, deps):
         cmd = [HIPCC] + COMMON + extra + ['-c', path, '-o', obj]
         proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -193,6 +193,9 @@ struct ConvProblem {
     const unsigned char *pin_codes = nullptr;
     int pin_mode = 0;            // STX_POOL_MAX / STX_POOL_AVE
     bool pin_mask = false;       // the blob under the pooling layer is rectified (the codes carry its signs)
+    // conv_h2.hip (optional): receives the specialised body of the injecting epilogue that the launch took
+    // (h2_variant's code), or 0 -- written by h2_launch where it picks the kernel
+    int *variant_out = nullptr;
 #ifdef STX_EXPERIMENT_BF3
     const void *x_split = nullptr;   // tools/experiments/conv_bf3.hip only
 #endif
@@ -313,6 +316,10 @@ bool h2_usable(const ConvProblem &p);       // what the kernel takes (shape, epi
 size_t h2_packed_floats(int K, int M);
 int h2_pack_weights(hipStream_t s, const float *w_caffe, int Mo, int Ko, int transpose_flip, float *packed);
 int h2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ksplit);
+// The injecting epilogue's specialised bodies (conv_h2_inject.hip): what a launch injects | where its mask comes from
+enum { kH2Style = 1, kH2Content = 2, kH2MaskNibbles = 4, kH2MaskBlob = 8 };
+int h2_variant(const ConvProblem &p, int pin, bool split);      // the body a launch takes, or 0: the generic one
+int h2_launch_variant(hipStream_t s, const WinoArgs &a, int n_wg, int cfg_id, int pin, int var);
 int h2_splitk_factor(const ConvConfig &cfg, const ConvProblem &p);
 bool h2_fuses_pool(const ConvProblem &p);
 bool h2_takes_pooled_input(const ConvConfig &cfg, const ConvProblem &p);   // ConvProblem::pin_codes

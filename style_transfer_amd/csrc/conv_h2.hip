@@ -125,8 +125,20 @@ __device__ long long g_h2_epi[8][8];     // epilogue, pass 0: loads issued, firs
 // window codes (ConvProblem::pin_codes); the staging rebuilds the four inputs of an x-tile from three
 // pooled gradients and three code bytes, the arithmetic of pool_bwd_codes_kernel (pool.hip) to the bit.
 // (PIN = 1 + the pooling mode: STX_POOL_MAX / STX_POOL_AVE)
-template <int EPI, int MB, int PB, int PIN>
+// VAR (EPI = kEpiDgradInject alone): what the launch injects and where its ReLU mask comes from, as compile-time
+// facts -- h2_variant's code, (1 style term | 2 content term) + 4 x (1 nibbles | 2 the fp32 blob).  0: the
+// generic body, which asks the arguments.  A launch uses one injection form and one mask form; the generic body
+// carries the state of all of them (descriptors, sg[16] / mk[16] / mkb[8], the content window) across the chunk
+// loop's 232 .. 243 registers and was the only convolution body that spilled.  The arithmetic is the generic body's.
+template <int EPI, int MB, int PB, int PIN, int VAR = 0>
 __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
+    static_assert(VAR == 0 || EPI == kEpiDgradInject, "variants are of the injecting epilogue");
+    static_assert(VAR == 0 || (((VAR & 3) == 1 || (VAR & 3) == 2) && ((VAR >> 2) == 1 || (VAR >> 2) == 2)), "h2_variant's codes");
+    // (constants where VAR says so: the branches on them fold, and what only the other forms need is dead)
+    const bool inj_style = VAR ? (VAR & 1) != 0 : a.inj.sgrad != nullptr;
+    const bool inj_content = VAR ? (VAR & 2) != 0 : a.inj.content != nullptr;
+    const bool mask_nibbles = VAR ? (VAR >> 2) == 1 : a.mask_codes != nullptr;
+    const bool mask_blob = VAR ? (VAR >> 2) == 2 : !a.mask_codes && a.mask;
     using G = Geo<PB>;
     [[maybe_unused]] constexpr int PR = G::PR, RT = G::RT, V_PIECE = G::V_PIECE, V_BYTES = G::V_BYTES, NU = G::NU, FULL = G::FULL;
     constexpr size_t kLdsBytes = G::kLds;
@@ -481,8 +493,8 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
     float s_scale = 0.f, c_scale = 0.f;
     if (EPI == kEpiDgradInject) {
         const float n = (float)((size_t)a.M * HW);
-        if (a.inj.sgrad) s_scale = a.inj.s_coef * (1.0f / (a.inj.s_abs_sum[0] / n + kEps));
-        if (a.inj.content) c_scale = a.inj.c_coef * (1.0f / (a.inj.c_sums[1] / n + kEps));
+        if (inj_style) s_scale = a.inj.s_coef * (1.0f / (a.inj.s_abs_sum[0] / n + kEps));
+        if (inj_content) c_scale = a.inj.c_coef * (1.0f / (a.inj.c_sums[1] / n + kEps));
     }
     const int hh = wave & 1, mrow = (wave >> 1) & 1, rqp = wave >> 2;
     const bool weven = (a.W & 1) == 0;
@@ -563,7 +575,7 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
     };
     int ccol[2] = {0, 0};
     auto content_columns = [&](const LaneRows &lr) __attribute__((always_inline)) {
-        if (EPI == kEpiDgradInject && content) {
+        if (EPI == kEpiDgradInject && inj_content) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const bool ok = lr.yy < a.H && xx0 < a.W;
@@ -710,7 +722,7 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
         const LaneRows lr = pbi == 0 && HOIST ? rows0 : lane_rows(pbi);
         if (!HOIST && pass == 0) content_columns(lr);
         int crow[2] = {0, 0};                                  // common.h: content_index, once per lane and pass
-        if (EPI == kEpiDgradInject && content) {
+        if (EPI == kEpiDgradInject && inj_content) {
 #pragma unroll
             for (int y = 0; y < 2; ++y) {
                 const bool ok = lr.yy + y < a.H && xx0 < a.W;
@@ -735,11 +747,11 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
                                                                rbias, (unsigned)half * 16u, (unsigned)c * 4u, 0))
                                : 0.f;
             } else if (EPI != kEpiPartial) {
-                if (a.mask_codes) mkb[n] = __builtin_amdgcn_raw_buffer_load_b8(rmc, lr.vmc, (unsigned)(c * cph * cpw), 0);
+                if (mask_nibbles) mkb[n] = __builtin_amdgcn_raw_buffer_load_b8(rmc, lr.vmc, (unsigned)(c * cph * cpw), 0);
 #pragma unroll
                 for (int y = 0; y < 2; ++y) {
-                    if (!a.mask_codes && a.mask && !(STX_H2_SKIP & 16)) mk[2 * n + y] = ld2(rmask, lr, y, so, even_c);
-                    if (EPI == kEpiDgradInject && a.inj.sgrad) sg[2 * n + y] = ld2(rsg, lr, y, so, even_c);
+                    if (mask_blob && !(STX_H2_SKIP & 16)) mk[2 * n + y] = ld2(rmask, lr, y, so, even_c);
+                    if (EPI == kEpiDgradInject && inj_style) sg[2 * n + y] = ld2(rsg, lr, y, so, even_c);
                 }
             }
         }
@@ -787,16 +799,16 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
                 } else if (EPI != kEpiPartial) {
 #pragma unroll
                     for (int y = 0; y < 2; ++y) {
-                        if (a.mask_codes) {
+                        if (mask_nibbles) {
                             const unsigned nib = mkb[n] >> (2 * y);
                             v[y].x = (nib & 1u) ? v[y].x : 0.f;
                             v[y].y = (nib & 2u) ? v[y].y : 0.f;
-                        } else if (a.mask && !(STX_H2_SKIP & 16)) {
+                        } else if (mask_blob && !(STX_H2_SKIP & 16)) {
                             v[y].x = mk[2 * n + y].x > 0.f ? v[y].x : 0.f;
                             v[y].y = mk[2 * n + y].y > 0.f ? v[y].y : 0.f;
                         }
                         if (EPI == kEpiDgradInject) {
-                            if (content) {
+                            if (inj_content) {
                                 // (one layer per tile evaluation takes this: read where it is used)
                                 const f32x2 ft = ld2(rft, lr, y, so, even_c);
                                 const int mm = c + 4 * half;
@@ -805,7 +817,7 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
                                 v[y].x += c_scale * (ft.x - cp[ccol[0]]);
                                 v[y].y += c_scale * (ft.y - cp[ccol[1]]);
                             }
-                            if (a.inj.sgrad) {
+                            if (inj_style) {
                                 v[y].x += s_scale * sg[2 * n + y].x;
                                 v[y].y += s_scale * sg[2 * n + y].y;
                             }
@@ -886,6 +898,53 @@ __global__ __launch_bounds__(NT) void conv_h2_kernel(WinoArgs a) {
     }
 #endif
 }
+
+template <int EPI, int MB, int PB, int PIN = 0, int VAR = 0>
+static int h2_launch_epi(hipStream_t s, const WinoArgs &args, int n_wg) {
+    auto kern = conv_h2_kernel<EPI, MB, PB, PIN, VAR>;
+    constexpr size_t kLdsBytes = Geo<PB>::kLds;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    if (e != hipSuccess) {
+        set_error("hipFuncSetAttribute(lds=%zu): %s", kLdsBytes, hipGetErrorString(e));
+        return STX_ERR_HIP;
+    }
+    kern<<<n_wg, NT, kLdsBytes, s>>>(args);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+// The specialised bodies of the injecting epilogue.  The library builds them in a translation unit of their own,
+// compiled beside this one (the kernel takes six seconds per instantiation): build.py compiles this file with
+// -DSTX_H2_SPLIT_UNITS, which leaves them out here, and conv_h2_inject.hip, which is this file up to and including
+// them (STX_H2_VARIANTS_ONLY).  A program that includes this file as it stands (tools/ubench/h2conv_bench.hip) gets
+// everything in one unit.
+#if defined(STX_H2_VARIANTS_ONLY) || !(defined(STX_H2_SPLIT_UNITS) || defined(STX_H2_DEV_SUBSET))
+//
+// What the tile path launches per tiling: a style term or a content term (never both but on a layer that is both
+// kinds of tap) onto a rectified blob, masked by its nibbles or by the fp32 blob; a style term also under a pooling
+// layer whose backward pass rides along (PIN).  Both terms at once, an un-rectified blob, a content term with a
+// pooled input: the generic body.
+int h2_launch_variant(hipStream_t s, const WinoArgs &a, int n_wg, int cfg_id, int pin, int var) {
+#define STX_H2_VAR(V, P)                                                                                      \
+    if (var == (V) && pin == (P))                                                                             \
+        return cfg_id == 1   ? h2_launch_epi<kEpiDgradInject, 2, 1, P, V>(s, a, n_wg)                         \
+               : cfg_id == 2 ? h2_launch_epi<kEpiDgradInject, 1, 2, P, V>(s, a, n_wg)                         \
+                             : h2_launch_epi<kEpiDgradInject, 1, 1, P, V>(s, a, n_wg);
+    STX_H2_VAR(kH2Style | kH2MaskNibbles, 0)
+    STX_H2_VAR(kH2Style | kH2MaskBlob, 0)
+    STX_H2_VAR(kH2Content | kH2MaskNibbles, 0)
+    STX_H2_VAR(kH2Content | kH2MaskBlob, 0)
+    STX_H2_VAR(kH2Style | kH2MaskNibbles, 1 + STX_POOL_MAX)
+    STX_H2_VAR(kH2Style | kH2MaskBlob, 1 + STX_POOL_MAX)
+    STX_H2_VAR(kH2Style | kH2MaskNibbles, 1 + STX_POOL_AVE)
+    STX_H2_VAR(kH2Style | kH2MaskBlob, 1 + STX_POOL_AVE)
+#undef STX_H2_VAR
+    set_error("h2_launch_variant: no specialised body %d for a pooled input of kind %d", var, pin);
+    return STX_ERR_UNSUPPORTED;
+}
+#endif
+#ifndef STX_H2_VARIANTS_ONLY
 
 // ------------------------------------------------------------------------------------------------
 // max |x| of an array into kAmaxSlots words of float bits (zeroed here first): what conv_h2_kernel needs
@@ -1091,28 +1150,32 @@ bool h2_fuses_pool(const ConvProblem &p) {
     return p.pool_out && p.epilogue == kEpiForward && (((size_t)p.y | (size_t)p.pool_out) & 7) == 0;
 }
 
-template <int EPI, int MB, int PB, int PIN = 0>
-static int h2_launch_epi(hipStream_t s, const WinoArgs &args, int n_wg) {
-    auto kern = conv_h2_kernel<EPI, MB, PB, PIN>;
-    constexpr size_t kLdsBytes = Geo<PB>::kLds;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-    if (e != hipSuccess) {
-        set_error("hipFuncSetAttribute(lds=%zu): %s", kLdsBytes, hipGetErrorString(e));
-        return STX_ERR_HIP;
-    }
-    kern<<<n_wg, NT, kLdsBytes, s>>>(args);
-    STX_CHECK_LAUNCH();
-    return STX_OK;
-}
-
 #ifdef STX_H2_DEV_SUBSET   // (register / ISA studies: tools/h2_regs.sh, tools/spill_map.py -- a few variants, in seconds)
 template __global__ void conv_h2_kernel<0, 2, 1, 0>(WinoArgs);
 template __global__ void conv_h2_kernel<0, 1, 2, 0>(WinoArgs);
 template __global__ void conv_h2_kernel<1, 2, 1, 0>(WinoArgs);
 template __global__ void conv_h2_kernel<3, 2, 1, 0>(WinoArgs);
 template __global__ void conv_h2_kernel<3, 1, 2, 1>(WinoArgs);
+// (the specialised bodies a VGG tile launches: style / nibbles, content / nibbles, style / fp32 blob with a pooled input)
+template __global__ void conv_h2_kernel<3, 2, 1, 0, kH2Style | kH2MaskNibbles>(WinoArgs);
+template __global__ void conv_h2_kernel<3, 2, 1, 0, kH2Content | kH2MaskNibbles>(WinoArgs);
+template __global__ void conv_h2_kernel<3, 1, 2, 1, kH2Style | kH2MaskBlob>(WinoArgs);
+template __global__ void conv_h2_kernel<3, 2, 1, 1, kH2Style | kH2MaskNibbles>(WinoArgs);
 #else
+// The specialised body of the injecting epilogue that a launch takes (conv_h2_kernel's VAR; h2_launch_variant has
+// them), or 0: the generic body, or no injection at all.  `pin`: 0 or 1 + the pooling mode of a pooled input.
+// STX_H2_INJECT_GENERIC=1: always the generic body (A/B measurements, and the tests' cross-check).
+int h2_variant(const ConvProblem &p, int pin, bool split) {
+    if (split || p.epilogue != kEpiDgrad) return 0;
+    const bool style = p.inject.sgrad != nullptr, content = p.inject.content != nullptr;
+    if (style == content) return 0;                  // nothing to inject; or both terms: the generic body
+    if (!p.mask_codes && !p.mask) return 0;          // an un-rectified blob
+    if (content && pin) return 0;
+    const char *env = sw_env("STX_H2_INJECT_GENERIC");
+    if (env && atoi(env) != 0) return 0;
+    return (style ? kH2Style : kH2Content) | (p.mask_codes ? kH2MaskNibbles : kH2MaskBlob);
+}
+
 int h2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ksplit) {
     if (!h2_usable(p) || !p.x_amax) {
         set_error("h2_launch: unsupported problem (K %d, epilogue %d, input maximum %s)", p.K, p.epilogue,
@@ -1174,6 +1237,10 @@ int h2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ks
         a.skip_y = p.skip_y && p.pool_codes != nullptr;
     }
     const int epi = split ? kEpiPartial : inject ? kEpiDgradInject : p.epilogue;
+    const int pin_kind = pin ? 1 + p.pin_mode : 0;
+    const int var = h2_variant(p, pin_kind, split);
+    if (p.variant_out) *p.variant_out = var;
+    if (var) return h2_launch_variant(s, a, n_wg, cfg.id, pin_kind, var);
 #define STX_H2_CASE(E)                                                                   \
     case E:                                                                              \
         STX_TRY(cfg.id == 1   ? (h2_launch_epi<E, 2, 1>(s, a, n_wg))                   \
@@ -1214,5 +1281,6 @@ int h2_launch(hipStream_t s, const ConvConfig &cfg, const ConvProblem &p, int ks
     return split ? splitk_reduce_launch(s, p, ksplit) : STX_OK;
 }
 #endif
+#endif      // !STX_H2_VARIANTS_ONLY
 
 }  // namespace stx

@@ -556,6 +556,9 @@ int stx_engine_query(stx_engine *e, int what, double *value) {
         }
         case STX_Q_TILE_EVALS: *value = (double)e->n_tile_evals; break;
         case STX_Q_PEERS_WITHOUT_ACCESS: *value = (double)peers_without_access(e->device); break;
+        case STX_Q_TILE_IO_DIRECT: *value = (double)e->n_tile_io_direct; break;
+        case STX_Q_INJECT_SPECIALISED: *value = (double)e->n_inject_specialised; break;
+        case STX_Q_INJECT_VARIANTS: *value = (double)e->inject_variants; break;
         default:
             set_error("stx_engine_query: unknown item %d", what);
             return STX_ERR_ARG;

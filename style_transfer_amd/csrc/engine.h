@@ -232,6 +232,9 @@ struct stx_engine {
     ScalarArena &A() { return arena[cur]; }
     size_t scalars_cap = 0;
     size_t n_tile_evals = 0;               // stx_sc_grad_tile calls (STX_Q_TILE_EVALS)
+    size_t n_tile_io_direct = 0;           // ... and their ends that needed no copy (STX_Q_TILE_IO_DIRECT)
+    size_t n_inject_specialised = 0;       // launches of conv_h2's specialised injecting bodies (STX_Q_INJECT_SPECIALISED)
+    unsigned inject_variants = 0;          // ... and which: bit h2_variant (STX_Q_INJECT_VARIANTS)
     std::vector<hipEvent_t> fence_events;     // stx_engine_wait: ring of events recorded on this stream
     size_t fence_next = 0;
     size_t dscalars_cap = 64;

@@ -134,8 +134,15 @@ int launch_conv(stx_engine *e, const ConvConfig &cfg, const ConvProblem &problem
         e->last_mark = e->marks_used++;
         p.clock_out = static_cast<long long *>(e->marks_buf.ptr) + 2 * (size_t)e->last_mark;
     }
+    int var = 0;     // the specialised injecting body the launch took, as h2_launch itself reports it
+    p.variant_out = &var;
     // (bookkeeping for stx_last_tile_flops)
-    return conv_dispatch(e->stream, cfg, p, &e->flop_algorithmic, &e->flop_issued);
+    const int rc = conv_dispatch(e->stream, cfg, p, &e->flop_algorithmic, &e->flop_issued);
+    if (var) {
+        ++e->n_inject_specialised;
+        e->inject_variants |= 1u << var;
+    }
+    return rc;
 }
 
 // The slots with max |x| of a blob's data / diff for a kernel that is about to read it: what its
@@ -669,6 +676,85 @@ static int sc_grad_run(stx_engine *e, const TilePlan &plan, PendingLoss &pl) {
     return STX_OK;
 }
 
+// Is [p, p + bytes) device memory of the engine's own GPU, float-aligned?  (Host memory, managed memory and another
+// GPU's memory keep the copies: hipMemcpyDefault finds its way to them, a kernel of this GPU need not.)
+static bool local_device_floats(const stx_engine *e, const void *p, int mem) {
+    if (mem == STX_HOST || (reinterpret_cast<uintptr_t>(p) & 3) != 0) return false;
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();     // (a pointer the runtime does not know: not an error of this call)
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice && attr.device == e->device;
+}
+
+static bool ranges_overlap(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bytes && y < x + bytes;
+}
+
+// Which ends of a tile evaluation can work on the caller's own buffers, with the input blob's data / diff as
+// non-owning views of them while the call is queued (TileIoView) -- the kernels whose reads of the blob's data
+// and whose writes of its diff have been checked against a caller's allocation, which ends with the tile
+// (DevBuf rounds up to 256 bytes) and is float-aligned, not 256-byte aligned:
+//   data  read by the first-layer kernel alone (conv_first.hip: dword buffer loads inside K H W floats; nobody asks
+//         for the blob's maximum, no pooling layer reads it, no convolution fuses a pooling layer over it);
+//   diff  written by the backward-into-image kernel alone (conv3x3_m4_kernel: one dword store per element of
+//         [M][H][W], every element; its vector loads are of the OTHER blob's gradient).
+// Every other graph keeps the copy at that end.  The input blob carries no loss term (sc_grad_prepare refuses a
+// tap on it), so nothing else reads its data or adds to its diff.
+static void tile_io_direct(stx_engine *e, const TileCall &c, const TilePlan &plan, bool *in_direct, bool *out_direct) {
+    const int data_blob = e->layers[0].top_blob;
+    const Blob &in = e->blobs[data_blob];
+    const size_t bytes = in.count() * sizeof(float);
+    *in_direct = *out_direct = false;
+    if (const char *env = sw_env("STX_TILE_IO_DIRECT"))
+        if (atoi(env) == 0) return;
+    if (plan.tap_of[data_blob] >= 0 || in.relu) return;
+    // (distinct buffers, and neither of them one of the blob's own: the engine's buffers keep today's path)
+    if (ranges_overlap(c.img, c.grad_out, bytes) || ranges_overlap(c.img, in.data.ptr, in.data.bytes) ||
+        ranges_overlap(c.img, in.diff.ptr, in.diff.bytes) || ranges_overlap(c.grad_out, in.data.ptr, in.data.bytes) ||
+        ranges_overlap(c.grad_out, in.diff.ptr, in.diff.bytes))
+        return;
+    std::vector<char> observed(e->blobs.size(), 0);
+    for (const Tap &tp : plan.order) observed[tp.blob] = 1;
+    int readers = 0;
+    bool first_only = true, small_only = true;
+    for (size_t li = 1; li < e->layers.size(); ++li) {
+        const Layer &L = e->layers[li];
+        if (L.type == STX_LAYER_RELU || L.bottom_blob != data_blob || !plan.needed[L.top_blob]) continue;
+        ++readers;
+        if (L.type != STX_LAYER_CONV) {
+            first_only = small_only = false;
+            continue;
+        }
+        const ConvParams &cp = e->sh->conv[li];
+        first_only &= conv_first_usable(cp.cin, cp.cout, cp.ks) &&
+                      !plan_fwd_conv(e, li, plan.needed, plan.order[0].blob, true, observed).pool;
+        small_only &= cp.ks == 3 && cp.cin <= 4;      // (run_conv_backward: conv_small_launch)
+    }
+    if (readers != 1) return;
+    *in_direct = first_only && local_device_floats(e, c.img, c.img_mem);
+    *out_direct = small_only && local_device_floats(e, c.grad_out, c.grad_mem);
+}
+
+// The input blob's data / diff pointed at the caller's buffers for as long as this object lives; the blob's own
+// buffers come back when it goes, on the error paths too.  Launches capture pointers when they are queued.
+struct TileIoView {
+    Blob &in;
+    void *const data, *const diff;
+    TileIoView(Blob &blob, const void *img, void *grad) : in(blob), data(blob.data.ptr), diff(blob.diff.ptr) {
+        if (img) in.data.ptr = const_cast<void *>(img);      // (read only: tile_io_direct)
+        if (grad) in.diff.ptr = grad;
+    }
+    ~TileIoView() {
+        in.data.ptr = data;
+        in.diff.ptr = diff;
+    }
+    TileIoView(const TileIoView &) = delete;
+    TileIoView &operator=(const TileIoView &) = delete;
+};
+
 static int sc_grad_eager(stx_engine *e, const TileCall &c, double *loss_out) {
     TilePlan plan;
     STX_TRY(sc_grad_prepare(e, c, plan));
@@ -680,15 +766,23 @@ static int sc_grad_eager(stx_engine *e, const TileCall &c, double *loss_out) {
         return STX_ERR_NOMEM;
     }
     Blob &in = e->blobs[e->layers[0].top_blob];
-    // (a tile handed over in the engine's own buffers, stx_tile_buffers, needs no copies)
-    if (c.img != in.data.ptr) STX_TRY(copy_in(e, in.data.ptr, c.img, c.img_mem, in.count() * sizeof(float)));
+    // (a tile handed over in the engine's own buffers, stx_tile_buffers, needs no copies; nor does one in device
+    // buffers of the caller's that the first and the last kernel can work on where they are)
+    bool in_direct, out_direct;
+    tile_io_direct(e, c, plan, &in_direct, &out_direct);
+    if (c.img != in.data.ptr && !in_direct)
+        STX_TRY(copy_in(e, in.data.ptr, c.img, c.img_mem, in.count() * sizeof(float)));
     PendingLoss pl;
     pl.out = loss_out;
-    STX_TRY(sc_grad_run(e, plan, pl));
-    if (c.grad_out != in.diff.ptr)
+    {
+        const TileIoView view(in, in_direct ? c.img : nullptr, out_direct ? c.grad_out : nullptr);
+        STX_TRY(sc_grad_run(e, plan, pl));
+    }
+    if (c.grad_out != in.diff.ptr && !out_direct)
         STX_TRY(copy_out(e, c.grad_out, c.grad_mem, in.diff.ptr, in.count() * sizeof(float)));
     e->A().pending.push_back(std::move(pl));
     ++e->n_tile_evals;
+    e->n_tile_io_direct += (in_direct ? 1 : 0) + (out_direct ? 1 : 0);
     return STX_OK;
 }
 

@@ -14,7 +14,7 @@ HOST, DEVICE = 0, 1
 LAYER_INPUT, LAYER_CONV, LAYER_RELU, LAYER_POOL = 0, 1, 2, 3
 POOL_MAX, POOL_AVE = 0, 1
 (Q_SHARED_ENGINES, Q_TARGET_UPLOADS, Q_TARGET_BYTES, Q_WEIGHT_BYTES, Q_TILE_EVALS,
- Q_PEERS_WITHOUT_ACCESS) = range(6)
+ Q_PEERS_WITHOUT_ACCESS, Q_TILE_IO_DIRECT, Q_INJECT_SPECIALISED, Q_INJECT_VARIANTS) = range(9)
 
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_double_p = ctypes.POINTER(ctypes.c_double)
