@@ -363,6 +363,50 @@ typedef struct stx_nnfm_cover_target {
  * whole set. */
 int stx_set_nnfm_cover_targets(stx_engine *e, const stx_nnfm_cover_target *targets, int n);
 
+/* The sliced Wasserstein term (not in the reference): the loss of Heitz et al., "A Sliced Wasserstein Loss for
+ * Neural Texture Synthesis" (CVPR 2021).  It holds the WHOLE distribution of a layer's feature vectors, not its
+ * second moments (the Gram and statistics terms) and not single vectors (NNFM).  A tapped blob F [C][h][w] -- the
+ * array the Gram term reads -- has n = h w columns f_i.  The caller gives D unit directions V [D][C] (float32) and
+ * a target Tq [D][Q] (float32): per direction a non-decreasing quantile function, sampled at u_q = (q + 1/2) / Q.
+ *   p[d][i]  = v_d . f_i                         (float32 accumulation; -0 counts as +0)
+ *   r_d(i)   = rank of i when p[d][.] is ordered ascending, equal values by ascending i  (a strict total order)
+ *   t[d][r]  = resample(Tq[d], Q -> n)[r]
+ *   g[d][i]  = p[d][i] - t[d][r_d(i)]
+ *   E        = (1/(D n)) sum_d sum_i g[d][i]^2
+ *   S[c][i]  = (1/D) sum_d g[d][i] V[d][c]       ( = n d(E/2)/dF with the ranks held )
+ *   loss        += lw weight E / 2
+ *   diff[layer] += lw weight S / (sum|S| / (C n) + EPS)      (the reference's normalize, as for the Gram term)
+ * resample(s[0 .. M-1], M -> K)[k] is one rule, in integer arithmetic, used here and in target making:
+ *   1. num = (2 k + 1) M - K in int64;
+ *   2. num <= 0: the result is s[0];
+ *   3. otherwise j = num div 2 K and a = float32(num mod 2 K) / float32(2 K);
+ *   4. j >= M - 1: the result is s[M - 1];
+ *   5. otherwise the result is fma(a, s[j + 1] - s[j], s[j]).
+ * With K = M this returns s[k] bit for bit.  A tile's term is the tile's own, as its Gram is.  No float atomics;
+ * every sum is added in a fixed order, and the order above is total, so the sort's form does not show: the same
+ * inputs give the same bits.  A blob whose targets are its own sorted projections (stx_swd_target with Q = n)
+ * contributes exactly 0 to the loss and to the gradient.
+ * (A struct tag only: stx_swd_target without `struct` is the function that makes a target, below.) */
+struct stx_swd_target {
+    const char *layer;
+    int channels;
+    int dirs;               /* D */
+    int quantiles;          /* Q */
+    const float *V;         /* [dirs][channels] */
+    const float *Tq;        /* [dirs][quantiles] */
+    int mem;
+    double weight;
+};
+/* Replaces all sliced Wasserstein targets of the engine's group (n = 0: none); one per layer at most.  V and Tq
+ * are copied.  They are shared like the style targets (stx_engine_create_shared) and
+ * stx_set_contents_and_styles clears them: call this behind it.  A layer with a target is part of every
+ * stx_sc_grad_tile evaluation under the rules of stx_set_stat_targets: the layer_weight of its tap if the tap
+ * list names it, lw = 1 otherwise, and all layers on one path.  The term follows the blob's NNFM term in the loss
+ * and in the gradient.  STX_ERR_ARG for a channel count other than the layer's, dirs < 1 or quantiles < 2;
+ * STX_ERR_UNSUPPORTED for channels not a multiple of 4, dirs > 4096, quantiles > 65536 and -- at the evaluation --
+ * a tile whose blob has n > 2^22 or dirs x (n padded to a power of two) >= 2^31. */
+int stx_set_swd_targets(stx_engine *e, const struct stx_swd_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -421,6 +465,13 @@ int stx_gram_matrix(stx_engine *e, const float *feat, int feat_mem, int channels
  * what stx_set_stat_targets takes, by the launches the term itself runs on a tile's blob. */
 int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channels, int hw,
                       float *mean_out, float *sd_out, int out_mem);
+
+/* The sliced Wasserstein target of a feature map [channels][h][w] along `dirs` directions V [dirs][channels]
+ * (stx_set_swd_targets): the projections as the term forms them, each direction's M = h w values sorted, and
+ * out [dirs][quantiles] = resample(sorted, M -> quantiles); with quantiles = M the sorted projections
+ * themselves.  V and out are STX_HOST; synchronous.  Refusals: those of the term. */
+int stx_swd_target(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, const float *V,
+                   int dirs, int quantiles, float *out);
 
 /* The NNFM bank of a feature map [channels][h][w]: its unit-normalised columns at (y, x) with y % stride == 0
  * and x % stride == 0, in raster order, as float32 rows [rows][channels], rows = ceil(h / stride) *
@@ -721,6 +772,11 @@ int stx_op_nnfm_knn_terms(stx_engine *e, const float *feat, int channels, int h,
  * alone. */
 int stx_op_nnfm_cover_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch, int k, float cover,
                             const float *bank, int rows, float *s_out, int *index_out, int *winner_out, double out[3]);
+/* The launches of a sliced Wasserstein target (stx_set_swd_targets) on given arrays (all STX_DEVICE; V
+ * [dirs][channels], Tq [dirs][quantiles]): out = {E / 2, sum |S|}; s_out = S [channels][h][w]; rank_out (or null)
+ * = r_d(i) [dirs][h w], which holds the sort to account.  Errors leave the outputs alone. */
+int stx_op_swd_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *V, int dirs,
+                     const float *Tq, int quantiles, float *s_out, int *rank_out, double out[2]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

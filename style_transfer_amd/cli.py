@@ -15,7 +15,7 @@ import numpy as np
 from PIL import Image
 
 from . import fastpng, lib
-from .config_system import (check_content_mask, check_nnfm_options, check_stat_options, check_style_masks,
+from .config_system import (check_content_mask, check_nnfm_options, check_stat_options, check_style_masks, check_swd_options,
                             parse_args)
 from .farm import TileFarm
 from .netspec import load_net
@@ -136,6 +136,7 @@ def main(argv=None):
         return 0
     check_stat_options(args, net.blob_names())
     check_nnfm_options(args, net.blob_names())
+    check_swd_options(args, net.blob_names())
     # Three things run side by side, each releasing the interpreter lock: the weight file is read
     # (or the seeded bank drawn) on one helper thread, the GPU runtime is woken up and the engines
     # (streams, scalar arenas) are created on another, and this thread decodes the pictures.

@@ -15,6 +15,7 @@ import math
 import os
 from pathlib import Path
 import sys
+import zlib
 
 import numpy as np
 
@@ -169,6 +170,24 @@ _EXTENSIONS = [
                                   'reach; every tile is asked to cover the whole bank, so --nnfm-stride matters '
                                   'more; a finite number >= 0, not with --nnfm-patch 3; read once per scale; 0 or '
                                   'absent: off (default: 0)')),
+    (('--swd-weight',), dict(metavar='WEIGHT', type=ffloat,
+                             help='sliced Wasserstein style factor (Heitz et al.): holds the whole distribution of '
+                                  'the feature vectors at the --swd-layers to that of the style picture(s), along '
+                                  'fixed random directions and by an exact sort -- contrast and rare colours that '
+                                  'the Gram term washes out; read once per scale; 0 or absent: off (default: 0)')),
+    (('--swd-layers',), dict(nargs='+', metavar='LAYER',
+                             help='layers of the sliced Wasserstein term as name or name:weight; the weights are '
+                                  'normalised to --swd-weight like those of a layer list and read once per scale; '
+                                  'with --style-multiscale the layers themselves stay those of the first scale, '
+                                  'whose targets are kept.  The term is not cheap: at a 1024 x 1024 tile the default '
+                                  'layers together take about 1.1 times the tile evaluation itself (4.2 ms beside '
+                                  '3.8 ms on an MI355X), and conv1_1 alone -- 64 rows of a million values to sort '
+                                  '-- 6.2 ms, 1.6 tile evaluations, which is why the default leaves it out '
+                                  '(default: conv2_1 conv3_1 conv4_1)')),
+    (('--swd-dirs',), dict(metavar='D', type=int,
+                           help='directions per layer of the sliced Wasserstein term, an integer from 1 to 4096: '
+                                'orthonormal bases drawn once per run from --seed and the layer name (default: the '
+                                "layer's channel count, one basis)")),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -455,6 +474,57 @@ def check_nnfm_options(args, known_layers=None):
                             known_layers)
 
 
+SWD_LAYERS_DEFAULT = ('conv2_1', 'conv3_1', 'conv4_1')
+SWD_QUANTILES = 4096        # samples of a direction's target quantile function
+SWD_MAX_DIRS = 4096
+
+
+def swd_layer_args(args):
+    """The layer list of the sliced Wasserstein term (``name`` or ``name:weight`` each): --swd-layers, or
+    conv2_1 conv3_1 conv4_1.  [] when the term is off (no --swd-weight, or 0)."""
+    if not option_on(args, 'swd_weight'):
+        return []
+    given = getattr(args, 'swd_layers', None) or SWD_LAYERS_DEFAULT
+    return [given] if isinstance(given, str) else list(given)
+
+
+def swd_dirs(args):
+    """--swd-dirs as an integer from 1 to 4096, or None (the default: every layer's channel count); anything
+    else, bools and floats included, is a ValueError."""
+    raw = raw_option(args, 'swd_dirs', None)
+    if raw is None:
+        return None
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 1 <= raw <= SWD_MAX_DIRS:
+        raise ValueError('--swd-dirs %r: an integer from 1 to %d is expected' % (raw, SWD_MAX_DIRS))
+    return int(raw)
+
+
+def swd_directions(seed, layer, channels, dirs):
+    """The directions V [dirs, channels] (float32, unit rows) of the sliced Wasserstein term at one layer:
+    ceil(dirs / channels) independent orthonormal bases -- the Q factors of Gaussian matrices drawn from PCG64
+    seeded with [seed, crc32(layer name)] -- concatenated and cut to ``dirs`` rows.  The same for the whole run:
+    L-BFGS and --style-multiscale need one objective, and targets of several scales are averaged."""
+    rng = np.random.Generator(np.random.PCG64([int(seed) & 0xffffffff, zlib.crc32(layer.encode())]))
+    bases = []
+    for _ in range(-(-int(dirs) // int(channels))):
+        q, r = np.linalg.qr(rng.standard_normal((channels, channels)))
+        bases.append((q * np.sign(np.diag(r))).T)       # (the sign that makes the factorisation unique)
+    return np.ascontiguousarray(np.concatenate(bases)[:dirs], np.float32)
+
+
+def check_swd_options(args, known_layers=None):
+    """--swd-weight / --swd-layers / --swd-dirs: refused before any GPU work together with --style-masks (there
+    is one set of targets and, with masks, one style set per picture), with --swd-dirs outside 1 .. 4096 and with
+    a bad layer list (check_layer_list).  Returns the layer names."""
+    items = swd_layer_args(args)
+    if not items:
+        return []
+    if not getattr(args, 'style_masks', None):      # (the refusal of --style-masks comes first)
+        swd_dirs(args)
+    return check_layer_list(args, items, '--swd-weight', '--swd-layers', 'one set of sliced Wasserstein targets',
+                            known_layers)
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -483,5 +553,6 @@ def parse_args(state=None, argv=None, config_py=None):
     check_lap_pools(args)
     check_stat_options(args)
     check_nnfm_options(args)
+    check_swd_options(args)
     check_photo_options(args)
     return args

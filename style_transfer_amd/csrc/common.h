@@ -496,6 +496,36 @@ int stat_finish_launch(hipStream_t s, const float *partials, int C, int HW, cons
 int stat_grad_launch(hipStream_t s, const float *feat, int C, int HW, const float *table, float *sgrad,
                      float *abs_partials, int *n_parts);
 
+// swd.hip: the sliced Wasserstein style term of a blob [C][n] along D directions V [D][C] against quantile
+// targets Tq [D][Q] (include/stx.h, stx_set_swd_targets).  The sort works on records of 64 bits, in rows padded
+// to swd_padded(n) -- a power of two, 2 at least -- and in LDS blocks of kSwdBlock records.
+constexpr int kSwdBlock = 8192;
+constexpr int kSwdMaxDirs = 4096, kSwdMaxQuantiles = 65536, kSwdMaxPixels = 1 << 22;
+int swd_padded(int n);
+// STX_ERR_ARG / STX_ERR_UNSUPPORTED with the message, as include/stx.h lists them (n = 1 where no blob is known yet)
+int swd_check(const char *who, int C, long long n, int D, int Q);
+// floats of the caller's that outlive the term's launches: the partials of E (swd_e_parts), then those of sum |S|
+// from the next multiple of 64
+int swd_e_parts(int n, int D);
+size_t swd_scratch_floats(int C, int n, int D);
+// floats of the work area, free again behind the term's last launch: the records [D][swd_padded(n)], then G [D][n]
+size_t swd_work_floats(int n, int D);
+// records [D][swd_padded(n)] = (order-preserving image of v_d . f_i, i), padded with sentinels that order last
+int swd_project_launch(hipStream_t s, const float *feat, int C, int n, const float *V, int D, void *records);
+// Sorts every row, in two calls: all launches but the last, then the last one.  Tq null: the last launch leaves
+// the sorted records in place.  Otherwise it ends in the rank pass and writes no records: G [D][n] = g, rank_out
+// [D][n] (or null), e_parts = the blocks' sums of g^2 / (D n).  swd_sort_passes: launches of both, each of which
+// reads and writes every record once.
+int swd_sort_launch(hipStream_t s, void *records, int n, int D);
+int swd_finish_launch(hipStream_t s, void *records, int n, int D, const float *Tq, int Q, float *G, int *rank_out,
+                      float *e_parts);
+int swd_sort_passes(int n);
+// sgrad [C][n] = V^T G / D; *n_parts partials of sum |sgrad| into abs_parts
+int swd_grad_launch(hipStream_t s, const float *V, const float *G, int C, int n, int D, float *sgrad, float *abs_parts,
+                    int *n_parts);
+// out [D][Q] = resample(sorted row, n -> Q)
+int swd_quantiles_launch(hipStream_t s, const void *records, int n, int D, int Q, float *out);
+
 // nnfm.hip: the nearest-neighbour feature matching term of a blob [C][n] against a bank [M][C] of unit rows
 // (include/stx.h, stx_set_nnfm_targets).  The search multiplies kNnfmQ query columns by kNnfmB bank rows per
 // workgroup, kNnfmK channels per LDS stage; with few query blocks the bank is cut into slices.

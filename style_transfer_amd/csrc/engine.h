@@ -136,6 +136,16 @@ struct NnfmTarget {
     }
 };
 
+// The sliced Wasserstein target of one tapped blob (stx_set_swd_targets): V [D][C] then Tq [D][Q] on the device.
+struct SwdTarget {
+    int blob, C, D, Q;
+    double weight;
+    std::unique_ptr<DevBuf> vt;
+    const float *V() const { return vt->f(); }
+    const float *Tq() const { return vt->f() + (size_t)D * C; }
+    void release() { vt->release(); }
+};
+
 struct LossTerm {
     size_t scalar_index;   // float in the host mirror of the scalar buffer
     double coef;
@@ -159,6 +169,7 @@ struct SharedState {
     std::vector<StatTarget> stats;     // (cleared with the targets)
     std::vector<ContentMask> cmasks;   // (cleared with the targets)
     std::vector<NnfmTarget> nnfms;     // (cleared with the targets)
+    std::vector<SwdTarget> swds;       // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -209,6 +220,8 @@ struct stx_engine {
     DevBuf masked_feat, masked_target; // a masked style term's F . m and a Gs (style_mask.hip), one term at a time
     DevBuf stat_scratch;               // stx_feature_stats / stx_op_stat_terms: partials, table, outputs
     DevBuf nnfm_scratch;               // stx_nnfm_bank / stx_op_nnfm_terms: rows, bank pieces, the term's scratch
+    DevBuf swd_work;                   // a sliced Wasserstein term's sort records and G (swd_work_floats), one term at a time
+    DevBuf swd_io;                     // stx_swd_target / stx_op_swd_terms: V, the quantiles, the term's scratch
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
     // reductions), each with a pinned host mirror, and the losses that will be published from
     // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
@@ -341,6 +354,7 @@ inline void clear_dependent_targets(SharedState &sh) {   // what is set behind t
     clear_targets(sh.stats);
     clear_targets(sh.cmasks);
     clear_targets(sh.nnfms);
+    clear_targets(sh.swds);
 }
 inline void clear_all_targets(SharedState &sh) {
     clear_targets(sh.contents);
@@ -377,7 +391,7 @@ struct TileCall {
     int grad_mem;
 };
 
-enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, Dream };
+enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, Swd, Dream };
 constexpr size_t kNoSlot = ~(size_t)0;
 constexpr size_t kResidualScalars = 2 + 2 * 1024;   // content_sums_launch: two sums and their partials
 
@@ -392,13 +406,14 @@ struct PlannedTerm {
     size_t scratch_off, scratch_len; // its region of the engine's term_scratch, in floats
     size_t sgrad_off;                // its blob S in the tap's gradient buffer (stx_engine::sgrad), in floats, or kNoSlot
     const NnfmTarget *nnfm = nullptr; // TermKind::Nnfm: the bank with its pieces
+    const SwdTarget *swd = nullptr;   // TermKind::Swd: the directions and quantiles
 };
 
 struct TilePlan {
     std::vector<Tap> order;         // taps, deepest first
     std::vector<char> needed;       // blobs on the path
     std::vector<int> tap_of;        // blob -> index into order, or -1
-    std::deque<stx_tap> extra;      // taps of the layers that only a statistics or NNFM target names (lw = 1);
+    std::deque<stx_tap> extra;      // taps of the layers that only a statistics, NNFM or SWD target names (lw = 1);
                                     // `order` points into it: a deque's elements stay where they are
     // The final sums of the loss terms are collected and run as ONE launch behind the forward pass
     // (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did); what they add up must outlive the term's
@@ -406,7 +421,7 @@ struct TilePlan {
     bool sums_late;
     bool interleave;                // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
     // The terms in queueing order -- shallowest tap first; per tap the content targets in sh->contents order,
-    // the style targets in sh->styles order, the statistics term, the NNFM term, Deep-Dream -- which is the order of
+    // the style targets in sh->styles order, the statistics term, the NNFM term, the SWD term, Deep-Dream -- which is the order of
     // PendingLoss::terms: the host adds the loss up in it.
     std::vector<PlannedTerm> terms;
     std::vector<size_t> first_term;     // per tap: its first record
@@ -469,6 +484,13 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
                       const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
                       const std::string &name, float *scratch, std::vector<SumJob> *defer, int k = 1, float cover = 0.f,
                       int *winner_out = nullptr, float *e_cov_out = nullptr);
+// The sliced Wasserstein term of a blob (swd.hip): projection -> sort with the rank pass -> S = V^T G / D into sgrad.
+// sc[2] = {E, sum |S|}, both from partials whose final sums join `defer` or are launched here.  scratch:
+// swd_scratch_floats(C, h * w, D) floats that outlive the call like term_scratch; the records and G live in the
+// engine's swd_work, which the next term may reuse.  rank_out (or null): r_d(i) [D][h * w].
+int launch_swd_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *V, int D,
+                     const float *Tq, int Q, float *sgrad, int *rank_out, float *sc, const std::string &name,
+                     float *scratch, std::vector<SumJob> *defer);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

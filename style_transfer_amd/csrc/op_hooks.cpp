@@ -174,6 +174,28 @@ int stx_op_stat_terms(stx_engine *e, const float *feat, int C, int h, int w, con
     return STX_OK;
 }
 
+int stx_op_swd_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *V, int D, const float *Tq,
+                     int Q, float *s_out, int *rank_out, double out[2]) {
+    if (!e || !feat || !V || !Tq || !s_out || !out || h <= 0 || w <= 0) {
+        set_error("stx_op_swd_terms: bad arguments");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(swd_check("stx_op_swd_terms", C, (long long)h * w, D, Q));
+    STX_TRY(e->set_device());
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
+    STX_TRY(e->swd_io.ensure(swd_scratch_floats(C, h * w, D) * sizeof(float)));
+    // the launches of a sliced Wasserstein target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_swd_terms(e, e->stream, feat, C, h, w, V, D, Tq, Q, s_out, rank_out, sc, "op", e->swd_io.f(),
+                             nullptr));
+    STX_TRY(scalars.fetch(&host));
+    out[0] = 0.5 * (double)host[0];
+    out[1] = (double)host[1];
+    return STX_OK;
+}
+
 int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *content,
                                 int content_h, int content_w, const float *mask_map, int oy, int ox,
                                 const int roll_xy[2], float *sgrad_out, double out[3]) {

@@ -1,7 +1,7 @@
 // libstx host side: the targets of an engine group (stx_set_*).
 //
 // The engines of one GPU share their targets (SharedState): the content maps and style Grams, and behind them
-// the style masks, the content mask, the statistics targets and the NNFM banks, which go when new contents
+// the style masks, the content mask, the statistics targets, the NNFM banks and the sliced Wasserstein targets, which go when new contents
 // and styles arrive.  Every setter is one swap (swap_targets) around a body that validates and copies.
 
 #include <cmath>
@@ -265,6 +265,39 @@ int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
         }
         return STX_OK;
     }, [&]() { clear_targets(stats); });
+}
+
+int stx_set_swd_targets(stx_engine *e, const struct stx_swd_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    auto &swds = e->sh->swds;
+    return swap_targets(e, "stx_set_swd_targets", [&](bool &) -> int {
+        clear_targets(swds);
+        for (int i = 0; i < n; ++i) {
+            const struct stx_swd_target &wt = targets[i];
+            const int blob = e->find_blob(wt.layer);
+            bool twice = false;
+            for (const SwdTarget &t : swds) twice |= t.blob == blob;
+            if (blob <= 0 || !wt.V || !wt.Tq || twice) {
+                set_error("sliced Wasserstein target %d: bad layer '%s' (unknown, the input, or given twice) or no data",
+                          i, wt.layer ? wt.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            if (wt.channels != e->blobs[blob].channels) {
+                set_error("sliced Wasserstein target %d: layer %s has %d channels, not %d", i, wt.layer,
+                          e->blobs[blob].channels, wt.channels);
+                return STX_ERR_ARG;
+            }
+            STX_TRY(swd_check("stx_set_swd_targets", wt.channels, 1, wt.dirs, wt.quantiles));
+            swds.push_back(SwdTarget{blob, wt.channels, wt.dirs, wt.quantiles, wt.weight,
+                                     std::unique_ptr<DevBuf>(new DevBuf)});
+            SwdTarget &t = swds.back();
+            const size_t v_bytes = (size_t)t.D * t.C * sizeof(float), q_bytes = (size_t)t.D * t.Q * sizeof(float);
+            STX_TRY(t.vt->ensure(v_bytes + q_bytes));
+            STX_TRY(copy_in(e, t.vt->ptr, wt.V, wt.mem, v_bytes));
+            STX_TRY(copy_in(e, t.vt->f() + (size_t)t.D * t.C, wt.Tq, wt.mem, q_bytes));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(swds); });
 }
 
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {

@@ -435,7 +435,8 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
     };
     const auto has_statistics = [&](int blob) {     // ... or an NNFM bank: a target that makes the layer part of the call
         return std::any_of(e->sh->stats.begin(), e->sh->stats.end(), [=](const StatTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->nnfms.begin(), e->sh->nnfms.end(), [=](const NnfmTarget &t) { return t.blob == blob; });
+               std::any_of(e->sh->nnfms.begin(), e->sh->nnfms.end(), [=](const NnfmTarget &t) { return t.blob == blob; }) ||
+               std::any_of(e->sh->swds.begin(), e->sh->swds.end(), [=](const SwdTarget &t) { return t.blob == blob; });
     };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
@@ -465,6 +466,13 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
         t.layer_weight = 1.0;
         plan.extra.push_back(t);
         order.push_back(Tap{nt.blob, &plan.extra.back()});
+    }
+    for (const SwdTarget &wt : e->sh->swds) {       // ... and a layer with a sliced Wasserstein target
+        if (tapped(wt.blob)) continue;
+        stx_tap t{};
+        t.layer_weight = 1.0;
+        plan.extra.push_back(t);
+        order.push_back(Tap{wt.blob, &plan.extra.back()});
     }
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");
@@ -901,6 +909,36 @@ int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channe
     STX_TRY(copy_out(e, mean_out, out_mem, mu, (size_t)channels * sizeof(float)));
     STX_TRY(copy_out(e, sd_out, out_mem, sd, (size_t)channels * sizeof(float)));
     if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_swd_target(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, const float *V,
+                   int dirs, int quantiles, float *out) {
+    if (!e || !feat || !V || !out || h <= 0 || w <= 0) {
+        set_error("stx_swd_target: bad arguments");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(swd_check("stx_swd_target", channels, (long long)h * w, dirs, quantiles));
+    STX_TRY(e->set_device());
+    const int n = h * w;
+    const float *src = feat;
+    if (feat_mem == STX_HOST) {
+        STX_TRY(e->upload.ensure((size_t)channels * n * sizeof(float)));
+        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, (size_t)channels * n * sizeof(float)));
+        src = e->upload.f();
+    }
+    const size_t v_floats = ((size_t)dirs * channels + 63) & ~(size_t)63;
+    STX_TRY(e->swd_io.ensure((v_floats + (size_t)dirs * quantiles) * sizeof(float)));
+    STX_TRY(e->swd_work.ensure(2 * (size_t)dirs * swd_padded(n) * sizeof(float)));
+    float *const v_dev = e->swd_io.f(), *const q_dev = v_dev + v_floats;
+    STX_TRY(copy_in(e, v_dev, V, STX_HOST, (size_t)dirs * channels * sizeof(float)));
+    // the first two steps of the term itself (launch_swd_terms), the sorted rows kept, then their resampling
+    STX_TRY(swd_project_launch(e->stream, src, channels, n, v_dev, dirs, e->swd_work.ptr));
+    STX_TRY(swd_sort_launch(e->stream, e->swd_work.ptr, n, dirs));
+    STX_TRY(swd_finish_launch(e->stream, e->swd_work.ptr, n, dirs, nullptr, 0, nullptr, nullptr, nullptr));
+    STX_TRY(swd_quantiles_launch(e->stream, e->swd_work.ptr, n, dirs, quantiles, q_dev));
+    STX_TRY(copy_out(e, out, STX_HOST, q_dev, (size_t)dirs * quantiles * sizeof(float)));
+    STX_HIP(hipStreamSynchronize(e->stream));
     return STX_OK;
 }
 

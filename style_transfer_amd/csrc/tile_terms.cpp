@@ -220,6 +220,40 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
     return STX_OK;
 }
 
+// The sliced Wasserstein term of one tapped blob (swd.hip): the projections as sort records, the segmented sort
+// whose last launch is the rank pass (G with the partials of E), S = V^T G / D with the partials of sum |S|.
+int launch_swd_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *V, int D,
+                     const float *Tq, int Q, float *sgrad, int *rank_out, float *sc, const std::string &name,
+                     float *scratch, std::vector<SumJob> *defer) {
+    const int n = h * w;
+    STX_TRY(swd_check("launch_swd_terms", C, (long long)h * w, D, Q));
+    // (grows when a larger blob than ever arrives; the stream orders the terms that share it)
+    STX_TRY(e->swd_work.ensure(swd_work_floats(n, D) * sizeof(float)));
+    void *const records = e->swd_work.ptr;
+    float *const G = e->swd_work.f() + 2 * (size_t)D * swd_padded(n);
+    const int n_e = swd_e_parts(n, D);
+    float *const e_parts = scratch, *const abs_parts = scratch + (((size_t)n_e + 63) & ~(size_t)63);
+    {
+        ProfScope scope(e, "swd project " + name, 2.0 * D * (double)C * n, stream);
+        STX_TRY(swd_project_launch(stream, feat, C, n, V, D, records));
+    }
+    {
+        ProfScope scope(e, "swd sort " + name + " x" + std::to_string(swd_sort_passes(n) - 1), 0.0, stream);
+        STX_TRY(swd_sort_launch(stream, records, n, D));
+    }
+    {       // (the sort's last launch: the steps left inside a block, then the rank pass from LDS)
+        ProfScope scope(e, "swd rank " + name, 0.0, stream);
+        STX_TRY(swd_finish_launch(stream, records, n, D, Tq, Q, G, rank_out, e_parts));
+    }
+    ProfScope scope(e, "swd grad " + name, 2.0 * D * (double)C * n, stream);
+    int n_abs = 0;
+    STX_TRY(swd_grad_launch(stream, V, G, C, n, D, sgrad, abs_parts, &n_abs));
+    if (!defer) return sum_partials2_launch(stream, e_parts, n_e, sc, abs_parts, n_abs, sc + 1);
+    defer->push_back(SumJob{e_parts, n_e, sc});
+    defer->push_back(SumJob{abs_parts, n_abs, sc + 1});
+    return STX_OK;
+}
+
 // A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
 // S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
 int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
@@ -245,6 +279,13 @@ static const StatTarget *stat_target_of(const stx_engine *e, int blob) {
 // The NNFM bank of `blob` (stx_set_nnfm_targets), or null.
 static const NnfmTarget *nnfm_target_of(const stx_engine *e, int blob) {
     for (const NnfmTarget &t : e->sh->nnfms)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
+
+// The sliced Wasserstein target of `blob` (stx_set_swd_targets), or null.
+static const SwdTarget *swd_target_of(const stx_engine *e, int blob) {
+    for (const SwdTarget &t : e->sh->swds)
         if (t.blob == blob) return &t;
     return nullptr;
 }
@@ -305,7 +346,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         const double lw = tp.t->layer_weight;
         plan.first_term[k] = plan.terms.size();
         // The tap's gradient buffer: the style slots, then (each group from a 256-byte boundary) the masked
-        // content slots, the statistics slot and the NNFM slot.
+        // content slots, the statistics slot, the NNFM slot and the SWD slot.
         size_t styles_here = 0;
         for (const StyleTarget &st : sh.styles) styles_here += tp.t->is_style && st.blob == tp.blob;
         size_t style_slot = 0, content_slot = align(styles_here * b.count());
@@ -377,6 +418,14 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k, nt->cover != 0.f), nnfm_slot);
             plan.terms.back().nnfm = nt;
         }
+        if (const SwdTarget *wt = swd_target_of(e, tp.blob)) {      // (its slot: behind the NNFM slot, if there is one)
+            STX_TRY(swd_check(("sliced Wasserstein target of layer " + b.name).c_str(), b.channels,
+                              (long long)b.h * b.w, wt->D, wt->Q));
+            const size_t swd_slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
+            add(TermKind::Swd, wt->Tq(), nullptr, ContentWindow{}, lw * wt->weight, 2,
+                swd_scratch_floats(b.channels, b.h * b.w, wt->D), swd_slot);
+            plan.terms.back().swd = wt;
+        }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
         // weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
         if (tp.t->is_dd)
@@ -434,6 +483,10 @@ int queue_tap_terms(TileRun &run, size_t k) {
             STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.nnfm->patch, t.target,
                                       t.nnfm->pieces_hi_lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch,
                                       run.defer(), t.nnfm->k, t.nnfm->cover));
+            break;
+        case TermKind::Swd:           // sc[0] = E, sc[1] = sum |S|
+            STX_TRY(launch_swd_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.swd->V(), t.swd->D, t.target,
+                                     t.swd->Q, sgrad, nullptr, sc, b.name, scratch, run.defer()));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

@@ -188,6 +188,7 @@ UNBROADCAST_OPTIONS = (
     ('content_mask', False, 'the mask is'),
     ('stat_weight', True, 'the statistics targets are'),
     ('nnfm_weight', True, 'the banks of style features are'),
+    ('swd_weight', True, 'the sliced Wasserstein targets are'),
 )
 
 
@@ -248,7 +249,7 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks, --content-mask, --stat-weight or --nnfm-weight is refused here
+    a run with --style-masks, --content-mask, --stat-weight, --nnfm-weight or --swd-weight is refused here
     (refuse_unbroadcast_options)."""
     if args is not None:
         refuse_unbroadcast_options(args)

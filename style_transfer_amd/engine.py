@@ -25,7 +25,7 @@ from .netspec import NetSpec
 
 _TYPE_CODES = {'Input': lib.LAYER_INPUT, 'Convolution': lib.LAYER_CONV, 'ReLU': lib.LAYER_RELU,
                'Pooling': lib.LAYER_POOL}
-EXTRA_TAP_KINDS = ('stat', 'nnfm')      # the targets that tap layers of their own, in the order of their taps
+EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd')   # the targets that tap layers of their own, in the order of their taps
 
 
 class DeviceArray:
@@ -365,6 +365,42 @@ class TileEngine:
         lib.call(call, self.handle, table, n)
         self.primary.extra_taps['nnfm'] = list(banks)
         del keep
+
+    def set_swd_targets(self, targets, weights=None):
+        """targets: {layer: (V [D, C], Tq [D, Q])} -- unit directions and, per direction, the quantile function
+        that ``swd_target`` gives for a style picture's feature map -- and weights: {layer: factor} (default 1
+        each); an empty dict: none (stx_set_swd_targets).  The library copies both.  Call it after
+        ``set_contents_and_styles``, which clears them.  A layer with a target is part of every tile evaluation
+        of the group from then on."""
+        keep, n = [], len(targets)
+        table = (lib.SwdTarget * max(1, n))()
+        for t, (layer, (V, Tq)) in zip(table, targets.items()):
+            vp, vmem, vobj = _as_arg(V)
+            qp, qmem, qobj = _as_arg(Tq)
+            if vmem != qmem or len(vobj.shape) != 2 or len(qobj.shape) != 2 or vobj.shape[0] != qobj.shape[0]:
+                raise ValueError('sliced Wasserstein target %s: V [D, C] and Tq [D, Q] on the same side are expected'
+                                 % layer)
+            keep += [vobj, qobj]
+            t.layer, t.channels, t.dirs, t.quantiles = (self._cstr(layer), int(vobj.shape[1]), int(vobj.shape[0]),
+                                                        int(qobj.shape[1]))
+            t.V, t.Tq, t.mem = vp, qp, vmem
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_swd_targets', self.handle, table, n)
+        self.primary.extra_taps['swd'] = list(targets)
+        del keep
+
+    def swd_target(self, feat, V, Q):
+        """Tq [D, Q] float32: per direction of V [D, C] the quantile function of a [C,h,w] feature map's
+        projections, sampled at (q + 1/2) / Q (stx_swd_target); with Q = h w the sorted projections themselves."""
+        ptr, mem, keep = _as_arg(feat)
+        c, h, w = (int(v) for v in keep.shape)
+        V = np.ascontiguousarray(V, np.float32)
+        if V.ndim != 2 or V.shape[1] != c:
+            raise ValueError('swd_target: V %s for a map of %d channels; [D, C] is expected' % (V.shape, c))
+        out = np.empty((V.shape[0], int(Q)), np.float32)
+        lib.call('stx_swd_target', self.handle, ptr, mem, c, h, w, V.ctypes.data, int(V.shape[0]), int(Q),
+                 out.ctypes.data)
+        return out
 
     def nnfm_bank(self, feat, stride=1, patch=1):
         """The bank of a [C,h,w] feature map as a DeviceArray [rows, C]: its unit-normalised columns at every

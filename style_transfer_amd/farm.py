@@ -186,8 +186,14 @@ class TileFarm:
     def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0):
         self._set_on_primaries('set_nnfm_targets', banks, weights, patch, k, *((cover,) if cover else ()))
 
+    def set_swd_targets(self, targets, weights=None):
+        self._set_on_primaries('set_swd_targets', targets, weights)
+
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)
+
+    def swd_target(self, feat, V, Q):
+        return self.master.swd_target(feat, V, Q)
 
     def nnfm_bank(self, feat, stride=1, patch=1):
         return self.master.nnfm_bank(feat, stride, patch)

@@ -80,6 +80,12 @@ class NnfmCoverTarget(ctypes.Structure):
                 ('weight', ctypes.c_double), ('cover', ctypes.c_float)]
 
 
+class SwdTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('dirs', ctypes.c_int),
+                ('quantiles', ctypes.c_int), ('V', ctypes.c_void_p), ('Tq', ctypes.c_void_p), ('mem', ctypes.c_int),
+                ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -115,6 +121,7 @@ SIGNATURES = {
     'stx_set_nnfm_patch_targets': [_vp, ctypes.POINTER(NnfmPatchTarget), _i],
     'stx_set_nnfm_knn_targets': [_vp, ctypes.POINTER(NnfmKnnTarget), _i],
     'stx_set_nnfm_cover_targets': [_vp, ctypes.POINTER(NnfmCoverTarget), _i],
+    'stx_set_swd_targets': [_vp, ctypes.POINTER(SwdTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -123,6 +130,7 @@ SIGNATURES = {
     'stx_tile_buffers': [_vp, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
     'stx_gram_matrix': [_vp, _vp, _i, _i, _i, _vp, _i],
     'stx_feature_stats': [_vp, _vp, _i, _i, _i, _vp, _vp, _i],
+    'stx_swd_target': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     'stx_nnfm_bank': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i],
     'stx_nnfm_patch_bank': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i],
     'stx_image_cut_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
@@ -166,6 +174,7 @@ SIGNATURES = {
     'stx_op_masked_style_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, _vp, c_double_p],
     'stx_op_masked_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, c_int_p, _vp, c_double_p],
     'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
+    'stx_op_swd_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],

@@ -10,9 +10,10 @@ import numpy as np
 from PIL import Image
 
 from . import image_ops
-from .config_system import (LAP_POOLS_DEFAULT, ValuePlaceholder, check_lap_pools, check_nnfm_options,
-                            check_photo_options, check_stat_options, ffloat, nnfm_bank_rows, nnfm_layer_args,
-                            nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on, stat_layer_args)
+from .config_system import (LAP_POOLS_DEFAULT, SWD_QUANTILES, ValuePlaceholder, check_lap_pools, check_nnfm_options,
+                            check_photo_options, check_stat_options, check_swd_options, ffloat, nnfm_bank_rows,
+                            nnfm_layer_args, nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on, stat_layer_args,
+                            swd_dirs, swd_directions, swd_layer_args)
 
 
 def parse_weights(args, master_weight):
@@ -142,6 +143,34 @@ class NnfmBanks(LayerTargets):
             farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k)
 
 
+class SwdTargets(LayerTargets):
+    """--swd-weight / --swd-layers / --swd-dirs (the sliced Wasserstein style term): per layer fixed directions V
+    (swd_directions: from --seed and the layer's name, the same for the whole run) and, per direction, the quantile
+    function of the style pictures' projections at SWD_QUANTILES samples, averaged over the variants like the Grams
+    -- the mean of quantile functions is the 1-D Wasserstein barycentre and stays non-decreasing; ``targets`` =
+    {layer: (V [D, C], Tq [D, Q])}."""
+    FLAG, WEIGHT, WHAT, layer_args = '--swd-layers', 'swd_weight', 'quantile target', staticmethod(swd_layer_args)
+
+    def __init__(self):
+        self._directions = {}       # {layer: V}, drawn at first use
+
+    def directions(self, st, layer, channels):
+        if layer not in self._directions:
+            self._directions[layer] = swd_directions(getattr(st.args, 'seed', 0), layer, channels,
+                                                     swd_dirs(st.args) or channels)
+        return self._directions[layer]
+
+    def take(self, st, layer, feat):
+        self._parts[layer].append(st.farm.swd_target(feat, self.directions(st, layer, feat.shape[0]), SWD_QUANTILES))
+
+    def finish(self, st, count, quiet):
+        self.targets = {layer: (self._directions[layer], sum(parts[1:], parts[0]) / np.float32(count))
+                        for layer, parts in self._parts.items() if parts}
+
+    def set_targets(self, farm, targets):
+        farm.set_swd_targets(targets, self.weights)
+
+
 class Masks(TargetTerm):
     """--style-masks / --content-mask (spatial control): ``st.style_masks`` and ``st.content_mask`` resized to the
     scale's content size.  Under --jitter the engines hold content maps of the rolled picture and shift nothing,
@@ -167,7 +196,7 @@ class Masks(TargetTerm):
 def target_terms(args, known_layers):
     """The target terms of a run, in the order they are sent; a bad option is refused here, before any GPU work.
     (The masks are handed to transfer_multiscale, so their term is always listed.)"""
-    checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks))
+    checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks), (check_swd_options, SwdTargets))
     return [cls() for check, cls in checked if check(args, known_layers)] + [Masks()]
 
 
