@@ -363,6 +363,46 @@ typedef struct stx_nnfm_cover_target {
  * whole set. */
 int stx_set_nnfm_cover_targets(stx_engine *e, const stx_nnfm_cover_target *targets, int n);
 
+/* The same term guided by regions ("semantic" style transfer: Champandard 2016, the guided forms of CNNMRF, STROTSS
+ * and NNST): a column may only pick rows of the style picture whose region it lies in.  The bank of a layer is cut
+ * into S segments, 1 <= S <= STX_NNFM_MAX_SEGMENTS; segment s holds the seg_rows[s] >= k unit rows of style picture
+ * s, segment after segment.  Every segment has a mask, one [H][W] picture in the image frame of the current targets,
+ * shared by every layer; the library keeps its block means at each layer's scale (the rule of stx_image_mask_map),
+ * and m_s(i) in [0, 1] is the tile's window of that map, taken exactly like a content map's (start // s, roll // s,
+ * wrapping, the same range error).  With r_i, x_i as above, for every segment s and column i:
+ *   J_{i,s} = the k best rows OF SEGMENT s for x_i    (the order rule of stx_set_nnfm_knn_targets; indices local
+ *                                                      to the segment)
+ *   t_{i,s} = (1/k) sum_r b_{J_{i,s,r}}               (float32, rank order, then scaled)
+ *   c_{i,s} = x_i . t_{i,s}                           (float32 fma in channel order, recomputed from (F, B, J))
+ *   E   = (2/n) sum_i sum_s m_s(i) (1 - c_{i,s})
+ *   S_i = sum_s m_s(i) ( -(t_{i,s} - c_{i,s} x_i) / r_i )        (segments added in ascending s; 0 for r_i = 0)
+ *   a   = sum_i sum_s m_s(i) / n
+ *   loss += lw w E / 2,  diff[layer] += lw w a S / (sum|S| / (C n) + EPS)
+ * a plays the part it plays in stx_set_content_mask: the normalisation would otherwise undo the masks' overall
+ * level.  Masks that partition the picture give a = 1; one segment with m = 1 is stx_set_nnfm_knn_targets byte for
+ * byte; m = 0 everywhere adds nothing.  Query blocks are 128 consecutive columns of the blob in row-major order, and
+ * segment s is searched for a block exactly when some column of the block has m_s > 0: with hard-edged masks that
+ * partition the picture the search does about 1/S of the work over the whole bank.  For a pair that is not searched
+ * no row of the segment is read.  No float atomics, every sum in a fixed order: the same inputs give the same bits.
+ * Patch 1 and no coverage part only.  STX_ERR_ARG: segments outside 1 .. STX_NNFM_MAX_SEGMENTS, a segment with fewer
+ * rows than k, k outside 1 .. 4, no masks or a bad mask size; every other refusal is that of stx_set_nnfm_targets. */
+#define STX_NNFM_MAX_SEGMENTS 8
+typedef struct stx_nnfm_guided_target {
+    const char *layer;
+    int channels;
+    int k;
+    int segments;
+    const int *seg_rows;    /* [segments] (host) */
+    const float *bank;      /* [sum of seg_rows][channels] */
+    int mem;
+    double weight;
+} stx_nnfm_guided_target;
+/* stx_set_nnfm_targets for guided banks: a layer has ONE bank, and any of the five calls replaces the whole set.
+ * masks: `segments` pictures [H][W] (host pointers to host or device arrays, by mask_mem); every target has
+ * `segments` segments. */
+int stx_set_nnfm_guided_targets(stx_engine *e, const stx_nnfm_guided_target *targets, int n,
+                                const float *const *masks, int segments, int H, int W, int mask_mem);
+
 /* The sliced Wasserstein term (not in the reference): the loss of Heitz et al., "A Sliced Wasserstein Loss for
  * Neural Texture Synthesis" (CVPR 2021).  It holds the WHOLE distribution of a layer's feature vectors, not its
  * second moments (the Gram and statistics terms) and not single vectors (NNFM).  A tapped blob F [C][h][w] -- the
@@ -772,6 +812,13 @@ int stx_op_nnfm_knn_terms(stx_engine *e, const float *feat, int channels, int h,
  * alone. */
 int stx_op_nnfm_cover_terms(stx_engine *e, const float *feat, int channels, int h, int w, int patch, int k, float cover,
                             const float *bank, int rows, float *s_out, int *index_out, int *winner_out, double out[3]);
+/* ... and of a guided target (stx_set_nnfm_guided_targets; all arrays STX_DEVICE but seg_rows): bank [sum of
+ * seg_rows][channels], mask_maps [segments][mh][mw], the window at (oy, ox) of each map rolled by roll_xy, in the
+ * maps' own pixels.  s_out = S (without a); index_out = J [segments][k][h w], local to the segment, -1 in all k ranks
+ * of the 128-column blocks in which no column has m_s > 0; out = {E, sum |S|, a}.  Errors leave the outputs alone. */
+int stx_op_nnfm_guided_terms(stx_engine *e, const float *feat, int channels, int h, int w, int k, const float *bank,
+                             const int *seg_rows, int segments, const float *mask_maps, int mh, int mw, int oy, int ox,
+                             const int roll_xy[2], float *s_out, int *index_out, double out[3]);
 /* The launches of a sliced Wasserstein target (stx_set_swd_targets) on given arrays (all STX_DEVICE; V
  * [dirs][channels], Tq [dirs][quantiles]): out = {E / 2, sum |S|}; s_out = S [channels][h][w]; rank_out (or null)
  * = r_d(i) [dirs][h w], which holds the sort to account.  Errors leave the outputs alone. */

@@ -16,7 +16,7 @@ from PIL import Image
 
 from . import fastpng, lib
 from .config_system import (check_content_mask, check_nnfm_options, check_stat_options, check_style_masks, check_swd_options,
-                            parse_args)
+                            nnfm_masks, parse_args)
 from .farm import TileFarm
 from .netspec import load_net
 from .transfer import StyleTransfer
@@ -159,6 +159,7 @@ def main(argv=None):
         content_image = Image.open(args.content_image).convert('RGB')
         style_images = [Image.open(p).convert('RGB') for p in args.style_images]
         style_masks = [Image.open(p).convert('L') for p in check_style_masks(args)]
+        guide_masks = [Image.open(p).convert('L') for p in nnfm_masks(args)]
         content_mask = check_content_mask(args)
         content_mask = Image.open(content_mask).convert('L') if content_mask else None
         initial_image = Image.open(args.init_image).convert('RGB') if args.init_image else None
@@ -177,7 +178,8 @@ def main(argv=None):
     try:
         transfer.transfer_multiscale([content_image], style_images, initial_image, aux_image,
                                      callback=progress, **({'style_masks': style_masks} if style_masks else {}),
-                                     **({'content_mask': content_mask} if content_mask is not None else {}))
+                                     **({'content_mask': content_mask} if content_mask is not None else {}),
+                                     **({'nnfm_masks': guide_masks} if guide_masks else {}))
         failed = False
     except (EOFError, KeyboardInterrupt):
         print()

@@ -170,6 +170,13 @@ _EXTENSIONS = [
                                   'reach; every tile is asked to cover the whole bank, so --nnfm-stride matters '
                                   'more; a finite number >= 0, not with --nnfm-patch 3; read once per scale; 0 or '
                                   'absent: off (default: 0)')),
+    (('--nnfm-masks',), dict(nargs='+', metavar='MASK',
+                             help='region-guided nearest-neighbour matching ("semantic" or "doodle" style transfer): '
+                                  "one greyscale picture per style image, in the content picture's frame; where a "
+                                  'mask is white the feature vectors of the result pick rows of THAT style picture '
+                                  'only, so sky takes from sky and town from town.  Restricts the nearest-neighbour '
+                                  'term alone (the Gram term stays one averaged style set); one to 8 style images, '
+                                  'not with --nnfm-patch 3, --nnfm-cover or --style-masks (default: no masks)')),
     (('--swd-weight',), dict(metavar='WEIGHT', type=ffloat,
                              help='sliced Wasserstein style factor (Heitz et al.): holds the whole distribution of '
                                   'the feature vectors at the --swd-layers to that of the style picture(s), along '
@@ -454,14 +461,30 @@ def nnfm_bank_rows(channels, h, w, stride=1, patch=1, rows_before=0):
     return rows
 
 
+NNFM_MAX_SEGMENTS = 8       # style pictures that --nnfm-masks can tell apart (STX_NNFM_MAX_SEGMENTS)
+
+
+def nnfm_masks(args):
+    """The paths of --nnfm-masks as a list; [] without the option."""
+    given = getattr(args, 'nnfm_masks', None)
+    if not given:
+        return []
+    return [given] if isinstance(given, str) else list(given)
+
+
 def check_nnfm_options(args, known_layers=None):
     """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k / --nnfm-cover: refused before any GPU
     work together with --style-masks (there is one bank and, with masks, one style set per picture), with a stride
     below 1, with a patch that is not 1 or 3, with a k outside 1 .. 4, with a cover that is not a finite number >= 0,
     with a cover other than 0 beside patch 3 (the coverage part has no patch form) and with a bad layer list
-    (check_layer_list).  Returns the layer names."""
+    (check_layer_list).  --nnfm-masks: refused without the term, with a mask count that is not the style images',
+    with more than 8 style images, with --nnfm-patch 3 and with a cover other than 0 (the guided term matches single
+    vectors and has no coverage part).  Returns the layer names."""
     items = nnfm_layer_args(args)
+    masks = nnfm_masks(args)
     if not items:
+        if masks and not getattr(args, 'style_masks', None):
+            raise ValueError('--nnfm-masks guides the nearest-neighbour term: --nnfm-weight is needed')
         return []
     if not getattr(args, 'style_masks', None):      # (the refusal of --style-masks comes first)
         nnfm_stride(args)
@@ -470,6 +493,20 @@ def check_nnfm_options(args, known_layers=None):
         if nnfm_cover(args) != 0 and nnfm_patch(args) != 1:
             raise ValueError('--nnfm-cover %g cannot be combined with --nnfm-patch 3: the coverage part matches '
                              'single feature vectors only' % nnfm_cover(args))
+        if masks:
+            styles = getattr(args, 'style_images', None)
+            if styles is not None and len(masks) != len(styles):
+                raise ValueError('--nnfm-masks: %d mask(s) for %d style image(s); one mask per style image is needed'
+                                 % (len(masks), len(styles)))
+            if len(masks) > NNFM_MAX_SEGMENTS:
+                raise ValueError('--nnfm-masks: %d masks; at most %d style images can be told apart'
+                                 % (len(masks), NNFM_MAX_SEGMENTS))
+            if nnfm_patch(args) != 1:
+                raise ValueError('--nnfm-masks cannot be combined with --nnfm-patch 3: the guided term matches '
+                                 'single feature vectors only')
+            if nnfm_cover(args) != 0:
+                raise ValueError('--nnfm-masks cannot be combined with --nnfm-cover %g: the guided term has no '
+                                 'coverage part' % nnfm_cover(args))
     return check_layer_list(args, items, '--nnfm-weight', '--nnfm-layers', 'one bank of style features',
                             known_layers)
 

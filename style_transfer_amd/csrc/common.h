@@ -607,6 +607,50 @@ int nnfm_cover_index_launch(hipStream_t s, const float *feat, int C, int n, cons
 // *n_e partials of E = E_fwd + cover E_cov there, *n_abs of sum |S| in x.cov.abs_parts.
 int nnfm_cover_grad_launch(hipStream_t s, const float *feat, int C, int n, const NnfmScratch &x, const float *bank,
                            int M, float cover, float *sgrad, int *n_e, int *n_abs);
+// The guided term (stx_set_nnfm_guided_targets; patch 1): the bank is cut into segments, one per style picture,
+// and column i looks into segment s with the weight m_s(i) of that picture's mask map.  Segment s holds the rows
+// [off[s], off[s] + rows[s]) of the bank; indices are local to a segment.
+constexpr int kNnfmMaxSegments = 8;     // (STX_NNFM_MAX_SEGMENTS)
+struct NnfmSegments {
+    int count;
+    int off[kNnfmMaxSegments], rows[kNnfmMaxSegments];
+    int total() const { return count ? off[count - 1] + rows[count - 1] : 0; }
+    int largest() const {
+        int m = 0;
+        for (int s = 0; s < count; ++s) m = rows[s] > m ? rows[s] : m;
+        return m;
+    }
+};
+// count segments of seg_rows[s] rows, one after the other
+NnfmSegments nnfm_segments(const int *seg_rows, int count);
+// floats of the caller's that one guided term takes (slices: nnfm_plan(n, the largest segment)), and their division
+size_t nnfm_guided_scratch_floats(int C, int n, const NnfmSegments &segs, int k);
+struct NnfmGuidedScratch {
+    unsigned short *xhi, *xlo;      // as NnfmScratch's
+    float *inv_r;                   // [n]
+    float *m;                       // [segments][n]: the tile's windows of the mask maps
+    unsigned char *active;          // [segments][query blocks]: some column of the block has m_s > 0
+    float *m_parts;                 // [segments][query blocks]: the blocks' sums of m_s
+    int *idx;                       // [segments][k][n], -1 in the blocks of a pair that is not searched
+    float *part_score;              // [segments][slices][k][n], or null with one slice
+    int *part_idx;
+    float *partials;                // ceil(n / 64) of E, then as many of sum |S|
+};
+NnfmGuidedScratch nnfm_guided_carve(float *scratch, int C, int n, const NnfmSegments &segs, int k);
+// One pass over the windows `win` (fh x fw = the blob's map) of maps [segments][win.ch][win.cw]: x.m, x.active,
+// x.m_parts and -1 into idx [segments][k][n] for the pairs that will not be searched; then, a launch behind it,
+// a_out[0] = sum m / n in double in a fixed order.
+int nnfm_mask_window_launch(hipStream_t s, const float *maps, const ContentWindow &win, const NnfmSegments &segs, int k,
+                            const NnfmGuidedScratch &x, int *idx, float *a_out);
+// nnfm_search_launch per (query block, slice, segment): idx_out [segments][k][n], written for the active pairs only.
+// pieces: of the whole bank, [total rows][C] hi then lo.
+int nnfm_guided_search_launch(hipStream_t s, const NnfmGuidedScratch &x, int n, const unsigned short *pieces,
+                              const NnfmSegments &segs, int C, int *idx_out, int k);
+// sgrad = a S [C][n], S_i = sum_s m_s(i) S_{i,s} over the segments with m_s(i) > 0 in ascending s (a: a_ptr[0], or 1
+// when null); *n_parts partials of E in x.partials, then as many of sum |S| (without a)
+int nnfm_guided_grad_launch(hipStream_t s, const float *feat, int C, int n, const NnfmGuidedScratch &x, const float *bank,
+                            const NnfmSegments &segs, const int *idx, const float *a_ptr, float *sgrad, int *n_parts,
+                            int k);
 
 // image_ops.hip
 int cut_tile_launch(hipStream_t s, const float *img, int H, int W, int rx, int ry, int y0, int x0,

@@ -128,11 +128,17 @@ struct NnfmTarget {
     std::unique_ptr<DevBuf> bank, pieces;
     int patch = 1, k = 1;
     float cover = 0.f;
+    // guided (stx_set_nnfm_guided_targets; segs.count > 0): the bank's segments and the block means of every
+    // segment's image-resolution mask at the blob's scale, maps [segments][mh][mw], addressed like a content map
+    NnfmSegments segs{};
+    int mh = 0, mw = 0;
+    std::unique_ptr<DevBuf> maps;
     // [rows][patch^2 C] hi, then as many lo
     const unsigned short *pieces_hi_lo() const { return static_cast<const unsigned short *>(pieces->ptr); }
     void release() {
         bank->release();
         pieces->release();
+        if (maps) maps->release();
     }
 };
 
@@ -391,7 +397,7 @@ struct TileCall {
     int grad_mem;
 };
 
-enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, Swd, Dream };
+enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, NnfmGuided, Swd, Dream };
 constexpr size_t kNoSlot = ~(size_t)0;
 constexpr size_t kResidualScalars = 2 + 2 * 1024;   // content_sums_launch: two sums and their partials
 
@@ -484,6 +490,16 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
                       const float *bank, const unsigned short *pieces, int rows, float *sgrad, int *idx_out, float *sc,
                       const std::string &name, float *scratch, std::vector<SumJob> *defer, int k = 1, float cover = 0.f,
                       int *winner_out = nullptr, float *e_cov_out = nullptr);
+// The guided nearest-neighbour term of a blob (nnfm.hip): prepare -> mask windows and a -> search per segment
+// (-> merge) -> S into sgrad.  sc[3] = {E, sum |S|, a}; a is final behind the window pass, the two others come from
+// partials whose final sums join `defer` or are launched here.  scratch: nnfm_guided_scratch_floats(C, h * w, segs, k)
+// floats that outlive the call like term_scratch.  maps [segments][win.ch][win.cw] and `win` the tile's window of
+// them.  idx_out (or null): the lists [segments][k][h * w].  scale_by_a: sgrad = a S (the tile path), else S itself.
+int launch_nnfm_guided_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                             const float *bank, const unsigned short *pieces, const NnfmSegments &segs,
+                             const float *maps, const ContentWindow &win, float *sgrad, int *idx_out, float *sc,
+                             const std::string &name, float *scratch, std::vector<SumJob> *defer, int k,
+                             bool scale_by_a);
 // The sliced Wasserstein term of a blob (swd.hip): projection -> sort with the rank pass -> S = V^T G / D into sgrad.
 // sc[2] = {E, sum |S|}, both from partials whose final sums join `defer` or are launched here.  scratch:
 // swd_scratch_floats(C, h * w, D) floats that outlive the call like term_scratch; the records and G live in the

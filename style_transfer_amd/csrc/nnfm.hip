@@ -32,9 +32,15 @@
 // The coverage part (stx_set_nnfm_cover_targets, patch 1): behind those, every bank row looks for ITS best column --
 // the same search with the operands exchanged -- and the nnfm_cover_* kernels turn the winners into an inverted
 // index (lists in ascending row order) and add every column's rows to S in that order.  Integer atomics only.
+// The guided term (stx_set_nnfm_guided_targets, patch 1): the bank is one segment per style picture and a column looks
+// into segment s with the weight m_s of that picture's mask map.  nnfm_mask_window_kernel reads the tile's windows of
+// the maps and marks the (segment, query block) pairs with a weight above 0, nnfm_search_kernel<false, K, true> searches
+// those pairs only, segment by segment (nnfm_merge_seg_kernel behind it when the bank was cut), and
+// nnfm_guided_grad_kernel adds m_s S_{i,s} over a column's segments in ascending s.
 
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 #include "common.h"
 #include "f16x2.h"
@@ -277,13 +283,41 @@ __device__ __forceinline__ void take_k_better(float s, int j, float (&best_s)[K]
 // tap-major, and the query operand is gathered from those pieces of the w-wide map: stage t of a row reads 32
 // channels of pixel p + tap(t), found from p's (y, x) -- the right neighbour of a row's last pixel is padding --
 // and zeros outside the map.
-template <bool PATCH, int K>
+// SEG (the guided term, stx_set_nnfm_guided_targets): grid (query blocks, slices, segments) -- the same search against
+// segment blockIdx.z's rows, with that segment's idx_out [K][n] / part_* [slices][K][n] planes.  A pair (segment,
+// query block) in which no column has m_s > 0 returns at once: none of the segment's rows is read.  Slices are sized
+// from the largest segment; one past a shorter segment's last block walks nothing and leaves empty places.  The
+// plain kernel has no such arguments (an empty struct behind the others) and keeps its instruction sequence.
+template <bool SEG>
+struct NnfmSegArgs {};
+template <>
+struct NnfmSegArgs<true> {
+    NnfmSegments segs;
+    const unsigned char *active;    // [segments][query blocks]
+};
+
+template <bool PATCH, int K, bool SEG = false>
 __global__ __launch_bounds__(256) void nnfm_search_kernel(const _Float16 *__restrict__ xhi, const _Float16 *__restrict__ xlo,
                                                           const NnfmQueries<PATCH> queries,
-                                                          const _Float16 *__restrict__ bhi,
-                                                          const _Float16 *__restrict__ blo, int M, int C, int b_blocks,
-                                                          int blocks_per_slice, int *__restrict__ idx_out,
-                                                          float *__restrict__ part_score, int *__restrict__ part_idx) {
+                                                          const _Float16 *__restrict__ bhi_all,
+                                                          const _Float16 *__restrict__ blo_all, int M_all, int C,
+                                                          int b_blocks_all, int blocks_per_slice,
+                                                          int *__restrict__ idx_all, float *__restrict__ part_score_all,
+                                                          int *__restrict__ part_idx_all, const NnfmSegArgs<SEG> seg) {
+    const _Float16 *bhi = bhi_all, *blo = blo_all;
+    int M = M_all, b_blocks = b_blocks_all;
+    int *idx_out = idx_all, *part_idx = part_idx_all;
+    float *part_score = part_score_all;
+    if constexpr (SEG) {
+        const int s = blockIdx.z;
+        if (!seg.active[s * gridDim.x + blockIdx.x]) return;
+        M = seg.segs.rows[s];
+        b_blocks = (M + kNnfmB - 1) / kNnfmB;
+        const size_t first = (size_t)seg.segs.off[s] * C, plane = (size_t)K * queries.n;
+        const size_t part = gridDim.y > 1 ? (size_t)s * gridDim.y * plane : 0;      // (one slice: no part_* arrays)
+        bhi += first, blo += first;
+        idx_out += s * plane, part_score += part, part_idx += part;
+    }
     // [X hi | X lo | B hi | B lo][row][kNnfmK halves + padding]; reused for the workgroup's final merge
     __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 128 * kLdsRow];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -490,11 +524,8 @@ __global__ __launch_bounds__(256) void nnfm_merge_kernel(const float *__restrict
 
 // K > 1: the best K of the slices' K each, part [slices][K][n] -> idx_out [K][n] (-1: fewer than K rows)
 template <int K>
-__global__ __launch_bounds__(256) void nnfm_merge_k_kernel(const float *__restrict__ part_score,
-                                                           const int *__restrict__ part_idx, int n, int slices,
-                                                           int *__restrict__ idx_out) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n) return;
+__device__ __forceinline__ void merge_k_body(const float *__restrict__ part_score, const int *__restrict__ part_idx,
+                                             int n, int slices, int *__restrict__ idx_out, const int q) {
     float s[K];
     int j[K];
 #pragma unroll
@@ -516,6 +547,29 @@ __global__ __launch_bounds__(256) void nnfm_merge_k_kernel(const float *__restri
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) idx_out[(size_t)k * n + q] = j[k] == INT_MAX ? -1 : j[k];
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void nnfm_merge_k_kernel(const float *__restrict__ part_score,
+                                                           const int *__restrict__ part_idx, int n, int slices,
+                                                           int *__restrict__ idx_out) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    merge_k_body<K>(part_score, part_idx, n, slices, idx_out, q);
+}
+
+// The guided term's merge, grid (256-column groups, segments): the same walk over segment blockIdx.y's planes, for
+// the pairs that were searched; the others keep the -1 that the window pass left.  (K = 1: a slice that took nothing
+// leaves (-inf, 0), which loses to every score a row can have.)
+template <int K>
+__global__ __launch_bounds__(256) void nnfm_merge_seg_kernel(const float *__restrict__ part_score,
+                                                             const int *__restrict__ part_idx, int n, int slices,
+                                                             const unsigned char *__restrict__ active, int q_blocks,
+                                                             int *__restrict__ idx_out) {
+    const int q = blockIdx.x * 256 + threadIdx.x, seg = blockIdx.y;
+    if (q >= n || !active[seg * q_blocks + q / kNnfmQ]) return;
+    const size_t plane = (size_t)K * n;
+    merge_k_body<K>(part_score + seg * slices * plane, part_idx + seg * slices * plane, n, slices, idx_out + seg * plane, q);
 }
 
 // ---------------------------------------------------------------------------------------------- grad
@@ -628,6 +682,134 @@ __global__ __launch_bounds__(64) void nnfm_grad_k_kernel(const float *__restrict
         }
     }
     const float one_minus = wave_sum_f(valid ? 1.f - c : 0.f);
+    sum_abs = wave_sum_f(sum_abs);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = one_minus * (2.f / (float)n);
+        partials[gridDim.x + blockIdx.x] = sum_abs;
+    }
+}
+
+// ------------------------------------------------------------------------------------------- guided
+// The guided term (stx_set_nnfm_guided_targets): the bank is S segments, one per style picture, and m_s(i) in
+// [0, 1] is the tile's window of segment s's mask map --
+//   E   = (2/n) sum_i sum_s m_s(i) (1 - c_{i,s}),   S_i = sum_s m_s(i) S_{i,s},   a = sum_i sum_s m_s(i) / n
+// with c_{i,s}, S_{i,s} the plain term's against segment s alone (the mean of its K best rows).
+//
+// The window pass, grid (query blocks, segments), one column per thread: m [S][n] read through the window exactly as
+// a content map is, the block's activity byte ("some column has m_s > 0": what the search and the merge look at),
+// the block's sum of m_s, and -1 into the K index planes of a block that will not be searched.
+__global__ __launch_bounds__(kNnfmQ) void nnfm_mask_window_kernel(const float *__restrict__ maps, ContentWindow w, int K,
+                                                                   float *__restrict__ m_out,
+                                                                   unsigned char *__restrict__ active,
+                                                                   float *__restrict__ m_parts, int *__restrict__ idx) {
+    __shared__ float red[kNnfmQ / 64];
+    const int n = w.fh * w.fw, seg = blockIdx.y;
+    const int i = blockIdx.x * kNnfmQ + threadIdx.x;
+    float m = 0.f;
+    if (i < n) {
+        const int y = i / w.fw, x = i - y * w.fw;
+        m = maps[(size_t)seg * w.ch * w.cw + content_index(w, 0, y, x)];
+        m_out[(size_t)seg * n + i] = m;
+    }
+    const int any = __syncthreads_or(m > 0.f);
+    const float sum = wave_sum_f(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    if (!any && i < n)
+        for (int r = 0; r < K; ++r) idx[((size_t)seg * K + r) * n + i] = -1;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        active[seg * gridDim.x + blockIdx.x] = any ? 1 : 0;
+        m_parts[seg * gridDim.x + blockIdx.x] = red[0] + red[1];
+    }
+}
+
+// a = sum m / n from the blocks' sums, ONE workgroup, double, a fixed order (content_mask_mean_kernel's)
+__global__ __launch_bounds__(256) void nnfm_mask_mean_kernel(const float *__restrict__ m_parts, int count, int n,
+                                                             float *__restrict__ a_out) {
+    __shared__ double red[256];
+    double sum = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) sum += (double)m_parts[i];
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a_out[0] = (float)(red[0] / (double)n);
+}
+
+// The gradient, nnfm_grad_k_kernel's geometry and arithmetic: a column walks the segments with m_s(i) > 0 in
+// ascending s, forms c_{i,s} and S_{i,s} as that kernel does against the segment's rows (idx [S][KK][n], local
+// indices; a -1 is never followed: a column with m_s > 0 lies in a searched block, and every index is clamped) and
+// adds m_s S_{i,s} to its column of S, which it alone reads and writes.  The first segment of a column writes the
+// product itself and the last one leaves sum |S| (the others add +0 to it) and the factor a, so one segment with
+// m == 1 gives the plain term's bits.  A column without a segment gets zeros.
+template <int KK>
+__global__ __launch_bounds__(64) void nnfm_guided_grad_kernel(const float *__restrict__ F, int C, int n,
+                                                              const float *__restrict__ inv_r,
+                                                              const float *__restrict__ bank, const NnfmSegments segs,
+                                                              int vec, const int *__restrict__ idx,
+                                                              const float *__restrict__ m,
+                                                              const float *__restrict__ a_ptr, float *S,
+                                                              float *__restrict__ partials) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = i < n;
+    const int ii = valid ? i : n - 1;
+    const float inv = inv_r[ii];
+    const float a = a_ptr ? a_ptr[0] : 1.f;
+    const float *__restrict__ f = F + ii;
+    float *out = S + ii;
+    unsigned bits = 0;      // the column's segments
+    for (int s = 0; s < segs.count; ++s)
+        if (valid && m[(size_t)s * n + ii] > 0.f) bits |= 1u << s;
+    const int s_first = bits ? __ffs(bits) - 1 : -1, s_last = bits ? 31 - __clz(bits) : -1;
+    float e = 0.f, sum_abs = 0.f;
+    for (int s = 0; s < segs.count; ++s) {
+        if (!(bits >> s & 1u)) continue;
+        const float mv = m[(size_t)s * n + ii];
+        const bool first = s == s_first, last = s == s_last;
+        unsigned at[KK];        // (rows x C stays below 2^31)
+#pragma unroll
+        for (int r = 0; r < KK; ++r) {
+            const unsigned ju = (unsigned)idx[((size_t)s * KK + r) * n + ii];
+            at[r] = ((unsigned)segs.off[s] + (ju < (unsigned)segs.rows[s] ? ju : 0u)) * (unsigned)C;
+        }
+        float c = 0.f;
+#pragma unroll 2
+        for (int ch = 0; ch < C; ch += 4) {
+            const float4 t = knn_mean4<KK>(bank, at, ch, vec);
+            c = fmaf(f[(size_t)ch * n] * inv, t.x, c);
+            c = fmaf(f[(size_t)(ch + 1) * n] * inv, t.y, c);
+            c = fmaf(f[(size_t)(ch + 2) * n] * inv, t.z, c);
+            c = fmaf(f[(size_t)(ch + 3) * n] * inv, t.w, c);
+        }
+        const float me = mv * (1.f - c);
+        e = first ? me : e + me;
+        // (two loops, so that a column's first segment -- with hard masks its only one -- reads nothing of S and
+        // the loop has no branch inside; a wave whose columns differ in this runs both under their masks)
+        const auto add_to_column = [&](auto first_tag) {
+#pragma unroll 2
+            for (int ch = 0; ch < C; ch += 4) {
+                const float4 t4 = knn_mean4<KK>(bank, at, ch, vec);
+                const float t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float x = f[(size_t)(ch + k) * n] * inv;
+                    const float ms = mv * -((t[k] - c * x) * inv);
+                    const float tot = decltype(first_tag)::value ? ms : out[(size_t)(ch + k) * n] + ms;
+                    sum_abs += last ? fabsf(tot) : 0.f;
+                    out[(size_t)(ch + k) * n] = last ? a * tot : tot;
+                }
+            }
+        };
+        if (first)
+            add_to_column(std::true_type{});
+        else
+            add_to_column(std::false_type{});
+    }
+    if (valid && !bits)
+        for (int ch = 0; ch < C; ++ch) out[(size_t)ch * n] = 0.f;
+    const float one_minus = wave_sum_f(e);
     sum_abs = wave_sum_f(sum_abs);
     if (threadIdx.x == 0) {
         partials[blockIdx.x] = one_minus * (2.f / (float)n);
@@ -1159,7 +1341,7 @@ void search_k_launch(hipStream_t s, const dim3 grid, const NnfmScratch &x, int n
     queries.n = n;
     if constexpr (PATCH) queries.w = w;
     nnfm_search_kernel<PATCH, K><<<grid, 256, 0, s>>>(xhi, xlo, queries, bhi, blo, M, C, p.b_blocks, p.blocks_per_slice,
-                                                      idx_out, x.part_score, x.part_idx);
+                                                      idx_out, x.part_score, x.part_idx, NnfmSegArgs<false>{});
     if (p.slices > 1 && hipPeekAtLastError() == hipSuccess)
         nnfm_merge_k_kernel<K><<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
 }
@@ -1212,10 +1394,12 @@ int nnfm_search_launch(hipStream_t s, const NnfmScratch &x, int h, int w, int pa
     }
     if (patch == 3)
         nnfm_search_kernel<true, 1><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<true>{n, w}, bhi, blo, M, C, p.b_blocks,
-                                                         p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+                                                         p.blocks_per_slice, idx_out, x.part_score, x.part_idx,
+                                                         NnfmSegArgs<false>{});
     else
         nnfm_search_kernel<false, 1><<<grid, 256, 0, s>>>(xhi, xlo, NnfmQueries<false>{n}, bhi, blo, M, C, p.b_blocks,
-                                                          p.blocks_per_slice, idx_out, x.part_score, x.part_idx);
+                                                          p.blocks_per_slice, idx_out, x.part_score, x.part_idx,
+                                                         NnfmSegArgs<false>{});
     STX_CHECK_LAUNCH();
     if (p.slices > 1) {
         nnfm_merge_kernel<<<ceil_div(n, 256), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices, idx_out);
@@ -1297,6 +1481,146 @@ int nnfm_cover_grad_launch(hipStream_t s, const float *feat, int C, int n, const
     STX_CHECK_LAUNCH();
     *n_e = nb + ceil_div(M, 64);
     *n_abs = (C / 64) * nb;
+    return STX_OK;
+}
+
+// ------------------------------------------------------------------------------------------- guided
+NnfmSegments nnfm_segments(const int *seg_rows, int count) {
+    NnfmSegments segs{};
+    segs.count = std::max(0, std::min(count, kNnfmMaxSegments));
+    long long off = 0;
+    for (int s = 0; s < segs.count; ++s) {
+        segs.off[s] = (int)std::min<long long>(off, INT_MAX);
+        segs.rows[s] = seg_rows[s];
+        off += std::max(seg_rows[s], 0);
+    }
+    return segs;
+}
+
+namespace {
+
+int check_guided(const char *who, int C, long long n, const NnfmSegments &segs, int k) {
+    STX_TRY(check_k(who, k));
+    long long total = 0;
+    for (int s = 0; s < segs.count; ++s) {
+        if (segs.rows[s] < k) {
+            set_error("%s: segment %d has %d rows, fewer than k = %d", who, s, segs.rows[s], k);
+            return STX_ERR_ARG;
+        }
+        total += segs.rows[s];
+    }
+    if (segs.count < 1) {
+        set_error("%s: no segments", who);
+        return STX_ERR_ARG;
+    }
+    return check_shape(who, C, n, total, 1);
+}
+
+// the floats of NnfmGuidedScratch behind the pieces and 1 / r, in its order
+struct GuidedSizes {
+    size_t m, active, m_parts, idx, part, partials;
+};
+GuidedSizes guided_sizes(int n, const NnfmSegments &segs, int k) {
+    const NnfmPlan p = nnfm_plan(n, segs.largest());
+    const size_t S = segs.count, pairs = S * p.q_blocks;
+    return GuidedSizes{round64(S * n), round64((pairs + 3) / 4), round64(pairs), round64(S * k * n),
+                       p.slices > 1 ? round64(S * p.slices * k * n) : 0, round64(2 * (size_t)ceil_div(n, 64))};
+}
+
+}  // namespace
+
+size_t nnfm_guided_scratch_floats(int C, int n, const NnfmSegments &segs, int k) {
+    const GuidedSizes z = guided_sizes(n, segs, k);
+    return 64 + nnfm_pieces_floats(n, C) + round64(n) + z.m + z.active + z.m_parts + z.idx + 2 * z.part + z.partials;
+}
+
+NnfmGuidedScratch nnfm_guided_carve(float *scratch, int C, int n, const NnfmSegments &segs, int k) {
+    const GuidedSizes z = guided_sizes(n, segs, k);
+    NnfmGuidedScratch x;
+    float *at = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+    x.xhi = reinterpret_cast<unsigned short *>(at);
+    x.xlo = x.xhi + (size_t)n * C;
+    at += nnfm_pieces_floats(n, C);
+    x.inv_r = at;
+    at += round64(n);
+    x.m = at;
+    at += z.m;
+    x.active = reinterpret_cast<unsigned char *>(at);
+    at += z.active;
+    x.m_parts = at;
+    at += z.m_parts;
+    x.idx = reinterpret_cast<int *>(at);
+    at += z.idx;
+    x.part_score = z.part ? at : nullptr;
+    at += z.part;
+    x.part_idx = z.part ? reinterpret_cast<int *>(at) : nullptr;
+    at += z.part;
+    x.partials = at;
+    return x;
+}
+
+int nnfm_mask_window_launch(hipStream_t s, const float *maps, const ContentWindow &win, const NnfmSegments &segs, int k,
+                            const NnfmGuidedScratch &x, int *idx, float *a_out) {
+    const int n = win.fh * win.fw, q_blocks = ceil_div(n, kNnfmQ);
+    if (win.oy < 0 || win.ox < 0 || win.oy + win.fh > win.ch || win.ox + win.fw > win.cw) {
+        set_error("nnfm_mask_window_launch: the window [%d+%d, %d+%d] exceeds the %dx%d mask map", win.oy, win.fh,
+                  win.ox, win.fw, win.ch, win.cw);
+        return STX_ERR_ARG;
+    }
+    nnfm_mask_window_kernel<<<dim3(q_blocks, segs.count), kNnfmQ, 0, s>>>(maps, win, k, x.m, x.active, x.m_parts, idx);
+    STX_CHECK_LAUNCH();
+    nnfm_mask_mean_kernel<<<1, 256, 0, s>>>(x.m_parts, segs.count * q_blocks, n, a_out);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+namespace {
+
+template <int K>
+void guided_search_k_launch(hipStream_t s, const NnfmGuidedScratch &x, int n, const _Float16 *bhi, const _Float16 *blo,
+                            const NnfmSegments &segs, int C, const NnfmPlan &p, int *idx_out) {
+    nnfm_search_kernel<false, K, true><<<dim3(p.q_blocks, p.slices, segs.count), 256, 0, s>>>(
+        reinterpret_cast<const _Float16 *>(x.xhi), reinterpret_cast<const _Float16 *>(x.xlo), NnfmQueries<false>{n}, bhi,
+        blo, 0, C, 0, p.blocks_per_slice, idx_out, x.part_score, x.part_idx, NnfmSegArgs<true>{segs, x.active});
+    if (p.slices > 1 && hipPeekAtLastError() == hipSuccess)
+        nnfm_merge_seg_kernel<K><<<dim3(ceil_div(n, 256), segs.count), 256, 0, s>>>(x.part_score, x.part_idx, n, p.slices,
+                                                                                   x.active, p.q_blocks, idx_out);
+}
+
+}  // namespace
+
+int nnfm_guided_search_launch(hipStream_t s, const NnfmGuidedScratch &x, int n, const unsigned short *pieces,
+                              const NnfmSegments &segs, int C, int *idx_out, int k) {
+    STX_TRY(check_guided("nnfm_guided_search_launch", C, n, segs, k));
+    const NnfmPlan p = nnfm_plan(n, segs.largest());        // (slices sized from the largest segment)
+    const _Float16 *const bhi = reinterpret_cast<const _Float16 *>(pieces), *const blo = bhi + (size_t)segs.total() * C;
+    if (k == 1)
+        guided_search_k_launch<1>(s, x, n, bhi, blo, segs, C, p, idx_out);
+    else if (k == 2)
+        guided_search_k_launch<2>(s, x, n, bhi, blo, segs, C, p, idx_out);
+    else if (k == 3)
+        guided_search_k_launch<3>(s, x, n, bhi, blo, segs, C, p, idx_out);
+    else
+        guided_search_k_launch<4>(s, x, n, bhi, blo, segs, C, p, idx_out);
+    STX_CHECK_LAUNCH();
+    return STX_OK;
+}
+
+int nnfm_guided_grad_launch(hipStream_t s, const float *feat, int C, int n, const NnfmGuidedScratch &x, const float *bank,
+                            const NnfmSegments &segs, const int *idx, const float *a_ptr, float *sgrad, int *n_parts,
+                            int k) {
+    STX_TRY(check_guided("nnfm_guided_grad_launch", C, n, segs, k));
+    const int blocks = ceil_div(n, 64), vec = reinterpret_cast<uintptr_t>(bank) % 16 == 0;
+    if (k == 1)
+        nnfm_guided_grad_kernel<1><<<blocks, 64, 0, s>>>(feat, C, n, x.inv_r, bank, segs, vec, idx, x.m, a_ptr, sgrad, x.partials);
+    else if (k == 2)
+        nnfm_guided_grad_kernel<2><<<blocks, 64, 0, s>>>(feat, C, n, x.inv_r, bank, segs, vec, idx, x.m, a_ptr, sgrad, x.partials);
+    else if (k == 3)
+        nnfm_guided_grad_kernel<3><<<blocks, 64, 0, s>>>(feat, C, n, x.inv_r, bank, segs, vec, idx, x.m, a_ptr, sgrad, x.partials);
+    else
+        nnfm_guided_grad_kernel<4><<<blocks, 64, 0, s>>>(feat, C, n, x.inv_r, bank, segs, vec, idx, x.m, a_ptr, sgrad, x.partials);
+    STX_CHECK_LAUNCH();
+    *n_parts = blocks;
     return STX_OK;
 }
 

@@ -312,6 +312,64 @@ int stx_op_nnfm_cover_terms(stx_engine *e, const float *feat, int C, int h, int 
     return hook_nnfm_terms(e, feat, C, h, w, patch, bank, rows, s_out, index_out, out, k, cover, winner_out);
 }
 
+int stx_op_nnfm_guided_terms(stx_engine *e, const float *feat, int C, int h, int w, int k, const float *bank,
+                             const int *seg_rows, int segments, const float *mask_maps, int mh, int mw, int oy, int ox,
+                             const int roll_xy[2], float *s_out, int *index_out, double out[3]) {
+    const char *const who = "stx_op_nnfm_guided_terms";
+    if (!e || !feat || !bank || !seg_rows || !mask_maps || !s_out || !index_out || !out || C <= 0 || h <= 0 || w <= 0) {
+        set_error("%s: bad arguments", who);
+        return STX_ERR_ARG;
+    }
+    if (segments < 1 || segments > kNnfmMaxSegments) {
+        set_error("%s: %d segments (1 to %d are expected)", who, segments, kNnfmMaxSegments);
+        return STX_ERR_ARG;
+    }
+    if (k < 1 || k > kNnfmMaxK) {
+        set_error("%s: k %d (1 to %d is expected)", who, k, kNnfmMaxK);
+        return STX_ERR_ARG;
+    }
+    long long rows = 0;
+    for (int s = 0; s < segments; ++s) {
+        if (seg_rows[s] < k) {
+            set_error("%s: segment %d has %d rows, fewer than k = %d", who, s, seg_rows[s], k);
+            return STX_ERR_ARG;
+        }
+        rows += seg_rows[s];
+    }
+    if (oy < 0 || ox < 0 || oy + h > mh || ox + w > mw) {
+        set_error("%s: window exceeds the mask maps", who);
+        return STX_ERR_ARG;
+    }
+    if (C % 64 != 0) {
+        set_error("%s: the channel count %d is not a multiple of 64", who, C);
+        return STX_ERR_UNSUPPORTED;
+    }
+    const long long n = (long long)h * w;
+    if (n >= (1ll << 31) / C || rows >= (1ll << 31) / C) {
+        set_error("%s: %lld columns against %lld rows of %d channels exceed 32-bit offsets", who, n, rows, C);
+        return STX_ERR_UNSUPPORTED;
+    }
+    const NnfmSegments segs = nnfm_segments(seg_rows, segments);
+    STX_TRY(e->set_device());
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(3, &sc));
+    const size_t pieces = nnfm_pieces_floats((int)rows, C);
+    STX_TRY(e->nnfm_scratch.ensure((pieces + nnfm_guided_scratch_floats(C, h * w, segs, k)) * sizeof(float)));
+    unsigned short *bhi = static_cast<unsigned short *>(e->nnfm_scratch.ptr);
+    // what the targets' setter does once, then the launches of a guided target of stx_sc_grad_tile, in the same order
+    STX_TRY(nnfm_split_rows_launch(e->stream, bank, (int)rows, C, bhi, bhi + (size_t)rows * C));
+    STX_TRY(launch_nnfm_guided_terms(e, e->stream, feat, C, h, w, bank, bhi, segs, mask_maps,
+                                     hook_window(C, h, w, mh, mw, oy, ox, roll_xy), s_out, index_out, sc, "op",
+                                     e->nnfm_scratch.f() + pieces, nullptr, k, false));
+    STX_TRY(scalars.fetch(&host));
+    out[0] = (double)host[0];
+    out[1] = (double)host[1];
+    out[2] = (double)host[2];
+    return STX_OK;
+}
+
 int stx_op_content_terms(stx_engine *e, const float *feat, int C, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]) {

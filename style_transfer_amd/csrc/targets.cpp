@@ -334,4 +334,75 @@ int stx_set_nnfm_cover_targets(stx_engine *e, const stx_nnfm_cover_target *targe
     return set_nnfm_banks(e, targets, n, "stx_set_nnfm_cover_targets");
 }
 
+int stx_set_nnfm_guided_targets(stx_engine *e, const stx_nnfm_guided_target *targets, int n,
+                                const float *const *masks, int segments, int H, int W, int mask_mem) {
+    const char *const who = "stx_set_nnfm_guided_targets";
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    if (segments < 1 || segments > STX_NNFM_MAX_SEGMENTS) {
+        set_error("%s: %d segments (1 to %d are expected)", who, segments, STX_NNFM_MAX_SEGMENTS);
+        return STX_ERR_ARG;
+    }
+    if (!masks || H <= 0 || W <= 0) {
+        set_error("%s: no masks or a bad mask size %dx%d", who, H, W);
+        return STX_ERR_ARG;
+    }
+    for (int s = 0; s < segments; ++s) {
+        if (masks[s]) continue;
+        set_error("%s: no mask for segment %d", who, s);
+        return STX_ERR_ARG;
+    }
+    std::vector<stx_nnfm_cover_target> as_cover;
+    for (int i = 0; i < n; ++i) {
+        const stx_nnfm_guided_target &t = targets[i];
+        if (t.k < 1 || t.k > kNnfmMaxK) {
+            set_error("NNFM target %d: k %d (1 to %d is expected)", i, t.k, kNnfmMaxK);
+            return STX_ERR_ARG;
+        }
+        if (t.segments != segments || !t.seg_rows) {
+            set_error("NNFM target %d: %d segments for %d masks", i, t.segments, segments);
+            return STX_ERR_ARG;
+        }
+        long long rows = 0;
+        for (int s = 0; s < segments; ++s) {
+            if (t.seg_rows[s] < t.k) {
+                set_error("NNFM target %d: segment %d has %d rows, fewer than k = %d", i, s, t.seg_rows[s], t.k);
+                return STX_ERR_ARG;
+            }
+            rows += t.seg_rows[s];
+        }
+        if (rows >= (1ll << 31) / std::max(t.channels, 1)) {
+            set_error("NNFM target %d: %lld rows of %d channels (rows x channels below 2^31 are expected)", i, rows,
+                      t.channels);
+            return STX_ERR_UNSUPPORTED;
+        }
+        as_cover.push_back(stx_nnfm_cover_target{t.layer, t.channels, 1, t.k, (int)rows, t.bank, t.mem, t.weight, 0.f});
+    }
+    // the banks as the other setters make them; then, in a swap of its own, every bank's segments and mask maps
+    STX_TRY(set_nnfm_banks(e, as_cover.data(), n, who));
+    auto &nnfms = e->sh->nnfms;
+    MaskSource source;
+    return swap_targets(e, who, [&](bool &) -> int {
+        for (int i = 0; i < n; ++i) {
+            NnfmTarget &t = nnfms[i];
+            const int scale = e->blobs[t.blob].scale;
+            t.segs = nnfm_segments(targets[i].seg_rows, segments);
+            t.mh = ceil_div(H, scale);
+            t.mw = ceil_div(W, scale);
+            t.maps.reset(new DevBuf);
+            STX_TRY(t.maps->ensure((size_t)segments * t.mh * t.mw * sizeof(float)));
+        }
+        for (int s = 0; s < segments; ++s) {       // (one staging of a host mask serves every layer)
+            STX_TRY(source.stage(e, masks[s], H, W, mask_mem));
+            for (int i = 0; i < n; ++i) {
+                NnfmTarget &t = nnfms[i];
+                STX_TRY(mask_map_launch(e->stream, source.src, H, W, e->blobs[t.blob].scale,
+                                        t.maps->f() + (size_t)s * t.mh * t.mw));
+            }
+            // (the staging buffer is reused by the next mask: its launches must have read it)
+            if (mask_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(nnfms); });
+}
+
 }  // extern "C"

@@ -220,6 +220,41 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
     return STX_OK;
 }
 
+// The guided nearest-neighbour term of one tapped blob (nnfm.hip; patch 1): as above, with the mask windows and a
+// between prepare and search, the search per (query block, slice, segment) and the gradient weighted by the masks.
+int launch_nnfm_guided_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                             const float *bank, const unsigned short *pieces, const NnfmSegments &segs,
+                             const float *maps, const ContentWindow &win, float *sgrad, int *idx_out, float *sc,
+                             const std::string &name, float *scratch, std::vector<SumJob> *defer, int k,
+                             bool scale_by_a) {
+    const int n = h * w;
+    const NnfmGuidedScratch x = nnfm_guided_carve(scratch, C, n, segs, k);
+    const NnfmPlan plan = nnfm_plan(n, segs.largest());
+    int *const idx = idx_out ? idx_out : x.idx;
+    const std::string tag = "nnfm guided " + (k > 1 ? "k" + std::to_string(k) + " " : std::string());
+    {
+        ProfScope scope(e, tag + "prepare " + name, 0.0, stream);
+        STX_TRY(nnfm_prepare_launch(stream, feat, C, h, w, 1, 1, nullptr, x.inv_r, x.xhi, x.xlo, nullptr));
+    }
+    {
+        ProfScope scope(e, tag + "window " + name, 0.0, stream);
+        STX_TRY(nnfm_mask_window_launch(stream, maps, win, segs, k, x, idx, sc + 2));
+    }
+    {       // (the flops of a search of every pair: what the activity bytes leave out is the gain)
+        ProfScope scope(e, tag + "search " + name + " x" + std::to_string(plan.slices) + " s" + std::to_string(segs.count),
+                        6.0 * n * (double)segs.total() * C, stream);
+        STX_TRY(nnfm_guided_search_launch(stream, x, n, pieces, segs, C, idx, k));
+    }
+    ProfScope scope(e, tag + "grad " + name, 0.0, stream);
+    int n_parts = 0;
+    STX_TRY(nnfm_guided_grad_launch(stream, feat, C, n, x, bank, segs, idx, scale_by_a ? sc + 2 : nullptr, sgrad,
+                                    &n_parts, k));
+    if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
+    defer->push_back(SumJob{x.partials, n_parts, sc});
+    defer->push_back(SumJob{x.partials + n_parts, n_parts, sc + 1});
+    return STX_OK;
+}
+
 // The sliced Wasserstein term of one tapped blob (swd.hip): the projections as sort records, the segmented sort
 // whose last launch is the rank pass (G with the partials of E), S = V^T G / D with the partials of sum |S|.
 int launch_swd_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, const float *V, int D,
@@ -414,8 +449,15 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
             nnfm_slot = align(nnfm_slot + b.count());
         }
         if (const NnfmTarget *nt = nnfm_target_of(e, tp.blob)) {
-            add(TermKind::Nnfm, nt->bank->f(), nullptr, ContentWindow{}, lw * nt->weight, 2,
-                nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k, nt->cover != 0.f), nnfm_slot);
+            if (nt->segs.count) {       // guided: the tile's window of the mask maps, taken as a content map's is
+                const ContentWindow win = content_window(b, nt->mh, nt->mw, c.start, c.rx, c.ry);
+                STX_TRY(check_window(win, "NNFM mask", b));
+                add(TermKind::NnfmGuided, nt->bank->f(), nt->maps->f(), win, lw * nt->weight, 3,
+                    nnfm_guided_scratch_floats(b.channels, b.h * b.w, nt->segs, nt->k), nnfm_slot);
+            } else {
+                add(TermKind::Nnfm, nt->bank->f(), nullptr, ContentWindow{}, lw * nt->weight, 2,
+                    nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k, nt->cover != 0.f), nnfm_slot);
+            }
             plan.terms.back().nnfm = nt;
         }
         if (const SwdTarget *wt = swd_target_of(e, tp.blob)) {      // (its slot: behind the NNFM slot, if there is one)
@@ -483,6 +525,11 @@ int queue_tap_terms(TileRun &run, size_t k) {
             STX_TRY(launch_nnfm_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.nnfm->patch, t.target,
                                       t.nnfm->pieces_hi_lo(), t.nnfm->rows, sgrad, nullptr, sc, b.name, scratch,
                                       run.defer(), t.nnfm->k, t.nnfm->cover));
+            break;
+        case TermKind::NnfmGuided:    // sc[0] = E, sc[1] = sum |S| (of S without a), sc[2] = a; sgrad = a S
+            STX_TRY(launch_nnfm_guided_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.target,
+                                             t.nnfm->pieces_hi_lo(), t.nnfm->segs, t.mask, t.win, sgrad, nullptr, sc,
+                                             b.name, scratch, run.defer(), t.nnfm->k, true));
             break;
         case TermKind::Swd:           // sc[0] = E, sc[1] = sum |S|
             STX_TRY(launch_swd_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.swd->V(), t.swd->D, t.target,

@@ -188,6 +188,7 @@ UNBROADCAST_OPTIONS = (
     ('content_mask', False, 'the mask is'),
     ('stat_weight', True, 'the statistics targets are'),
     ('nnfm_weight', True, 'the banks of style features are'),
+    ('nnfm_masks', False, 'the masks are'),
     ('swd_weight', True, 'the sliced Wasserstein targets are'),
 )
 

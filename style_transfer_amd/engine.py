@@ -324,7 +324,7 @@ class TileEngine:
         self.primary.extra_taps['stat'] = list(targets)
         del keep
 
-    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0):
+    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0, segments=None, masks=None):
         """banks: {layer: B [rows, C]} -- unit rows, what ``nnfm_bank`` gives for a style picture's feature map
         (banks of several pictures concatenated) -- and weights: {layer: factor} (default 1 each); an empty
         dict: none.  The library copies a bank and builds its fp16 pieces once, here.  Call it after ``set_contents_and_styles``, which clears the banks.  A layer with a bank is part of
@@ -334,7 +334,14 @@ class TileEngine:
         the mean of its k best rows (stx_set_nnfm_knn_targets); with k = 1 the calls are those without it.
         ``cover`` above 0: that factor times the coverage part -- every bank row pulls its most similar vector
         towards itself -- is added (stx_set_nnfm_cover_targets; patch 1 only); with 0 the calls are those
-        without it."""
+        without it.  ``segments`` = {layer: [rows of style picture 0's part of the bank, of picture 1's, ...]} and
+        ``masks`` = one [H, W] array in [0, 1] per style picture, in the frame of the current targets: the guided
+        term (stx_set_nnfm_guided_targets; patch 1, no cover) -- a feature vector looks into a picture's rows with
+        the weight of that picture's mask."""
+        if (segments is None) != (masks is None):
+            raise ValueError('NNFM banks: segments and masks go together')
+        if masks is not None:
+            return self._set_nnfm_guided_targets(banks, weights, patch, k, cover, segments, masks)
         if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 4:
             raise ValueError('NNFM banks, k %r: an integer from 1 to 4 is expected' % (k,))
         if isinstance(cover, bool) or not isinstance(cover, (int, float)) or not 0 <= cover < float('inf'):
@@ -363,6 +370,46 @@ class TileEngine:
             if cover != 0:
                 t.cover = float(cover)
         lib.call(call, self.handle, table, n)
+        self.primary.extra_taps['nnfm'] = list(banks)
+        del keep
+
+    def _set_nnfm_guided_targets(self, banks, weights, patch, k, cover, segments, masks):
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 4:
+            raise ValueError('NNFM banks, k %r: an integer from 1 to 4 is expected' % (k,))
+        if patch != 1 or cover != 0:
+            raise ValueError('NNFM banks with masks, patch %r and cover %r: the guided term matches single vectors '
+                             'and has no coverage part' % (patch, cover))
+        if not 1 <= len(masks) <= lib.NNFM_MAX_SEGMENTS:
+            raise ValueError('NNFM banks with masks: %d masks (1 to %d are expected)' % (len(masks),
+                                                                                       lib.NNFM_MAX_SEGMENTS))
+        keep, n, shape, mems = [], len(banks), None, set()
+        mask_ptrs = (ctypes.c_void_p * len(masks))()
+        for si, mask in enumerate(masks):
+            ptr, mem, obj = _as_arg(mask)
+            if len(obj.shape) != 2 or (shape is not None and tuple(obj.shape) != shape):
+                raise ValueError('NNFM mask %d: [H, W] arrays of one size are expected, not %s' % (si, tuple(obj.shape)))
+            shape = tuple(obj.shape)
+            keep.append(obj)
+            mems.add(mem)
+            mask_ptrs[si] = ptr
+        if len(mems) != 1:
+            raise ValueError('NNFM masks: all on the host or all on the device')
+        table = (lib.NnfmGuidedTarget * max(1, n))()
+        for t, (layer, bank) in zip(table, banks.items()):
+            ptr, mem, obj = _as_arg(bank)
+            rows = [int(r) for r in segments[layer]]
+            if len(obj.shape) != 2 or len(rows) != len(masks) or sum(rows) != int(obj.shape[0]):
+                raise ValueError('NNFM bank %s: a [rows, C] array and %d segment row counts that add up to its rows '
+                                 'are expected, not %s and %s' % (layer, len(masks), tuple(obj.shape), rows))
+            if min(rows) < k:
+                raise ValueError('NNFM bank %s: a segment of %d rows, fewer than k = %d' % (layer, min(rows), k))
+            seg_rows = (ctypes.c_int * len(rows))(*rows)
+            keep += [obj, seg_rows]
+            t.layer, t.channels, t.k, t.segments, t.seg_rows = self._cstr(layer), int(obj.shape[1]), k, len(rows), seg_rows
+            t.bank, t.mem = ptr, mem
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_nnfm_guided_targets', self.handle, table, n, mask_ptrs, len(masks), int(shape[0]),
+                 int(shape[1]), mems.pop())
         self.primary.extra_taps['nnfm'] = list(banks)
         del keep
 

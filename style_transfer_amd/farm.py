@@ -183,7 +183,13 @@ class TileFarm:
     def set_stat_targets(self, targets, weights=None):
         self._set_on_primaries('set_stat_targets', targets, weights)
 
-    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0):
+    def set_nnfm_targets(self, banks, weights=None, patch=1, k=1, cover=0.0, segments=None, masks=None):
+        if masks is not None or segments is not None:
+            for e in self.engines:
+                e.sync()
+            for e in self.primaries():
+                e.set_nnfm_targets(banks, weights, patch, k, cover, segments=segments, masks=masks)
+            return
         self._set_on_primaries('set_nnfm_targets', banks, weights, patch, k, *((cover,) if cover else ()))
 
     def set_swd_targets(self, targets, weights=None):

@@ -80,6 +80,15 @@ class NnfmCoverTarget(ctypes.Structure):
                 ('weight', ctypes.c_double), ('cover', ctypes.c_float)]
 
 
+NNFM_MAX_SEGMENTS = 8       # STX_NNFM_MAX_SEGMENTS
+
+
+class NnfmGuidedTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('k', ctypes.c_int),
+                ('segments', ctypes.c_int), ('seg_rows', ctypes.POINTER(ctypes.c_int)), ('bank', ctypes.c_void_p),
+                ('mem', ctypes.c_int), ('weight', ctypes.c_double)]
+
+
 class SwdTarget(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('dirs', ctypes.c_int),
                 ('quantiles', ctypes.c_int), ('V', ctypes.c_void_p), ('Tq', ctypes.c_void_p), ('mem', ctypes.c_int),
@@ -121,6 +130,8 @@ SIGNATURES = {
     'stx_set_nnfm_patch_targets': [_vp, ctypes.POINTER(NnfmPatchTarget), _i],
     'stx_set_nnfm_knn_targets': [_vp, ctypes.POINTER(NnfmKnnTarget), _i],
     'stx_set_nnfm_cover_targets': [_vp, ctypes.POINTER(NnfmCoverTarget), _i],
+    'stx_set_nnfm_guided_targets': [_vp, ctypes.POINTER(NnfmGuidedTarget), _i, ctypes.POINTER(ctypes.c_void_p), _i, _i,
+                                    _i, _i],
     'stx_set_swd_targets': [_vp, ctypes.POINTER(SwdTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
@@ -179,6 +190,8 @@ SIGNATURES = {
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_cover_terms': [_vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _vp, _i, _vp, _vp, _vp, c_double_p],
+    'stx_op_nnfm_guided_terms': [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.POINTER(ctypes.c_int), _i, _vp, _i, _i, _i, _i,
+                                 ctypes.POINTER(ctypes.c_int), _vp, _vp, c_double_p],
     'stx_op_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, c_int_p, _vp, c_double_p],
     'stx_last_tile_ms': [_vp, c_float_p],
     'stx_last_tile_flops': [_vp, c_double_p, c_double_p],

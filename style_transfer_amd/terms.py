@@ -56,11 +56,12 @@ def _nothing(self, *args, **kwargs):
 class TargetTerm:
     """A term whose targets live in the engines.  Per scale ``read(st)`` comes first.  When the style targets are
     made (preprocess_images) the term sees every variant's feature maps at its ``layers``: ``begin()``,
-    ``take(st, layer, feat)`` per variant and layer, ``finish(st, count, quiet)`` with the variant count.
+    ``take(st, layer, feat)`` per variant and layer, ``picture_done(st, index)`` behind the variants of style
+    picture ``index``, ``finish(st, count, quiet)`` with the variant count.
     ``send(st, roll)`` follows every set_contents_and_styles, which clears the engines' copy (``roll``: the
     iteration's shift under --jitter).  ``drop()`` goes with the style targets."""
     layers = ()
-    read = begin = take = finish = send = drop = _nothing
+    read = begin = take = picture_done = finish = send = drop = _nothing
 
 
 class LayerTargets(TargetTerm):
@@ -108,14 +109,28 @@ class NnfmBanks(LayerTargets):
     """--nnfm-weight / --nnfm-layers / --nnfm-stride / --nnfm-patch / --nnfm-k / --nnfm-cover (nearest-neighbour feature matching):
     per layer one bank of the style pictures' unit feature vectors (3 x 3 patches of them with --nnfm-patch 3), built
     on the master GPU and concatenated over the variants; ``targets`` = {layer: DeviceArray [rows, patch^2 C]}.  The
-    banks do not depend on --nnfm-k or --nnfm-cover, which are read once per scale and go with the targets."""
+    banks do not depend on --nnfm-k or --nnfm-cover, which are read once per scale and go with the targets.
+    --nnfm-masks (``st.nnfm_masks``): the rows of a style picture -- of all its ladder sizes with --style-multiscale
+    -- are one segment of a bank, ``segments`` = {layer: [rows of picture 0, of picture 1, ...]}, and the masks,
+    resized to the scale and rolled under --jitter like the style masks, go to the engines with the banks."""
     FLAG, WEIGHT, WHAT, layer_args = '--nnfm-layers', 'nnfm_weight', 'bank', staticmethod(nnfm_layer_args)
     targets_patch = 1       # --nnfm-patch of the banks in ``targets``
+    masks = segments = _roll = None     # [H, W] float32 arrays in [0, 1] of the scale; {layer: [rows per picture]}
 
     def read(self, st):
         super().read(st)
         self.stride, self.patch, self.k = nnfm_stride(st.args), nnfm_patch(st.args), nnfm_k(st.args)
         self.cover = nnfm_cover(st.args)
+        if getattr(st, 'nnfm_masks', None) is not None:
+            self.masks = [mask_at_size(mask, st.img.shape[1:]) for mask in st.nnfm_masks]
+
+    def begin(self):
+        super().begin()
+        self._seg_rows = {layer: [] for layer in self.layers}
+
+    def picture_done(self, st, index):
+        for layer, parts in self._parts.items():
+            self._seg_rows[layer].append(sum(part.shape[0] for part in parts) - sum(self._seg_rows[layer]))
 
     def take(self, st, layer, feat):
         # (a bank past the library's offsets is refused before this part is allocated)
@@ -125,8 +140,11 @@ class NnfmBanks(LayerTargets):
     def finish(self, st, count, quiet):
         self.targets = {layer: st.engine.concat_rows(parts) for layer, parts in self._parts.items()}
         self.targets_patch = self.patch
+        self.segments = {layer: list(rows) for layer, rows in self._seg_rows.items()}
         if not quiet:
-            print('NNFM bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0])
+            def seg_note(layer):
+                return ' (%s)' % ' + '.join(map(str, self.segments[layer])) if self.masks is not None else ''
+            print('NNFM bank rows: ' + ', '.join('%s %d%s' % (layer, bank.shape[0], seg_note(layer))
                                                  for layer, bank in self.targets.items()) +
                   ('; patch %d' % self.patch if self.patch != 1 else '') + ('; k %d' % self.k if self.k != 1 else '') +
                   ('; cover %g' % self.cover if self.cover != 0 else ''))
@@ -136,8 +154,20 @@ class NnfmBanks(LayerTargets):
             bank.free()
         self.targets = None
 
+    def send(self, st, roll=None):
+        self._roll = roll       # (the masks move with the picture)
+        super().send(st, roll)
+
     def set_targets(self, farm, targets):
-        if self.cover != 0:
+        if self.masks is not None:
+            counts = {len(self.segments[layer]) for layer in targets}
+            if counts - {len(self.masks)}:
+                raise ValueError('--nnfm-masks: %d mask(s) for %s style picture(s)'
+                                 % (len(self.masks), ' / '.join(map(str, sorted(counts)))))
+            farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k, self.cover,
+                                  segments={layer: self.segments[layer] for layer in targets},
+                                  masks=[rolled_mask(mask, self._roll) for mask in self.masks])
+        elif self.cover != 0:
             farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k, self.cover)
         else:
             farm.set_nnfm_targets(targets, self.weights, self.targets_patch, self.k)

@@ -152,6 +152,7 @@ class StyleTransfer:
         # handed to transfer_multiscale.  With style masks every style picture is a style set of its own.
         self.style_masks = None
         self.content_mask = None
+        self.nnfm_masks = None
         # the optional terms of the run (terms.py), each list in the order of its library calls
         self.target_terms = terms.target_terms(args, farm.layers())
         self.image_terms = terms.image_terms(args)
@@ -255,6 +256,8 @@ class StyleTransfer:
                         feat.free()
                     count += 1
                     variants += 1
+                for term in self.target_terms:
+                    term.picture_done(self, index)
                 if self.style_masks is not None and count:     # one style set per picture
                     self.styles.append({layer: gram / count for layer, gram in total.items()})
                     total, count = {}, 0
@@ -489,11 +492,12 @@ class StyleTransfer:
         raise ValueError(args.optimizer)
 
     def transfer_multiscale(self, content_images, style_images, initial_image=None, aux_image=None,
-                            callback=None, style_masks=None, content_mask=None):
+                            callback=None, style_masks=None, content_mask=None, nnfm_masks=None):
         """Runs the planned pyramid (plan_scales), coarsest level first; every level starts from
         the Lanczos-upsampled averaged iterate of the one before (style_transfer.py:832-909).
         ``style_masks`` (--style-masks): one greyscale PIL picture per style image; ``content_mask``
-        (--content-mask): one greyscale PIL picture that weights the content term."""
+        (--content-mask): one greyscale PIL picture that weights the content term; ``nnfm_masks`` (--nnfm-masks):
+        one greyscale PIL picture per style image, the regions of the nearest-neighbour term."""
         args = self.args
         if any(image.size != content_images[0].size for image in content_images):
             raise ValueError('All of the content images must be the same size')
@@ -503,6 +507,11 @@ class StyleTransfer:
                                  'is needed' % (len(style_masks), len(style_images)))
             self.style_masks = list(style_masks)
             self.styles = []
+        if nnfm_masks:
+            if len(nnfm_masks) != len(style_images):
+                raise ValueError('--nnfm-masks: %d mask(s) for %d style image(s); one mask per style image '
+                                 'is needed' % (len(nnfm_masks), len(style_images)))
+            self.nnfm_masks = list(nnfm_masks)
         if content_mask is not None:
             if not args.content_layers:
                 raise ValueError('--content-mask needs a content term: --content-layers is empty')

@@ -4,6 +4,7 @@
     python tools/bench_nnfm.py --patch 3 [--out profiles/nnfm_patch_times.txt]
     python tools/bench_nnfm.py --k 1 2 4 [--out profiles/nnfm_knn_times.txt]
     python tools/bench_nnfm.py --cover [--out profiles/nnfm_cover_times.txt]
+    python tools/bench_nnfm.py --masks 2 [--out ...]; --masks 4 (both tables: profiles/nnfm_guided_times.txt)
 
 stx_op_nnfm_terms at the blob shapes of a 1024^2 tile -- conv3_1 (256 x 256^2) and conv4_1 (512 x 128^2) --
 against the banks of a 512^2 and of a 1024^2 style picture at --nnfm-stride 1 and 2, and at the shapes of a
@@ -33,6 +34,16 @@ lists' rows to S), each with its ratio to the forward group it stands beside (in
 gradient).  Two rows per shape: random unit rows, whose winners spread over the columns (`longest` = the longest
 list), and `one list` -- every bank row a noisy copy of column 0's direction, so that ONE column owns all M rows:
 the worst case of the index's ordering pass and of the gradient's walk (fewer repetitions).
+
+--masks S: the guided term (--nnfm-masks, stx_op_nnfm_guided_terms, K = 1) at the same shapes against a bank of S
+equal segments, M rows each, under hard stripe masks that partition the map -- `v`: S vertical stripes, `h`: S
+horizontal ones.  `window` is the mask pass with the launch that gives a, `gsearch` and `ggrad` the guided search
+(with its merge) and gradient.  Beside them, in the same run, the unguided search (stx_op_nnfm_terms) against ONE
+segment's rows (`one`) and against the whole bank of S M rows (`whole`), with the ratios gsearch / one and gsearch /
+whole, and the unguided gradient over the whole bank (`grad`).  `pairs` is the share of the (segment, 128-column
+block) pairs that are searched: a query block is 128 consecutive columns in row-major order, so a horizontal stripe
+gives every block to one segment (1 / S), while a vertical stripe does so only where it is at least 128 columns
+wide -- on a map of 128 columns or fewer every block crosses all S stripes and nothing is left out.
 """
 
 import argparse
@@ -134,6 +145,79 @@ def measure_cover(eng, rng, c, side, rows, reps, one_list):
     return {k: float(np.median(v)) for k, v in times.items()}, slices, longest
 
 
+def stripe_maps(side, segments, kind):
+    """[segments, side, side]: hard stripes that partition the map, vertical (`v`) or horizontal (`h`)."""
+    owner = np.arange(side) * segments // side
+    line = (np.arange(segments)[:, None] == owner[None, :]).astype(np.float32)      # [segments, side]
+    maps = np.empty((segments, side, side), np.float32)
+    maps[:] = line[:, None, :] if kind == 'v' else line[:, :, None]
+    return maps
+
+
+def measure_guided(eng, rng, c, side, rows, segments, kind, reps):
+    """Median ms of the guided call's groups, its slice count and the share of searched pairs."""
+    feat = eng.to_device(np.maximum(rng.standard_normal((c, side, side)), 0).astype(np.float32) + np.float32(1e-3))
+    bank = eng.to_device(unit_rows(rng, segments * rows, c))
+    maps_host = stripe_maps(side, segments, kind)
+    maps = eng.to_device(maps_host)
+    n = side * side
+    s_out = eng.empty((c, side, side))
+    idx = eng.empty((segments * n,), np.int32)
+    out = (ctypes.c_double * 3)()
+    seg_rows, roll = (ctypes.c_int * segments)(*[rows] * segments), (ctypes.c_int * 2)(0, 0)
+    call = lambda: lib.call('stx_op_nnfm_guided_terms', eng.handle, feat.ptr, c, side, side, 1, bank.ptr, seg_rows,
+                            segments, maps.ptr, side, side, 0, 0, roll, s_out.ptr, idx.ptr, out)
+    for _ in range(2):
+        call()
+    times = {'prepare': [], 'window': [], 'search': [], 'grad': []}
+    slices = 1
+    eng.profile(True)
+    for _ in range(reps):
+        call()
+        for label, ms, _ in eng.profile_read():
+            words = label.split()
+            if words[:2] == ['nnfm', 'guided'] and words[2] in times:
+                times[words[2]].append(ms)
+                if words[2] == 'search':
+                    slices = int(words[-2][1:])
+    eng.profile(False)
+    for buf in (feat, bank, maps, s_out, idx):
+        buf.free()
+    blocks = -(-n // 128)
+    padded = np.zeros((segments, blocks * 128), np.float32)
+    padded[:, :n] = maps_host.reshape(segments, n)
+    pairs = float((padded.reshape(segments, blocks, 128) > 0).any(axis=2).mean())
+    return {k: float(np.median(v)) for k, v in times.items()}, slices, pairs
+
+
+def guided_lines(eng, rng, opts):
+    S = opts.masks
+    lines = ['# --nnfm-masks: stx_op_nnfm_guided_terms (K = 1), %d equal segments of M rows under hard stripe masks, '
+             'device-event ms per group (median of %d after 2 warm-up calls)' % (S, opts.reps),
+             '# device: %s' % torch.cuda.get_device_name(0),
+             '# one, whole = the search of stx_op_nnfm_terms against M and against %d M rows, grad = its gradient over the '
+             'whole bank; all of one run' % S,
+             '# pairs = searched (segment, 128-column block) pairs / all; g/one = gsearch / one; g/whole = gsearch / whole',
+             '%6s %8s %4s %7s %7s %6s %2s %4s %6s %6s %8s %9s %9s %9s %9s %9s %9s %7s %7s'
+             % ('tile', 'blob', 'C', 'n', 'M', 'stride', 'S', 'mask', 'slices', 'pairs', 'prepare', 'window', 'gsearch',
+                'ggrad', 'one', 'whole', 'grad', 'g/one', 'g/whole')]
+    for tile, shapes in ((1024, TILE_1024), (256, TILE_256)):
+        for blob, c, side, style_side in shapes:
+            for stride in (1, 2):
+                rows = (-(-style_side // stride)) ** 2
+                one, _ = measure(eng, rng, c, side, rows, opts.reps)
+                whole, _ = measure(eng, rng, c, side, S * rows, opts.reps)
+                for kind in ('v', 'h'):
+                    t, slices, pairs = measure_guided(eng, rng, c, side, rows, S, kind, opts.reps)
+                    line = ('%6d %8s %4d %7d %7d %6d %2d %4s %6d %6.3f %8.4f %9.4f %9.4f %9.4f %9.4f %9.4f %9.4f %7.3f %7.3f'
+                            % (tile, blob, c, side * side, rows, stride, S, kind, slices, pairs, t['prepare'], t['window'],
+                               t['search'], t['grad'], one['search'], whole['search'], whole['grad'],
+                               t['search'] / one['search'], t['search'] / whole['search']))
+                    lines.append(line)
+                    print(line, flush=True)
+    return lines
+
+
 def cover_lines(eng, rng, opts):
     lines = ['# --nnfm-cover: stx_op_nnfm_cover_terms (cover 1, K = 1), device-event ms per group (median of %d, `one '
              'list` rows of %d, after 2 warm-up calls)' % (opts.reps, min(opts.reps, 5)),
@@ -209,16 +293,21 @@ def main():
                     help='rows per query, K = 1 first: every K is set beside the K = 1 of the same run')
     ap.add_argument('--cover', action='store_true',
                     help='the coverage part (--nnfm-cover): reverse search, index and gradient beside the forward groups')
+    ap.add_argument('--masks', type=int, default=0, choices=(2, 4),
+                    help='the guided term (--nnfm-masks) over S equal segments under stripe masks, beside the unguided '
+                         'search against one segment and against the whole bank')
     opts = ap.parse_args()
-    if opts.cover and (opts.patch != 1 or opts.k != [1]):
-        ap.error('--cover: the table is that of patch 1 and K = 1')
+    if (opts.cover or opts.masks) and (opts.patch != 1 or opts.k != [1]):
+        ap.error('--cover, --masks: the table is that of patch 1 and K = 1')
+    if opts.cover and opts.masks:
+        ap.error('--cover and --masks are two tables')
     if opts.k[0] != 1:
         ap.error('--k: the list begins with 1, the row the others are set beside')
     if not torch.cuda.is_available():
         sys.exit('bench_nnfm: no GPU')
     net = builtin_net('vgg19')
     eng = TileEngine(net, 0, synthetic_weights(net, 0))
-    lines = (cover_lines if opts.cover else table_lines)(eng, np.random.RandomState(0), opts)
+    lines = (cover_lines if opts.cover else guided_lines if opts.masks else table_lines)(eng, np.random.RandomState(0), opts)
     text = '\n'.join(lines) + '\n'
     if opts.out:
         os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
