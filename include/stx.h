@@ -447,6 +447,47 @@ struct stx_swd_target {
  * a tile whose blob has n > 2^22 or dirs x (n padded to a power of two) >= 2^31. */
 int stx_set_swd_targets(stx_engine *e, const struct stx_swd_target *targets, int n);
 
+/* The self-similarity content term (not in the reference): the content loss of STROTSS (Kolkin et al., CVPR 2019;
+ * NNST uses the same term).  The content term pins feature VALUES; this one holds the PATTERN of similarities
+ * between positions -- two places that look alike in the content picture should look alike in the result, two that
+ * differ should differ -- and leaves the features themselves free.  A tapped blob F [C][h][w] lies at a layer that
+ * holds a content map of content_index 0; c is the tile's window of that map, the very window the content term
+ * takes (start // s, roll // s, wrapping, the same range error).
+ * The sample grid: g is the smallest integer >= 1 with ceil(h/g) ceil(w/g) <= points; the positions are (a g, b g)
+ * in raster order, N = ceil(h/g) ceil(w/g) of them (--nnfm-stride's rule).  f_i is the column of F at position i,
+ * c_i that of c.  All sums run in a fixed order.
+ *   r_i   = |f_i|,  x_i = f_i / r_i            (r_i = 0: x_i = 0, 1/r_i = 0);   y_i likewise from c_i
+ *   DX_ij = 1 - x_i . x_j  (i != j),  DX_ii = 0 exactly;                 DC likewise from y
+ *   sX_j  = sum_i DX_ij + N 1e-6;                                        sC likewise
+ *   PX_ij = DX_ij / sX_j,  PC_ij = DC_ij / sC_j          (every column a distribution of distances)
+ *   d_ij  = PX_ij - PC_ij,  T_ij = sign(d_ij)  (sign(0) = 0)
+ *   E     = (1/N) sum_ij |d_ij|                          (0 <= E <= 2)
+ *   u_j   = sum_k T_kj PX_kj
+ *   A_ij  = (T_ij - u_j) / sX_j  (i != j),  A_ii = 0
+ *   q_i   = - sum_j (A_ij + A_ji) x_j
+ *   S_i   = (q_i - (q_i . x_i) x_i) / (2 r_i)  at the sampled positions, 0 elsewhere   ( = N d(E/2)/d f_i, T held )
+ *   loss        += lw weight E / 2
+ *   diff[layer] += lw weight S / (sum|S| / (C h w) + EPS)      (the reference's normalize, as for every term)
+ * The N 1e-6 is part of the definition: it keeps a tile of one colour (all y_i equal, DC at rounding noise)
+ * well-defined.  N = 1 gives E = 0 and S = 0.  Both sides go through the same kernels in the same order, so a blob
+ * that equals its window has d = 0 bit for bit and changes no bit of the loss or of the gradient.  D is formed in
+ * float32 (float32 products, float32 accumulation): T is the sign of a difference of nearly equal numbers wherever
+ * result and content agree.  No float atomics; the same inputs give the same bits. */
+struct stx_selfsim_target {
+    const char *layer;
+    int points;             /* the most grid positions, 2 .. 4096 */
+    double weight;
+};
+/* Replaces all self-similarity targets of the engine's group (n = 0: none); one per layer at most.  A target
+ * carries no data of its own: the term reads the layer's content map of content_index 0, and a layer that holds
+ * none is STX_ERR_ARG here.  The targets are shared like the style targets (stx_engine_create_shared) and
+ * stx_set_contents_and_styles clears them: call this behind it.  A layer with a target is part of every
+ * stx_sc_grad_tile evaluation under the rules of stx_set_stat_targets: the layer_weight of its tap if the tap list
+ * names it, lw = 1 otherwise, and all layers on one path; whether the tap says is_content does not matter.  The
+ * term follows the blob's SWD term in the loss and in the gradient.  STX_ERR_ARG for points outside 2 .. 4096;
+ * STX_ERR_UNSUPPORTED for a layer whose channel count is not a multiple of 64. */
+int stx_set_selfsim_targets(stx_engine *e, const struct stx_selfsim_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -824,6 +865,12 @@ int stx_op_nnfm_guided_terms(stx_engine *e, const float *feat, int channels, int
  * = r_d(i) [dirs][h w], which holds the sort to account.  Errors leave the outputs alone. */
 int stx_op_swd_terms(stx_engine *e, const float *feat, int channels, int h, int w, const float *V, int dirs,
                      const float *Tq, int quantiles, float *s_out, int *rank_out, double out[2]);
+/* The launches of a self-similarity target (stx_set_selfsim_targets) on two plain arrays [channels][h][w] (all
+ * STX_DEVICE): the blob and, in place of the content map's window, an array of the blob's size.  sgrad = S
+ * [channels][h][w], zero off the grid; sc = {E, sum |S|}; signs_out (or null) = T as int8 [N][N], which holds the
+ * signs to account.  Errors leave the outputs alone. */
+int stx_op_selfsim_terms(stx_engine *e, const float *feat, const float *content, int channels, int h, int w,
+                         int points, float *sgrad, double sc[2], signed char *signs_out);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

@@ -195,6 +195,28 @@ _EXTENSIONS = [
                            help='directions per layer of the sliced Wasserstein term, an integer from 1 to 4096: '
                                 'orthonormal bases drawn once per run from --seed and the layer name (default: the '
                                 "layer's channel count, one basis)")),
+    (('--selfsim-weight',), dict(metavar='WEIGHT', type=ffloat,
+                                 help='self-similarity content factor (STROTSS, NNST): holds the pattern of '
+                                      'similarities between positions of the content picture -- places that look '
+                                      'alike there should look alike in the result, places that differ should '
+                                      'differ -- and leaves the feature values free, so it does not fight the '
+                                      'per-pixel style terms (--nnfm-weight, --swd-weight) as the content term '
+                                      'does; with -cw 0 or an empty --content-layers it replaces that term.  '
+                                      '--content-mask weights the content term only and leaves this one alone.  '
+                                      'At its default (conv4_2, 1024 points) the term takes 0.41 ms beside a 3.8 ms '
+                                      'evaluation of a 1024 x 1024 tile on an MI355X, a ninth of it, and about as '
+                                      'much beside the 0.83 ms of a 256 x 256 tile; with --selfsim-points 4096, 1.5 '
+                                      'ms; read once per scale; 0 or absent: off (default: 0)')),
+    (('--selfsim-layers',), dict(nargs='+', metavar='LAYER',
+                                 help='layers of the self-similarity term as name or name:weight; the weights are '
+                                      'normalised to --selfsim-weight like those of a layer list and read once per '
+                                      'scale; a content map is taken at every one of them (default: the names of '
+                                      '--content-layers, or conv4_2 when that list is empty)')),
+    (('--selfsim-points',), dict(metavar='N', type=int,
+                                 help='most sample positions of the self-similarity term per tile and layer, an '
+                                      'integer from 2 to 4096: the blob is thinned to every g-th row and column, g '
+                                      'the smallest step that fits; the term forms two N x N matrices, so its cost '
+                                      'grows with N squared (default: 1024)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -365,11 +387,12 @@ def stat_layer_args(args):
     return [given] if isinstance(given, str) else list(given)
 
 
-def check_layer_list(args, items, weight_flag, layers_flag, one_set, known_layers=None):
+def check_layer_list(args, items, weight_flag, layers_flag, one_set, known_layers=None, style_side=True):
     """A ``LAYER[:weight]`` list of a style term that has one set of targets (``one_set`` says of what): refused
     together with --style-masks, with a malformed entry, with a layer named twice, with weights that are all 0
-    or -- when the network's layers are known -- with a layer it does not have.  Returns the layer names."""
-    if getattr(args, 'style_masks', None):
+    or -- when the network's layers are known -- with a layer it does not have.  Returns the layer names.
+    ``style_side`` False: the list of a content-side term, which --style-masks leaves alone."""
+    if style_side and getattr(args, 'style_masks', None):
         raise ValueError('%s cannot be combined with --style-masks: there is %s, and masks make every style '
                          'picture a style set of its own' % (weight_flag, one_set))
     names, total = [], 0.0
@@ -562,6 +585,53 @@ def check_swd_options(args, known_layers=None):
                             known_layers)
 
 
+SELFSIM_POINTS_DEFAULT = 1024
+SELFSIM_MAX_POINTS = 4096
+
+
+def selfsim_layer_args(args):
+    """The layer list of the self-similarity content term (``name`` or ``name:weight`` each): --selfsim-layers, or
+    the names of --content-layers, or conv4_2 when that list is empty.  [] when the term is off (no
+    --selfsim-weight, or 0)."""
+    if not option_on(args, 'selfsim_weight'):
+        return []
+    given = getattr(args, 'selfsim_layers', None)
+    if not given:
+        content = getattr(args, 'content_layers', None) or []
+        content = [content] if isinstance(content, str) else list(content)
+        given = [str(item).partition(':')[0] for item in content] or ['conv4_2']
+    return [given] if isinstance(given, str) else list(given)
+
+
+def selfsim_points(args):
+    """--selfsim-points as an integer from 2 to 4096 (default 1024); anything else, bools and floats included, is a
+    ValueError."""
+    raw = raw_option(args, 'selfsim_points', SELFSIM_POINTS_DEFAULT)
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 2 <= raw <= SELFSIM_MAX_POINTS:
+        raise ValueError('--selfsim-points %r: an integer from 2 to %d is expected' % (raw, SELFSIM_MAX_POINTS))
+    return int(raw)
+
+
+def selfsim_grid(h, w, points):
+    """(g, rows, columns) of the term's sample grid on an h x w blob: g is the smallest integer >= 1 with
+    ceil(h / g) ceil(w / g) <= points; the positions are (a g, b g) in raster order (include/stx.h)."""
+    g = 1
+    while -(-h // g) * -(-w // g) > points:
+        g += 1
+    return g, -(-h // g), -(-w // g)
+
+
+def check_selfsim_options(args, known_layers=None):
+    """--selfsim-weight / --selfsim-layers / --selfsim-points: refused before any GPU work with --selfsim-points
+    outside 2 .. 4096 and with a bad layer list (check_layer_list).  A content-side term: --style-masks and
+    --content-mask leave it alone.  Returns the layer names."""
+    items = selfsim_layer_args(args)
+    if not items:
+        return []
+    selfsim_points(args)
+    return check_layer_list(args, items, '--selfsim-weight', '--selfsim-layers', '', known_layers, style_side=False)
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -591,5 +661,6 @@ def parse_args(state=None, argv=None, config_py=None):
     check_stat_options(args)
     check_nnfm_options(args)
     check_swd_options(args)
+    check_selfsim_options(args)
     check_photo_options(args)
     return args

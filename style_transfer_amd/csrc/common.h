@@ -526,6 +526,48 @@ int swd_grad_launch(hipStream_t s, const float *V, const float *G, int C, int n,
 // out [D][Q] = resample(sorted row, n -> Q)
 int swd_quantiles_launch(hipStream_t s, const void *records, int n, int D, int Q, float *out);
 
+// selfsim.hip: the self-similarity content term of a blob [C][h][w] against the tile's window of a content map
+// (include/stx.h, stx_set_selfsim_targets), on a sample grid of at most `points` positions.
+constexpr int kSelfsimMaxPoints = 4096;
+constexpr float kSelfsimEps = 1e-6f;
+// g = the smallest integer >= 1 with ceil(h / g) ceil(w / g) <= points; the positions (a g, b g), a < gh, b < gw,
+// in raster order; N = gh gw
+struct SelfsimGrid {
+    int g, gh, gw, N;
+};
+SelfsimGrid selfsim_grid(int h, int w, int points);
+// STX_ERR_ARG for points outside 2 .. kSelfsimMaxPoints, STX_ERR_UNSUPPORTED for channels not a multiple of 64
+int selfsim_check(const char *who, int C, int points);
+// One side of the term: planes [C][mh][mw] at p, the sampled pixel (y, x) read at ((oy + y) mod mh, (ox + x) mod mw).
+// A plain [C][h][w] array is {p, h, w, 0, 0}; a content map's window is the map with origin (oy - sy, ox - sx).
+struct SelfsimSource {
+    const float *p;
+    int mh, mw, oy, ox;
+};
+// The term's scratch, all of which outlives its launches (the final sums of e_parts and abs_parts may be deferred).
+struct SelfsimScratch {
+    float *rows;            // [2][N][C]: the unit columns of F, then of the window
+    float *inv_r;           // [2][N]
+    float *D;               // [2][N][N]: DX then DC; the column pass leaves A where DX was
+    float *col_parts;       // [2][ceil(N / 64)][N]: column sums of D per block of 64 rows
+    float *u_parts;         // [ceil(N / 64)][N]
+    float *q;               // [N][C]
+    signed char *T;         // [N][N]
+    float *e_parts;         // ceil(N / 64)^2 partials of E
+    float *abs_parts;       // ceil(N / 64) partials of sum |S|
+    size_t floats;
+};
+SelfsimScratch selfsim_scratch(float *base, int C, int N);
+size_t selfsim_scratch_floats(int C, int N);
+int selfsim_prepare_launch(hipStream_t s, const SelfsimSource &feat, const SelfsimSource &content, int C,
+                           const SelfsimGrid &gr, const SelfsimScratch &x);
+int selfsim_dist_launch(hipStream_t s, int C, int N, const SelfsimScratch &x);
+// signs: T int8 [N][N] (x.T, or the caller's array); *n_e partials of E in x.e_parts
+int selfsim_cols_launch(hipStream_t s, int N, const SelfsimScratch &x, signed char *signs, int *n_e);
+// sgrad [C][h][w] = S (cleared first when the grid skips pixels); *n_abs partials of sum |S| in x.abs_parts
+int selfsim_grad_launch(hipStream_t s, int C, int h, int w, const SelfsimGrid &gr, const SelfsimScratch &x,
+                        float *sgrad, int *n_abs);
+
 // nnfm.hip: the nearest-neighbour feature matching term of a blob [C][n] against a bank [M][C] of unit rows
 // (include/stx.h, stx_set_nnfm_targets).  The search multiplies kNnfmQ query columns by kNnfmB bank rows per
 // workgroup, kNnfmK channels per LDS stage; with few query blocks the bank is cut into slices.

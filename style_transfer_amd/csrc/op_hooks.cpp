@@ -196,6 +196,28 @@ int stx_op_swd_terms(stx_engine *e, const float *feat, int C, int h, int w, cons
     return STX_OK;
 }
 
+int stx_op_selfsim_terms(stx_engine *e, const float *feat, const float *content, int C, int h, int w, int points,
+                         float *sgrad, double sc_out[2], signed char *signs_out) {
+    if (!e || !feat || !content || !sgrad || !sc_out || h <= 0 || w <= 0) {
+        set_error("stx_op_selfsim_terms: bad arguments");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(selfsim_check("stx_op_selfsim_terms", C, points));
+    STX_TRY(e->set_device());
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
+    STX_TRY(e->selfsim_io.ensure(selfsim_scratch_floats(C, selfsim_grid(h, w, points).N) * sizeof(float)));
+    // the launches of a self-similarity target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_selfsim_terms(e, e->stream, feat, SelfsimSource{content, h, w, 0, 0}, C, h, w, points, sgrad,
+                                 signs_out, sc, "op", e->selfsim_io.f(), nullptr));
+    STX_TRY(scalars.fetch(&host));
+    sc_out[0] = (double)host[0];
+    sc_out[1] = (double)host[1];
+    return STX_OK;
+}
+
 int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *content,
                                 int content_h, int content_w, const float *mask_map, int oy, int ox,
                                 const int roll_xy[2], float *sgrad_out, double out[3]) {

@@ -1,7 +1,7 @@
 // libstx host side: the targets of an engine group (stx_set_*).
 //
 // The engines of one GPU share their targets (SharedState): the content maps and style Grams, and behind them
-// the style masks, the content mask, the statistics targets, the NNFM banks and the sliced Wasserstein targets, which go when new contents
+// the style masks, the content mask, the statistics targets, the NNFM banks, the sliced Wasserstein and the self-similarity targets, which go when new contents
 // and styles arrive.  Every setter is one swap (swap_targets) around a body that validates and copies.
 
 #include <cmath>
@@ -298,6 +298,33 @@ int stx_set_swd_targets(stx_engine *e, const struct stx_swd_target *targets, int
         }
         return STX_OK;
     }, [&]() { clear_targets(swds); });
+}
+
+int stx_set_selfsim_targets(stx_engine *e, const struct stx_selfsim_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    auto &selfsims = e->sh->selfsims;
+    return swap_targets(e, "stx_set_selfsim_targets", [&](bool &) -> int {
+        clear_targets(selfsims);
+        for (int i = 0; i < n; ++i) {
+            const struct stx_selfsim_target &ft = targets[i];
+            const int blob = e->find_blob(ft.layer);
+            bool twice = false, has_map = false;
+            for (const SelfsimTarget &t : selfsims) twice |= t.blob == blob;
+            if (blob <= 0 || twice) {
+                set_error("self-similarity target %d: bad layer '%s' (unknown, the input, or given twice)", i,
+                          ft.layer ? ft.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            for (const ContentTarget &ct : e->sh->contents) has_map |= ct.blob == blob && ct.index == 0;
+            if (!has_map) {
+                set_error("self-similarity target %d: layer %s holds no content map of content_index 0", i, ft.layer);
+                return STX_ERR_ARG;
+            }
+            STX_TRY(selfsim_check("stx_set_selfsim_targets", e->blobs[blob].channels, ft.points));
+            selfsims.push_back(SelfsimTarget{blob, ft.points, ft.weight});
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(selfsims); });
 }
 
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {

@@ -436,7 +436,9 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
     const auto has_statistics = [&](int blob) {     // ... or an NNFM bank: a target that makes the layer part of the call
         return std::any_of(e->sh->stats.begin(), e->sh->stats.end(), [=](const StatTarget &t) { return t.blob == blob; }) ||
                std::any_of(e->sh->nnfms.begin(), e->sh->nnfms.end(), [=](const NnfmTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->swds.begin(), e->sh->swds.end(), [=](const SwdTarget &t) { return t.blob == blob; });
+               std::any_of(e->sh->swds.begin(), e->sh->swds.end(), [=](const SwdTarget &t) { return t.blob == blob; }) ||
+               std::any_of(e->sh->selfsims.begin(), e->sh->selfsims.end(),
+                           [=](const SelfsimTarget &t) { return t.blob == blob; });
     };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
@@ -473,6 +475,13 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
         t.layer_weight = 1.0;
         plan.extra.push_back(t);
         order.push_back(Tap{wt.blob, &plan.extra.back()});
+    }
+    for (const SelfsimTarget &ft : e->sh->selfsims) {   // ... and a layer with a self-similarity target
+        if (tapped(ft.blob)) continue;
+        stx_tap t{};
+        t.layer_weight = 1.0;
+        plan.extra.push_back(t);
+        order.push_back(Tap{ft.blob, &plan.extra.back()});
     }
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");

@@ -289,6 +289,37 @@ int launch_swd_terms(stx_engine *e, hipStream_t stream, const float *feat, int C
     return STX_OK;
 }
 
+// The self-similarity content term of one tapped blob (selfsim.hip): both sides' unit columns on the sample grid,
+// the two distance matrices in one launch, the column pass (T, the partials of E, A), q = -(A + A^T) X with its
+// projection into the blob's layout (the partials of sum |S|).
+int launch_selfsim_terms(stx_engine *e, hipStream_t stream, const float *feat, const SelfsimSource &content, int C,
+                         int h, int w, int points, float *sgrad, signed char *signs_out, float *sc,
+                         const std::string &name, float *scratch, std::vector<SumJob> *defer) {
+    STX_TRY(selfsim_check("launch_selfsim_terms", C, points));
+    const SelfsimGrid gr = selfsim_grid(h, w, points);
+    const SelfsimScratch x = selfsim_scratch(scratch, C, gr.N);
+    const double product = 2.0 * (double)gr.N * gr.N * C;
+    {
+        ProfScope scope(e, "selfsim prepare " + name, 0.0, stream);
+        STX_TRY(selfsim_prepare_launch(stream, SelfsimSource{feat, h, w, 0, 0}, content, C, gr, x));
+    }
+    {
+        ProfScope scope(e, "selfsim dist " + name, 2.0 * product, stream);
+        STX_TRY(selfsim_dist_launch(stream, C, gr.N, x));
+    }
+    int n_e = 0, n_abs = 0;
+    {
+        ProfScope scope(e, "selfsim cols " + name, 0.0, stream);
+        STX_TRY(selfsim_cols_launch(stream, gr.N, x, signs_out ? signs_out : x.T, &n_e));
+    }
+    ProfScope scope(e, "selfsim grad " + name, product, stream);
+    STX_TRY(selfsim_grad_launch(stream, C, h, w, gr, x, sgrad, &n_abs));
+    if (!defer) return sum_partials2_launch(stream, x.e_parts, n_e, sc, x.abs_parts, n_abs, sc + 1);
+    defer->push_back(SumJob{x.e_parts, n_e, sc});
+    defer->push_back(SumJob{x.abs_parts, n_abs, sc + 1});
+    return STX_OK;
+}
+
 // A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
 // S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
 int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
@@ -321,6 +352,13 @@ static const NnfmTarget *nnfm_target_of(const stx_engine *e, int blob) {
 // The sliced Wasserstein target of `blob` (stx_set_swd_targets), or null.
 static const SwdTarget *swd_target_of(const stx_engine *e, int blob) {
     for (const SwdTarget &t : e->sh->swds)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
+
+// The self-similarity target of `blob` (stx_set_selfsim_targets), or null.
+static const SelfsimTarget *selfsim_target_of(const stx_engine *e, int blob) {
+    for (const SelfsimTarget &t : e->sh->selfsims)
         if (t.blob == blob) return &t;
     return nullptr;
 }
@@ -381,7 +419,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         const double lw = tp.t->layer_weight;
         plan.first_term[k] = plan.terms.size();
         // The tap's gradient buffer: the style slots, then (each group from a 256-byte boundary) the masked
-        // content slots, the statistics slot, the NNFM slot and the SWD slot.
+        // content slots, the statistics slot, the NNFM slot, the SWD slot and the self-similarity slot.
         size_t styles_here = 0;
         for (const StyleTarget &st : sh.styles) styles_here += tp.t->is_style && st.blob == tp.blob;
         size_t style_slot = 0, content_slot = align(styles_here * b.count());
@@ -468,6 +506,23 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 swd_scratch_floats(b.channels, b.h * b.w, wt->D), swd_slot);
             plan.terms.back().swd = wt;
         }
+        if (const SelfsimTarget *ft = selfsim_target_of(e, tp.blob)) {  // (its slot: behind the SWD slot, if there is one)
+            STX_TRY(selfsim_check(("self-similarity target of layer " + b.name).c_str(), b.channels, ft->points));
+            const ContentTarget *map = nullptr;     // the layer's content map of content_index 0, whatever the tap says
+            for (const ContentTarget &ct : sh.contents)
+                if (ct.blob == tp.blob && ct.index == 0 && !map) map = &ct;
+            if (!map) {
+                set_error("self-similarity target of layer %s: no content map of content_index 0 there", b.name.c_str());
+                return STX_ERR_STATE;
+            }
+            const ContentWindow win = content_window(b, map->h, map->w, c.start, c.rx, c.ry);
+            STX_TRY(check_window(win, "content", b));
+            size_t slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
+            if (swd_target_of(e, tp.blob)) slot = align(slot + b.count());
+            add(TermKind::Selfsim, map->feat->f(), nullptr, win, lw * ft->weight, 2,
+                selfsim_scratch_floats(b.channels, selfsim_grid(b.h, b.w, ft->points).N), slot);
+            plan.terms.back().points = ft->points;
+        }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
         // weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
         if (tp.t->is_dd)
@@ -534,6 +589,13 @@ int queue_tap_terms(TileRun &run, size_t k) {
         case TermKind::Swd:           // sc[0] = E, sc[1] = sum |S|
             STX_TRY(launch_swd_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.swd->V(), t.swd->D, t.target,
                                      t.swd->Q, sgrad, nullptr, sc, b.name, scratch, run.defer()));
+            break;
+        case TermKind::Selfsim:       // sc[0] = E, sc[1] = sum |S|; the window as the content term addresses it
+            STX_TRY(launch_selfsim_terms(e, e->stream, b.data.f(),
+                                         SelfsimSource{t.target, t.win.ch, t.win.cw, t.win.oy - t.win.sy,
+                                                       t.win.ox - t.win.sx},
+                                         b.channels, b.h, b.w, t.points, sgrad, nullptr, sc, b.name, scratch,
+                                         run.defer()));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

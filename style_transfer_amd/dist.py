@@ -190,6 +190,7 @@ UNBROADCAST_OPTIONS = (
     ('nnfm_weight', True, 'the banks of style features are'),
     ('nnfm_masks', False, 'the masks are'),
     ('swd_weight', True, 'the sliced Wasserstein targets are'),
+    ('selfsim_weight', True, 'the self-similarity targets are'),
 )
 
 
@@ -250,7 +251,7 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks, --content-mask, --stat-weight, --nnfm-weight or --swd-weight is refused here
+    a run with --style-masks, --content-mask, --stat-weight, --nnfm-weight, --swd-weight or --selfsim-weight is refused here
     (refuse_unbroadcast_options)."""
     if args is not None:
         refuse_unbroadcast_options(args)

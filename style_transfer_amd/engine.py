@@ -25,7 +25,8 @@ from .netspec import NetSpec
 
 _TYPE_CODES = {'Input': lib.LAYER_INPUT, 'Convolution': lib.LAYER_CONV, 'ReLU': lib.LAYER_RELU,
                'Pooling': lib.LAYER_POOL}
-EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd')   # the targets that tap layers of their own, in the order of their taps
+# the targets that tap layers of their own, in the order of their taps
+EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd', 'selfsim')
 
 
 class DeviceArray:
@@ -435,6 +436,19 @@ class TileEngine:
         lib.call('stx_set_swd_targets', self.handle, table, n)
         self.primary.extra_taps['swd'] = list(targets)
         del keep
+
+    def set_selfsim_targets(self, points, weights=None):
+        """points: {layer: the most grid positions, 2 .. 4096} -- one self-similarity target per layer, each at a layer
+        that holds a content map of content_index 0, which is all the term reads -- and weights: {layer: factor}
+        (default 1 each); an empty dict: none (stx_set_selfsim_targets).  Call it after ``set_contents_and_styles``,
+        which clears them.  A layer with a target is part of every tile evaluation of the group from then on."""
+        n = len(points)
+        table = (lib.SelfsimTarget * max(1, n))()
+        for t, (layer, count) in zip(table, points.items()):
+            t.layer, t.points = self._cstr(layer), int(count)
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_selfsim_targets', self.handle, table, n)
+        self.primary.extra_taps['selfsim'] = list(points)
 
     def swd_target(self, feat, V, Q):
         """Tq [D, Q] float32: per direction of V [D, C] the quantile function of a [C,h,w] feature map's

@@ -195,6 +195,9 @@ class TileFarm:
     def set_swd_targets(self, targets, weights=None):
         self._set_on_primaries('set_swd_targets', targets, weights)
 
+    def set_selfsim_targets(self, points, weights=None):
+        self._set_on_primaries('set_selfsim_targets', points, weights)
+
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)
 

@@ -95,6 +95,10 @@ class SwdTarget(ctypes.Structure):
                 ('weight', ctypes.c_double)]
 
 
+class SelfsimTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('points', ctypes.c_int), ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -133,6 +137,7 @@ SIGNATURES = {
     'stx_set_nnfm_guided_targets': [_vp, ctypes.POINTER(NnfmGuidedTarget), _i, ctypes.POINTER(ctypes.c_void_p), _i, _i,
                                     _i, _i],
     'stx_set_swd_targets': [_vp, ctypes.POINTER(SwdTarget), _i],
+    'stx_set_selfsim_targets': [_vp, ctypes.POINTER(SelfsimTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -186,6 +191,7 @@ SIGNATURES = {
     'stx_op_masked_content_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, c_int_p, _vp, c_double_p],
     'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_swd_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, c_double_p],
+    'stx_op_selfsim_terms': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, c_double_p, _vp],
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],

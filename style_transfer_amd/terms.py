@@ -11,9 +11,10 @@ from PIL import Image
 
 from . import image_ops
 from .config_system import (LAP_POOLS_DEFAULT, SWD_QUANTILES, ValuePlaceholder, check_lap_pools, check_nnfm_options,
-                            check_photo_options, check_stat_options, check_swd_options, ffloat, nnfm_bank_rows,
-                            nnfm_layer_args, nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on, stat_layer_args,
-                            swd_dirs, swd_directions, swd_layer_args)
+                            check_photo_options, check_selfsim_options, check_stat_options, check_swd_options, ffloat,
+                            nnfm_bank_rows, nnfm_layer_args, nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on,
+                            selfsim_layer_args, selfsim_points, stat_layer_args, swd_dirs, swd_directions,
+                            swd_layer_args)
 
 
 def parse_weights(args, master_weight):
@@ -59,8 +60,9 @@ class TargetTerm:
     ``take(st, layer, feat)`` per variant and layer, ``picture_done(st, index)`` behind the variants of style
     picture ``index``, ``finish(st, count, quiet)`` with the variant count.
     ``send(st, roll)`` follows every set_contents_and_styles, which clears the engines' copy (``roll``: the
-    iteration's shift under --jitter).  ``drop()`` goes with the style targets."""
-    layers = ()
+    iteration's shift under --jitter).  ``drop()`` goes with the style targets.  ``content_layers``: the layers whose
+    content maps the term reads; preprocess_images takes the content features there too."""
+    layers = content_layers = ()
     read = begin = take = picture_done = finish = send = drop = _nothing
 
 
@@ -201,6 +203,23 @@ class SwdTargets(LayerTargets):
         farm.set_swd_targets(targets, self.weights)
 
 
+class SelfsimTargets(TargetTerm):
+    """--selfsim-weight / --selfsim-layers / --selfsim-points (the self-similarity content term): the term reads the
+    content maps at its layers (``content_layers``) and has no data of its own -- per layer the most grid positions
+    and a weight.  Under --jitter the maps are retaken every iteration with the contents, and ``send`` re-arms the
+    term behind them."""
+    weights = points = None     # {layer: weight} of the scale; --selfsim-points
+
+    def read(self, st):
+        names, self.weights = parse_weights(selfsim_layer_args(st.args), getattr(st.args, 'selfsim_weight'))
+        self.content_layers, self.points = tuple(names), selfsim_points(st.args)
+
+    def send(self, st, roll=None):
+        # (the term goes with content maps: under --jitter there are none until the first step)
+        if self.weights and st.contents:
+            st.farm.set_selfsim_targets({layer: self.points for layer in self.weights}, self.weights)
+
+
 class Masks(TargetTerm):
     """--style-masks / --content-mask (spatial control): ``st.style_masks`` and ``st.content_mask`` resized to the
     scale's content size.  Under --jitter the engines hold content maps of the rolled picture and shift nothing,
@@ -226,7 +245,8 @@ class Masks(TargetTerm):
 def target_terms(args, known_layers):
     """The target terms of a run, in the order they are sent; a bad option is refused here, before any GPU work.
     (The masks are handed to transfer_multiscale, so their term is always listed.)"""
-    checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks), (check_swd_options, SwdTargets))
+    checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks), (check_swd_options, SwdTargets),
+               (check_selfsim_options, SelfsimTargets))
     return [cls() for check, cls in checked if check(args, known_layers)] + [Masks()]
 
 

@@ -222,7 +222,8 @@ class StyleTransfer:
         ``color_from`` (--preserve-color match): every style variant is recoloured on the GPU to the
         colour mean and covariance of this picture before its features are taken.  The target terms see the
         same feature maps at their own layers (terms.TargetTerm): the features are taken at the union of the
-        lists, once."""
+        lists, once; likewise the content maps at the union of ``content_layers`` and every term's
+        ``content_layers`` (a map that no content tap and no term's target names has no effect)."""
         farm, tile = self.farm, self.args.tile_size
         if roll is None:
             print('Preprocessing the style image(s)...')
@@ -267,10 +268,16 @@ class StyleTransfer:
                 term.finish(self, variants, quiet=roll is not None)
         if roll is None:
             print('Preprocessing the content image(s)...')
-        self.contents += [farm.prepare_features_device(self.pil_to_image(image), content_layers,
+        map_layers = self._content_map_layers(content_layers)
+        self.contents += [farm.prepare_features_device(self.pil_to_image(image), map_layers,
                                                        tile, passes=10 if roll is None else 1,
                                                        roll=roll)
                           for image in content_images]
+
+    def _content_map_layers(self, content_layers):
+        """The layers where content maps are taken: the content layers, then those the target terms read."""
+        return list(dict.fromkeys(list(content_layers) +
+                                  [layer for term in self.target_terms for layer in term.content_layers]))
 
     def _send_targets(self, roll=None):
         """The contents and styles to the engines, then every target term's (``roll``: --jitter's shift)."""
@@ -362,7 +369,8 @@ class StyleTransfer:
             self.old_avg = self.engine.empty(self.img.shape)
         self.old_avg.copy_from(self.img)
         self.step += 1
-        deepest_content = [l for l in reversed(self.farm.layers()) if l in content_layers][0]
+        # (the deepest layer with a content map: the iteration's shift is a multiple of its scale)
+        deepest_content = [l for l in reversed(self.farm.layers()) if l in self._content_map_layers(content_layers)][0]
         jitter_scale, _ = self.farm.layer_info(deepest_content)
         img_size = np.array(self.img.shape[-2:])
 
