@@ -36,6 +36,15 @@ def masked_content_gradient(F, c, m):
     return s / (asum / s.size + float(EPS))
 
 
+def masked_content_term32(resid, m):
+    """(E, a S0 / (sum|S0| / S0.size + EPS)) of one masked content term in the oracle's own float32 operations, from
+    the residual F - c and the mask window m: what ``MaskedContentOracleModel`` adds at weight 1."""
+    a = np.float32(float(m.astype(np.float64).sum()) / m.size)
+    s0 = resid * m
+    half = float(np.dot(s0.ravel(), resid.ravel())) / 2
+    return half, a * l1_normalize(s0)
+
+
 class MaskedContentOracleModel(OracleModel):
     """``OracleModel`` whose content term acts through ``cmask`` = {layer: mask map [ceil(H/s), ceil(W/s)]}
     (None: the plain term).  The maps are rolled with the content maps (``roll_contents``)."""
@@ -84,10 +93,9 @@ class MaskedContentOracleModel(OracleModel):
                         continue
                     m = self.cmask[b][fy:fy + fh, fx:fx + fw]
                     assert m.shape == (fh, fw), 'mask window outside the map'
-                    a = np.float32(float(m.astype(np.float64).sum()) / m.size)
-                    s0 = resid * m
-                    loss += lw * content_weight[b] * float(np.dot(s0.ravel(), resid.ravel())) / 2
-                    diff += np.float32(lw * content_weight[b]) * (a * l1_normalize(s0))
+                    half, s = masked_content_term32(resid, m)
+                    loss += lw * content_weight[b] * half
+                    diff += np.float32(lw * content_weight[b]) * s
             if b in style_layers:
                 for style in self.styles:
                     gdiff = gram_lower(feat) - style[b]

@@ -46,6 +46,16 @@ def window(full, fy, fx, fh, fw):
     return full[..., fy:fy + fh, fx:fx + fw]
 
 
+def masked_style_term32(feat, m, Gs):
+    """(1/2 |D|^2, a S / (sum|S| / S.size + EPS) [like feat]) of one masked style term in the oracle's own float32
+    operations: what ``MaskedOracleModel`` adds at weight 1."""
+    a = np.float32(float((m.astype(np.float64) ** 2).sum()) / m.size)
+    fm = feat * m
+    gdiff = gram_lower(fm) - a * Gs
+    sgrad = symm_lower_times(gdiff, fm.reshape(fm.shape[0], -1)) * m.ravel()
+    return half_sq_norm(gdiff), (a * l1_normalize(sgrad)).reshape(feat.shape)
+
+
 class MaskedOracleModel(OracleModel):
     """``OracleModel`` whose style i acts through ``masks[i]`` = {layer: mask map [ceil(H/s), ceil(W/s)]}
     (None: everywhere, the plain term).  The maps are rolled with the content maps (``roll_contents``)."""
@@ -107,12 +117,9 @@ class MaskedOracleModel(OracleModel):
                         continue
                     m = window(full, fy, fx, fh, fw)
                     assert m.shape == (fh, fw), 'mask window outside the map'
-                    a = np.float32(float((m.astype(np.float64) ** 2).sum()) / m.size)
-                    fm = feat * m
-                    gdiff = gram_lower(fm) - a * style[b]
-                    sgrad = symm_lower_times(gdiff, fm.reshape(fm.shape[0], -1)) * m.ravel()
-                    loss += lw * style_weight[b] * half_sq_norm(gdiff) / len(self.styles)
-                    diff += np.float32(coef) * (a * l1_normalize(sgrad)).reshape(feat.shape)
+                    half, s = masked_style_term32(feat, m, style[b])
+                    loss += lw * style_weight[b] * half / len(self.styles)
+                    diff += np.float32(coef) * s
             if b in dd_layers:
                 loss -= lw * dd_weight[b] * half_sq_norm(feat)
                 diff -= np.float32(lw * dd_weight[b]) * l1_normalize(feat.copy())

@@ -13,6 +13,10 @@ Nothing here is held against an oracle (the per-feature files do that).  Held ar
     only the order differs, all terms of a family share a sign: |loss - sum loss_f| <= 64 * 2^-52 * sum |loss_f|.
     Gradient: fp32 rounding and the power-of-two scales of the fp16-split kernels differ between the runs:
     max |g - sum g_f| <= GRAD_TOL * sum_f max |g_f|, no pixel excluded.
+What additivity cannot see: a mistake in the layout.  If two terms' slots or scratch regions overlap, the full run and
+every share run read the same overwritten memory and the shares still add up to the whole (run once: plan_terms with
+the SWD slot laid over the NNFM slot passes this file).  tests/test_gpu_terms_meet.py holds the combined evaluation --
+with NNFM, SWD and self-similarity targets too -- against an independent reference of all terms at once.
 Every case prints its figures before it asserts (pytest -s).
 
 Observed on an MI355X, before and after the term list was planned (the same bits): loss off by 0 on both tiles
