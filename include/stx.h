@@ -488,6 +488,44 @@ struct stx_selfsim_target {
  * STX_ERR_UNSUPPORTED for a layer whose channel count is not a multiple of 64. */
 int stx_set_selfsim_targets(stx_engine *e, const struct stx_selfsim_target *targets, int n);
 
+/* The shifted-Gram style term (not in the reference): the long-range statistic of Berger & Memisevic,
+ * "Incorporating long-range consistency in CNN-based texture generation" (ICLR 2017).  The Gram, statistics and SWD
+ * terms read a layer's feature vectors as a bag and NNFM reads 3 x 3 patches at most; this term holds the Gram
+ * matrix of a blob against a copy of itself translated by delta pixels to the style picture's, for a list Delta of
+ * offsets delta = (dy, dx), each along one axis: (0, d) or (d, 0), d >= 1.  A tapped blob F [C][h][w] -- the array
+ * the Gram term reads -- with n = h w; per offset P_d = {p : p and p + delta both in the map}, n_d = (h - dy)(w - dx):
+ *   X_d[a][b] = (1 / (C n_d)) sum_{p in P_d} F_a(p) F_b(p + delta)          full C x C, not symmetric
+ *   D_d       = X_d - T_d                                                   T_d: the target, [C][C]
+ *   E         = (1/|Delta|) sum_d sum_ab D_d[a][b]^2
+ *   S_a(p)    = (1/|Delta|) sum_d (n / n_d) [ sum_b D_d[a][b] F_b(p + delta) [p + delta in the map]
+ *                                           + sum_b D_d[b][a] F_b(p - delta) [p - delta in the map] ]
+ *                                                                           ( = C n d(E/2)/dF_a(p), exactly )
+ *   loss        += lw weight E / 2
+ *   diff[layer] += lw weight S / (sum|S| / (C n) + EPS)      (the reference's normalize, as for every term)
+ * The mean is over pairs (1 / n_d), so a style picture and a tile of different sizes have comparable X.  A tile's
+ * term is the tile's own, as its Gram is: pairs across a tile edge are not counted.  C is a multiple of 32
+ * (STX_ERR_UNSUPPORTED otherwise), 1 <= |Delta| <= 16; an offset that leaves an evaluated tile blob without a pair
+ * (n_d < 1) is STX_ERR_ARG at the evaluation, before any launch, and the message names the layer and the offset.
+ * No atomics; partial sums are added in a fixed order: the same inputs give the same bits.  X_d is rounded to
+ * float32 once and D, E and S are formed from the rounded values: a tile whose X_d equal the targets (those
+ * stx_shift_gram gives for the same array) contributes exactly 0 to the loss and changes no bit of the gradient. */
+struct stx_shift_target {
+    const char *layer;
+    int channels;
+    int n_offsets;          /* |Delta|, 1 .. 16 */
+    const int *offsets;     /* host, [n_offsets][2] = dy, dx */
+    const float *grams;     /* T, [n_offsets][channels][channels] */
+    int mem;                /* of grams */
+    double weight;
+};
+/* Replaces all shifted-Gram targets of the engine's group (n = 0: none); one per layer at most.  They are shared
+ * like the style targets (stx_engine_create_shared) and stx_set_contents_and_styles clears them: call this behind it.
+ * A channel count other than the layer's is STX_ERR_ARG here.  A layer with a target is part of every
+ * stx_sc_grad_tile evaluation under the rules of stx_set_stat_targets: the layer_weight of its tap if the tap list
+ * names it, lw = 1 otherwise, an empty tap list accepted, and all layers on one path.  The term follows the blob's
+ * self-similarity term in the loss and in the gradient. */
+int stx_set_shift_targets(stx_engine *e, const struct stx_shift_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -553,6 +591,12 @@ int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channe
  * themselves.  V and out are STX_HOST; synchronous.  Refusals: those of the term. */
 int stx_swd_target(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, const float *V,
                    int dirs, int quantiles, float *out);
+
+/* The shifted Grams X_d of a feature map [channels][h][w] for the offsets [n_offsets][2] = dy, dx (host): what
+ * stx_set_shift_targets takes, by the launches the term itself runs on a tile's blob.  out [n_offsets][channels]
+ * [channels] is STX_HOST; synchronous.  Refusals: those of the term. */
+int stx_shift_gram(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, const int *offsets,
+                   int n_offsets, float *out);
 
 /* The NNFM bank of a feature map [channels][h][w]: its unit-normalised columns at (y, x) with y % stride == 0
  * and x % stride == 0, in raster order, as float32 rows [rows][channels], rows = ceil(h / stride) *
@@ -871,6 +915,11 @@ int stx_op_swd_terms(stx_engine *e, const float *feat, int channels, int h, int 
  * signs to account.  Errors leave the outputs alone. */
 int stx_op_selfsim_terms(stx_engine *e, const float *feat, const float *content, int channels, int h, int w,
                          int points, float *sgrad, double sc[2], signed char *signs_out);
+/* The launches of a shifted-Gram target (stx_set_shift_targets) on given arrays (feat, grams [n_offsets][channels]
+ * [channels] and s_out STX_DEVICE; offsets host): out = {E / 2, sum |S|}; s_out = S [channels][h][w].  Errors leave
+ * the outputs alone. */
+int stx_op_shift_terms(stx_engine *e, const float *feat, int channels, int h, int w, const int *offsets,
+                       int n_offsets, const float *grams, float *s_out, double out[2]);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

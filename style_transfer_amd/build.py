@@ -39,6 +39,7 @@ SOURCES = {
     'nnfm.hip': ['-ffp-contract=off'],
     'swd.hip': ['-ffp-contract=off'],
     'selfsim.hip': ['-ffp-contract=off'],
+    'shiftgram.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'targets.cpp': [],

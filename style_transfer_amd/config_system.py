@@ -217,6 +217,25 @@ _EXTENSIONS = [
                                       'integer from 2 to 4096: the blob is thinned to every g-th row and column, g '
                                       'the smallest step that fits; the term forms two N x N matrices, so its cost '
                                       'grows with N squared (default: 1024)')),
+    (('--shift-weight',), dict(metavar='WEIGHT', type=ffloat,
+                               help='shifted-Gram style factor (Berger & Memisevic): holds the Gram matrices of the '
+                                    'feature maps at the --shift-layers against copies of themselves moved by the '
+                                    '--shift-offsets to those of the style picture(s) -- the arrangement of a '
+                                    'regular texture (brickwork, weave, hatching at a fixed pitch), which every '
+                                    'other style term is blind to.  The term is not cheap: at its defaults it '
+                                    'takes 8.2 ms beside a 3.8 ms evaluation of a 1024 x 1024 tile on an MI355X, 2.2 '
+                                    'tile evaluations (0.8 ms beside 0.8 ms at 256 x 256); fewer --shift-offsets or '
+                                    '--shift-layers cut it in proportion; read once per scale; 0 or absent: off '
+                                    '(default: 0)')),
+    (('--shift-layers',), dict(nargs='+', metavar='LAYER',
+                               help='layers of the shifted-Gram term as name or name:weight; the weights are '
+                                    'normalised to --shift-weight like those of a layer list and read once per scale; '
+                                    'with --style-multiscale the layers themselves stay those of the first scale, '
+                                    'whose targets are kept (default: conv1_1 conv2_1 conv3_1)')),
+    (('--shift-offsets',), dict(nargs='+', metavar='D', type=int,
+                                help="distances of the shifted-Gram term in the layer's own pixels, one to 8 positive "
+                                     'integers; each D gives the offsets (0, D) and (D, 0).  A tile blob must be '
+                                     'larger than D on both axes; read once per scale (default: 2 4 8)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -632,6 +651,65 @@ def check_selfsim_options(args, known_layers=None):
     return check_layer_list(args, items, '--selfsim-weight', '--selfsim-layers', '', known_layers, style_side=False)
 
 
+SHIFT_LAYERS_DEFAULT = ('conv1_1', 'conv2_1', 'conv3_1')
+SHIFT_OFFSETS_DEFAULT = (2, 4, 8)
+SHIFT_MAX_DISTANCES = 8
+
+
+def shift_layer_args(args):
+    """The layer list of the shifted-Gram term (``name`` or ``name:weight`` each): --shift-layers, or conv1_1
+    conv2_1 conv3_1.  [] when the term is off (no --shift-weight, or 0)."""
+    if not option_on(args, 'shift_weight'):
+        return []
+    given = getattr(args, 'shift_layers', None) or SHIFT_LAYERS_DEFAULT
+    return [given] if isinstance(given, str) else list(given)
+
+
+def shift_offsets(args):
+    """--shift-offsets as the term's offsets [(dy, dx), ...]: every distance D gives (0, D) and (D, 0), in the
+    order given (default 2 4 8).  One to 8 distinct positive integers; anything else, bools and floats included, is
+    a ValueError."""
+    raw = raw_option(args, 'shift_offsets', None)
+    if raw is None:
+        raw = SHIFT_OFFSETS_DEFAULT
+    if isinstance(raw, (int, np.integer)) and not isinstance(raw, bool):
+        raw = [raw]
+    if not isinstance(raw, (list, tuple)) or not 1 <= len(raw) <= SHIFT_MAX_DISTANCES:
+        raise ValueError('--shift-offsets %r: one to %d positive integers are expected' % (raw, SHIFT_MAX_DISTANCES))
+    offsets = []
+    for d in raw:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 1:
+            raise ValueError('--shift-offsets %r: a positive integer is expected' % (d,))
+        if (0, int(d)) in offsets:
+            raise ValueError('--shift-offsets: distance %d is given twice' % d)
+        offsets += [(0, int(d)), (int(d), 0)]
+    return offsets
+
+
+def check_shift_tile(offsets, layer, scale, tile_hw):
+    """An offset that leaves a tile's blob at ``layer`` (``scale`` image pixels per blob pixel, ceil mode) without a
+    pair of pixels is refused before any GPU work."""
+    h, w = (-(-int(v) // int(scale)) for v in tile_hw)
+    for dy, dx in offsets:
+        if h - dy < 1 or w - dx < 1:
+            raise ValueError('--shift-offsets %d: a %d x %d tile is a %d x %d map at layer %s, which holds no pair of '
+                             'pixels at that distance (raise --min-size or drop the offset)'
+                             % (max(dy, dx), tile_hw[1], tile_hw[0], w, h, layer))
+
+
+def check_shift_options(args, known_layers=None):
+    """--shift-weight / --shift-layers / --shift-offsets: refused before any GPU work together with --style-masks
+    (there is one set of targets and, with masks, one style set per picture), with bad offsets and with a bad layer
+    list (check_layer_list).  Returns the layer names."""
+    items = shift_layer_args(args)
+    if not items:
+        return []
+    if not getattr(args, 'style_masks', None):      # (the refusal of --style-masks comes first)
+        shift_offsets(args)
+    return check_layer_list(args, items, '--shift-weight', '--shift-layers', 'one set of shifted-Gram targets',
+                            known_layers)
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -662,5 +740,6 @@ def parse_args(state=None, argv=None, config_py=None):
     check_nnfm_options(args)
     check_swd_options(args)
     check_selfsim_options(args)
+    check_shift_options(args)
     check_photo_options(args)
     return args

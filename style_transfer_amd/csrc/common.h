@@ -568,6 +568,41 @@ int selfsim_cols_launch(hipStream_t s, int N, const SelfsimScratch &x, signed ch
 int selfsim_grad_launch(hipStream_t s, int C, int h, int w, const SelfsimGrid &gr, const SelfsimScratch &x,
                         float *sgrad, int *n_abs);
 
+// shiftgram.hip: the shifted-Gram style term of a blob [C][h][w] for a list of axis-aligned offsets against targets
+// [offsets][C][C] (include/stx.h, stx_set_shift_targets).  P_d, the pairs of an offset in raster order, is cut into
+// slices of shift_slice_len(h w) pairs; a map has shift_slices(h w) of them at most.
+constexpr int kShiftMaxOffsets = 16;
+struct ShiftOffsets {       // (a kernel argument)
+    int n;
+    int dy[kShiftMaxOffsets], dx[kShiftMaxOffsets];
+};
+int shift_slice_len(int HW);
+int shift_slices(int HW);
+// STX_ERR_ARG for a count outside 1 .. kShiftMaxOffsets or an offset that is not (0, d) or (d, 0) with d >= 1,
+// STX_ERR_UNSUPPORTED for channels not a multiple of 32; `out` (or null) receives the list
+int shift_check_offsets(const char *who, int C, const int *offsets /*[n][2] = dy, dx*/, int n_offsets,
+                        ShiftOffsets *out);
+// STX_ERR_ARG when an offset leaves an h x w map without a pair (the message names `who` and the offset)
+int shift_check_map(const char *who, int C, int h, int w, const ShiftOffsets &off);
+// The term's scratch, all of which outlives its launches (the final sums of e_parts and abs_parts may be deferred).
+struct ShiftScratch {
+    float *partials;        // [offsets][shift_slices][C][C]
+    float *weights;         // [offsets][2][C][C]: (n / (n_d |Delta|)) D_d, then its transpose
+    float *e_parts;         // [offsets][ceil(C C / 256)] partials of E
+    float *abs_parts;       // [ceil(C / 64)][ceil(h w / 64)] partials of sum |S|
+    size_t floats;
+};
+ShiftScratch shift_scratch(float *base, int C, int HW, int n_offsets);
+size_t shift_scratch_floats(int C, int HW, int n_offsets);
+int shift_cross_launch(hipStream_t s, const float *feat, int C, int h, int w, const ShiftOffsets &off,
+                       const ShiftScratch &x);
+// targets [offsets][C][C]: the weights and *n_e partials of E in x.e_parts.  Or, targets null: x_out [offsets][C][C] = X.
+int shift_merge_launch(hipStream_t s, int C, int h, int w, const ShiftOffsets &off, const ShiftScratch &x,
+                       const float *targets, float *x_out, int *n_e);
+// sgrad [C][h][w] = S; *n_abs partials of sum |S| in x.abs_parts
+int shift_grad_launch(hipStream_t s, const float *feat, int C, int h, int w, const ShiftOffsets &off,
+                      const ShiftScratch &x, float *sgrad, int *n_abs);
+
 // nnfm.hip: the nearest-neighbour feature matching term of a blob [C][n] against a bank [M][C] of unit rows
 // (include/stx.h, stx_set_nnfm_targets).  The search multiplies kNnfmQ query columns by kNnfmB bank rows per
 // workgroup, kNnfmK channels per LDS stage; with few query blocks the bank is cut into slices.

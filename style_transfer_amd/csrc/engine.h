@@ -160,6 +160,15 @@ struct SelfsimTarget {
     void release() {}
 };
 
+// The shifted-Gram targets of one tapped blob (stx_set_shift_targets): the offsets and T [n][C][C] on the device.
+struct ShiftTarget {
+    int blob, C;
+    ShiftOffsets off;
+    double weight;
+    std::unique_ptr<DevBuf> grams;
+    void release() { grams->release(); }
+};
+
 struct LossTerm {
     size_t scalar_index;   // float in the host mirror of the scalar buffer
     double coef;
@@ -185,6 +194,7 @@ struct SharedState {
     std::vector<NnfmTarget> nnfms;     // (cleared with the targets)
     std::vector<SwdTarget> swds;       // (cleared with the targets)
     std::vector<SelfsimTarget> selfsims;   // (cleared with the targets)
+    std::vector<ShiftTarget> shifts;   // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -238,6 +248,7 @@ struct stx_engine {
     DevBuf swd_work;                   // a sliced Wasserstein term's sort records and G (swd_work_floats), one term at a time
     DevBuf swd_io;                     // stx_swd_target / stx_op_swd_terms: V, the quantiles, the term's scratch
     DevBuf selfsim_io;                 // stx_op_selfsim_terms: the term's scratch
+    DevBuf shift_io;                   // stx_shift_gram / stx_op_shift_terms: the term's scratch, X
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
     // reductions), each with a pinned host mirror, and the losses that will be published from
     // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
@@ -372,6 +383,7 @@ inline void clear_dependent_targets(SharedState &sh) {   // what is set behind t
     clear_targets(sh.nnfms);
     clear_targets(sh.swds);
     clear_targets(sh.selfsims);
+    clear_targets(sh.shifts);
 }
 inline void clear_all_targets(SharedState &sh) {
     clear_targets(sh.contents);
@@ -408,7 +420,7 @@ struct TileCall {
     int grad_mem;
 };
 
-enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, NnfmGuided, Swd, Selfsim, Dream };
+enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, NnfmGuided, Swd, Selfsim, Shift, Dream };
 constexpr size_t kNoSlot = ~(size_t)0;
 constexpr size_t kResidualScalars = 2 + 2 * 1024;   // content_sums_launch: two sums and their partials
 
@@ -425,13 +437,14 @@ struct PlannedTerm {
     const NnfmTarget *nnfm = nullptr; // TermKind::Nnfm: the bank with its pieces
     const SwdTarget *swd = nullptr;   // TermKind::Swd: the directions and quantiles
     int points = 0;                   // TermKind::Selfsim: the most grid positions (target = the content map, win its window)
+    const ShiftTarget *shift = nullptr;   // TermKind::Shift: the offsets (target = T)
 };
 
 struct TilePlan {
     std::vector<Tap> order;         // taps, deepest first
     std::vector<char> needed;       // blobs on the path
     std::vector<int> tap_of;        // blob -> index into order, or -1
-    std::deque<stx_tap> extra;      // taps of the layers that only a statistics, NNFM, SWD or self-similarity target names (lw = 1);
+    std::deque<stx_tap> extra;      // taps of the layers that only a statistics, NNFM, SWD, self-similarity or shifted-Gram target names (lw = 1);
                                     // `order` points into it: a deque's elements stay where they are
     // The final sums of the loss terms are collected and run as ONE launch behind the forward pass
     // (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did); what they add up must outlive the term's
@@ -439,7 +452,7 @@ struct TilePlan {
     bool sums_late;
     bool interleave;                // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
     // The terms in queueing order -- shallowest tap first; per tap the content targets in sh->contents order,
-    // the style targets in sh->styles order, the statistics term, the NNFM term, the SWD term, the self-similarity term, Deep-Dream -- which is the order of
+    // the style targets in sh->styles order, the statistics term, the NNFM term, the SWD term, the self-similarity term, the shifted-Gram term, Deep-Dream -- which is the order of
     // PendingLoss::terms: the host adds the loss up in it.
     std::vector<PlannedTerm> terms;
     std::vector<size_t> first_term;     // per tap: its first record
@@ -526,6 +539,12 @@ int launch_swd_terms(stx_engine *e, hipStream_t stream, const float *feat, int C
 int launch_selfsim_terms(stx_engine *e, hipStream_t stream, const float *feat, const SelfsimSource &content, int C,
                          int h, int w, int points, float *sgrad, signed char *signs_out, float *sc,
                          const std::string &name, float *scratch, std::vector<SumJob> *defer);
+// The shifted-Gram term of a blob (shiftgram.hip): cross-Gram partials -> merge against the targets -> S into sgrad.
+// sc[2] = {E, sum |S|}, both from partials whose final sums join `defer` or are launched here.  scratch:
+// shift_scratch_floats(C, h * w, off.n) floats that outlive the call like term_scratch.  targets [off.n][C][C].
+int launch_shift_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                       const ShiftOffsets &off, const float *targets, float *sgrad, float *sc, const std::string &name,
+                       float *scratch, std::vector<SumJob> *defer);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

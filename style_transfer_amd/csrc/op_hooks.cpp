@@ -218,6 +218,29 @@ int stx_op_selfsim_terms(stx_engine *e, const float *feat, const float *content,
     return STX_OK;
 }
 
+int stx_op_shift_terms(stx_engine *e, const float *feat, int C, int h, int w, const int *offsets, int n_offsets,
+                       const float *grams, float *s_out, double out[2]) {
+    if (!e || !feat || !grams || !s_out || !out) {
+        set_error("stx_op_shift_terms: bad arguments");
+        return STX_ERR_ARG;
+    }
+    ShiftOffsets off;
+    STX_TRY(shift_check_offsets("stx_op_shift_terms", C, offsets, n_offsets, &off));
+    STX_TRY(shift_check_map("stx_op_shift_terms", C, h, w, off));
+    STX_TRY(e->set_device());
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
+    STX_TRY(e->shift_io.ensure(shift_scratch_floats(C, h * w, n_offsets) * sizeof(float)));
+    // the launches of a shifted-Gram target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_shift_terms(e, e->stream, feat, C, h, w, off, grams, s_out, sc, "op", e->shift_io.f(), nullptr));
+    STX_TRY(scalars.fetch(&host));
+    out[0] = 0.5 * (double)host[0];
+    out[1] = (double)host[1];
+    return STX_OK;
+}
+
 int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *content,
                                 int content_h, int content_w, const float *mask_map, int oy, int ox,
                                 const int roll_xy[2], float *sgrad_out, double out[3]) {

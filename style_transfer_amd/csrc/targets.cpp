@@ -327,6 +327,38 @@ int stx_set_selfsim_targets(stx_engine *e, const struct stx_selfsim_target *targ
     }, [&]() { clear_targets(selfsims); });
 }
 
+int stx_set_shift_targets(stx_engine *e, const struct stx_shift_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    auto &shifts = e->sh->shifts;
+    return swap_targets(e, "stx_set_shift_targets", [&](bool &) -> int {
+        clear_targets(shifts);
+        for (int i = 0; i < n; ++i) {
+            const struct stx_shift_target &ht = targets[i];
+            const int blob = e->find_blob(ht.layer);
+            bool twice = false;
+            for (const ShiftTarget &t : shifts) twice |= t.blob == blob;
+            if (blob <= 0 || !ht.grams || !ht.offsets || twice) {
+                set_error("shifted-Gram target %d: bad layer '%s' (unknown, the input, or given twice) or no data", i,
+                          ht.layer ? ht.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            if (ht.channels != e->blobs[blob].channels) {
+                set_error("shifted-Gram target %d: layer %s has %d channels, not %d", i, ht.layer,
+                          e->blobs[blob].channels, ht.channels);
+                return STX_ERR_ARG;
+            }
+            ShiftOffsets off;
+            STX_TRY(shift_check_offsets("stx_set_shift_targets", ht.channels, ht.offsets, ht.n_offsets, &off));
+            shifts.push_back(ShiftTarget{blob, ht.channels, off, ht.weight, std::unique_ptr<DevBuf>(new DevBuf)});
+            ShiftTarget &t = shifts.back();
+            const size_t bytes = (size_t)off.n * t.C * t.C * sizeof(float);
+            STX_TRY(t.grams->ensure(bytes));
+            STX_TRY(copy_in(e, t.grams->ptr, ht.grams, ht.mem, bytes));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(shifts); });
+}
+
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
     std::vector<stx_nnfm_cover_target> as_knn;

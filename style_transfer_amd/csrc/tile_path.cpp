@@ -438,7 +438,8 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
                std::any_of(e->sh->nnfms.begin(), e->sh->nnfms.end(), [=](const NnfmTarget &t) { return t.blob == blob; }) ||
                std::any_of(e->sh->swds.begin(), e->sh->swds.end(), [=](const SwdTarget &t) { return t.blob == blob; }) ||
                std::any_of(e->sh->selfsims.begin(), e->sh->selfsims.end(),
-                           [=](const SelfsimTarget &t) { return t.blob == blob; });
+                           [=](const SelfsimTarget &t) { return t.blob == blob; }) ||
+               std::any_of(e->sh->shifts.begin(), e->sh->shifts.end(), [=](const ShiftTarget &t) { return t.blob == blob; });
     };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
@@ -482,6 +483,13 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
         t.layer_weight = 1.0;
         plan.extra.push_back(t);
         order.push_back(Tap{ft.blob, &plan.extra.back()});
+    }
+    for (const ShiftTarget &ht : e->sh->shifts) {       // ... and a layer with a shifted-Gram target
+        if (tapped(ht.blob)) continue;
+        stx_tap t{};
+        t.layer_weight = 1.0;
+        plan.extra.push_back(t);
+        order.push_back(Tap{ht.blob, &plan.extra.back()});
     }
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");
@@ -918,6 +926,36 @@ int stx_feature_stats(stx_engine *e, const float *feat, int feat_mem, int channe
     STX_TRY(copy_out(e, mean_out, out_mem, mu, (size_t)channels * sizeof(float)));
     STX_TRY(copy_out(e, sd_out, out_mem, sd, (size_t)channels * sizeof(float)));
     if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_shift_gram(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, const int *offsets,
+                   int n_offsets, float *out) {
+    if (!e || !feat || !out) {
+        set_error("stx_shift_gram: bad arguments");
+        return STX_ERR_ARG;
+    }
+    ShiftOffsets off;
+    STX_TRY(shift_check_offsets("stx_shift_gram", channels, offsets, n_offsets, &off));
+    STX_TRY(shift_check_map("stx_shift_gram", channels, h, w, off));
+    STX_TRY(e->set_device());
+    const int n = h * w;
+    const float *src = feat;
+    if (feat_mem == STX_HOST) {
+        STX_TRY(e->upload.ensure((size_t)channels * n * sizeof(float)));
+        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, (size_t)channels * n * sizeof(float)));
+        src = e->upload.f();
+    }
+    const size_t x_floats = (size_t)n_offsets * channels * channels;
+    const size_t scratch_floats = shift_scratch_floats(channels, n, n_offsets);
+    STX_TRY(e->shift_io.ensure((scratch_floats + x_floats) * sizeof(float)));
+    const ShiftScratch x = shift_scratch(e->shift_io.f(), channels, n, n_offsets);
+    float *const x_dev = e->shift_io.f() + scratch_floats;
+    // the first two launches of the term itself (launch_shift_terms): a tile's own X are its targets
+    STX_TRY(shift_cross_launch(e->stream, src, channels, h, w, off, x));
+    STX_TRY(shift_merge_launch(e->stream, channels, h, w, off, x, nullptr, x_dev, nullptr));
+    STX_TRY(copy_out(e, out, STX_HOST, x_dev, x_floats * sizeof(float)));
+    STX_HIP(hipStreamSynchronize(e->stream));
     return STX_OK;
 }
 

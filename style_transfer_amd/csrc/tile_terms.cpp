@@ -320,6 +320,31 @@ int launch_selfsim_terms(stx_engine *e, hipStream_t stream, const float *feat, c
     return STX_OK;
 }
 
+// The shifted-Gram term of one tapped blob (shiftgram.hip): the slices' partials of every offset's cross-Gram, their
+// merge against the targets (the gradient's weights and the partials of E), S with the partials of sum |S|.
+int launch_shift_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
+                       const ShiftOffsets &off, const float *targets, float *sgrad, float *sc, const std::string &name,
+                       float *scratch, std::vector<SumJob> *defer) {
+    STX_TRY(shift_check_map("launch_shift_terms", C, h, w, off));
+    const ShiftScratch x = shift_scratch(scratch, C, h * w, off.n);
+    const double product = 2.0 * off.n * (double)C * C * h * w;
+    int n_e = 0, n_abs = 0;
+    {
+        ProfScope scope(e, "shift cross " + name, product, stream);
+        STX_TRY(shift_cross_launch(stream, feat, C, h, w, off, x));
+    }
+    {
+        ProfScope scope(e, "shift merge " + name, 0.0, stream);
+        STX_TRY(shift_merge_launch(stream, C, h, w, off, x, targets, nullptr, &n_e));
+    }
+    ProfScope scope(e, "shift grad " + name, 2.0 * product, stream);
+    STX_TRY(shift_grad_launch(stream, feat, C, h, w, off, x, sgrad, &n_abs));
+    if (!defer) return sum_partials2_launch(stream, x.e_parts, n_e, sc, x.abs_parts, n_abs, sc + 1);
+    defer->push_back(SumJob{x.e_parts, n_e, sc});
+    defer->push_back(SumJob{x.abs_parts, n_abs, sc + 1});
+    return STX_OK;
+}
+
 // A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
 // S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
 int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
@@ -359,6 +384,13 @@ static const SwdTarget *swd_target_of(const stx_engine *e, int blob) {
 // The self-similarity target of `blob` (stx_set_selfsim_targets), or null.
 static const SelfsimTarget *selfsim_target_of(const stx_engine *e, int blob) {
     for (const SelfsimTarget &t : e->sh->selfsims)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
+
+// The shifted-Gram target of `blob` (stx_set_shift_targets), or null.
+static const ShiftTarget *shift_target_of(const stx_engine *e, int blob) {
+    for (const ShiftTarget &t : e->sh->shifts)
         if (t.blob == blob) return &t;
     return nullptr;
 }
@@ -419,7 +451,8 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         const double lw = tp.t->layer_weight;
         plan.first_term[k] = plan.terms.size();
         // The tap's gradient buffer: the style slots, then (each group from a 256-byte boundary) the masked
-        // content slots, the statistics slot, the NNFM slot, the SWD slot and the self-similarity slot.
+        // content slots, the statistics slot, the NNFM slot, the SWD slot, the self-similarity slot and the
+        // shifted-Gram slot.
         size_t styles_here = 0;
         for (const StyleTarget &st : sh.styles) styles_here += tp.t->is_style && st.blob == tp.blob;
         size_t style_slot = 0, content_slot = align(styles_here * b.count());
@@ -523,6 +556,15 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 selfsim_scratch_floats(b.channels, selfsim_grid(b.h, b.w, ft->points).N), slot);
             plan.terms.back().points = ft->points;
         }
+        if (const ShiftTarget *ht = shift_target_of(e, tp.blob)) {      // (its slot: behind the self-similarity slot, if there is one)
+            STX_TRY(shift_check_map(("shifted-Gram target of layer " + b.name).c_str(), b.channels, b.h, b.w, ht->off));
+            size_t slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
+            if (swd_target_of(e, tp.blob)) slot = align(slot + b.count());
+            if (selfsim_target_of(e, tp.blob)) slot = align(slot + b.count());
+            add(TermKind::Shift, ht->grams->f(), nullptr, ContentWindow{}, lw * ht->weight, 2,
+                shift_scratch_floats(b.channels, b.h * b.w, ht->off.n), slot);
+            plan.terms.back().shift = ht;
+        }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
         // weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
         if (tp.t->is_dd)
@@ -596,6 +638,10 @@ int queue_tap_terms(TileRun &run, size_t k) {
                                                        t.win.ox - t.win.sx},
                                          b.channels, b.h, b.w, t.points, sgrad, nullptr, sc, b.name, scratch,
                                          run.defer()));
+            break;
+        case TermKind::Shift:         // sc[0] = E, sc[1] = sum |S|
+            STX_TRY(launch_shift_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.shift->off, t.target, sgrad, sc,
+                                       b.name, scratch, run.defer()));
             break;
         }
         run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});

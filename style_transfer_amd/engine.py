@@ -26,7 +26,7 @@ from .netspec import NetSpec
 _TYPE_CODES = {'Input': lib.LAYER_INPUT, 'Convolution': lib.LAYER_CONV, 'ReLU': lib.LAYER_RELU,
                'Pooling': lib.LAYER_POOL}
 # the targets that tap layers of their own, in the order of their taps
-EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd', 'selfsim')
+EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd', 'selfsim', 'shift')
 
 
 class DeviceArray:
@@ -112,6 +112,14 @@ def _as_arg(arr):
         return t.data_ptr(), (lib.DEVICE if t.is_cuda else lib.HOST), t
     host = np.ascontiguousarray(arr, np.float32)
     return host.ctypes.data, lib.HOST, host
+
+
+def _shift_offsets(offsets):
+    """Offsets [n, 2] = (dy, dx) of the shifted-Gram term as a C int array of 2 n entries (the library checks them)."""
+    flat = np.asarray(offsets)
+    if flat.ndim != 2 or flat.shape[1] != 2 or flat.shape[0] < 1 or flat.dtype.kind not in 'iu':
+        raise ValueError('shifted-Gram offsets %r: an [n, 2] list of integer (dy, dx) pairs is expected' % (offsets,))
+    return (ctypes.c_int * flat.size)(*[int(v) for v in flat.ravel()])
 
 
 class PendingTile:
@@ -449,6 +457,37 @@ class TileEngine:
             t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
         lib.call('stx_set_selfsim_targets', self.handle, table, n)
         self.primary.extra_taps['selfsim'] = list(points)
+
+    def set_shift_targets(self, targets, weights=None):
+        """targets: {layer: (offsets [n, 2] = dy, dx, T [n, C, C])} -- what ``shift_gram`` gives for a style picture's
+        feature map at those offsets -- and weights: {layer: factor} (default 1 each); an empty dict: none
+        (stx_set_shift_targets).  The library copies both.  Call it after ``set_contents_and_styles``, which clears
+        them.  A layer with a target is part of every tile evaluation of the group from then on."""
+        keep, n = [], len(targets)
+        table = (lib.ShiftTarget * max(1, n))()
+        for t, (layer, (offsets, grams)) in zip(table, targets.items()):
+            offs = _shift_offsets(offsets)
+            gp, gmem, gobj = _as_arg(grams)
+            if len(gobj.shape) != 3 or gobj.shape[0] != len(offs) // 2 or gobj.shape[1] != gobj.shape[2]:
+                raise ValueError('shifted-Gram target %s: T %s for %d offsets; [n, C, C] is expected'
+                                 % (layer, tuple(gobj.shape), len(offs) // 2))
+            keep += [offs, gobj]
+            t.layer, t.channels, t.n_offsets, t.offsets = self._cstr(layer), int(gobj.shape[1]), len(offs) // 2, offs
+            t.grams, t.mem = gp, gmem
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_shift_targets', self.handle, table, n)
+        self.primary.extra_taps['shift'] = list(targets)
+        del keep
+
+    def shift_gram(self, feat, offsets):
+        """X [n, C, C] float32: the shifted Grams of a [C,h,w] feature map at ``offsets`` [n, 2] = (dy, dx), each
+        (0, d) or (d, 0) with d >= 1 (stx_shift_gram): the targets of the shifted-Gram style term."""
+        ptr, mem, keep = _as_arg(feat)
+        c, h, w = (int(v) for v in keep.shape)
+        offs = _shift_offsets(offsets)
+        out = np.empty((len(offs) // 2, c, c), np.float32)
+        lib.call('stx_shift_gram', self.handle, ptr, mem, c, h, w, offs, len(offs) // 2, out.ctypes.data)
+        return out
 
     def swd_target(self, feat, V, Q):
         """Tq [D, Q] float32: per direction of V [D, C] the quantile function of a [C,h,w] feature map's

@@ -198,8 +198,14 @@ class TileFarm:
     def set_selfsim_targets(self, points, weights=None):
         self._set_on_primaries('set_selfsim_targets', points, weights)
 
+    def set_shift_targets(self, targets, weights=None):
+        self._set_on_primaries('set_shift_targets', targets, weights)
+
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)
+
+    def shift_gram(self, feat, offsets):
+        return self.master.shift_gram(feat, offsets)
 
     def swd_target(self, feat, V, Q):
         return self.master.swd_target(feat, V, Q)

@@ -99,6 +99,12 @@ class SelfsimTarget(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('points', ctypes.c_int), ('weight', ctypes.c_double)]
 
 
+class ShiftTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('n_offsets', ctypes.c_int),
+                ('offsets', ctypes.POINTER(ctypes.c_int)), ('grams', ctypes.c_void_p), ('mem', ctypes.c_int),
+                ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -138,6 +144,7 @@ SIGNATURES = {
                                     _i, _i],
     'stx_set_swd_targets': [_vp, ctypes.POINTER(SwdTarget), _i],
     'stx_set_selfsim_targets': [_vp, ctypes.POINTER(SelfsimTarget), _i],
+    'stx_set_shift_targets': [_vp, ctypes.POINTER(ShiftTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -147,6 +154,7 @@ SIGNATURES = {
     'stx_gram_matrix': [_vp, _vp, _i, _i, _i, _vp, _i],
     'stx_feature_stats': [_vp, _vp, _i, _i, _i, _vp, _vp, _i],
     'stx_swd_target': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
+    'stx_shift_gram': [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _vp],
     'stx_nnfm_bank': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i],
     'stx_nnfm_patch_bank': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i],
     'stx_image_cut_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
@@ -192,6 +200,7 @@ SIGNATURES = {
     'stx_op_stat_terms': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, c_double_p],
     'stx_op_swd_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_selfsim_terms': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, c_double_p, _vp],
+    'stx_op_shift_terms': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],

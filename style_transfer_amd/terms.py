@@ -10,11 +10,12 @@ import numpy as np
 from PIL import Image
 
 from . import image_ops
+from .farm import tile_grid
 from .config_system import (LAP_POOLS_DEFAULT, SWD_QUANTILES, ValuePlaceholder, check_lap_pools, check_nnfm_options,
                             check_photo_options, check_selfsim_options, check_stat_options, check_swd_options, ffloat,
                             nnfm_bank_rows, nnfm_layer_args, nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on,
                             selfsim_layer_args, selfsim_points, stat_layer_args, swd_dirs, swd_directions,
-                            swd_layer_args)
+                            swd_layer_args, check_shift_options, check_shift_tile, shift_layer_args, shift_offsets)
 
 
 def parse_weights(args, master_weight):
@@ -220,6 +221,34 @@ class SelfsimTargets(TargetTerm):
             st.farm.set_selfsim_targets({layer: self.points for layer in self.weights}, self.weights)
 
 
+class ShiftTargets(LayerTargets):
+    """--shift-weight / --shift-layers / --shift-offsets (the shifted-Gram style term): per layer the Gram matrices
+    of the style pictures' feature maps against themselves moved by every offset, averaged over the variants like the
+    Grams; ``targets`` = {layer: (offsets [(dy, dx), ...], T [n, C, C])}.  The offsets are read once per scale; an
+    offset that leaves a tile's blob of the scale without a pair of pixels is refused there, before any GPU work.
+    Kept targets (--style-multiscale) go to the engines with the offsets they were taken at."""
+    FLAG, WEIGHT, WHAT, layer_args = '--shift-layers', 'shift_weight', 'shifted-Gram target', staticmethod(shift_layer_args)
+    offsets = None      # [(dy, dx), ...] of the scale
+
+    def read(self, st):
+        super().read(st)
+        self.offsets = shift_offsets(st.args)
+        tiles = {(y1 - y0, x1 - x0) for y0, y1, x0, x1 in tile_grid(st.img.shape[1:], st.args.tile_size)}
+        for layer in self.layers:
+            for tile_hw in sorted(tiles):
+                check_shift_tile(self.offsets, layer, st.farm.layer_info(layer)[0], tile_hw)
+
+    def take(self, st, layer, feat):
+        self._parts[layer].append(st.farm.shift_gram(feat, self.offsets))
+
+    def finish(self, st, count, quiet):
+        self.targets = {layer: (list(self.offsets), sum(parts[1:], parts[0]) / np.float32(count))
+                        for layer, parts in self._parts.items() if parts}
+
+    def set_targets(self, farm, targets):
+        farm.set_shift_targets(targets, self.weights)
+
+
 class Masks(TargetTerm):
     """--style-masks / --content-mask (spatial control): ``st.style_masks`` and ``st.content_mask`` resized to the
     scale's content size.  Under --jitter the engines hold content maps of the rolled picture and shift nothing,
@@ -246,7 +275,7 @@ def target_terms(args, known_layers):
     """The target terms of a run, in the order they are sent; a bad option is refused here, before any GPU work.
     (The masks are handed to transfer_multiscale, so their term is always listed.)"""
     checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks), (check_swd_options, SwdTargets),
-               (check_selfsim_options, SelfsimTargets))
+               (check_selfsim_options, SelfsimTargets), (check_shift_options, ShiftTargets))
     return [cls() for check, cls in checked if check(args, known_layers)] + [Masks()]
 
 
