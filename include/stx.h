@@ -526,6 +526,53 @@ struct stx_shift_target {
  * self-similarity term in the loss and in the gradient. */
 int stx_set_shift_targets(stx_engine *e, const struct stx_shift_target *targets, int n);
 
+/* The contextual style term (not in the reference): the contextual loss of Mechrez, Talmi, Zelnik-Manor, "The
+ * Contextual Loss for Image Transformation with Non-Aligned Data" (ECCV 2018).  The Gram, statistics, SWD and
+ * shifted-Gram terms hold global statistics and the NNFM family takes hard nearest neighbours; this term matches
+ * softly and free of scale: each sampled feature vector of the result spreads a softmax over the whole style bank
+ * at a temperature that follows its own best distance, and each bank row is credited with the best share any
+ * vector gives it.  A tapped blob F [C][h][w]; the sample grid is that of stx_set_selfsim_targets: g the smallest
+ * integer >= 1 with ceil(h/g) ceil(w/g) <= points, positions (a g, b g) in raster order, N of them, columns f_i.
+ * The bank is built once per target from raw style rows y_k [M][C] (stx_cx_bank):
+ *   mu = (1/M) sum_k y_k,   b_k = (y_k - mu) / |y_k - mu|       (zero where the norm is 0; sums in double)
+ * and with eps = 1e-5, eta = h (the bandwidth), all sums in a fixed order:
+ *   z_i  = f_i - mu,  r_i = |z_i|,  x_i = z_i / r_i              (r_i = 0: x_i = 0, 1/r_i = 0)
+ *   s_ik = x_i . b_k                                             (float32 products, float32 accumulation)
+ *   k*_i = argmax_k s_ik (the LOWEST k among equal scores),  a_i = 1 - s_{i,k*_i},  tau_i = eta (a_i + eps)
+ *   e_ik = exp((s_ik - s_{i,k*_i}) / tau_i),  Z_i = sum_k e_ik,  p_ik = e_ik / Z_i,  u_i = sum_k p_ik s_ik
+ *   i*_k = argmax_i p_ik (the LOWEST i among equal values),  m_k = p_{i*_k,k}
+ *   CX   = (1/M) sum_k m_k,   E = -log CX                        (E >= 0; N = M = 1 gives E = 0, S = 0)
+ *   P_i  = sum_{k: i*_k = i} p_ik,   Q_i = sum_{k: i*_k = i} p_ik s_ik
+ *   g_ik = -(1/(M CX)) [ p_ik (1[i*_k = i] - P_i) / tau_i  +  1[k = k*_i] eta (Q_i - P_i u_i) / tau_i^2 ]
+ *   q_i  = sum_k g_ik b_k
+ *   S_i  = (q_i - (q_i . x_i) x_i) / r_i  at the grid positions, 0 elsewhere    ( = dE/df_i with k*, i* held )
+ *   loss        += lw weight E                                   (E whole: it is no half square)
+ *   diff[layer] += lw weight S / (sum|S| / (C h w) + EPS)        (the reference's normalize, as for every term)
+ * p_ik is the paper's CX_ij: its exp((1 - d~) / h) differs from e_ik by a factor that cancels in the row
+ * normalisation, and the form above cannot overflow.  The second part of g is the derivative through the row
+ * minimum.  Two identical columns f_i tie exactly in i*, and E has a kink there.  A tile's term is the tile's own:
+ * every tile's sample is asked to cover the whole bank, as with stx_set_nnfm_cover_targets.  exp is the accurate
+ * expf.  No atomics, no scratch memory; every sum in a fixed order: the same inputs give the same bits. */
+struct stx_cx_target {
+    const char *layer;
+    int channels;
+    int rows;               /* M, 1 .. 16384 */
+    const float *raw_rows;  /* y, [rows][channels]: raw feature vectors (stx_cx_rows), not normalised */
+    int mem;                /* of raw_rows */
+    int points;             /* the most grid positions, 2 .. 4096 */
+    double h;               /* the bandwidth eta, > 0 */
+    double weight;
+};
+/* Replaces all contextual targets of the engine's group (n = 0: none); one per layer at most.  The rows are copied
+ * and mu and the bank are built here.  The targets are shared like the style targets (stx_engine_create_shared)
+ * and stx_set_contents_and_styles clears them: call this behind it.  A layer with a target is part of every
+ * stx_sc_grad_tile evaluation under the rules of stx_set_stat_targets: the layer_weight of its tap if the tap list
+ * names it, lw = 1 otherwise, an empty tap list accepted, and all layers on one path.  The term follows the blob's
+ * shifted-Gram term in the loss and in the gradient.  STX_ERR_ARG for a channel count other than the layer's,
+ * points outside 2 .. 4096, rows outside 1 .. 16384, h <= 0 or not finite; STX_ERR_UNSUPPORTED for channels not a
+ * multiple of 64 and for points x rows > 2^24 (the two N x M matrices exist in memory). */
+int stx_set_cx_targets(stx_engine *e, const struct stx_cx_target *targets, int n);
+
 /* --------------------------------------------------------------------------- the hot path */
 /* Replaces CaffeModel.eval_features_tile via FeatureMapRequest (style_transfer.py:156,221-228,
  * 421-427): forward the tile and return the post-ReLU maps of the requested blobs.
@@ -597,6 +644,19 @@ int stx_swd_target(stx_engine *e, const float *feat, int feat_mem, int channels,
  * [channels] is STX_HOST; synchronous.  Refusals: those of the term. */
 int stx_shift_gram(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, const int *offsets,
                    int n_offsets, float *out);
+
+/* The raw rows of a feature map [channels][h][w] for a contextual bank (stx_set_cx_targets): its columns on the
+ * grid of a budget of `rows` positions (the rule of the term's sample grid), in raster order, as float32 rows
+ * [N][channels], N = ceil(h / g) ceil(w / g) <= rows, bit for bit.  Rows of several pictures are concatenated by
+ * the caller.  rows < 1 is STX_ERR_ARG; channels not a multiple of 64 (the term's own limit): STX_ERR_UNSUPPORTED,
+ * before any launch. */
+int stx_cx_rows(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int rows, float *rows_out,
+                int out_mem);
+/* mu [channels] and the centred unit rows bank [rows][channels] of raw rows [rows][channels], as
+ * stx_set_cx_targets builds them: column sums and norms in double in a fixed order.  Synchronous.  Channels not a
+ * multiple of 64: STX_ERR_UNSUPPORTED; rows outside 1 .. 16384: STX_ERR_ARG. */
+int stx_cx_bank(stx_engine *e, const float *raw_rows, int mem, int channels, int rows, float *mu_out, float *bank_out,
+                int out_mem);
 
 /* The NNFM bank of a feature map [channels][h][w]: its unit-normalised columns at (y, x) with y % stride == 0
  * and x % stride == 0, in raster order, as float32 rows [rows][channels], rows = ceil(h / stride) *
@@ -920,6 +980,13 @@ int stx_op_selfsim_terms(stx_engine *e, const float *feat, const float *content,
  * the outputs alone. */
 int stx_op_shift_terms(stx_engine *e, const float *feat, int channels, int h, int w, const int *offsets,
                        int n_offsets, const float *grams, float *s_out, double out[2]);
+/* The launches of a contextual target (stx_set_cx_targets) on given device arrays: feat [channels][h][w], bank
+ * [rows][channels] and mu [channels] as stx_cx_bank gives them, sgrad [channels][h][w] = S; sc = {E, sum |S|}.
+ * kbest_out (or null): k* as int32 [N]; winner_out (or null): i* as int32 [rows] -- the decisions to account.
+ * Errors leave the outputs alone. */
+int stx_op_cx_terms(stx_engine *e, const float *feat, int channels, int h, int w, int points, const float *bank,
+                    const float *mu, int rows, double eta, float *sgrad, double sc[2], int *kbest_out,
+                    int *winner_out);
 int stx_op_content_terms(stx_engine *e, const float *feat, int channels, int h, int w,
                          const float *content, int content_h, int content_w, int oy, int ox,
                          const int roll_xy[2], float *normalized_out, double sums[2]);

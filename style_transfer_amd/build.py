@@ -40,6 +40,7 @@ SOURCES = {
     'swd.hip': ['-ffp-contract=off'],
     'selfsim.hip': ['-ffp-contract=off'],
     'shiftgram.hip': ['-ffp-contract=off'],
+    'cx.hip': ['-ffp-contract=off'],
     'conv_dispatch.cpp': [],
     'engine.cpp': [],
     'targets.cpp': [],

@@ -15,8 +15,9 @@ import numpy as np
 from PIL import Image
 
 from . import fastpng, lib
-from .config_system import (check_content_mask, check_nnfm_options, check_selfsim_options, check_shift_options,
-                            check_stat_options, check_style_masks, check_swd_options, nnfm_masks, parse_args)
+from .config_system import (check_content_mask, check_cx_options, check_nnfm_options, check_selfsim_options,
+                            check_shift_options, check_stat_options, check_style_masks, check_swd_options, nnfm_masks,
+                            parse_args)
 from .farm import TileFarm
 from .netspec import load_net
 from .transfer import StyleTransfer
@@ -139,6 +140,7 @@ def main(argv=None):
     check_swd_options(args, net.blob_names())
     check_selfsim_options(args, net.blob_names())
     check_shift_options(args, net.blob_names())
+    check_cx_options(args, net.blob_names())
     # Three things run side by side, each releasing the interpreter lock: the weight file is read
     # (or the seeded bank drawn) on one helper thread, the GPU runtime is woken up and the engines
     # (streams, scalar arenas) are created on another, and this thread decodes the pictures.

@@ -236,6 +236,35 @@ _EXTENSIONS = [
                                 help="distances of the shifted-Gram term in the layer's own pixels, one to 8 positive "
                                      'integers; each D gives the offsets (0, D) and (D, 0).  A tile blob must be '
                                      'larger than D on both axes; read once per scale (default: 2 4 8)')),
+    (('--cx-weight',), dict(metavar='WEIGHT', type=ffloat,
+                            help='contextual style factor (Mechrez et al., the contextual loss): soft, scale-free '
+                                 'matching of feature vectors -- at the --cx-layers every sampled feature vector of '
+                                 'the result spreads a softmax over a bank of the style picture(s)\' feature vectors '
+                                 'at a temperature that follows its own best distance, and every bank row is credited '
+                                 'with the best share any vector gives it; between the global statistics (Gram, '
+                                 '--stat-weight, --swd-weight) and the hard matches of --nnfm-weight.  The term '
+                                 'belongs to one tile: every tile\'s sample is asked to cover the whole bank, as '
+                                 'with --nnfm-cover.  At its defaults (two layers, 1024 points, a bank of 4096 rows) '
+                                 'the term takes 0.52 ms beside a 3.7 ms evaluation of a 1024 x 1024 tile on an '
+                                 'MI355X, 0.14 tile evaluations (0.47 ms beside 0.82 ms at 256 x 256, 0.57); read '
+                                 'once per scale; 0 or absent: off (default: 0)')),
+    (('--cx-layers',), dict(nargs='+', metavar='LAYER',
+                            help='layers of the contextual term as name or name:weight; the weights are normalised '
+                                 'to --cx-weight like those of a layer list and read once per scale; with '
+                                 '--style-multiscale the layers themselves stay those of the first scale, whose '
+                                 'banks are kept (default: conv3_2 conv4_2)')),
+    (('--cx-points',), dict(metavar='N', type=int,
+                            help='most sample positions per tile and layer of the contextual term, an integer from '
+                                 '2 to 4096: the blob is thinned to every g-th row and column, g the smallest step '
+                                 'that fits; the term forms two N x M matrices against a bank of M rows, and N x M '
+                                 'may not pass 2^24 (default: 1024)')),
+    (('--cx-rows',), dict(metavar='M', type=int,
+                          help='most bank rows of the contextual term per style picture and size, by the same grid '
+                               'rule; the banks of all style pictures (and, with --style-multiscale, sizes) are '
+                               'concatenated, to 16384 rows at most (default: 4096)')),
+    (('--cx-h',), dict(metavar='H', type=ffloat,
+                       help='bandwidth of the contextual term, a number above 0: the softmax temperature of a '
+                            'feature vector is H times (its best cosine distance + 1e-5) (default: 0.5)')),
     (('--photo-weight',), dict(metavar='WEIGHT', type=ffloat,
                                help='photorealism factor (Luan et al., Deep Photo Style Transfer): penalises a '
                                     "result that is not locally an affine function of the content picture's "
@@ -710,6 +739,83 @@ def check_shift_options(args, known_layers=None):
                             known_layers)
 
 
+CX_LAYERS_DEFAULT = ('conv3_2', 'conv4_2')
+CX_POINTS_DEFAULT = 1024
+CX_MAX_POINTS = 4096
+CX_ROWS_DEFAULT = 4096
+CX_MAX_ROWS = 16384
+CX_MAX_CELLS = 2 ** 24
+CX_H_DEFAULT = 0.5
+
+
+def cx_layer_args(args):
+    """The layer list of the contextual term (``name`` or ``name:weight`` each): --cx-layers, or conv3_2 conv4_2.
+    [] when the term is off (no --cx-weight, or 0)."""
+    if not option_on(args, 'cx_weight'):
+        return []
+    given = getattr(args, 'cx_layers', None) or CX_LAYERS_DEFAULT
+    return [given] if isinstance(given, str) else list(given)
+
+
+def cx_points(args):
+    """--cx-points as an integer from 2 to 4096 (default 1024); anything else, bools and floats included, is a
+    ValueError."""
+    raw = raw_option(args, 'cx_points', CX_POINTS_DEFAULT)
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 2 <= raw <= CX_MAX_POINTS:
+        raise ValueError('--cx-points %r: an integer from 2 to %d is expected' % (raw, CX_MAX_POINTS))
+    return int(raw)
+
+
+def cx_rows(args):
+    """--cx-rows as an integer from 1 to 16384 (default 4096); anything else, bools and floats included, is a
+    ValueError."""
+    raw = raw_option(args, 'cx_rows', CX_ROWS_DEFAULT)
+    if isinstance(raw, bool) or not isinstance(raw, (int, np.integer)) or not 1 <= raw <= CX_MAX_ROWS:
+        raise ValueError('--cx-rows %r: an integer from 1 to %d is expected' % (raw, CX_MAX_ROWS))
+    return int(raw)
+
+
+def cx_h(args):
+    """--cx-h as a finite float above 0 (default 0.5); anything else, bools and strings included, is a ValueError."""
+    raw = raw_option(args, 'cx_h', CX_H_DEFAULT)
+    if (isinstance(raw, bool) or not isinstance(raw, (int, float, np.integer, np.floating)) or not np.isfinite(raw)
+            or not np.float32(raw) > 0):
+        raise ValueError('--cx-h %r: a finite number above 0 is expected' % (raw,))
+    return float(raw)
+
+
+def check_cx_bank(total, points, rows):
+    """A contextual bank of ``total`` rows past the library's limits -- 16384 rows, points x rows up to 2^24 -- is a
+    ValueError that names both options."""
+    if total > CX_MAX_ROWS or points * total > CX_MAX_CELLS:
+        raise ValueError('the contextual bank would have %d rows: with --cx-points %d at most %d are possible; lower '
+                         '--cx-rows (now %d) or --cx-points'
+                         % (total, points, min(CX_MAX_ROWS, CX_MAX_CELLS // points), rows))
+
+
+def cx_bank_rows(h, w, rows, rows_before=0, points=CX_POINTS_DEFAULT):
+    """Rows that an h x w feature map adds to a contextual bank under a budget of ``rows`` (the grid rule of
+    selfsim_grid); a bank past the limits (check_cx_bank) is refused before anything is allocated."""
+    _, gh, gw = selfsim_grid(h, w, rows)
+    check_cx_bank(rows_before + gh * gw, points, rows)
+    return gh * gw
+
+
+def check_cx_options(args, known_layers=None):
+    """--cx-weight / --cx-layers / --cx-points / --cx-rows / --cx-h: refused before any GPU work together with
+    --style-masks (there is one bank and, with masks, one style set per picture, as for --nnfm-weight), with points
+    outside 2 .. 4096, rows outside 1 .. 16384, a bandwidth that is not a finite number above 0, and with a bad
+    layer list (check_layer_list).  Returns the layer names."""
+    items = cx_layer_args(args)
+    if not items:
+        return []
+    if not getattr(args, 'style_masks', None):      # (the refusal of --style-masks comes first)
+        cx_points(args)
+        cx_rows(args)
+        cx_h(args)
+    return check_layer_list(args, items, '--cx-weight', '--cx-layers', 'one contextual bank', known_layers)
+
+
 def parse_args(state=None, argv=None, config_py=None):
     """Returns the merged options.  ``config_py`` defaults to ``config.py`` beside the entry
     script of THIS package (the repository's ``style_transfer.py``), like the reference, which
@@ -741,5 +847,6 @@ def parse_args(state=None, argv=None, config_py=None):
     check_swd_options(args)
     check_selfsim_options(args)
     check_shift_options(args)
+    check_cx_options(args)
     check_photo_options(args)
     return args

@@ -568,6 +568,53 @@ int selfsim_cols_launch(hipStream_t s, int N, const SelfsimScratch &x, signed ch
 int selfsim_grad_launch(hipStream_t s, int C, int h, int w, const SelfsimGrid &gr, const SelfsimScratch &x,
                         float *sgrad, int *n_abs);
 
+// cx.hip: the contextual style term of a blob [C][h][w], sampled on the grid of selfsim_grid, against a bank [M][C]
+// of centred unit rows with the mean mu [C] of the raw rows (include/stx.h, stx_set_cx_targets).
+constexpr int kCxMaxPoints = 4096;
+constexpr int kCxMaxRows = 16384;
+constexpr long long kCxMaxCells = 1ll << 24;    // points x M: the two score matrices exist in memory
+constexpr float kCxEps = 1e-5f;
+// STX_ERR_ARG for points outside 2 .. kCxMaxPoints, M outside 1 .. kCxMaxRows, eta <= 0 or not finite;
+// STX_ERR_UNSUPPORTED for channels not a multiple of 64 and for points x M > kCxMaxCells
+int cx_check(const char *who, int C, int points, long long M, double eta);
+// rows of the bank per K slice of the gradient product (a multiple of 32); ceil(M / it) slices
+int cx_slice_len(int C, int N, int M);
+// The term's scratch, all of which outlives its launches (the final sums of e_part and abs_parts may be deferred).
+struct CxScratch {
+    float *rows;            // [N][C]: the unit columns of F - mu
+    float *inv_r;           // [N]
+    float *S;               // [N][M]: the scores; the second row pass leaves g there
+    float *P;               // [N][M]
+    float *best_val;        // [ceil(M / 64)][N]: a row's best score per block of 64 columns ...
+    int *best_idx;          // ... and its lowest column
+    int *kstar;             // [N]
+    float *tau, *u, *row_p; // [N] each: tau_i, u_i, P_i
+    float *col_val;         // [ceil(N / 64)][M]: a column's best p per block of 64 rows ...
+    int *col_idx;           // ... and its lowest row
+    int *winner;            // [M]: i*_k
+    float *m_parts;         // ceil(M / 256) partials of sum_k m_k
+    float *qp;              // [slices][N][C]: the gradient product's partial tiles
+    float *e_part;          // E, one "partial"
+    float *dot_parts;       // [C / 64][N]: a channel block's share of q_i . x_i
+    float *abs_parts;       // (C / 64) ceil(N / 64) partials of sum |S|
+    size_t floats;
+};
+CxScratch cx_scratch(float *base, int C, int N, int M);
+size_t cx_scratch_floats(int C, int N, int M);
+// rows [N][C] = the raw columns of feat on the grid
+int cx_rows_launch(hipStream_t s, const float *feat, int C, int h, int w, const SelfsimGrid &gr, float *rows);
+// mu [C] and bank [M][C] from raw rows [M][C] (all on the device)
+int cx_bank_launch(hipStream_t s, const float *raw, int C, int M, float *mu, float *bank);
+int cx_prepare_launch(hipStream_t s, const float *feat, int C, int h, int w, const SelfsimGrid &gr, const float *mu,
+                      const CxScratch &x);
+int cx_score_launch(hipStream_t s, int C, int N, int M, const float *bank, const CxScratch &x);
+int cx_rows_pass_launch(hipStream_t s, int N, int M, float eta, const CxScratch &x);
+// the column pass and the second row pass; kbest_out [N], winner_out [M] (device, or null): the decisions
+int cx_cols_pass_launch(hipStream_t s, int N, int M, float eta, const CxScratch &x, int *kbest_out, int *winner_out);
+// sgrad [C][h][w] = S (cleared first when the grid skips pixels); *n_abs partials of sum |S| in x.abs_parts
+int cx_grad_launch(hipStream_t s, int C, int h, int w, const SelfsimGrid &gr, int M, const float *bank,
+                   const CxScratch &x, float *sgrad, int *n_abs);
+
 // shiftgram.hip: the shifted-Gram style term of a blob [C][h][w] for a list of axis-aligned offsets against targets
 // [offsets][C][C] (include/stx.h, stx_set_shift_targets).  P_d, the pairs of an offset in raster order, is cut into
 // slices of shift_slice_len(h w) pairs; a map has shift_slices(h w) of them at most.

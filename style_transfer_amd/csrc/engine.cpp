@@ -417,7 +417,7 @@ void stx_engine_destroy(stx_engine *e) {
         }
         clear_all_targets(*e->sh);
     }
-    DevBuf *bufs[] = {&e->shift_io, &e->selfsim_io, &e->swd_work, &e->swd_io, &e->nnfm_scratch, &e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
+    DevBuf *bufs[] = {&e->cx_io, &e->shift_io, &e->selfsim_io, &e->swd_work, &e->swd_io, &e->nnfm_scratch, &e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
                       &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();

@@ -169,6 +169,18 @@ struct ShiftTarget {
     void release() { grams->release(); }
 };
 
+// The contextual target of one tapped blob (stx_set_cx_targets): the bank's centred unit rows [rows][C], then the
+// mean mu [C] of the raw rows, on the device.
+struct CxTarget {
+    int blob, C, rows, points;
+    float eta;
+    double weight;
+    std::unique_ptr<DevBuf> data;
+    const float *bank() const { return data->f(); }
+    const float *mu() const { return data->f() + (size_t)rows * C; }
+    void release() { data->release(); }
+};
+
 struct LossTerm {
     size_t scalar_index;   // float in the host mirror of the scalar buffer
     double coef;
@@ -195,6 +207,7 @@ struct SharedState {
     std::vector<SwdTarget> swds;       // (cleared with the targets)
     std::vector<SelfsimTarget> selfsims;   // (cleared with the targets)
     std::vector<ShiftTarget> shifts;   // (cleared with the targets)
+    std::vector<CxTarget> cxs;         // (cleared with the targets)
     int n_contents = 0, n_styles = 0;
     std::vector<stx_engine *> members;
     std::mutex mutex;                  // packs and target swaps (members may be driven by different threads)
@@ -249,6 +262,7 @@ struct stx_engine {
     DevBuf swd_io;                     // stx_swd_target / stx_op_swd_terms: V, the quantiles, the term's scratch
     DevBuf selfsim_io;                 // stx_op_selfsim_terms: the term's scratch
     DevBuf shift_io;                   // stx_shift_gram / stx_op_shift_terms: the term's scratch, X
+    DevBuf cx_io;                      // stx_cx_rows / stx_cx_bank / stx_op_cx_terms: staged rows, the term's scratch
     // Loss scalars of the calls queued so far: device floats (tile terms) and doubles (image-op
     // reductions), each with a pinned host mirror, and the losses that will be published from
     // them.  TWO arenas: stx_fence closes the current one behind an event and opens the other, so
@@ -384,6 +398,7 @@ inline void clear_dependent_targets(SharedState &sh) {   // what is set behind t
     clear_targets(sh.swds);
     clear_targets(sh.selfsims);
     clear_targets(sh.shifts);
+    clear_targets(sh.cxs);
 }
 inline void clear_all_targets(SharedState &sh) {
     clear_targets(sh.contents);
@@ -420,7 +435,7 @@ struct TileCall {
     int grad_mem;
 };
 
-enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, NnfmGuided, Swd, Selfsim, Shift, Dream };
+enum class TermKind { Content, MaskedContent, Style, MaskedStyle, Stat, Nnfm, NnfmGuided, Swd, Selfsim, Shift, Cx, Dream };
 constexpr size_t kNoSlot = ~(size_t)0;
 constexpr size_t kResidualScalars = 2 + 2 * 1024;   // content_sums_launch: two sums and their partials
 
@@ -438,13 +453,14 @@ struct PlannedTerm {
     const SwdTarget *swd = nullptr;   // TermKind::Swd: the directions and quantiles
     int points = 0;                   // TermKind::Selfsim: the most grid positions (target = the content map, win its window)
     const ShiftTarget *shift = nullptr;   // TermKind::Shift: the offsets (target = T)
+    const CxTarget *cx = nullptr;     // TermKind::Cx: the bank with mu, the points and the bandwidth
 };
 
 struct TilePlan {
     std::vector<Tap> order;         // taps, deepest first
     std::vector<char> needed;       // blobs on the path
     std::vector<int> tap_of;        // blob -> index into order, or -1
-    std::deque<stx_tap> extra;      // taps of the layers that only a statistics, NNFM, SWD, self-similarity or shifted-Gram target names (lw = 1);
+    std::deque<stx_tap> extra;      // taps of the layers that only a statistics, NNFM, SWD, self-similarity, shifted-Gram or contextual target names (lw = 1);
                                     // `order` points into it: a deque's elements stay where they are
     // The final sums of the loss terms are collected and run as ONE launch behind the forward pass
     // (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did); what they add up must outlive the term's
@@ -452,7 +468,7 @@ struct TilePlan {
     bool sums_late;
     bool interleave;                // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
     // The terms in queueing order -- shallowest tap first; per tap the content targets in sh->contents order,
-    // the style targets in sh->styles order, the statistics term, the NNFM term, the SWD term, the self-similarity term, the shifted-Gram term, Deep-Dream -- which is the order of
+    // the style targets in sh->styles order, the statistics term, the NNFM term, the SWD term, the self-similarity term, the shifted-Gram term, the contextual term, Deep-Dream -- which is the order of
     // PendingLoss::terms: the host adds the loss up in it.
     std::vector<PlannedTerm> terms;
     std::vector<size_t> first_term;     // per tap: its first record
@@ -545,6 +561,13 @@ int launch_selfsim_terms(stx_engine *e, hipStream_t stream, const float *feat, c
 int launch_shift_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w,
                        const ShiftOffsets &off, const float *targets, float *sgrad, float *sc, const std::string &name,
                        float *scratch, std::vector<SumJob> *defer);
+// The contextual term of a blob (cx.hip): prepare -> scores -> row pass -> column pass -> gradient into sgrad.
+// sc[2] = {E, sum |S|}: E enters the loss whole (LossTerm: the full coefficient), sum |S| from partials; both final
+// sums join `defer` or are launched here.  scratch: cx_scratch_floats(C, N, rows) floats that outlive the call like
+// term_scratch.  kbest_out [N], winner_out [rows] (device, or null): the decisions k*, i*.
+int launch_cx_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int points,
+                    const float *bank, const float *mu, int rows, float eta, float *sgrad, int *kbest_out,
+                    int *winner_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer);
 // A content term through a weight map (content_mask.hip): a from the window of the map, then S = a (m d) into
 // sgrad.  sc[3] = {sum m d^2, sum |m d|, a}; the two final sums join `defer` or are launched here.  partials:
 // kContentMaskScratchFloats floats that outlive the call like term_scratch.

@@ -241,6 +241,29 @@ int stx_op_shift_terms(stx_engine *e, const float *feat, int C, int h, int w, co
     return STX_OK;
 }
 
+int stx_op_cx_terms(stx_engine *e, const float *feat, int C, int h, int w, int points, const float *bank,
+                    const float *mu, int rows, double eta, float *sgrad, double sc_out[2], int *kbest_out,
+                    int *winner_out) {
+    if (!e || !feat || !bank || !mu || !sgrad || !sc_out || h <= 0 || w <= 0) {
+        set_error("stx_op_cx_terms: bad arguments");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(cx_check("stx_op_cx_terms", C, points, rows, (double)(float)eta));
+    STX_TRY(e->set_device());
+    HookScalars scalars(e);
+    float *sc;
+    const float *host;
+    STX_TRY(scalars.take(2, &sc));
+    STX_TRY(e->cx_io.ensure(cx_scratch_floats(C, selfsim_grid(h, w, points).N, rows) * sizeof(float)));
+    // the launches of a contextual target of stx_sc_grad_tile, in the same order
+    STX_TRY(launch_cx_terms(e, e->stream, feat, C, h, w, points, bank, mu, rows, (float)eta, sgrad, kbest_out,
+                            winner_out, sc, "op", e->cx_io.f(), nullptr));
+    STX_TRY(scalars.fetch(&host));
+    sc_out[0] = (double)host[0];
+    sc_out[1] = (double)host[1];
+    return STX_OK;
+}
+
 int stx_op_masked_content_terms(stx_engine *e, const float *feat, int C, int h, int w, const float *content,
                                 int content_h, int content_w, const float *mask_map, int oy, int ox,
                                 const int roll_xy[2], float *sgrad_out, double out[3]) {

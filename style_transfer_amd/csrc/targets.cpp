@@ -359,6 +359,45 @@ int stx_set_shift_targets(stx_engine *e, const struct stx_shift_target *targets,
     }, [&]() { clear_targets(shifts); });
 }
 
+int stx_set_cx_targets(stx_engine *e, const struct stx_cx_target *targets, int n) {
+    if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
+    auto &cxs = e->sh->cxs;
+    std::vector<std::unique_ptr<DevBuf>> raws;      // the copied raw rows; they go behind the swap's wait
+    const int rc = swap_targets(e, "stx_set_cx_targets", [&](bool &) -> int {
+        clear_targets(cxs);
+        for (int i = 0; i < n; ++i) {
+            const struct stx_cx_target &xt = targets[i];
+            const int blob = e->find_blob(xt.layer);
+            bool twice = false;
+            for (const CxTarget &t : cxs) twice |= t.blob == blob;
+            if (blob <= 0 || !xt.raw_rows || twice) {
+                set_error("contextual target %d: bad layer '%s' (unknown, the input, or given twice) or no rows", i,
+                          xt.layer ? xt.layer : "(null)");
+                return STX_ERR_ARG;
+            }
+            if (xt.channels != e->blobs[blob].channels) {
+                set_error("contextual target %d: layer %s has %d channels, not %d", i, xt.layer,
+                          e->blobs[blob].channels, xt.channels);
+                return STX_ERR_ARG;
+            }
+            STX_TRY(cx_check("stx_set_cx_targets", xt.channels, xt.points, xt.rows, (double)(float)xt.h));
+            cxs.push_back(CxTarget{blob, xt.channels, xt.rows, xt.points, (float)xt.h, xt.weight,
+                                   std::unique_ptr<DevBuf>(new DevBuf)});
+            CxTarget &t = cxs.back();
+            const size_t floats = (size_t)t.rows * t.C;
+            STX_TRY(t.data->ensure((floats + t.C) * sizeof(float)));
+            raws.emplace_back(new DevBuf);
+            DevBuf &raw = *raws.back();
+            STX_TRY(raw.ensure(floats * sizeof(float)));
+            STX_TRY(copy_in(e, raw.ptr, xt.raw_rows, xt.mem, floats * sizeof(float)));
+            STX_TRY(cx_bank_launch(e->stream, raw.f(), t.C, t.rows, t.data->f() + floats, t.data->f()));
+        }
+        return STX_OK;
+    }, [&]() { clear_targets(cxs); });
+    for (auto &raw : raws) raw->release();
+    return rc;
+}
+
 int stx_set_nnfm_targets(stx_engine *e, const stx_nnfm_target *targets, int n) {
     if (!e || n < 0 || (n && !targets)) return STX_ERR_ARG;
     std::vector<stx_nnfm_cover_target> as_knn;

@@ -439,7 +439,8 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
                std::any_of(e->sh->swds.begin(), e->sh->swds.end(), [=](const SwdTarget &t) { return t.blob == blob; }) ||
                std::any_of(e->sh->selfsims.begin(), e->sh->selfsims.end(),
                            [=](const SelfsimTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->shifts.begin(), e->sh->shifts.end(), [=](const ShiftTarget &t) { return t.blob == blob; });
+               std::any_of(e->sh->shifts.begin(), e->sh->shifts.end(), [=](const ShiftTarget &t) { return t.blob == blob; }) ||
+               std::any_of(e->sh->cxs.begin(), e->sh->cxs.end(), [=](const CxTarget &t) { return t.blob == blob; });
     };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
@@ -490,6 +491,13 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
         t.layer_weight = 1.0;
         plan.extra.push_back(t);
         order.push_back(Tap{ht.blob, &plan.extra.back()});
+    }
+    for (const CxTarget &xt : e->sh->cxs) {             // ... and a layer with a contextual target
+        if (tapped(xt.blob)) continue;
+        stx_tap t{};
+        t.layer_weight = 1.0;
+        plan.extra.push_back(t);
+        order.push_back(Tap{xt.blob, &plan.extra.back()});
     }
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");
@@ -985,6 +993,63 @@ int stx_swd_target(stx_engine *e, const float *feat, int feat_mem, int channels,
     STX_TRY(swd_finish_launch(e->stream, e->swd_work.ptr, n, dirs, nullptr, 0, nullptr, nullptr, nullptr));
     STX_TRY(swd_quantiles_launch(e->stream, e->swd_work.ptr, n, dirs, quantiles, q_dev));
     STX_TRY(copy_out(e, out, STX_HOST, q_dev, (size_t)dirs * quantiles * sizeof(float)));
+    STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_cx_rows(stx_engine *e, const float *feat, int feat_mem, int channels, int h, int w, int rows, float *rows_out,
+                int out_mem) {
+    if (!e || !feat || !rows_out || channels <= 0 || h <= 0 || w <= 0 || rows < 1) {
+        set_error("stx_cx_rows: bad arguments (%d channels, a %dx%d map, %d rows)", channels, h, w, rows);
+        return STX_ERR_ARG;
+    }
+    if (channels % 64 != 0) {       // (the gather walks the channels in whole blocks of 64, as the term does)
+        set_error("stx_cx_rows: %d channels (a multiple of 64 is expected)", channels);
+        return STX_ERR_UNSUPPORTED;
+    }
+    STX_TRY(e->set_device());
+    const SelfsimGrid gr = selfsim_grid(h, w, rows);
+    const size_t in_bytes = (size_t)channels * h * w * sizeof(float), out_floats = (size_t)gr.N * channels;
+    const float *src = feat;
+    if (feat_mem == STX_HOST) {
+        STX_TRY(e->upload.ensure(in_bytes));
+        STX_TRY(copy_in(e, e->upload.ptr, feat, STX_HOST, in_bytes));
+        src = e->upload.f();
+    }
+    float *dst = rows_out;
+    if (out_mem == STX_HOST) {
+        STX_TRY(e->cx_io.ensure(out_floats * sizeof(float)));
+        dst = e->cx_io.f();
+    }
+    STX_TRY(cx_rows_launch(e->stream, src, channels, h, w, gr, dst));
+    if (out_mem == STX_HOST) STX_TRY(copy_out(e, rows_out, STX_HOST, dst, out_floats * sizeof(float)));
+    if (feat_mem == STX_HOST || out_mem == STX_HOST) STX_HIP(hipStreamSynchronize(e->stream));
+    return STX_OK;
+}
+
+int stx_cx_bank(stx_engine *e, const float *raw_rows, int mem, int channels, int rows, float *mu_out, float *bank_out,
+                int out_mem) {
+    if (!e || !raw_rows || !mu_out || !bank_out) {
+        set_error("stx_cx_bank: bad arguments");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(cx_check("stx_cx_bank", channels, 2, rows, 1.0));
+    STX_TRY(e->set_device());
+    // the staged rows, then (a host destination) the bank and mu
+    const size_t floats = (size_t)rows * channels, staged = mem == STX_HOST ? floats : 0;
+    STX_TRY(e->cx_io.ensure((staged + (out_mem == STX_HOST ? floats + channels : 0)) * sizeof(float)));
+    const float *src = raw_rows;
+    if (mem == STX_HOST) {
+        STX_TRY(copy_in(e, e->cx_io.ptr, raw_rows, STX_HOST, floats * sizeof(float)));
+        src = e->cx_io.f();
+    }
+    float *bank = out_mem == STX_HOST ? e->cx_io.f() + staged : bank_out;
+    float *mu = out_mem == STX_HOST ? bank + floats : mu_out;
+    STX_TRY(cx_bank_launch(e->stream, src, channels, rows, mu, bank));
+    if (out_mem == STX_HOST) {
+        STX_TRY(copy_out(e, bank_out, STX_HOST, bank, floats * sizeof(float)));
+        STX_TRY(copy_out(e, mu_out, STX_HOST, mu, (size_t)channels * sizeof(float)));
+    }
     STX_HIP(hipStreamSynchronize(e->stream));
     return STX_OK;
 }

@@ -345,6 +345,41 @@ int launch_shift_terms(stx_engine *e, hipStream_t stream, const float *feat, int
     return STX_OK;
 }
 
+// The contextual term of one tapped blob (cx.hip): the unit columns of F - mu on the sample grid, the scores with
+// the slots of the row maxima, the row pass (k*, tau, p), the column pass (i*, the partials of CX) with the second
+// row pass (g, E), q = g B in K slices with its projection into the blob's layout (the partials of sum |S|).
+int launch_cx_terms(stx_engine *e, hipStream_t stream, const float *feat, int C, int h, int w, int points,
+                    const float *bank, const float *mu, int rows, float eta, float *sgrad, int *kbest_out,
+                    int *winner_out, float *sc, const std::string &name, float *scratch, std::vector<SumJob> *defer) {
+    STX_TRY(cx_check("launch_cx_terms", C, points, rows, eta));
+    const SelfsimGrid gr = selfsim_grid(h, w, points);
+    const CxScratch x = cx_scratch(scratch, C, gr.N, rows);
+    const double product = 2.0 * (double)gr.N * rows * C;
+    {
+        ProfScope scope(e, "cx prepare " + name, 0.0, stream);
+        STX_TRY(cx_prepare_launch(stream, feat, C, h, w, gr, mu, x));
+    }
+    {
+        ProfScope scope(e, "cx score " + name, product, stream);
+        STX_TRY(cx_score_launch(stream, C, gr.N, rows, bank, x));
+    }
+    {
+        ProfScope scope(e, "cx rows " + name, 0.0, stream);
+        STX_TRY(cx_rows_pass_launch(stream, gr.N, rows, eta, x));
+    }
+    {
+        ProfScope scope(e, "cx cols " + name, 0.0, stream);
+        STX_TRY(cx_cols_pass_launch(stream, gr.N, rows, eta, x, kbest_out, winner_out));
+    }
+    int n_abs = 0;
+    ProfScope scope(e, "cx grad " + name, product, stream);
+    STX_TRY(cx_grad_launch(stream, C, h, w, gr, rows, bank, x, sgrad, &n_abs));
+    if (!defer) return sum_partials2_launch(stream, x.e_part, 1, sc, x.abs_parts, n_abs, sc + 1);
+    defer->push_back(SumJob{x.e_part, 1, sc});
+    defer->push_back(SumJob{x.abs_parts, n_abs, sc + 1});
+    return STX_OK;
+}
+
 // A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
 // S = a (m d) with the partials of sum m d^2 and sum |m d|, added like content_sums_launch's.
 int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *feat, const float *content,
@@ -391,6 +426,13 @@ static const SelfsimTarget *selfsim_target_of(const stx_engine *e, int blob) {
 // The shifted-Gram target of `blob` (stx_set_shift_targets), or null.
 static const ShiftTarget *shift_target_of(const stx_engine *e, int blob) {
     for (const ShiftTarget &t : e->sh->shifts)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
+
+// The contextual target of `blob` (stx_set_cx_targets), or null.
+static const CxTarget *cx_target_of(const stx_engine *e, int blob) {
+    for (const CxTarget &t : e->sh->cxs)
         if (t.blob == blob) return &t;
     return nullptr;
 }
@@ -451,8 +493,8 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         const double lw = tp.t->layer_weight;
         plan.first_term[k] = plan.terms.size();
         // The tap's gradient buffer: the style slots, then (each group from a 256-byte boundary) the masked
-        // content slots, the statistics slot, the NNFM slot, the SWD slot, the self-similarity slot and the
-        // shifted-Gram slot.
+        // content slots, the statistics slot, the NNFM slot, the SWD slot, the self-similarity slot, the
+        // shifted-Gram slot and the contextual slot.
         size_t styles_here = 0;
         for (const StyleTarget &st : sh.styles) styles_here += tp.t->is_style && st.blob == tp.blob;
         size_t style_slot = 0, content_slot = align(styles_here * b.count());
@@ -565,6 +607,16 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 shift_scratch_floats(b.channels, b.h * b.w, ht->off.n), slot);
             plan.terms.back().shift = ht;
         }
+        if (const CxTarget *xt = cx_target_of(e, tp.blob)) {            // (its slot: behind the shifted-Gram slot, if there is one)
+            STX_TRY(cx_check(("contextual target of layer " + b.name).c_str(), b.channels, xt->points, xt->rows, xt->eta));
+            size_t slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
+            if (swd_target_of(e, tp.blob)) slot = align(slot + b.count());
+            if (selfsim_target_of(e, tp.blob)) slot = align(slot + b.count());
+            if (shift_target_of(e, tp.blob)) slot = align(slot + b.count());
+            add(TermKind::Cx, xt->bank(), nullptr, ContentWindow{}, lw * xt->weight, 2,
+                cx_scratch_floats(b.channels, selfsim_grid(b.h, b.w, xt->points).N, xt->rows), slot);
+            plan.terms.back().cx = xt;
+        }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
         // weight -- loss -= lw*dd*1/2|F|^2, diff -= lw*dd*normalize(F)
         if (tp.t->is_dd)
@@ -577,7 +629,8 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
 // moment the tapped blob is complete, in the middle of the forward pass, while the blob is
 // still in the L2 / Infinity Cache the convolution just wrote it through (the shallow blobs
 // were re-fetched from HBM when all taps ran after the forward pass: 1.1 GB per tile by PMC).
-// Each enters the loss with half its coefficient and the tap's gradient with all of it.
+// Each enters the loss with half its coefficient (the contextual term, whose E is no square: with all of it) and
+// the tap's gradient with all of it.
 int queue_tap_terms(TileRun &run, size_t k) {
     stx_engine *e = run.e;
     const TilePlan &plan = run.plan;
@@ -643,8 +696,12 @@ int queue_tap_terms(TileRun &run, size_t k) {
             STX_TRY(launch_shift_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.shift->off, t.target, sgrad, sc,
                                        b.name, scratch, run.defer()));
             break;
+        case TermKind::Cx:            // sc[0] = E (which enters the loss whole), sc[1] = sum |S|
+            STX_TRY(launch_cx_terms(e, e->stream, b.data.f(), b.channels, b.h, b.w, t.cx->points, t.target, t.cx->mu(),
+                                    t.cx->rows, t.cx->eta, sgrad, nullptr, nullptr, sc, b.name, scratch, run.defer()));
+            break;
         }
-        run.pl.terms.push_back(LossTerm{si, t.coef * 0.5});
+        run.pl.terms.push_back(LossTerm{si, t.kind == TermKind::Cx ? t.coef : t.coef * 0.5});
         run.terms[k].push_back(sgrad ? Term{Term::Gradient, sgrad, abs_sum, (float)t.coef, ContentWindow{}}
                                      : Term{Term::Residual, t.target, sc, (float)t.coef, t.win});
     }

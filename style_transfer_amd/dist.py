@@ -192,6 +192,7 @@ UNBROADCAST_OPTIONS = (
     ('swd_weight', True, 'the sliced Wasserstein targets are'),
     ('selfsim_weight', True, 'the self-similarity targets are'),
     ('shift_weight', True, 'the shifted-Gram targets are'),
+    ('cx_weight', True, 'the contextual banks are'),
 )
 
 
@@ -252,7 +253,7 @@ def broadcast_targets(contents, styles, device, group=None, args=None):
     broadcast reads it where it lies), so the caller keeps the DeviceArray alive for as long as it
     uses the returned tensor -- `DeviceArray.free()` / `StyleTransfer._drop_contents()` end both.
     The other ranks get allocations of their own.  ``args``: the run's options, when the caller has them --
-    a run with --style-masks, --content-mask, --stat-weight, --nnfm-weight, --swd-weight, --selfsim-weight or --shift-weight is refused here
+    a run with --style-masks, --content-mask, --stat-weight, --nnfm-weight, --swd-weight, --selfsim-weight, --shift-weight or --cx-weight is refused here
     (refuse_unbroadcast_options)."""
     if args is not None:
         refuse_unbroadcast_options(args)

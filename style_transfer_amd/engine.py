@@ -20,13 +20,13 @@ import ctypes
 import numpy as np
 
 from . import lib
-from .config_system import nnfm_bank_rows
+from .config_system import nnfm_bank_rows, selfsim_grid
 from .netspec import NetSpec
 
 _TYPE_CODES = {'Input': lib.LAYER_INPUT, 'Convolution': lib.LAYER_CONV, 'ReLU': lib.LAYER_RELU,
                'Pooling': lib.LAYER_POOL}
 # the targets that tap layers of their own, in the order of their taps
-EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd', 'selfsim', 'shift')
+EXTRA_TAP_KINDS = ('stat', 'nnfm', 'swd', 'selfsim', 'shift', 'cx')
 
 
 class DeviceArray:
@@ -487,6 +487,38 @@ class TileEngine:
         offs = _shift_offsets(offsets)
         out = np.empty((len(offs) // 2, c, c), np.float32)
         lib.call('stx_shift_gram', self.handle, ptr, mem, c, h, w, offs, len(offs) // 2, out.ctypes.data)
+        return out
+
+    def set_cx_targets(self, banks, weights=None, points=1024, h=0.5):
+        """banks: {layer: Y [rows, C]} -- RAW feature vectors, what ``cx_rows`` gives for a style picture's feature
+        map (rows of several pictures concatenated) -- and weights: {layer: factor} (default 1 each); an empty dict:
+        none (stx_set_cx_targets).  The library copies the rows and builds their mean and the centred unit rows
+        once, here.  ``points``: the most sample positions per tile, 2 to 4096; ``h``: the bandwidth, above 0.
+        Call it after ``set_contents_and_styles``, which clears the targets.  A layer with a target is part of
+        every tile evaluation of the group from then on."""
+        keep, n = [], len(banks)
+        table = (lib.CxTarget * max(1, n))()
+        for t, (layer, rows) in zip(table, banks.items()):
+            ptr, mem, obj = _as_arg(rows)
+            if len(obj.shape) != 2:
+                raise ValueError('contextual bank %s: a [rows, C] array is expected' % layer)
+            keep.append(obj)
+            t.layer, t.channels, t.rows = self._cstr(layer), int(obj.shape[1]), int(obj.shape[0])
+            t.raw_rows, t.mem, t.points, t.h = ptr, mem, int(points), float(h)
+            t.weight = float(weights.get(layer, 1.0)) if weights is not None else 1.0
+        lib.call('stx_set_cx_targets', self.handle, table, n)
+        self.primary.extra_taps['cx'] = list(banks)
+        del keep
+
+    def cx_rows(self, feat, rows):
+        """The raw rows of a [C,h,w] feature map for a contextual bank as a DeviceArray [N, C]: its columns on the
+        grid of a budget of ``rows`` positions (config_system.selfsim_grid), raster order (stx_cx_rows).  Nothing
+        travels through the host when ``feat`` is on the device."""
+        ptr, mem, keep = _as_arg(feat)
+        c, h, w = (int(v) for v in keep.shape)
+        _, gh, gw = selfsim_grid(h, w, int(rows))
+        out = DeviceArray(self, (gh * gw, c))
+        lib.call('stx_cx_rows', self.handle, ptr, mem, c, h, w, int(rows), out.ptr, lib.DEVICE)
         return out
 
     def swd_target(self, feat, V, Q):

@@ -201,8 +201,14 @@ class TileFarm:
     def set_shift_targets(self, targets, weights=None):
         self._set_on_primaries('set_shift_targets', targets, weights)
 
+    def set_cx_targets(self, banks, weights=None, points=1024, h=0.5):
+        self._set_on_primaries('set_cx_targets', banks, weights, points, h)
+
     def feature_stats(self, feat):
         return self.master.feature_stats(feat)
+
+    def cx_rows(self, feat, rows):
+        return self.master.cx_rows(feat, rows)
 
     def shift_gram(self, feat, offsets):
         return self.master.shift_gram(feat, offsets)

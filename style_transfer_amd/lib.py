@@ -105,6 +105,12 @@ class ShiftTarget(ctypes.Structure):
                 ('weight', ctypes.c_double)]
 
 
+class CxTarget(ctypes.Structure):
+    _fields_ = [('layer', ctypes.c_char_p), ('channels', ctypes.c_int), ('rows', ctypes.c_int),
+                ('raw_rows', ctypes.c_void_p), ('mem', ctypes.c_int), ('points', ctypes.c_int),
+                ('h', ctypes.c_double), ('weight', ctypes.c_double)]
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -145,6 +151,7 @@ SIGNATURES = {
     'stx_set_swd_targets': [_vp, ctypes.POINTER(SwdTarget), _i],
     'stx_set_selfsim_targets': [_vp, ctypes.POINTER(SelfsimTarget), _i],
     'stx_set_shift_targets': [_vp, ctypes.POINTER(ShiftTarget), _i],
+    'stx_set_cx_targets': [_vp, ctypes.POINTER(CxTarget), _i],
     'stx_set_content_mask': [_vp, _vp, _i, _i, _i],
     'stx_features_tile': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_char_p), _i,
                           ctypes.POINTER(_vp), _i],
@@ -155,6 +162,8 @@ SIGNATURES = {
     'stx_feature_stats': [_vp, _vp, _i, _i, _i, _vp, _vp, _i],
     'stx_swd_target': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     'stx_shift_gram': [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _vp],
+    'stx_cx_rows': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i],
+    'stx_cx_bank': [_vp, _vp, _i, _i, _i, _vp, _vp, _i],
     'stx_nnfm_bank': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i],
     'stx_nnfm_patch_bank': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i],
     'stx_image_cut_tile': [_vp, _vp, _i, _i, c_int_p, _i, _i, _i, _i, _vp],
@@ -201,6 +210,7 @@ SIGNATURES = {
     'stx_op_swd_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_selfsim_terms': [_vp, _vp, _vp, _i, _i, _i, _i, _vp, c_double_p, _vp],
     'stx_op_shift_terms': [_vp, _vp, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _i, _vp, _vp, c_double_p],
+    'stx_op_cx_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, ctypes.c_double, _vp, c_double_p, _vp, _vp],
     'stx_op_nnfm_terms': [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_patch_terms': [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],
     'stx_op_nnfm_knn_terms': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, c_double_p],

@@ -15,7 +15,8 @@ from .config_system import (LAP_POOLS_DEFAULT, SWD_QUANTILES, ValuePlaceholder, 
                             check_photo_options, check_selfsim_options, check_stat_options, check_swd_options, ffloat,
                             nnfm_bank_rows, nnfm_layer_args, nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on,
                             selfsim_layer_args, selfsim_points, stat_layer_args, swd_dirs, swd_directions,
-                            swd_layer_args, check_shift_options, check_shift_tile, shift_layer_args, shift_offsets)
+                            swd_layer_args, check_shift_options, check_shift_tile, shift_layer_args, shift_offsets,
+                            check_cx_bank, check_cx_options, cx_bank_rows, cx_h, cx_layer_args, cx_points, cx_rows)
 
 
 def parse_weights(args, master_weight):
@@ -249,6 +250,44 @@ class ShiftTargets(LayerTargets):
         farm.set_shift_targets(targets, self.weights)
 
 
+class CxTargets(LayerTargets):
+    """--cx-weight / --cx-layers / --cx-points / --cx-rows / --cx-h (the contextual style term): per layer one bank
+    of the style pictures' RAW feature vectors on a grid of at most --cx-rows positions per picture and size,
+    gathered on the master GPU and concatenated over the variants; ``targets`` = {layer: DeviceArray [rows, C]}.  The
+    engines centre and normalise the rows when they take them.  Points and bandwidth are read once per scale and go
+    with the targets; a bank past the library's limits is refused before its part is allocated."""
+    FLAG, WEIGHT, WHAT, layer_args = '--cx-layers', 'cx_weight', 'bank', staticmethod(cx_layer_args)
+    points = rows = h = None    # --cx-points, --cx-rows, --cx-h of the scale
+
+    def read(self, st):
+        super().read(st)
+        self.points, self.rows, self.h = cx_points(st.args), cx_rows(st.args), cx_h(st.args)
+
+    def take(self, st, layer, feat):
+        cx_bank_rows(feat.shape[1], feat.shape[2], self.rows, sum(part.shape[0] for part in self._parts[layer]),
+                     self.points)
+        self._parts[layer].append(st.farm.cx_rows(feat, self.rows))
+
+    def finish(self, st, count, quiet):
+        self.targets = {layer: st.engine.concat_rows(parts) for layer, parts in self._parts.items()}
+        if not quiet:
+            print('CX bank rows: ' + ', '.join('%s %d' % (layer, bank.shape[0]) for layer, bank in self.targets.items()))
+
+    def drop(self):
+        for bank in (self.targets or {}).values():
+            bank.free()
+        self.targets = None
+
+    def send(self, st, roll=None):
+        for layer in self.weights or ():        # (kept banks of an earlier scale against this scale's points)
+            if self.targets and layer in self.targets:
+                check_cx_bank(self.targets[layer].shape[0], self.points, self.rows)
+        super().send(st, roll)
+
+    def set_targets(self, farm, targets):
+        farm.set_cx_targets(targets, self.weights, self.points, self.h)
+
+
 class Masks(TargetTerm):
     """--style-masks / --content-mask (spatial control): ``st.style_masks`` and ``st.content_mask`` resized to the
     scale's content size.  Under --jitter the engines hold content maps of the rolled picture and shift nothing,
@@ -275,7 +314,8 @@ def target_terms(args, known_layers):
     """The target terms of a run, in the order they are sent; a bad option is refused here, before any GPU work.
     (The masks are handed to transfer_multiscale, so their term is always listed.)"""
     checked = ((check_stat_options, StatTargets), (check_nnfm_options, NnfmBanks), (check_swd_options, SwdTargets),
-               (check_selfsim_options, SelfsimTargets), (check_shift_options, ShiftTargets))
+               (check_selfsim_options, SelfsimTargets), (check_shift_options, ShiftTargets),
+               (check_cx_options, CxTargets))
     return [cls() for check, cls in checked if check(args, known_layers)] + [Masks()]
 
 
