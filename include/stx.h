@@ -897,6 +897,60 @@ int stx_image_lap(stx_engine *e, const float *img, float *grad, int H, int W, in
 int stx_image_photo(stx_engine *e, const float *img, const float *content, float *grad, int H, int W,
                     double eps, double scale, double *loss_out);
 
+/* The temporal-consistency term for video (Ruder, Dosovitskiy, Brox, "Artistic Style Transfer for
+ * Videos", 2016): earlier stylised frames, warped to the current frame by optical flow and composited,
+ * hold the iterate wherever the flow is reliable.  All arrays are STX_DEVICE float32: pictures
+ * [3][H][W] in the network's input format, un-rolled; flows [2][H][W], plane 0 horizontal and plane 1
+ * vertical; weight [H][W].
+ *
+ * stx_image_flow_warp composites ONE earlier frame `prev` into target / weight.  flow_b is the backward
+ * flow (current frame -> that frame), flow_f the forward flow (that frame -> current) or NULL; (su, sv)
+ * scale the flows' components to pixels of this H x W (a flow resampled from W0 x H0: su = W / W0, sv =
+ * H / H0).  Every value between the float32 inputs and outputs is float64 on the device, each operation
+ * rounded once in the order written here.  For pixel (x, y):
+ *   u = su * flow_b[0][y][x],  v = sv * flow_b[1][y][x]
+ *   unknown     a flow vector with a component that is not finite or above 1e9 in magnitude BEFORE
+ *               scaling (Middlebury's marker)
+ *   q           = (x + u, y + v);   inside: 0 <= qx <= W - 1 and 0 <= qy <= H - 1
+ *   taps        x0 = min(floor(qx), W - 2), fx = qx - x0;  y0, fy likewise
+ *   mix(p)      = top + fy * (bottom - top),  top = p[y0][x0] + fx * (p[y0][x0+1] - p[y0][x0]),
+ *               bottom the same on row y0 + 1;   value = mix(prev plane), per plane
+ *   forward     (fu, fv) = (su * mix(flow_f[0]), sv * mix(flow_f[1])); an unknown vector at any of the
+ *               four taps makes the pixel unreliable
+ *   consistent  (u + fu)^2 + (v + fv)^2 <= 0.01 * (((u^2 + v^2) + fu^2) + fv^2) + 0.5
+ *               (every pixel is consistent when flow_f is NULL)
+ *   boundary    ux = (u(x+1, y) - u(x-1, y)) / 2 and uy, vx, vy likewise on the scaled flow, indices
+ *               clamped to the picture (replicated border):
+ *               ((ux^2 + uy^2) + vx^2) + vy^2 > 0.01 * (u^2 + v^2) + 0.002, or an unknown neighbour
+ *   c           = known and inside and consistent and not boundary
+ * The constants are Ruder's and are in pixels of the H x W at hand, whatever scale of a pyramid that
+ * is: a flow scaled down to a coarse level meets the same absolute 0.5 and 0.002, so the tests are
+ * relatively looser there.
+ * Composite (Ruder's long-term rule with binary weights; called closest frame first, the closest
+ * reliable frame wins):  first != 0 means the accumulators count as zero (there is no memset pass);
+ * if the weight before is 0 and c holds, target = (float)value on the three planes and weight = 1;
+ * else, if first, target = 0 and weight = 0; else both stay as they are.  Each pixel writes only its
+ * own outputs; no atomics: the same inputs give the same bits.  Traffic with flow_f and first: flow_b
+ * 8 + flow_f 8 + prev 12 read (the stencil's neighbours and the taps are other lanes' lines), target
+ * 12 + weight 4 written: 44 B per pixel.  A null pointer other than flow_f, H < 2, W < 2 or a scale
+ * factor that is not finite is STX_ERR_ARG.  Asynchronous.
+ *
+ * stx_image_temporal is the term, per element in float32:
+ *   w' = min(max(weight, 0), 1), NaN as 0 (fractional weights are allowed)
+ *   d  = (img - target) / 127.5f
+ *   grad = (scale * w') * d + grad            loss = scale * 63.75 * sum w' * d^2
+ * so grad is the exact derivative of loss, and at w' = 1 it is the auxiliary-image term's gradient
+ * (stx_image_regularizers) at aux_scale = scale.  One pass; the sum goes through per-block partials
+ * that are added in double in a fixed order.  grad is read and written at most once: a pixel with w' =
+ * 0 is skipped and an element whose addend is zero is not written, so img == target wherever w' > 0,
+ * or a weight of all zeros, gives a loss of exactly 0 and leaves every bit of grad alone.  The term
+ * ignores the iteration's shift, like stx_image_lap.  A null pointer or H, W <= 0 is STX_ERR_ARG.
+ * *loss_out (host) is written at the next stx_sync; asynchronous like stx_image_lap. */
+int stx_image_flow_warp(stx_engine *e, const float *prev, const float *flow_b, const float *flow_f,
+                        int H, int W, double su, double sv, int first, float *target, float *weight);
+int stx_image_temporal(stx_engine *e, const float *img, float *grad, const float *target,
+                       const float *weight, int H, int W, double scale, double *loss_out);
+
 /* ------------------------------------------------------------- single-kernel test hooks */
 /* Direct entry points to the individual kernels, used by tests/ to check each against the
  * oracle (x, w, b, y: STX_DEVICE).  w is the Caffe layout [Cout][Cin][k][k]. */

@@ -36,6 +36,7 @@ SOURCES = {
     'lap.hip': ['-ffp-contract=off'],
     'stat.hip': ['-ffp-contract=off'],
     'photo.hip': ['-ffp-contract=off'],
+    'temporal.hip': ['-ffp-contract=off'],
     'nnfm.hip': ['-ffp-contract=off'],
     'swd.hip': ['-ffp-contract=off'],
     'selfsim.hip': ['-ffp-contract=off'],

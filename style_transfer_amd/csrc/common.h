@@ -841,6 +841,14 @@ int photo_blocks(int H, int W);
 int photo_launch(hipStream_t s, const float *img, const float *content, float *grad, int H, int W,
                  double eps, double scale, double *loss_term, float *scratch);
 
+// temporal.hip: the temporal-consistency term.  flow_warp_launch composites one earlier frame warped by a flow
+// into target / weight (H, W >= 2; flow_f may be null); temporal_launch adds the masked term's gradient and leaves
+// *loss_term = sum w' d^2 (without scale * 63.75); scratch holds kBlocks floats.
+int flow_warp_launch(hipStream_t s, const float *prev, const float *flow_b, const float *flow_f, int H, int W,
+                     double su, double sv, int first, float *target, float *weight);
+int temporal_launch(hipStream_t s, const float *img, float *grad, const float *target, const float *weight,
+                    int H, int W, double scale, double *loss_term, float *scratch);
+
 // image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,
                 float *avg, size_t n, double lr, double b1, double b2, double bp1, double c1,

@@ -1,6 +1,7 @@
 // libstx host side: the entries that work on whole images, feature maps and parameter vectors
 // (stx_image_*, stx_map_*, stx_vec_*, stx_adam_step) -- thin wrappers that check their arguments and
-// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip / photo.hip on the engine's stream.
+// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip / photo.hip / temporal.hip on the
+// engine's stream.
 
 #include <cmath>
 #include <cstdint>
@@ -334,6 +335,45 @@ int stx_image_photo(stx_engine *e, const float *img, const float *content, float
     // (the engine's reduction scratch holds kBlocks floats and more: one partial per workgroup)
     return queue_dterms(e, {scale}, loss_out, [&](double *term) {
         return photo_launch(e->stream, img, content, grad, H, W, eps, scale, term, e->red_scratch.f());
+    });
+}
+
+// ---- the temporal-consistency term (temporal.hip) ----
+
+int stx_image_flow_warp(stx_engine *e, const float *prev, const float *flow_b, const float *flow_f, int H, int W,
+                        double su, double sv, int first, float *target, float *weight) {
+    if (!e || !prev || !flow_b || !target || !weight) {
+        set_error("stx_image_flow_warp: %s is null", !e ? "the engine" : !prev ? "prev" : !flow_b ? "flow_b" :
+                  !target ? "target" : "weight");
+        return STX_ERR_ARG;
+    }
+    if (H < 2 || W < 2) {
+        set_error("stx_image_flow_warp: a %d x %d picture holds no 2 x 2 taps", H, W);
+        return STX_ERR_ARG;
+    }
+    if (!std::isfinite(su) || !std::isfinite(sv)) {
+        set_error("stx_image_flow_warp: scale factors (%g, %g), but finite values are needed", su, sv);
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    return flow_warp_launch(e->stream, prev, flow_b, flow_f, H, W, su, sv, first, target, weight);
+}
+
+int stx_image_temporal(stx_engine *e, const float *img, float *grad, const float *target, const float *weight,
+                       int H, int W, double scale, double *loss_out) {
+    if (!e || !img || !grad || !target || !weight || !loss_out) {
+        set_error("stx_image_temporal: %s is null", !e ? "the engine" : !img ? "img" : !grad ? "grad" :
+                  !target ? "target" : !weight ? "weight" : "loss_out");
+        return STX_ERR_ARG;
+    }
+    if (H <= 0 || W <= 0) {
+        set_error("stx_image_temporal: a %d x %d picture", H, W);
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    // (the engine's reduction scratch holds kBlocks floats and more: one partial per workgroup)
+    return queue_dterms(e, {scale * 63.75}, loss_out, [&](double *term) {
+        return temporal_launch(e->stream, img, grad, target, weight, H, W, scale, term, e->red_scratch.f());
     });
 }
 

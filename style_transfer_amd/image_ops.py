@@ -180,6 +180,35 @@ def photo_loss(engine, img, grad, content, eps, scale):
     return out
 
 
+# ---------------------------------------------------------------------- --temporal-weight
+def flow_warp(engine, prev, flow_b, flow_f, su, sv, first, target, weight):
+    """Composites one earlier frame ``prev`` [3,H,W], warped by the backward flow ``flow_b`` [2,H,W], into
+    ``target`` [3,H,W] / ``weight`` [H,W] wherever the flow is reliable and no closer frame has the pixel
+    (include/stx.h has the definition).  ``flow_f``: the forward flow for the consistency test, or None; (su,
+    sv): what scales the flows' components to pixels of this size; ``first``: the accumulators count as zero."""
+    _, H, W = prev.shape
+    for name, arr, shape in (('flow_b', flow_b, (2, H, W)), ('flow_f', flow_f, (2, H, W)),
+                             ('target', target, (3, H, W)), ('weight', weight, (H, W))):
+        if arr is not None and tuple(arr.shape) != shape:
+            raise ValueError('flow_warp: %s of shape %s for a picture of %dx%d' % (name, tuple(arr.shape), W, H))
+    lib.call('stx_image_flow_warp', engine.handle, prev.ptr, flow_b.ptr, flow_f.ptr if flow_f is not None else None,
+             H, W, float(su), float(sv), int(bool(first)), target.ptr, weight.ptr)
+
+
+def temporal_loss(engine, img, grad, target, weight, scale):
+    """grad += the gradient of scale * 63.75 * sum w' ((img - target) / 127.5)^2 with w' = ``weight`` [H,W]
+    clipped to [0, 1] (the temporal-consistency term; include/stx.h has the definition).  ``img``, ``grad``,
+    ``target``: DeviceArrays [3,H,W].  Returns a PendingScalar with the loss (valid after sync)."""
+    _, H, W = img.shape
+    if tuple(target.shape) != tuple(img.shape) or tuple(weight.shape) != (H, W):
+        raise ValueError('temporal_loss: a target of shape %s and a weight of shape %s for an image of %dx%d'
+                         % (tuple(target.shape), tuple(weight.shape), W, H))
+    out = engine.keep_until_sync(PendingScalar())
+    lib.call('stx_image_temporal', engine.handle, img.ptr, grad.ptr, target.ptr, weight.ptr, H, W, float(scale),
+             ctypes.byref(out._v))
+    return out
+
+
 def adam_step(engine, params, grad, g1, g2, p1, avg, lr, b1, b2, bp1, corr1, corr2, corrp):
     lib.call('stx_adam_step', engine.handle, params.ptr, grad.ptr, g1.ptr, g2.ptr, p1.ptr, avg.ptr,
              params.size, float(lr), float(b1), float(b2), float(bp1), float(corr1), float(corr2),

@@ -181,6 +181,8 @@ SIGNATURES = {
     'stx_image_lap_target': [_vp, _vp, _i, _i, _i, c_int_p, _vp],
     'stx_image_lap': [_vp, _vp, _vp, _i, _i, _i, c_int_p, c_double_p, _vp, _d, c_double_p],
     'stx_image_photo': [_vp, _vp, _vp, _vp, _i, _i, _d, _d, c_double_p],
+    'stx_image_flow_warp': [_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp],
+    'stx_image_temporal': [_vp, _vp, _vp, _vp, _vp, _i, _i, _d, c_double_p],
     'stx_adam_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _d, _d, _d, _d, _d, _d, _d],
     'stx_vec_dot': [_vp, _vp, _vp, _sz, c_double_p],
     'stx_vec_axpy': [_vp, _d, _vp, _vp, _sz],

@@ -16,7 +16,10 @@ from .config_system import (LAP_POOLS_DEFAULT, SWD_QUANTILES, ValuePlaceholder, 
                             nnfm_bank_rows, nnfm_layer_args, nnfm_cover, nnfm_k, nnfm_patch, nnfm_stride, option_on,
                             selfsim_layer_args, selfsim_points, stat_layer_args, swd_dirs, swd_directions,
                             swd_layer_args, check_shift_options, check_shift_tile, shift_layer_args, shift_offsets,
-                            check_cx_bank, check_cx_options, cx_bank_rows, cx_h, cx_layer_args, cx_points, cx_rows)
+                            check_cx_bank, check_cx_options, cx_bank_rows, cx_h, cx_layer_args, cx_points, cx_rows,
+                            check_temporal_options)
+from .flow import read_flo
+from .resample import resample_device
 
 
 def parse_weights(args, master_weight):
@@ -419,7 +422,78 @@ class PhotoTerm(ImageTerm):
                                           st.layer_weights['data'] * photo_weight), st.engine)
 
 
+class TemporalTerm(ImageTerm):
+    """--temporal-weight / --prev-images / --flows / --flows-fwd / --temporal-init (temporal consistency for
+    video): the earlier stylised frames and their flows are read when the run is set up; the flows go to the
+    master GPU at first use and stay there.  Per scale ``target`` [3,H,W] and ``weight`` [H,W] are the composite
+    of the earlier frames warped to this frame (image_ops.flow_warp, closest frame first); the previous
+    scale's are freed when the next ones are made."""
+
+    def __init__(self, args):
+        prev, flows, fwd = check_temporal_options(args)
+        self.pictures = [Image.open(path).convert('RGB') for path in prev]
+        with Image.open(args.content_image) as content:
+            self.size0 = content.size           # (W0, H0): the content picture as loaded, the flows' frame
+
+        def load(path):
+            flow = read_flo(path)
+            if (flow.shape[2], flow.shape[1]) != tuple(self.size0):
+                raise ValueError('%s: a flow of %d x %d, but the content picture %s is %d x %d'
+                                 % (path, flow.shape[2], flow.shape[1], args.content_image, *self.size0))
+            return flow
+        self.flows_b = [load(path) for path in flows]
+        self.flows_f = [load(path) for path in fwd] or [None] * len(flows)
+        self.target = self.weight = None
+        self._on_device = False
+
+    def composite(self, st, hw):
+        """Makes ``target`` and ``weight`` for a scale of h x w, unless they are that scale's already."""
+        h, w = int(hw[0]), int(hw[1])
+        if self.weight is not None and tuple(self.weight.shape) == (h, w):
+            return
+        eng = st.engine
+        if not self._on_device:
+            self.flows_b = [eng.to_device(flow) for flow in self.flows_b]
+            self.flows_f = [eng.to_device(flow) if flow is not None else None for flow in self.flows_f]
+            self._on_device = True
+        target, weight = eng.empty((3, h, w)), eng.empty((h, w))
+        su, sv = w / self.size0[0], h / self.size0[1]
+        for index, (picture, flow_b, flow_f) in enumerate(zip(self.pictures, self.flows_b, self.flows_f)):
+            # exactly as aux_image is brought to a scale
+            prev = eng.to_device(st.pil_to_image(picture.resize((w, h), Image.LANCZOS)))
+            # The flows are resampled like pictures.  An unknown marker (1e10) smears through the Lanczos window
+            # into values that are still huge: they point far outside the frame, so c = 0 there -- around an
+            # unknown pixel a few more pixels go free, which is the conservative outcome.
+            scaled_b = resample_device(eng, flow_b, (h, w))
+            scaled_f = resample_device(eng, flow_f, (h, w)) if flow_f is not None else None
+            image_ops.flow_warp(eng, prev, scaled_b, scaled_f, su, sv, index == 0, target, weight)
+            for arr in (prev, scaled_b, scaled_f):
+                if arr is not None:
+                    arr.free()
+        for arr in (self.target, self.weight):
+            if arr is not None:
+                arr.free()
+        self.target, self.weight = target, weight
+
+    def prepare(self, st, picture):
+        self.composite(st, st.img.shape[1:])
+
+    def start_image(self, st, content):
+        """--temporal-init: the start image [3,h,w] (host) of the scale whose content picture is the PIL image
+        ``content`` -- the composite where its weight is set, the content picture elsewhere."""
+        self.composite(st, (content.size[1], content.size[0]))
+        return np.where(self.weight.get()[None] > 0, self.target.get(), st.pil_to_image(content))
+
+    def add(self, st, loss, params, roll):
+        temporal_weight = getattr(st.args, 'temporal_weight', 0)
+        if temporal_weight:
+            loss.add(image_ops.temporal_loss(st.engine, params, st.grad, self.target, self.weight,
+                                             st.layer_weights['data'] * temporal_weight), st.engine)
+
+
 def image_terms(args):
     """The image terms of a run, in the order they join the loss; a bad option is refused here."""
-    weights = (('swt_weight', SwtTerm), ('lap_weight', LapTerm), ('photo_weight', PhotoTerm))
+    weights = (('swt_weight', SwtTerm), ('lap_weight', LapTerm), ('photo_weight', PhotoTerm),
+               ('temporal_weight', TemporalTerm))
+    check_temporal_options(args)        # (--temporal-init without the term has no term to refuse it)
     return [cls(args) for name, cls in weights if option_on(args, name)]

@@ -480,12 +480,17 @@ class StyleTransfer:
                          transfer=self)
 
     # ------------------------------------------------------------------------- all scales
-    def _first_iterate(self, plan, initial_image):
+    def _first_iterate(self, plan, initial_image, content=None):
         """The start image of the coarsest level and its optimizer (style_transfer.py:883-900):
-        the supplied --init-image, or uniform noise drawn from the global RNG."""
+        the supplied --init-image, or uniform noise drawn from the global RNG.  With --temporal-init it is
+        the temporal term's composite of the earlier frames, made here for the level (``content``: its
+        first content picture, which fills what no flow reaches), and counts as a supplied picture."""
         args = self.args
         w, h = plan.content_wh
-        if initial_image:
+        if getattr(args, 'temporal_init', False):
+            term, = [term for term in self.image_terms if isinstance(term, terms.TemporalTerm)]
+            start, initial_image = term.start_image(self, content), True
+        elif initial_image:
             start = self.pil_to_image(initial_image.resize((w, h), Image.LANCZOS))
         else:
             start = self.pil_to_image(np.random.uniform(0, 255, size=(h, w, 3)))
@@ -558,7 +563,10 @@ class StyleTransfer:
                     self.aux_image = self.engine.to_device(
                         self.pil_to_image(aux_image.resize((w, h), Image.LANCZOS)))
                 if previous is None:
-                    self.optimizer = self._first_iterate(plan, initial_image)
+                    if getattr(args, 'temporal_init', False):
+                        self.optimizer = self._first_iterate(plan, initial_image, contents[0])
+                    else:
+                        self.optimizer = self._first_iterate(plan, initial_image)
                 else:
                     # model.resize_image (style_transfer.py:399-401): Lanczos, on the GPU
                     self.img = resample_device(self.engine, previous, (h, w))
