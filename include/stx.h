@@ -951,6 +951,66 @@ int stx_image_flow_warp(stx_engine *e, const float *prev, const float *flow_b, c
 int stx_image_temporal(stx_engine *e, const float *img, float *grad, const float *target,
                        const float *weight, int H, int W, double scale, double *loss_out);
 
+/* Optical flow for the term above, estimated from two grey frames: the robust variational method of
+ * Brox, Bruhn, Papenberg, Weickert ("High Accuracy Optical Flow Estimation Based on a Theory for
+ * Warping", ECCV 2004) in the discretisation of Sanchez, Monzon, Salgado ("Robust Optical Flow
+ * Estimation", IPOL 2013): coarse to fine with warping, a lagged nonlinearity, red-black SOR.  Every
+ * count is fixed; there is no stopping test.
+ *
+ * I1 (the frame the flow starts from) and I2 (the frame it points into) are [H][W] STX_DEVICE float32
+ * in 0 ... 255; flow_out is [2][H][W] STX_DEVICE float32, plane 0 horizontal and plane 1 vertical: the
+ * displacement w with I1(p) ~ I2(p + w(p)), which stx_image_flow_warp reads as flow_b when I1 is the
+ * current frame.  No unknown markers are written.  Every value in between is float64 on the device,
+ * each operation rounded once in the order written here (sums from left to right as bracketed).
+ *   sample(P, qx, qy) on a picture P [H][W]: qx = min(max(qx, 0), W - 1), x0 = min(floor(qx), W - 2),
+ *       fx = qx - x0 (y likewise; the taps of stx_image_flow_warp);  top = (1 - fx) * P[y0][x0] + fx *
+ *       P[y0][x0+1], bottom the same on row y0 + 1, value = (1 - fy) * top + fy * bottom  (exact at
+ *       whole coordinates, the last row and column included)
+ *   resample(P, h, w): sample(P, (x + 0.5) * (W / w) - 0.5, (y + 0.5) * (H / h) - 0.5) for x < w, y < h
+ *   dx(P) = (P[y][min(x+1, W-1)] - P[y][max(x-1, 0)]) / 2,  dy(P) likewise along y
+ * Pyramid: level 0 is the input; h' = floor(h * eta + 0.5), w' likewise; a level is added while
+ *   min(h', w') >= 16, up to `levels` of them.  sigma = 0.6 * sqrt(1 / (eta * eta) - 1), r =
+ *   ceil(3 * sigma), k[i] = exp(-(i * i) / (2 * sigma * sigma)) for i = -r .. r, divided by their sum
+ *   (added from -r up).  A level is resample(G, h', w') of the level below it, G its Gaussian: along x
+ *   first, then along y, indices clamped, each a sum from i = -r up that starts at 0.
+ * The coarsest level starts from u = v = 0; a finer one from u = resample(u_coarse, h, w) * (w /
+ *   w_coarse), v = resample(v_coarse, h, w) * (h / h_coarse).
+ * Per level, with A = I1's and B = I2's picture: Ax = dx(A), Ay = dy(A), Bx = dx(B), By = dy(B), Bxx =
+ *   dx(Bx), Bxy = dy(Bx), Byy = dy(By).  Then `outer` times:
+ *     Iz = sample(B, x + u, y + v) - A;  Ix, Iy, Ixx, Ixy, Iyy = sample of Bx, By, Bxx, Bxy, Byy there;
+ *     Ixz = Ix - Ax, Iyz = Iy - Ay;  du = dv = 0
+ *     `inner` times, with Su = u + du, Sv = v + dv:
+ *       b  = (Iz + Ix * du) + Iy * dv;  gx = (Ixz + Ixx * du) + Ixy * dv;  gy = (Iyz + Ixy * du) + Iyy * dv
+ *       psiD = 0.5 / sqrt((b * b + gamma * (gx * gx + gy * gy)) + eps * eps)
+ *       psiS = 0.5 / sqrt((((dx(Su)^2 + dy(Su)^2) + dx(Sv)^2) + dy(Sv)^2) + eps * eps)
+ *       g_n  = (alpha * (psiS(p) + psiS(n))) / 2 for the neighbours n = left, right, up, down, and 0 for
+ *              one outside the picture;  gs = ((g_left + g_right) + g_up) + g_down
+ *       A11 = psiD * (Ix * Ix + gamma * (Ixx * Ixx + Ixy * Ixy))
+ *       A12 = psiD * (Ix * Iy + gamma * (Ixx * Ixy + Ixy * Iyy))
+ *       A22 = psiD * (Iy * Iy + gamma * (Ixy * Ixy + Iyy * Iyy))
+ *       c1  = psiD * (Ix * Iz + gamma * (Ixx * Ixz + Ixy * Iyz))
+ *       c2  = psiD * (Iy * Iz + gamma * (Ixy * Ixz + Iyy * Iyz))
+ *       `sor` sweeps, each two half-sweeps: the pixels with (x + y) even, then the odd ones.  A pixel of
+ *       the half-sweep's colour takes, with s(S) = ((g_left * S_left + g_right * S_right) + g_up * S_up)
+ *       + g_down * S_down (a neighbour outside: its index clamped, its weight 0):
+ *         du = (1 - omega) * du + omega * ((((s(Su) - gs * u) - A12 * dv) - c1) / (A11 + gs))
+ *         dv = (1 - omega) * dv + omega * ((((s(Sv) - gs * v) - A12 * du) - c2) / (A22 + gs))   (the new du)
+ *         Su = u + du,  Sv = v + dv
+ *     u = u + du, v = v + dv
+ * flow_out = (float)u, (float)v of level 0.  Identical frames give a flow of exactly 0.  No atomics: the
+ * same inputs give the same bits.  With levels = outer = inner = 1 and a small sor the call is one
+ * linear solve.
+ *
+ * Asynchronous: the launches are queued on the engine's stream.  The workspace (about 300 bytes per pixel) is
+ * the engine's; it is freed at the next stx_sync, when the call's work is done.  STX_ERR_ARG, before
+ * anything is allocated or launched: a null pointer, H or W below 16 or above 32768, a parameter that is
+ * not finite, alpha <= 0, gamma < 0, eta outside (0.25, 0.95), omega outside (0, 2), eps <= 0, or a
+ * count below 1.  The defaults are alpha 18, gamma 6, eta 0.75, omega 1.8, eps 0.001, outer 5, inner 1,
+ * sor 10 and as many levels as fit (any large count). */
+typedef struct { double alpha, gamma, eta, omega, eps; int levels, outer, inner, sor; } stx_flow_params;
+int stx_image_flow_estimate(stx_engine *e, const float *I1, const float *I2, int H, int W,
+                            const stx_flow_params *p, float *flow_out);
+
 /* ------------------------------------------------------------- single-kernel test hooks */
 /* Direct entry points to the individual kernels, used by tests/ to check each against the
  * oracle (x, w, b, y: STX_DEVICE).  w is the Caffe layout [Cout][Cin][k][k]. */

@@ -37,6 +37,7 @@ SOURCES = {
     'stat.hip': ['-ffp-contract=off'],
     'photo.hip': ['-ffp-contract=off'],
     'temporal.hip': ['-ffp-contract=off'],
+    'flow.hip': ['-ffp-contract=off'],
     'nnfm.hip': ['-ffp-contract=off'],
     'swd.hip': ['-ffp-contract=off'],
     'selfsim.hip': ['-ffp-contract=off'],

@@ -290,6 +290,20 @@ _EXTENSIONS = [
                             help='one forward optical flow per earlier frame, from that frame to the current one, '
                                  'for the forward-backward consistency test; without them only motion boundaries '
                                  'and the frame\'s edge make a pixel unreliable (default: none)')),
+    (('--prev-contents',), dict(nargs='+', metavar='IMAGE',
+                                help='the earlier CONTENT frames, one per --prev-images entry, closest first: the '
+                                     "backward and the forward flow of every earlier frame are estimated on the GPU "
+                                     "from the content frames at the content picture's size as loaded (Brox et al. "
+                                     '2004, a variational solver in float64), instead of being read from --flows / '
+                                     '--flows-fwd; the consistency test is always on.  Both flows of one earlier '
+                                     'frame at 1024 x 1024 take 35 ms on an MI355X (11.5 ms of device time each), '
+                                     'once per run: 0.019 of a whole --size 1024 run; python -m '
+                                     'style_transfer_amd.flow writes the same flows as .flo files (default: none)')),
+    (('--flow-alpha',), dict(metavar='ALPHA', type=ffloat,
+                             help='smoothness weight of the flow estimator, finite and above 0 (default: 18)')),
+    (('--flow-gamma',), dict(metavar='GAMMA', type=ffloat,
+                             help='weight of the gradient-constancy term of the flow estimator, finite and 0 or '
+                                  'more (default: 6)')),
     (('--temporal-init',), dict(action='store_true',
                                 help='start from the warped earlier frame(s), and from the content picture where no '
                                      'flow is reliable, instead of noise (default: off)')),
@@ -439,13 +453,38 @@ def check_photo_options(args):
 
 
 TEMPORAL_MAX_FRAMES = 4
+FLOW_DEFAULTS = dict(flow_alpha=18.0, flow_gamma=6.0)
+
+
+def flow_value(args, name):
+    """--flow-alpha (finite, above 0) or --flow-gamma (finite, 0 or more) as a float, or its default."""
+    value = getattr(args, name, FLOW_DEFAULTS[name])
+    option = '--' + name.replace('_', '-')
+    try:
+        number = float(value)
+        ok = math.isfinite(number) and (number > 0 if name == 'flow_alpha' else number >= 0)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%s %s: a finite value %s is needed' % (option, value,
+                                                                  'above 0' if name == 'flow_alpha' else 'of 0 or more'))
+    return number
+
+
+def temporal_prev_contents(args):
+    """The --prev-contents paths (closest first), [] when not given; ``check_temporal_options`` checks them."""
+    given = getattr(args, 'prev_contents', None)
+    return [given] if isinstance(given, str) else list(given or [])
 
 
 def check_temporal_options(args):
     """--temporal-weight / --prev-images / --flows / --flows-fwd / --temporal-init: refused before any GPU work
     are a weight that is on without earlier frames or without flows, lists of different lengths, more than four
     frames, and --temporal-init together with --init-image or without the term.  Returns (pictures, backward
-    flows, forward flows) as lists of paths, all empty when the term is off."""
+    flows, forward flows) as lists of paths, all empty when the term is off.  With --prev-contents
+    (``temporal_prev_contents`` returns them) the flows are estimated: both lists of flows are then empty, and
+    refused are --flows or --flows-fwd beside it, a count other than --prev-images', and --prev-contents, --flow-alpha
+    or --flow-gamma without the term or, the latter two, without --prev-contents or out of range."""
     def paths(name):
         given = getattr(args, name, None)
         return [given] if isinstance(given, str) else list(given or [])
@@ -456,11 +495,31 @@ def check_temporal_options(args):
         if not on:
             raise ValueError('--temporal-init starts from the warped --prev-images, which only the temporal term '
                              'makes: --temporal-weight is off')
+    contents = paths('prev_contents')
+    for name, option in (('flow_alpha', '--flow-alpha'), ('flow_gamma', '--flow-gamma')):
+        if hasattr(args, name):
+            if not contents:
+                raise ValueError('%s sets the flow estimator of --prev-contents, which is not given' % option)
+            flow_value(args, name)
+    if contents and not on:
+        raise ValueError('--prev-contents gives the frames that the flows of the temporal term are estimated from: '
+                         '--temporal-weight is off')
     if not on:
         return [], [], []
     prev, flows, fwd = paths('prev_images'), paths('flows'), paths('flows_fwd')
     if not prev:
         raise ValueError('--temporal-weight needs the earlier stylised frame(s): --prev-images is missing')
+    if contents:
+        for name, given in (('--flows', flows), ('--flows-fwd', fwd)):
+            if given:
+                raise ValueError('--prev-contents estimates both flows of every earlier frame, and %s names files to '
+                                 'read them from; give one of them' % name)
+        if len(prev) > TEMPORAL_MAX_FRAMES:
+            raise ValueError('--prev-images: %d frames, but %d at most are taken' % (len(prev), TEMPORAL_MAX_FRAMES))
+        if len(contents) != len(prev):
+            raise ValueError('--prev-contents: %d content frame(s) for %d --prev-images; one per earlier frame is needed'
+                             % (len(contents), len(prev)))
+        return prev, [], []
     if not flows:
         raise ValueError('--temporal-weight needs a backward flow per earlier frame: --flows is missing')
     if len(prev) > TEMPORAL_MAX_FRAMES:

@@ -849,6 +849,15 @@ int flow_warp_launch(hipStream_t s, const float *prev, const float *flow_b, cons
 int temporal_launch(hipStream_t s, const float *img, float *grad, const float *target, const float *weight,
                     int H, int W, double scale, double *loss_term, float *scratch);
 
+// flow.hip: the optical-flow estimator (stx_image_flow_estimate; the caller has checked the parameters).
+// flow_levels fills the pyramid's sizes (kFlowMaxLevels entries at most) and returns their count; `work` holds
+// flow_workspace_doubles(...) doubles and is read and written by the queued launches only.
+constexpr int kFlowMaxLevels = 256;
+int flow_levels(int H, int W, double eta, int levels, int *hs, int *ws);
+size_t flow_workspace_doubles(int H, int W, double eta, int levels);
+int flow_estimate_launch(hipStream_t s, const float *I1, const float *I2, int H, int W, const stx_flow_params &p,
+                         float *flow_out, double *work);
+
 // image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,
                 float *avg, size_t n, double lr, double b1, double b2, double bp1, double c1,

@@ -1,7 +1,7 @@
 // libstx host side: the entries that work on whole images, feature maps and parameter vectors
 // (stx_image_*, stx_map_*, stx_vec_*, stx_adam_step) -- thin wrappers that check their arguments and
-// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip / photo.hip / temporal.hip on the
-// engine's stream.
+// queue a few launches of image_ops.hip / reduce.hip / swt.hip / lap.hip / photo.hip / temporal.hip /
+// flow.hip on the engine's stream.
 
 #include <cmath>
 #include <cstdint>
@@ -375,6 +375,46 @@ int stx_image_temporal(stx_engine *e, const float *img, float *grad, const float
     return queue_dterms(e, {scale * 63.75}, loss_out, [&](double *term) {
         return temporal_launch(e->stream, img, grad, target, weight, H, W, scale, term, e->red_scratch.f());
     });
+}
+
+// ---- the optical-flow estimator of --prev-contents (flow.hip) ----
+
+int stx_image_flow_estimate(stx_engine *e, const float *I1, const float *I2, int H, int W,
+                            const stx_flow_params *p, float *flow_out) {
+    if (!e || !I1 || !I2 || !p || !flow_out) {
+        set_error("stx_image_flow_estimate: %s is null", !e ? "the engine" : !I1 ? "I1" : !I2 ? "I2" :
+                  !p ? "the parameters" : "flow_out");
+        return STX_ERR_ARG;
+    }
+    if (H < 16 || W < 16 || H > 32768 || W > 32768) {
+        set_error("stx_image_flow_estimate: a %d x %d picture, but sides from 16 to 32768 are needed", H, W);
+        return STX_ERR_ARG;
+    }
+    const struct { const char *name; double value; bool ok; } reals[] = {
+        {"alpha", p->alpha, p->alpha > 0},
+        {"gamma", p->gamma, p->gamma >= 0},
+        {"eta", p->eta, p->eta > 0.25 && p->eta < 0.95},
+        {"omega", p->omega, p->omega > 0 && p->omega < 2},
+        {"eps", p->eps, p->eps > 0},
+    };
+    for (const auto &r : reals)
+        if (!std::isfinite(r.value) || !r.ok) {
+            set_error("stx_image_flow_estimate: %s = %g, but %s is needed", r.name, r.value,
+                      "alpha > 0, gamma >= 0, 0.25 < eta < 0.95, 0 < omega < 2, eps > 0, all finite");
+            return STX_ERR_ARG;
+        }
+    const struct { const char *name; int value; } counts[] = {
+        {"levels", p->levels}, {"outer", p->outer}, {"inner", p->inner}, {"sor", p->sor}};
+    for (const auto &c : counts)
+        if (c.value < 1) {
+            set_error("stx_image_flow_estimate: %s = %d, but a count of at least 1 is needed", c.name, c.value);
+            return STX_ERR_ARG;
+        }
+    STX_TRY(e->set_device());
+    // The workspace is the engine's: it grows here if it has to and goes back at the next stx_sync, when the
+    // launches queued here are done (engine.cpp, do_sync) -- the call itself waits for nothing.
+    STX_TRY(e->flow_work.ensure(flow_workspace_doubles(H, W, p->eta, p->levels) * sizeof(double)));
+    return flow_estimate_launch(e->stream, I1, I2, H, W, *p, flow_out, static_cast<double *>(e->flow_work.ptr));
 }
 
 int stx_adam_step(stx_engine *e, float *params, const float *grad, float *g1, float *g2, float *p1,

@@ -1,7 +1,21 @@
-"""Optical flow files in the Middlebury ``.flo`` format, which the temporal term reads (--flows, --flows-fwd):
-little endian; the float32 magic 202021.25; int32 width, int32 height; then H * W interleaved (u, v) float32
-pairs, row by row.  A vector with a component above 1e9 in magnitude marks a pixel whose flow is unknown.
+"""Optical flow for the temporal term.
+
+Files in the Middlebury ``.flo`` format, which the term reads (--flows, --flows-fwd): little endian; the float32
+magic 202021.25; int32 width, int32 height; then H * W interleaved (u, v) float32 pairs, row by row.  A vector with
+a component above 1e9 in magnitude marks a pixel whose flow is unknown.
+
+The estimator behind --prev-contents (stx_image_flow_estimate, include/stx.h: Brox et al. 2004 on the GPU), and a
+command line that writes its result as a ``.flo`` file, so that flows can be computed once and reused:
+
+    python -m style_transfer_amd.flow FROM.png TO.png OUT.flo [--flow-alpha A] [--flow-gamma G] [--device N]
+
+OUT.flo is the displacement w with FROM(p) ~ TO(p + w(p)): with FROM the current content frame and TO an earlier one
+it is that frame's --flows entry, the other way round its --flows-fwd entry.
 """
+
+import argparse
+import math
+import sys
 
 import numpy as np
 
@@ -36,3 +50,109 @@ def write_flo(path, array):
         f.write(np.float32(FLO_MAGIC).astype('<f4').tobytes())
         f.write(np.array([flow.shape[2], flow.shape[1]], '<i4').tobytes())
         f.write(np.ascontiguousarray(flow.transpose(1, 2, 0)).astype('<f4').tobytes())
+
+
+# ------------------------------------------------------------------------------------------ the estimator
+FLOW_ALPHA_DEFAULT, FLOW_GAMMA_DEFAULT = 18.0, 6.0
+FLOW_MIN_SIDE = 16
+
+
+def grey(picture):
+    """L = 0.299 R + 0.587 G + 0.114 B of the 8-bit RGB picture as loaded (a PIL image of any mode), as float32
+    [H, W] in 0 ... 255: what the estimator is fed."""
+    rgb = np.asarray(picture.convert('RGB'), np.float32)
+    return np.float32(0.299) * rgb[..., 0] + np.float32(0.587) * rgb[..., 1] + np.float32(0.114) * rgb[..., 2]
+
+
+def pyramid_sizes(height, width, eta=0.75, levels=None):
+    """The estimator's pyramid as [(h, w)] from the input up: h' = floor(h eta + 0.5), and a level is added while
+    min(h', w') >= 16, up to ``levels`` (None: as many as fit)."""
+    sizes = [(int(height), int(width))]
+    while levels is None or len(sizes) < levels:
+        h, w = (int(math.floor(n * eta + 0.5)) for n in sizes[-1])
+        if min(h, w) < FLOW_MIN_SIDE:
+            break
+        sizes.append((h, w))
+    return sizes
+
+
+def launch_count(height, width, eta=0.75, levels=None, outer=5, inner=1, sor=10):
+    """Kernel launches of one estimate (csrc/flow.hip): the conversion, the coarsest level's zero start and the
+    output, two per step down of the pyramid, one per step up of the flow, and per level the derivatives and ``outer``
+    times [the warp and ``inner`` times (psiS, the coefficients, 2 ``sor`` half-sweeps)]."""
+    n = len(pyramid_sizes(height, width, eta, levels))
+    return 3 + 3 * (n - 1) + n * (1 + outer * (1 + inner * (2 + 2 * sor)))
+
+
+def estimate_flow(engine, pil_from, pil_to, **params):
+    """The flow [2, H, W] (a DeviceArray on ``engine``'s GPU) from the PIL picture ``pil_from`` into ``pil_to``, both
+    of one size: FROM(p) ~ TO(p + w(p)).  ``params``: the estimator's parameters (image_ops.flow_params).  The grey
+    pictures are freed, and the sync that waits for the estimate gives the library's workspace back."""
+    from . import image_ops
+    if pil_from.size != pil_to.size:
+        raise ValueError('estimate_flow: pictures of %d x %d and %d x %d, but one size is needed'
+                         % (pil_from.size + pil_to.size))
+    if min(pil_from.size) < FLOW_MIN_SIDE:
+        raise ValueError('estimate_flow: a picture of %d x %d, but the estimator needs %d pixels a side'
+                         % (pil_from.size + (FLOW_MIN_SIDE,)))
+    i1, i2 = engine.to_device(grey(pil_from)), engine.to_device(grey(pil_to))
+    try:
+        return image_ops.flow_estimate(engine, i1, i2, params)
+    finally:
+        engine.sync()           # (the frames are read by the queued launches)
+        i1.free()
+        i2.free()
+
+
+def build_flow_parser():
+    ap = argparse.ArgumentParser(prog='python -m style_transfer_amd.flow',
+                                 description='Optical flow between two frames as a Middlebury .flo file '
+                                             '(Brox et al. 2004 on the GPU): FROM(p) ~ TO(p + flow(p)).')
+    ap.add_argument('frame_from', metavar='FROM', help='the frame the flow starts from')
+    ap.add_argument('frame_to', metavar='TO', help='the frame the flow points into, of the same size')
+    ap.add_argument('out', metavar='OUT.flo', help='where the flow is written')
+    ap.add_argument('--flow-alpha', type=float, default=FLOW_ALPHA_DEFAULT, metavar='ALPHA',
+                    help='smoothness weight, above 0 (default: %(default)s)')
+    ap.add_argument('--flow-gamma', type=float, default=FLOW_GAMMA_DEFAULT, metavar='GAMMA',
+                    help='weight of the gradient-constancy term, 0 or more (default: %(default)s)')
+    ap.add_argument('--device', type=int, default=0, metavar='N', help='the GPU (default: %(default)s)')
+    return ap
+
+
+def parse_flow_args(argv=None):
+    """The command line's options, checked: everything that can be refused before an engine exists is refused here
+    (a ValueError that names the option or the file)."""
+    from PIL import Image
+    from .config_system import flow_value
+    opts = build_flow_parser().parse_args(argv)
+    opts.flow_alpha, opts.flow_gamma = flow_value(opts, 'flow_alpha'), flow_value(opts, 'flow_gamma')
+    if opts.device < 0:
+        raise ValueError('--device %d: a device number of 0 or more is needed' % opts.device)
+    with Image.open(opts.frame_from) as a, Image.open(opts.frame_to) as b:
+        if a.size != b.size:
+            raise ValueError('%s is %d x %d, but %s is %d x %d: the frames must have one size'
+                             % ((opts.frame_from,) + a.size + (opts.frame_to,) + b.size))
+        if min(a.size) < FLOW_MIN_SIDE:
+            raise ValueError('%s is %d x %d, but the estimator needs %d pixels a side'
+                             % ((opts.frame_from,) + a.size + (FLOW_MIN_SIDE,)))
+    return opts
+
+
+def main(argv=None):
+    from PIL import Image
+    from .engine import TileEngine
+    from .netspec import builtin_net
+    opts = parse_flow_args(argv)
+    engine = TileEngine(builtin_net('vgg19'), opts.device)         # (no weights: only the image entries are used)
+    try:
+        with Image.open(opts.frame_from) as a, Image.open(opts.frame_to) as b:
+            flow = estimate_flow(engine, a, b, alpha=opts.flow_alpha, gamma=opts.flow_gamma)
+        write_flo(opts.out, flow.get())
+        flow.free()
+    finally:
+        engine.close()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -195,6 +195,38 @@ def flow_warp(engine, prev, flow_b, flow_f, su, sv, first, target, weight):
              H, W, float(su), float(sv), int(bool(first)), target.ptr, weight.ptr)
 
 
+def flow_params(params=None):
+    """A lib.FlowParams from a dict of the estimator's parameters (alpha, gamma, eta, omega, eps, levels, outer,
+    inner, sor); what is missing or None takes its default, an unknown name is a ValueError."""
+    params = dict(params or {})
+    unknown = sorted(set(params) - set(lib.FLOW_DEFAULTS))
+    if unknown:
+        raise ValueError('flow_estimate: unknown parameter(s) %s; there are %s'
+                         % (', '.join(unknown), ', '.join(lib.FLOW_DEFAULTS)))
+    values = {name: default if params.get(name) is None else params[name] for name, default in lib.FLOW_DEFAULTS.items()}
+    return lib.FlowParams(*[(int if isinstance(lib.FLOW_DEFAULTS[name], int) else float)(values[name])
+                            for name, _ in lib.FlowParams._fields_])
+
+
+def flow_estimate(engine, i1, i2, params=None):
+    """The optical flow [2,H,W] from the grey frame ``i1`` [H,W] into ``i2`` [H,W] (0 ... 255): the displacement w
+    with i1(p) ~ i2(p + w(p)), which ``flow_warp`` takes as ``flow_b`` when ``i1`` is the current frame (include/stx.h
+    has the definition).  ``params``: a dict of the estimator's parameters, see ``flow_params``.  Asynchronous; the
+    result is a new DeviceArray."""
+    if len(i1.shape) != 2 or tuple(i2.shape) != tuple(i1.shape):
+        raise ValueError('flow_estimate: frames of shape %s and %s, but two [H, W] pictures of one size are needed'
+                         % (tuple(i1.shape), tuple(i2.shape)))
+    H, W = i1.shape
+    c_params = flow_params(params)
+    out = engine.empty((2, H, W))
+    try:
+        lib.call('stx_image_flow_estimate', engine.handle, i1.ptr, i2.ptr, H, W, ctypes.byref(c_params), out.ptr)
+    except lib.StxError:
+        out.free()
+        raise
+    return out
+
+
 def temporal_loss(engine, img, grad, target, weight, scale):
     """grad += the gradient of scale * 63.75 * sum w' ((img - target) / 127.5)^2 with w' = ``weight`` [H,W]
     clipped to [0, 1] (the temporal-consistency term; include/stx.h has the definition).  ``img``, ``grad``,

@@ -111,6 +111,18 @@ class CxTarget(ctypes.Structure):
                 ('h', ctypes.c_double), ('weight', ctypes.c_double)]
 
 
+class FlowParams(ctypes.Structure):
+    """stx_flow_params; the defaults are the estimator's (include/stx.h).  FLOW_LEVELS_ALL: as many levels as fit."""
+    _fields_ = [('alpha', ctypes.c_double), ('gamma', ctypes.c_double), ('eta', ctypes.c_double),
+                ('omega', ctypes.c_double), ('eps', ctypes.c_double), ('levels', ctypes.c_int),
+                ('outer', ctypes.c_int), ('inner', ctypes.c_int), ('sor', ctypes.c_int)]
+
+
+FLOW_LEVELS_ALL = 1 << 20
+FLOW_DEFAULTS = dict(alpha=18.0, gamma=6.0, eta=0.75, omega=1.8, eps=0.001, levels=FLOW_LEVELS_ALL, outer=5, inner=1,
+                     sor=10)
+
+
 class Tap(ctypes.Structure):
     _fields_ = [('layer', ctypes.c_char_p), ('layer_weight', ctypes.c_double),
                 ('is_content', ctypes.c_int), ('content_weight', ctypes.c_double),
@@ -183,6 +195,7 @@ SIGNATURES = {
     'stx_image_photo': [_vp, _vp, _vp, _vp, _i, _i, _d, _d, c_double_p],
     'stx_image_flow_warp': [_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp],
     'stx_image_temporal': [_vp, _vp, _vp, _vp, _vp, _i, _i, _d, c_double_p],
+    'stx_image_flow_estimate': [_vp, _vp, _vp, _i, _i, ctypes.POINTER(FlowParams), _vp],
     'stx_adam_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _d, _d, _d, _d, _d, _d, _d],
     'stx_vec_dot': [_vp, _vp, _vp, _sz, c_double_p],
     'stx_vec_axpy': [_vp, _d, _vp, _vp, _sz],

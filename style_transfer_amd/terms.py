@@ -17,8 +17,8 @@ from .config_system import (LAP_POOLS_DEFAULT, SWD_QUANTILES, ValuePlaceholder, 
                             selfsim_layer_args, selfsim_points, stat_layer_args, swd_dirs, swd_directions,
                             swd_layer_args, check_shift_options, check_shift_tile, shift_layer_args, shift_offsets,
                             check_cx_bank, check_cx_options, cx_bank_rows, cx_h, cx_layer_args, cx_points, cx_rows,
-                            check_temporal_options)
-from .flow import read_flo
+                            check_temporal_options, flow_value, temporal_prev_contents)
+from .flow import estimate_flow, read_flo
 from .resample import resample_device
 
 
@@ -427,13 +427,26 @@ class TemporalTerm(ImageTerm):
     video): the earlier stylised frames and their flows are read when the run is set up; the flows go to the
     master GPU at first use and stay there.  Per scale ``target`` [3,H,W] and ``weight`` [H,W] are the composite
     of the earlier frames warped to this frame (image_ops.flow_warp, closest frame first); the previous
-    scale's are freed when the next ones are made."""
+    scale's are freed when the next ones are made.  With --prev-contents no flow is read: both flows of every
+    earlier frame are estimated on the master GPU at first use (flow.estimate_flow, at the content picture's size as
+    loaded) -- ``flows_b[k]`` from the current content frame into earlier frame k, ``flows_f[k]`` the other way --
+    and from there the path is the same."""
 
     def __init__(self, args):
         prev, flows, fwd = check_temporal_options(args)
         self.pictures = [Image.open(path).convert('RGB') for path in prev]
         with Image.open(args.content_image) as content:
             self.size0 = content.size           # (W0, H0): the content picture as loaded, the flows' frame
+            self.frames = []                    # (--prev-contents: the current content frame, then the earlier ones)
+            if temporal_prev_contents(args):
+                self.frames.append(content.convert('RGB'))
+        for path in temporal_prev_contents(args):
+            frame = Image.open(path).convert('RGB')
+            if frame.size != tuple(self.size0):
+                raise ValueError('--prev-contents %s: a frame of %d x %d, but the content picture %s is %d x %d'
+                                 % (path, frame.size[0], frame.size[1], args.content_image, *self.size0))
+            self.frames.append(frame)
+        self.flow_params = dict(alpha=flow_value(args, 'flow_alpha'), gamma=flow_value(args, 'flow_gamma'))
 
         def load(path):
             flow = read_flo(path)
@@ -453,8 +466,14 @@ class TemporalTerm(ImageTerm):
             return
         eng = st.engine
         if not self._on_device:
-            self.flows_b = [eng.to_device(flow) for flow in self.flows_b]
-            self.flows_f = [eng.to_device(flow) if flow is not None else None for flow in self.flows_f]
+            if self.frames:
+                current, earlier = self.frames[0], self.frames[1:]
+                self.flows_b = [estimate_flow(eng, current, frame, **self.flow_params) for frame in earlier]
+                self.flows_f = [estimate_flow(eng, frame, current, **self.flow_params) for frame in earlier]
+                self.frames = []
+            else:
+                self.flows_b = [eng.to_device(flow) for flow in self.flows_b]
+                self.flows_f = [eng.to_device(flow) if flow is not None else None for flow in self.flows_f]
             self._on_device = True
         target, weight = eng.empty((3, h, w)), eng.empty((h, w))
         su, sv = w / self.size0[0], h / self.size0[1]
