@@ -1011,6 +1011,48 @@ typedef struct { double alpha, gamma, eta, omega, eps; int levels, outer, inner,
 int stx_image_flow_estimate(stx_engine *e, const float *I1, const float *I2, int H, int W,
                             const stx_flow_params *p, float *flow_out);
 
+/* Screened-Poisson output stage (Mechrez, Shechtman, Zelnik-Manor, "Photorealistic Style Transfer with
+ * Screened Poisson Equation", BMVC 2017): the stylised picture keeps its colours and its gradients are pulled
+ * to the content picture's.  Per channel the output f minimises
+ *     sum_p (f_p - s_p)^2 + lambda * sum over edges pq ((f_p - f_q) - (c_p - c_q))^2
+ * over the 4-connected grid, solved for the correction e = f - s from e = 0 by a fixed count of multigrid
+ * W-cycles.  Every count is fixed; there is no stopping test.
+ *
+ * img (s) and content (c) are [3][H][W] STX_DEVICE float32 in one frame (BGR minus mean, as the iterate is kept);
+ * out is [3][H][W] STX_DEVICE float32, distinct from both.  Every value in between is float64 on the device, each
+ * operation rounded once in the order written here (sums from left to right as bracketed); a channel never reads
+ * another.
+ *   N(p): the neighbours left, right, up, down of p that lie inside the level; n(p) = |N(p)| as a double.
+ *   S(a)_p = ((a_left + a_right) + a_up) + a_down, a neighbour outside the level entering as +0.0.
+ *   d = (double)c - (double)s
+ *   b = lambda * (n * d - S(d));  e = 0                                       (level 0)
+ * Levels: level 0 is the picture; H' = ceil(H / 2), W' = ceil(W / 2), lambda' = lambda / 4.  A level is the
+ *   coarsest when min(H, W) <= 2 or lambda <= 0.05 (at most 9 levels for lambda <= 1000).
+ * Half-sweep of colour k on a level: every pixel with ((y + x) & 1) == k takes
+ *     e = (b + lambda * S(e)) / (1 + lambda * n)
+ *   (its neighbours are of the other colour).  A sweep "k first" is the half-sweeps k, then 1 - k.
+ * Visit of level l (its e and b given):
+ *   the coarsest level: 20 sweeps, 0 first.
+ *   any other: 2 sweeps, 0 first;
+ *     r = (b + lambda * S(e)) - (1 + lambda * n) * e  (never stored), and on level l + 1
+ *     b'[Y][X] = (((r[2Y][2X] + r[2Y][2X+1]) + r[2Y+1][2X]) + r[2Y+1][2X+1]) / count, a child outside level l
+ *     entering as +0.0 and count the existing children (1, 2 or 4);  e' = 0;
+ *     two visits of level l + 1, the second continuing from the first's e';
+ *     e = e + (0.75 * (0.75 * e'[Y][X] + 0.25 * e'[Y][Xn]) + 0.25 * (0.75 * e'[Yn][X] + 0.25 * e'[Yn][Xn]))
+ *     with Y = y >> 1, Yn = Y + 1 for an odd y and Y - 1 for an even one, clamped to the level (X, Xn likewise);
+ *     2 sweeps, 1 first.
+ * `cycles` visits of level 0, then out = (float)((double)s + e).
+ * Where s equals c bit for bit, b = +0 and e = +0 throughout, so out is s bit for bit.  No atomics and no
+ * reductions: the same inputs give the same bits.  A cycle leaves 0.1 to 0.3 of the error for lambda up to 1000
+ * (DESIGN.md 3.26); the host's default is 9 cycles.
+ *
+ * Asynchronous: the launches are queued on the engine's stream.  The workspace (e and b of every level, 64 bytes
+ * per pixel) is the engine's; it is freed at the next stx_sync, when the call's work is done.  STX_ERR_ARG, before
+ * anything is allocated or launched and with out untouched: a null pointer, H or W below 1 or above 32768, lambda
+ * not finite, <= 0 or > 1000, cycles outside 1 .. 32, out overlapping img or content. */
+int stx_image_poisson(stx_engine *e, const float *img, const float *content, float *out, int H, int W,
+                      double lambda, int cycles);
+
 /* ------------------------------------------------------------- single-kernel test hooks */
 /* Direct entry points to the individual kernels, used by tests/ to check each against the
  * oracle (x, w, b, y: STX_DEVICE).  w is the Caffe layout [Cout][Cin][k][k]. */

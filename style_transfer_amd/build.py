@@ -38,6 +38,7 @@ SOURCES = {
     'photo.hip': ['-ffp-contract=off'],
     'temporal.hip': ['-ffp-contract=off'],
     'flow.hip': ['-ffp-contract=off'],
+    'poisson.hip': ['-ffp-contract=off'],
     'nnfm.hip': ['-ffp-contract=off'],
     'swd.hip': ['-ffp-contract=off'],
     'selfsim.hip': ['-ffp-contract=off'],

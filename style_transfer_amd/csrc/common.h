@@ -858,6 +858,15 @@ size_t flow_workspace_doubles(int H, int W, double eta, int levels);
 int flow_estimate_launch(hipStream_t s, const float *I1, const float *I2, int H, int W, const stx_flow_params &p,
                          float *flow_out, double *work);
 
+// poisson.hip: the screened-Poisson output stage (stx_image_poisson; the caller has checked the arguments).
+// poisson_levels fills the levels' sizes and lambdas (kPoissonMaxLevels entries at most) and returns their count;
+// `work` holds poisson_workspace_doubles(...) doubles and is read and written by the queued launches only.
+constexpr int kPoissonMaxLevels = 16;
+int poisson_levels(int H, int W, double lambda, int *hs, int *ws, double *lambdas);
+size_t poisson_workspace_doubles(int H, int W, double lambda);
+int poisson_launch(hipStream_t s, const float *img, const float *content, float *out, int H, int W, double lambda,
+                   int cycles, double *work);
+
 // image_ops.hip
 int adam_launch(hipStream_t s, float *params, const float *grad, float *g1, float *g2, float *p1,
                 float *avg, size_t n, double lr, double b1, double b2, double bp1, double c1,

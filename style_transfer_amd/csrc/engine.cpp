@@ -87,6 +87,7 @@ static void publish_arena(stx_engine::ScalarArena &a) {
 int do_sync(stx_engine *e) {
     STX_HIP(hipStreamSynchronize(e->stream));
     e->flow_work.release();     // (the flow estimator's workspace, about 300 B per pixel: its launches are done)
+    e->poisson_work.release();  // (the screened-Poisson stage's, 64 B per pixel)
     // the closed arena (if any) is the older one
     publish_arena(e->arena[e->cur ^ 1]);
     publish_arena(e->arena[e->cur]);
@@ -419,7 +420,7 @@ void stx_engine_destroy(stx_engine *e) {
         clear_all_targets(*e->sh);
     }
     DevBuf *bufs[] = {&e->cx_io, &e->shift_io, &e->selfsim_io, &e->swd_work, &e->swd_io, &e->nnfm_scratch, &e->stat_scratch, &e->masked_feat, &e->masked_target, &e->splitk, &e->gram_partials, &e->gram, &e->dsym, &e->dsym_pieces, &e->symm_partials,
-                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->flow_work, &e->first_gram, &e->color_sums};
+                      &e->upload, &e->red_scratch, &e->swt_scratch, &e->lap_scratch, &e->flow_work, &e->poisson_work, &e->first_gram, &e->color_sums};
     for (DevBuf *b : bufs) b->release();
     for (stx_engine::SwtTable &t : e->swt_tables) t.taps.release();
     for (stx_engine::ScalarArena &a : e->arena) {

@@ -302,6 +302,7 @@ struct stx_engine {
     std::vector<SwtTable> swt_tables;  // built at first use, kept: a step uploads nothing
     DevBuf lap_scratch;                // stx_image_lap / _target: pooled maps, cell values, partials
     DevBuf flow_work;                  // stx_image_flow_estimate: pyramid and planes; released at the next sync
+    DevBuf poisson_work;               // stx_image_poisson: e and b of every level; released at the next sync
 
     bool winograd = true;   // 1-D Winograd F(2,3) for the 3x3 layers (STX_WINOGRAD=0: direct only)
     bool autotune = true;   // tile-config autotuning (process-wide cache, see conv_choose)

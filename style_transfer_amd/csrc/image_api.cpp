@@ -417,6 +417,42 @@ int stx_image_flow_estimate(stx_engine *e, const float *I1, const float *I2, int
     return flow_estimate_launch(e->stream, I1, I2, H, W, *p, flow_out, static_cast<double *>(e->flow_work.ptr));
 }
 
+// ---- the screened-Poisson output stage of --poisson-lambda (poisson.hip) ----
+
+int stx_image_poisson(stx_engine *e, const float *img, const float *content, float *out, int H, int W,
+                      double lambda, int cycles) {
+    if (!e || !img || !content || !out) {
+        set_error("stx_image_poisson: %s is null", !e ? "the engine" : !img ? "img" : !content ? "content" : "out");
+        return STX_ERR_ARG;
+    }
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) {
+        set_error("stx_image_poisson: a %d x %d picture, but sides from 1 to 32768 are needed", H, W);
+        return STX_ERR_ARG;
+    }
+    if (!std::isfinite(lambda) || !(lambda > 0.0) || lambda > 1000.0) {
+        set_error("stx_image_poisson: lambda = %g, but a finite value above 0 and up to 1000 is needed", lambda);
+        return STX_ERR_ARG;
+    }
+    if (cycles < 1 || cycles > 32) {
+        set_error("stx_image_poisson: cycles = %d, but a count from 1 to 32 is needed", cycles);
+        return STX_ERR_ARG;
+    }
+    const size_t n = 3 * (size_t)H * W;
+    const auto overlaps = [&](const float *in) {
+        return reinterpret_cast<uintptr_t>(out) < reinterpret_cast<uintptr_t>(in + n) &&
+               reinterpret_cast<uintptr_t>(in) < reinterpret_cast<uintptr_t>(out + n);
+    };
+    if (overlaps(img) || overlaps(content)) {
+        set_error("stx_image_poisson: out overlaps %s; a buffer of its own is needed", overlaps(img) ? "img" : "content");
+        return STX_ERR_ARG;
+    }
+    STX_TRY(e->set_device());
+    // The workspace is the engine's: it grows here if it has to and goes back at the next stx_sync, when the
+    // launches queued here are done (engine.cpp, do_sync) -- the call itself waits for nothing.
+    STX_TRY(e->poisson_work.ensure(poisson_workspace_doubles(H, W, lambda) * sizeof(double)));
+    return poisson_launch(e->stream, img, content, out, H, W, lambda, cycles, static_cast<double *>(e->poisson_work.ptr));
+}
+
 int stx_adam_step(stx_engine *e, float *params, const float *grad, float *g1, float *g2, float *p1,
                   float *avg_out, size_t n, double lr, double b1, double b2, double bp1, double corr1,
                   double corr2, double corrp) {

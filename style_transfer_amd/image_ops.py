@@ -227,6 +227,26 @@ def flow_estimate(engine, i1, i2, params=None):
     return out
 
 
+def poisson(engine, img, content, lam, cycles=None):
+    """The screened-Poisson output stage: a new DeviceArray [3,H,W] with the colours of ``img`` and the gradients of
+    ``content`` (both [3,H,W] on the engine's GPU, one frame), the minimiser of sum (f - img)^2 + ``lam`` sum over
+    edges ((f_p - f_q) - (c_p - c_q))^2 per channel after ``cycles`` multigrid W-cycles (None: the default;
+    include/stx.h has the definition).  Asynchronous; the sync that waits for it gives the workspace back."""
+    from .config_system import POISSON_CYCLES_DEFAULT
+    if len(img.shape) != 3 or img.shape[0] != 3 or tuple(content.shape) != tuple(img.shape):
+        raise ValueError('poisson: pictures of shape %s and %s, but two [3, H, W] pictures of one size are needed'
+                         % (tuple(img.shape), tuple(content.shape)))
+    _, H, W = img.shape
+    out = engine.empty((3, H, W))
+    try:
+        lib.call('stx_image_poisson', engine.handle, img.ptr, content.ptr, out.ptr, H, W, float(lam),
+                 int(POISSON_CYCLES_DEFAULT if cycles is None else cycles))
+    except lib.StxError:
+        out.free()
+        raise
+    return out
+
+
 def temporal_loss(engine, img, grad, target, weight, scale):
     """grad += the gradient of scale * 63.75 * sum w' ((img - target) / 127.5)^2 with w' = ``weight`` [H,W]
     clipped to [0, 1] (the temporal-consistency term; include/stx.h has the definition).  ``img``, ``grad``,

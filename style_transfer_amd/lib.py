@@ -196,6 +196,7 @@ SIGNATURES = {
     'stx_image_flow_warp': [_vp, _vp, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp],
     'stx_image_temporal': [_vp, _vp, _vp, _vp, _vp, _i, _i, _d, c_double_p],
     'stx_image_flow_estimate': [_vp, _vp, _vp, _i, _i, ctypes.POINTER(FlowParams), _vp],
+    'stx_image_poisson': [_vp, _vp, _vp, _vp, _i, _i, _d, _i],
     'stx_adam_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _d, _d, _d, _d, _d, _d, _d],
     'stx_vec_dot': [_vp, _vp, _vp, _sz, c_double_p],
     'stx_vec_axpy': [_vp, _d, _vp, _vp, _sz],

@@ -23,6 +23,7 @@ import numpy as np
 from PIL import Image
 
 from . import image_ops, lib, terms
+from .config_system import check_poisson_options
 from .optimizers import AdamOptimizer, LBFGSOptimizer
 from .resample import resample_device
 from .terms import lap_pool_weights, mask_at_size, parse_weights, rolled_mask      # (their users import them here)
@@ -148,6 +149,9 @@ class StyleTransfer:
         # The scale's first content picture on the master GPU, DeviceArray [3,H,W]: at most one copy, owned here,
         # made once per scale when 'luma' or an image term reads it (transfer) and freed there at the next.
         self.content_picture = None
+        # --poisson-lambda: (lambda, cycles) of the screened-Poisson stage that every written picture goes through
+        # first (output_u8), or None.  Changes no step.
+        self.poisson = check_poisson_options(args)
         # --style-masks / --content-mask (spatial control): greyscale PIL pictures in the content picture's frame,
         # handed to transfer_multiscale.  With style masks every style picture is a style set of its own.
         self.style_masks = None
@@ -174,15 +178,24 @@ class StyleTransfer:
 
     def output_u8(self, params=None):
         """RGB HWC uint8 array of a device iterate (default: the current one), as every picture of
-        the run is written: under --preserve-color luma with the content picture's chroma."""
+        the run is written: under --poisson-lambda through the screened-Poisson stage first, under
+        --preserve-color luma with the content picture's chroma."""
         params = self.current_raw if params is None else params
-        if self.preserve_color == 'luma':
-            if self.content_picture is None or self.content_picture.shape != params.shape:
-                raise ValueError('--preserve-color luma: no content picture of size %dx%d is kept '
-                                 '(pictures are written at the size of the scale being optimised)'
-                                 % (params.shape[2], params.shape[1]))
-            return image_ops.to_u8_luma(self.engine, params, self.content_picture, self.mean)
-        return image_ops.to_u8(self.engine, params, self.mean)
+        luma = self.preserve_color == 'luma'
+        if (luma or self.poisson) and (self.content_picture is None or self.content_picture.shape != params.shape):
+            raise ValueError('%s: no content picture of size %dx%d is kept '
+                             '(pictures are written at the size of the scale being optimised)'
+                             % ('--preserve-color luma' if luma else '--poisson-lambda', params.shape[2],
+                                params.shape[1]))
+        solved = image_ops.poisson(self.engine, params, self.content_picture, *self.poisson) if self.poisson else None
+        try:
+            picture = params if solved is None else solved
+            if luma:
+                return image_ops.to_u8_luma(self.engine, picture, self.content_picture, self.mean)
+            return image_ops.to_u8(self.engine, picture, self.mean)
+        finally:
+            if solved is not None:      # (read back: its launches are done)
+                solved.free()
 
     @property
     def current_output(self):
@@ -286,10 +299,10 @@ class StyleTransfer:
             term.send(self, roll)
 
     def _keep_content_picture(self, image):
-        """The scale's first content picture to the master GPU, once, when --preserve-color luma or an image term
-        reads it; the previous scale's is freed here.  The image terms prepare their scale from it; a copy that
-        only such preparation needed is freed again."""
-        luma = self.preserve_color == 'luma'
+        """The scale's first content picture to the master GPU, once, when --preserve-color luma, --poisson-lambda or
+        an image term reads it; the previous scale's is freed here.  The image terms prepare their scale from it; a
+        copy that only such preparation needed is freed again."""
+        luma = self.preserve_color == 'luma' or bool(self.poisson)     # (either reads the picture at every write)
         if self.content_picture is not None:
             self.content_picture.free()
             self.content_picture = None
