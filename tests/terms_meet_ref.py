@@ -3,16 +3,17 @@
 Each per-feature reference file holds an ``OracleModel`` subclass that is a copy of ``sc_grad_tile`` with its own term
 added, and the copies do not compose.  ``MeetOracleModel`` has one ``sc_grad_tile``: per tapped blob it walks ONE list
 of terms in the library's order -- contents (masked or not), styles (masked or not), statistics, NNFM, SWD,
-self-similarity, Deep-Dream -- and adds each one the same way:
+self-similarity, shifted Gram, contextual, Deep-Dream -- and adds each one the same way:
 
     loss += sign lw w half / share
     diff += sign float32(lw w / share) S          S float32: the oracle's own operations (content, style, dream, masked)
     diff += sign float32((lw w / share) S)        S float64: a term of a tests/*_ref.py file
 
 with (half, S) = the term's callable on the blob's float32 features, ``start`` and the blob's window (fy, fx, fh, fw)
-in a map of the content picture's frame; S is L1-normalised by the callable.  ``share`` is the number of style sets for
-a style term and 1 otherwise; ``sign`` is -1 for Deep-Dream.  A layer that only an extra term names joins the order;
-its layer weight is ``layer_weights.get(layer, 1.0)`` like every other layer's.
+in a map of the content picture's frame; S is L1-normalised by the callable.  ``half`` is half the term's energy for
+every family but the contextual one, whose loss is lw w E: its callable returns the whole E.  ``share`` is the number
+of style sets for a style term and 1 otherwise; ``sign`` is -1 for Deep-Dream.  A layer that only an extra term names
+joins the order; its layer weight is ``layer_weights.get(layer, 1.0)`` like every other layer's.
 
 No term's arithmetic is stated here: the callables are adapters over oracle.num_ops and the tests/*_ref.py files.
 With exactly one optional kind armed the evaluation equals that kind's own ``*OracleModel`` bit for bit
@@ -22,17 +23,18 @@ import numpy as np
 
 from oracle.num_ops import gram_lower, half_sq_norm, l1_normalize, roll_xy, symm_lower_times
 from oracle.tile_path import OracleModel
-from tests import (content_mask_ref, masked_style_ref, nnfm_cover_ref, nnfm_guided_ref, nnfm_knn_ref, nnfm_patch_ref,
-                   nnfm_ref, selfsim_ref, stat_ref, swd_ref)
+from tests import (content_mask_ref, cx_ref, masked_style_ref, nnfm_cover_ref, nnfm_guided_ref, nnfm_knn_ref,
+                   nnfm_patch_ref, nnfm_ref, selfsim_ref, shift_ref, stat_ref, swd_ref)
 from tests.masked_style_ref import mask_map
 
-FAMILIES = ['content', 'style', 'statistics', 'nnfm', 'swd', 'selfsim', 'dream']
-EXTRA_ORDER = ['statistics', 'nnfm', 'swd', 'selfsim']       # the library's order behind the styles
+FAMILIES = ['content', 'style', 'statistics', 'nnfm', 'swd', 'selfsim', 'shift', 'cx', 'dream']
+EXTRA_ORDER = ['statistics', 'nnfm', 'swd', 'selfsim', 'shift', 'cx']       # the library's order behind the styles
 
 
 class Term:
     """One term of one layer: ``fn(feat, start, window) -> (half, S normalised)`` as the oracle evaluates it and
-    ``fn64(feat, start, window) -> half`` with every reduction in float64."""
+    ``fn64(feat, start, window) -> half`` with every reduction in float64.  ``half`` is what the loss takes lw w
+    times: E / 2 for every family but 'cx', whose loss is lw w E -- for that family the field is the whole E."""
 
     def __init__(self, name, family, weight, fn, fn64, share=1, sign=1):
         self.name, self.family, self.weight, self.fn, self.fn64 = name, family, float(weight), fn, fn64
@@ -90,11 +92,28 @@ def selfsim_term(om, layer, points):
     return fn
 
 
+def shift_term(offsets, T):
+    def fn(feat, start, window):
+        half, S, _ = shift_ref.shift_terms(feat, offsets, T)
+        return half, shift_ref.normalized(S)
+    return fn
+
+
+def cx_term(raw_rows, points, eta):
+    """The whole E, not half of it: this term's loss is lw w E (``Term``)."""
+    mu, B = cx_ref.bank(raw_rows)
+
+    def fn(feat, start, window):
+        t = cx_ref.terms(feat, B, mu, points, eta)
+        return t.E, cx_ref.normalized(t.S)
+    return fn
+
+
 class MeetOracleModel(OracleModel):
     """``OracleModel`` with
       ``cmask``        {layer: mask map} or None -- every content term acts through it (content_mask_ref),
       ``style_masks``  per style set {layer: mask map} or None (masked_style_ref),
-      ``extras``       {layer: [(family, weight, callable)]} -- statistics, nnfm, swd, selfsim terms,
+      ``extras``       {layer: [(family, weight, callable)]} -- statistics, nnfm, swd, selfsim, shift, cx terms,
       ``guided_maps``  {layer: [S, mh, mw]} -- the NNFM mask maps that ``nnfm_guided_term`` reads.
     ``roll_contents`` rolls every map of the content picture's frame: content maps, content mask, style masks and
     NNFM masks."""

@@ -3,42 +3,62 @@ ONE independent reference of the combined evaluation (tests/terms_meet_ref.MeetO
 every per-feature oracle by tests/test_terms_meet_host.py).
 
 plan_terms (csrc/tile_terms.cpp) cuts every tap's gradient buffer into slots -- style, masked content, statistics,
-NNFM, SWD, self-similarity, each group from a 256-byte boundary -- and gives the terms places in one scratch buffer
-and one scalar arena.  tests/test_gpu_all_terms.py repeats a call per family with the other weights at zero; two slots
-that overlap are overwritten alike in every one of its runs, so its shares still add up.  Here the scenes of
-tests/terms_meet.py put all six slot kinds on one blob (vgg19 'crowded', 'guided'), the SWD slot directly behind the
-statistics slot, a layer that only an extra target taps, one residual and one gradient term in one injecting epilogue
-('fused pair'), channel counts that are no multiple of 64 so that the alignment moves a slot (ragged-max / ragged-ave:
-the content mask acts on every content target, so the masked content term on c3 and the unmasked one on c5 are two
-scenes, 'ragged masked' and 'ragged fused'), and un-rectified and pooled blobs (mixed-max).
+NNFM, SWD, self-similarity, shifted Gram, contextual, each group from a 256-byte boundary -- and gives the terms
+places in one scratch buffer and one scalar arena.  The slot of each optional kind is computed by its own copy of a
+chain "behind the NNFM slot if there is one, behind the SWD slot if there is one, ...".
+tests/test_gpu_all_terms.py repeats a call per family with the other weights at zero; two slots that overlap are
+overwritten alike in every one of its runs, so its shares still add up.  Here the scenes of tests/terms_meet.py put
+six slot kinds on one blob (vgg19 'crowded', 'guided') and all eight ('full house': conv3_1; on conv2_1 the shift slot
+directly behind the statistics slot and the cx slot behind it), the SWD slot directly behind the statistics slot, a
+layer that only an extra target taps, one residual and one gradient term in one injecting epilogue ('fused pair';
+'fused new pair' with a shift and a contextual target), channel counts that are no multiple of 64 so that the
+alignment moves a slot (ragged-max / ragged-ave: the content mask acts on every content target, so the masked content
+term on c3 and the unmasked one on c5 are two scenes, 'ragged masked' and 'ragged fused'; 'ragged shift' puts the
+shifted-Gram term on 96 and 160 channels), and un-rectified and pooled blobs (mixed-max; 'mixed cx' with contextual
+targets on the un-rectified blob under a pool and beside statistics and self-similarity).  The contextual term is the
+one term whose energy enters the loss whole, not halved.
 
 Per scene and tile (every figure is printed before it is asserted, pytest -s):
   1. finite results, the same bits on a second run, under STX_SUMS_LATE=0 and under STX_TERMS_LATE=1;
   2. the loss within TIGHT = 1e-5 of the float64 loss of the composite reference on the oracle's activations (no
      per-feature file states a wider tile-level bound for its term);
   3. the gradient: l2_rel < FLIP_L2 = 1e-2 against the reference's backward pass on the GPU's activations and against
-     the oracle's own pass -- the bound of the NNFM / SWD / self-similarity tile tests, whose indices, ranks and signs
-     are discrete decisions; max_rel is printed;
+     the oracle's own pass -- the bound of the NNFM / SWD / self-similarity / contextual tile tests, whose indices,
+     ranks and signs are discrete decisions; max_rel is printed;
   4. teeth, from the reference alone: every term's own image gradient has a norm of at least 5 FLIP_L2 of the whole
      gradient's and every family's loss is at least 100 TIGHT of the sum of the absolute shares -- a term that is lost,
      doubled or replaced by its neighbour slot's S moves the results past 2 and 3;
   5. additivity with the forward pass fixed, as in tests/test_gpu_all_terms.py and with its bounds, over content,
-     style, statistics, nnfm, swd, selfsim and dream;
-  6. 'crowded' with the statistics target of conv3_1 left out, and with its NNFM target left out (the slot chain
-     shifts): 2 and 3 against the reference armed the same way.
+     style, statistics, nnfm, swd, selfsim, shift, cx and dream;
+  6. 'crowded' with the statistics target of conv3_1 left out, and with its NNFM target left out; 'full house' with
+     the self-similarity, the shifted-Gram or the SWD target of conv3_1 left out (the slot chain shifts by one, two or
+     three links): 2 and 3 against the reference armed the same way.
 Then the scale chain with these terms armed (stx_amax_audit), the buffers that grow with the tile, a second engine of
 the sharing group, a TileFarm step and one command line with every option that it allows together.
 
-The command line refuses --style-masks beside --stat-weight, --nnfm-weight and --swd-weight (masks make every style
-picture a style set of its own; those terms have one set of targets), so "every option together" is two runs.
+The command line refuses --style-masks beside --stat-weight, --nnfm-weight, --swd-weight, --shift-weight and
+--cx-weight (masks make every style picture a style set of its own; those terms have one set of targets), so "every
+option together" is two runs.
 
-Observed on an MI355X, worst of the 16 scene / tile cases and the four with a target left out
+Observed on an MI355X, worst of the 26 scene / tile cases and the ten with a target left out
 (profiles/terms_meet_parity.txt, written by this file under STX_TERMS_MEET_STATS=<path>): loss off by 1.7e-6 of the
-float64 reference (7.2e-7 with every target armed); gradient l2_rel 1.9e-6 on the GPU's blobs and 5.6e-6 against the
-oracle's pass, max_rel 1.7e-5; additivity: loss off by at most 3.6e-15 (0 in 14 cases), gradient by 6.4e-7 of the
-shares' maxima; smallest |g_t| / |g| 0.052, smallest loss share 2.5e-3; farm step: loss 6.8e-7, l2_rel 2.2e-5.  With
-plan_terms' SWD slot laid over the NNFM slot (run once, not kept) item 3 fails at l2_rel 1.1e-1 and 9.8e-2 on the
-crowded tiles while tests/test_gpu_all_terms.py passes; the loss does not move (it is summed from scratch partials)."""
+float64 reference (7.2e-7 with every target armed; 1.7e-7 on the four newer scenes); gradient l2_rel 1.9e-6 on the
+GPU's blobs and 6.5e-6 against the oracle's pass, max_rel 1.7e-5; additivity: loss off by at most 1.4e-14 of a bound of
+1.8e-12 (0 in 21 cases), gradient by 6.6e-7 of the shares' maxima; smallest |g_t| / |g| 0.052 (0.056 on the newer
+scenes), smallest loss share 2.2e-3; farm step: loss 6.8e-7, l2_rel 2.2e-5.  No discrete decision of the contextual
+term differed from the reference's in any case (tests/test_terms_meet_host.py caps the undecided ones on the CPU).
+
+Mutations of the library, each run once and not kept, both inside the tap's own buffer:
+  * plan_terms' SWD slot laid over the NNFM slot: item 3 fails at l2_rel 1.1e-1 and 9.8e-2 on the crowded tiles while
+    tests/test_gpu_all_terms.py passes; the loss does not move (it is summed from scratch partials);
+  * plan_terms' contextual slot laid over the shifted-Gram slot (the shift link of the contextual branch removed):
+    tests/test_gpu_all_terms.py passes; item 3 fails on 'full house' at l2_rel 1.9e-1 on both tiles and both legs, on
+    its six cases with a target left out (1.9e-1 to 2.0e-1; 1.0e-1 without shift:conv3_1, where conv2_1 alone still
+    overlaps) and on its farm step (2.0e-1); the loss stays within 1.7e-7; every older scene passes;
+  * the contextual term halved in queue_tap_terms: item 2 fails on every case with a contextual target -- the loss is
+    off by 4.7e-1 and 3.7e-1 of the reference on 'full house', 8.9e-2 and 5.8e-2 on 'fused new pair', 2.9e-1 and
+    2.6e-1 on 'mixed cx', 3.4e-1 on the farm step -- while the gradients stay at 1e-6 and tests/test_gpu_all_terms.py,
+    which arms no contextual target, passes."""
 
 import functools
 import os
@@ -57,7 +77,7 @@ from tests.test_gpu_all_terms import GRAD_TOL
 
 pytestmark = pytest.mark.gpu
 FLIP_L2 = 1e-2
-NEWER = {'statistics', 'nnfm', 'swd', 'selfsim'}
+NEWER = {'statistics', 'nnfm', 'swd', 'selfsim', 'shift', 'cx'}
 _ENGINES = {}
 
 
@@ -125,7 +145,41 @@ def _contents_of_the_scene(sc, eng, th, tw):
     """What the scene's line in the issue says it contains, from the plan's inputs."""
     spec = sc.spec
     tapped = sc.om.order_of(sc.cl, sc.sl, sc.dl)
-    if sc.name in ('crowded', 'guided'):
+    grids = tm.cx_grids(sc, lambda l: eng.feature_shape(l, th, tw))         # {layer: (g, N)}
+    assert all(tuple(v[1]) == ((0, 1), (1, 0), (0, 2), (2, 0)) for v in spec['shift'].values())
+    if sc.name == 'full house':
+        assert tm.slot_kinds(sc, 'conv3_1') == ['style', 'masked content', 'statistics', 'nnfm', 'swd', 'selfsim',
+                                                'shift', 'cx']
+        assert spec['n_styles'] == 2 and sc.style_masks[0] is not None and sc.style_masks[1] is None
+        assert tm.slot_kinds(sc, 'conv2_1') == ['style', 'statistics', 'shift', 'cx']   # no nnfm / swd / selfsim link
+        assert tm.slot_kinds(sc, 'conv3_2') == ['shift'] and 'conv3_2' not in sc.cl + sc.sl + sc.dl
+        assert tapped[0] == 'conv3_3' and tapped[0] in sc.dl and tapped[1] == 'conv3_2'
+        assert grids == {(64, 48): {'conv2_1': (2, 192), 'conv3_1': (1, 192)},
+                         (37, 53): {'conv2_1': (2, 140), 'conv3_1': (1, 140)}}[(th, tw)]
+        assert all(200 <= len(bank) < 1000 and len(bank) % 64 for bank in sc.cx.values())
+    elif sc.name == 'fused new pair':
+        assert sc.content_mask is None
+        pairs = [tm.slot_kinds(sc, l) for l in sc.cl]
+        assert sorted(pairs) == [['cx'], ['shift']] and not set(sc.cl) & set(sc.sl + sc.dl)
+        assert all(tapped.index(l) > 0 for l in sc.cl)          # not the deepest tap: the epilogue above injects
+        assert grids == {'conv3_2': (1, 192 if (th, tw) == (64, 48) else 140)}
+    elif sc.name == 'ragged shift':
+        assert tm.slot_kinds(sc, 'c4') == ['style', 'statistics', 'shift'] and spec['n_styles'] == 2
+        assert tm.slot_kinds(sc, 'c6') == ['swd', 'shift'] and not grids
+        assert [eng.feature_shape(l, th, tw)[0] for l in ('c4', 'c6')] == [96, 160]
+        counts = {l: int(np.prod(eng.feature_shape(l, th, tw))) for l in tapped}
+        ragged = [l for l in tapped if counts[l] % 64 and len(tm.slot_kinds(sc, l)) > 1]
+        _record('%s %s %dx%d: blob sizes %s; align moves a slot on %s' % (sc.name, sc.graph, th, tw, counts, ragged))
+        if (th, tw) == (37, 53):        # c4: 96 x 19 x 27 = 49248 floats, 769.5 times 64
+            assert 'c4' in ragged and any('shift' in tm.slot_kinds(sc, l) for l in ragged)
+    elif sc.name == 'mixed cx':
+        assert tm.slot_kinds(sc, 'c3') == ['nnfm', 'cx'] and spec['nnfm']['c3'][1:] == (1, 1, 0.0)
+        assert tm.slot_kinds(sc, 'c5') == ['statistics', 'selfsim', 'cx'] and sc.cl == ['c5']
+        assert tm.slot_kinds(sc, 'c4') == ['shift'] and 'c4' not in sc.cl + sc.sl + sc.dl
+        assert [eng.feature_shape(l, th, tw)[0] for l in ('c3', 'c4', 'c5')] == [128, 256, 128]
+        assert grids == {(64, 80): {'c3': (3, 154), 'c5': (2, 80)},
+                         (37, 53): {'c3': (2, 140), 'c5': (1, 140)}}[(th, tw)]
+    elif sc.name in ('crowded', 'guided'):
         assert tm.slot_kinds(sc, 'conv3_1') == ['style', 'masked content', 'statistics', 'nnfm', 'swd', 'selfsim']
         assert spec['n_styles'] == 2 and sc.style_masks[0] is not None and sc.style_masks[1] is None
         assert tm.slot_kinds(sc, 'conv2_1') == ['style', 'statistics', 'swd']       # SWD directly behind statistics
@@ -219,18 +273,29 @@ def test_every_kind_of_term_against_the_composite_reference(name, graph, th, tw,
     assert grad_err <= GRAD_TOL
 
 
-@pytest.mark.parametrize('drop', [('statistics', 'conv3_1'), ('nnfm', 'conv3_1')])
+# (scene, the target left out, the slot kinds of conv3_1 that move up)
+DROPS = [('crowded', ('statistics', 'conv3_1'), ['nnfm', 'swd', 'selfsim']),
+         ('crowded', ('nnfm', 'conv3_1'), ['swd', 'selfsim']),
+         ('full house', ('selfsim', 'conv3_1'), ['shift', 'cx']),
+         ('full house', ('shift', 'conv3_1'), ['cx']),
+         ('full house', ('swd', 'conv3_1'), ['selfsim', 'shift', 'cx'])]
+
+
+@pytest.mark.parametrize('drop', DROPS)
 @pytest.mark.parametrize('th,tw,start,roll', tm.VGG_TILES)
 def test_a_layers_terms_do_not_depend_on_their_neighbours(drop, th, tw, start, roll):
-    """'crowded' without one target of conv3_1 -- not zero-weighted: the slots behind it move up."""
-    sc, whole = tm.scene('crowded', 'vgg19', drop), tm.scene('crowded', 'vgg19')
-    assert drop[0] not in tm.slot_kinds(sc, 'conv3_1') and len(tm.slot_kinds(sc, 'conv3_1')) == 5
+    """'crowded' and 'full house' without one target of conv3_1 -- not zero-weighted: the slots behind it move up."""
+    name, drop, moved = drop
+    sc, whole = tm.scene(name, 'vgg19', drop), tm.scene(name, 'vgg19')
+    kinds = tm.slot_kinds(whole, 'conv3_1')
+    assert tm.slot_kinds(sc, 'conv3_1') == [k for k in kinds if k != drop[0]] and len(kinds) == len(set(kinds))
+    assert kinds[kinds.index(drop[0]) + 1:] == moved and len(kinds) == (6 if name == 'crowded' else 8)
     eng = gpu_engine()
     tile = tm.cut_tile(sc.full, th, tw, start, roll)
     try:
         first = tm.evaluate(eng, sc, tile, start, roll)
-        _against_the_reference('crowded without %s:%s %dx%d' % (drop + (th, tw)), sc, eng, first, tile, th, tw, start,
-                               roll, drop)
+        _against_the_reference('%s without %s:%s %dx%d' % ((name,) + drop + (th, tw)), sc, eng, first, tile, th, tw,
+                               start, roll, drop)
         full = tm.evaluate(eng, whole, tile, start, roll)
     finally:
         tm.disarm(eng)
@@ -249,10 +314,12 @@ def _stand_alone(eng, sc, tile):
 
 
 @pytest.mark.parametrize('switches', ['default', 'h2a', 'pool-bwd-unfused'])
-@pytest.mark.parametrize('name,graph', [('crowded', 'vgg19'), ('ragged masked', 'ragged-max')])
+@pytest.mark.parametrize('name,graph', [('crowded', 'vgg19'), ('ragged masked', 'ragged-max'),
+                                        ('full house', 'vgg19'), ('ragged shift', 'ragged-max')])
 def test_recorded_maxima_with_the_newer_terms_armed(name, graph, switches, monkeypatch):
-    """tests/test_gpu_amax_chain.py's audit with statistics, masked content, NNFM, SWD and self-similarity injected,
-    fused and stand-alone: the next fp16-split backward convolution scales by the maximum the injecting kernel left."""
+    """tests/test_gpu_amax_chain.py's audit with statistics, masked content, NNFM, SWD, self-similarity, shifted-Gram
+    and contextual terms injected, fused and stand-alone: the next fp16-split backward convolution scales by the
+    maximum the injecting kernel left."""
     for switch in ('STX_CONV_ALGO', 'STX_CONV_H2', 'STX_CONV_H2_BWD', 'STX_POOL_FWD_FUSE', 'STX_POOL_BWD_FUSE'):
         monkeypatch.delenv(switch, raising=False)
     for switch, value in {'default': {}, 'h2a': {'STX_CONV_ALGO': 'h2a'},
@@ -294,10 +361,20 @@ def test_recorded_maxima_with_the_newer_terms_armed(name, graph, switches, monke
     bwd = {l[1] for l, k in zip(lines, kinds) if 'bwd' in k and 'own' in k}
     fused_newer = [b for b in bwd if b in terms and b not in stand_alone and terms[b][-1].family in NEWER]
     crowded_behind = [b for b in bwd if b in stand_alone and gradient_terms[b] >= 4]
+    last_slot = {b: (tm.slot_kinds(sc, b) or [None])[-1] for b in terms}
+    behind_newest = [b for b in bwd if b in stand_alone and last_slot[b] in ('shift', 'cx')]
     _record('%s: %d audit lines; stand-alone injection on %s; bwd lines behind a fused newer term: %s, behind a '
-            'stand-alone injection of four or more gradient terms: %s'
-            % (case, len(lines), sorted(stand_alone), fused_newer, crowded_behind))
-    assert fused_newer, lines
+            'stand-alone injection of four or more gradient terms: %s, behind a stand-alone injection whose last '
+            'slot is shift or cx: %s'
+            % (case, len(lines), sorted(stand_alone), fused_newer, crowded_behind,
+               ['%s (%s)' % (b, last_slot[b]) for b in behind_newest]))
+    if name == 'ragged shift':  # (c6 carries two gradient terms, swd and shift: its injection stands alone)
+        assert [b for b in behind_newest if last_slot[b] == 'shift'], lines
+    else:
+        assert fused_newer, lines
+    if name == 'full house':
+        assert [b for b in fused_newer if terms[b][-1].family in ('shift', 'cx')], lines
+        assert [b for b in behind_newest if last_slot[b] == 'cx'], lines
     if graph == 'vgg19':        # (no fp16-split backward convolution reads a crowded blob of `ragged`: K = 72, 40)
         assert crowded_behind, lines
 
@@ -313,7 +390,17 @@ def _fresh_engine():
 def test_scratch_and_slots_grow_and_shrink_with_the_tile():
     """term_scratch, sgrad[k], swd_work and masked_feat are ensured per call: small, large, small again on one
     engine; then every target cleared."""
-    sc = tm.scene('crowded', 'vgg19')
+    _grow_and_shrink('crowded')
+
+
+def test_scratch_and_slots_grow_and_shrink_with_all_eight_slot_kinds():
+    """The same on 'full house': the shifted-Gram and the contextual regions (int arrays and the [N][M] planes, whose
+    N changes with the tile's grid) grow, shrink and are cleared with the others."""
+    _grow_and_shrink('full house')
+
+
+def _grow_and_shrink(name):
+    sc = tm.scene(name, 'vgg19')
     eng, _ = _fresh_engine()
     other, _ = _fresh_engine()
     try:
@@ -334,7 +421,7 @@ def test_scratch_and_slots_grow_and_shrink_with_the_tile():
         other.close()
 
 
-@pytest.mark.parametrize('name', ['crowded', 'guided'])
+@pytest.mark.parametrize('name', ['crowded', 'guided', 'full house'])
 def test_a_second_engine_of_the_sharing_group_returns_the_same_bits(name):
     from style_transfer_amd.engine import TileEngine
     sc = tm.scene(name, 'vgg19')
@@ -356,7 +443,7 @@ def test_a_second_engine_of_the_sharing_group_returns_the_same_bits(name):
     assert back[0] == first[0] and np.array_equal(back[1], first[1])
 
 
-@pytest.mark.parametrize('name', ['crowded', 'guided'])
+@pytest.mark.parametrize('name', ['crowded', 'guided', 'full house'])
 def test_a_farm_step_with_every_kind_of_term(name):
     """A 96 x 80 image in 2 x 2 tiles with roll (8, -16): the four kinds of map window (content, content mask, style
     mask, NNFM mask -- the last one in 'guided') are cut under one roll."""
@@ -402,12 +489,15 @@ CLI_BASE = ['-ci', '../c.png', '-si', '../s.png', '--size', '96', '--min-size', 
             '--model', 'vgg19', '--weights', 'synthetic:0', '--devices', '0', '-oi', 'out.png']
 CLI_SHARED = ['--selfsim-weight', '1', '--content-mask', '../cm.png', '--lap-weight', '30']
 # --style-masks makes every style picture a style set of its own; the command line refuses it beside the terms that
-# have one set of targets (--stat-weight, --nnfm-weight, --swd-weight).  The options that go together are two sets:
+# have one set of targets (--stat-weight, --nnfm-weight, --swd-weight, --shift-weight, --cx-weight).  The options that
+# go together are two sets:
 CLI_SETS = {
     'banks': (['--stat-weight', '1', '--nnfm-weight', '1', '--nnfm-k', '3', '--nnfm-cover', '1', '--nnfm-stride', '2',
-               '--swd-weight', '1'] + CLI_SHARED,
+               '--swd-weight', '1', '--shift-weight', '1', '--shift-offsets', '1', '2', '--cx-weight', '1',
+               '--cx-points', '64', '--cx-rows', '100'] + CLI_SHARED,
               [r'stat_weight=1\.0', r'nnfm_weight=1\.0', r'nnfm_k=3', r'nnfm_cover=1\.0', r'nnfm_stride=2',
-               r'swd_weight=1\.0', r'selfsim_weight=1\.0', r"content_mask='\.\./cm\.png'", r'lap_weight=30\.0']),
+               r'swd_weight=1\.0', r'shift_weight=1\.0', r'shift_offsets=\[1, 2\]', r'cx_weight=1\.0', r'cx_points=64',
+               r'cx_rows=100', r'selfsim_weight=1\.0', r"content_mask='\.\./cm\.png'", r'lap_weight=30\.0']),
     'masks': (['--style-masks', '../sm.png'] + CLI_SHARED,
               [r"style_masks=\['\.\./sm\.png'\]", r'selfsim_weight=1\.0', r"content_mask='\.\./cm\.png'",
                r'lap_weight=30\.0']),
@@ -443,6 +533,6 @@ def test_cli_with_every_option_that_goes_together(which, tmp_path, monkeypatch, 
 
 def test_cli_refuses_style_masks_beside_the_single_target_terms():
     from style_transfer_amd.config_system import parse_args
-    for option in ('--stat-weight', '--nnfm-weight', '--swd-weight'):
+    for option in ('--stat-weight', '--nnfm-weight', '--swd-weight', '--shift-weight', '--cx-weight'):
         with pytest.raises(ValueError, match='cannot be combined with --style-masks'):
             parse_args(argv=CLI_BASE + [option, '1', '--style-masks', '../sm.png'])

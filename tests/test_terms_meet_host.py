@@ -1,9 +1,13 @@
 """The composite reference of tests/terms_meet_ref.py, pinned on the CPU before the GPU tests trust it.
 
 With exactly one optional kind armed, ``MeetOracleModel`` gives the loss and the gradient of that kind's own
-``*OracleModel`` bit for bit -- statistics, the five NNFM forms, SWD, self-similarity, masked content, masked style --
-on a 24 x 20 tile with taps up to conv3_1, under a window and a roll.  The sum of ``term_gradients`` equals the full
-gradient to float32 rounding."""
+``*OracleModel`` bit for bit -- statistics, the five NNFM forms, SWD, self-similarity, shifted Gram, contextual, masked
+content, masked style -- on a 24 x 20 tile with taps up to conv3_1, under a window and a roll.  The sum of
+``term_gradients`` equals the full gradient to float32 rounding, with all nine families armed.
+
+The scenes of tests/terms_meet.py that arm a contextual target are held here, on the CPU, to the condition that makes
+their GPU cases meaningful: on the oracle's blobs of every tile the decisions a float32 implementation cannot be held
+to (cx_ref.undecided) stay within cx_ref.undecided_cap -- at most 1 of a cap of 2 per target as the scenes stand."""
 
 import copy
 import functools
@@ -14,8 +18,8 @@ import pytest
 from oracle.caffe_net import synthetic_weights
 from style_transfer_amd.config_system import swd_directions
 from style_transfer_amd.netspec import builtin_net
-from tests import (content_mask_ref, masked_style_ref, nnfm_cover_ref, nnfm_guided_ref, nnfm_knn_ref, nnfm_patch_ref,
-                   nnfm_ref, selfsim_ref, stat_ref, swd_ref, terms_meet_ref)
+from tests import (content_mask_ref, cx_ref, masked_style_ref, nnfm_cover_ref, nnfm_guided_ref, nnfm_knn_ref,
+                   nnfm_patch_ref, nnfm_ref, selfsim_ref, shift_ref, stat_ref, swd_ref, terms_meet_ref)
 
 FRAME = (48, 40)
 TH, TW, START, ROLL = 24, 20, (16, 8), (-8, 12)
@@ -26,6 +30,8 @@ CW = {'conv2_2': 0.05}
 SW = {l: 1 / 3 for l in SL}
 DL, DW = ['conv3_1'], {'conv3_1': 0.02}
 EXTRA_LAYERS = ['conv1_2', 'conv2_2', 'conv3_1']
+OFFSETS = [(0, 1), (1, 0), (0, 2), (2, 0)]
+CX_POINTS = 40      # the 24 x 20 tile: 12 x 10 positions on conv2_2 (g = 2, N = 30), 6 x 5 on conv3_1 (g = 1, N = 30)
 
 
 def _smooth_mask(hw, seed=0):
@@ -143,6 +149,59 @@ def test_selfsim():
     _same(_run(meet), _run(own))
 
 
+def _shift_targets(feats, layers):
+    return {l: (OFFSETS, np.float32(shift_ref.shift_gram(feats[0][l], OFFSETS))) for l in layers}
+
+
+def _cx_banks(feats, layers):
+    """Raw rows: every position of the style pictures' maps."""
+    return {l: np.ascontiguousarray(np.concatenate([f[l].reshape(f[l].shape[0], -1).T for f in feats]), np.float32)
+            for l in layers}
+
+
+def test_shift():
+    """On a layer that is also a style tap (conv2_1) and on one that nothing else taps (conv1_2)."""
+    feats = _scene()[4]
+    meet, own = _pair(shift_ref.ShiftOracleModel)
+    weights = {'conv2_1': 0.7, 'conv1_2': 1.3}
+    assert 'conv2_1' in SL and 'conv1_2' not in SL + CL + DL
+    own.shift_targets = {l: (offs, np.float64(T)) for l, (offs, T) in _shift_targets(feats, weights).items()}
+    own.shift_weights = weights
+    for l, (offs, T) in _shift_targets(feats, weights).items():
+        meet.add_extra(l, 'shift', weights[l], terms_meet_ref.shift_term(offs, T))
+    _same(_run(meet), _run(own))
+
+
+@pytest.mark.parametrize('eta', [0.5, 0.1])
+def test_cx(eta):
+    """Beside the content term (conv2_2, where the grid step is 2) and beside a Gram tap (conv3_1, C = 256)."""
+    feats, tile = _scene()[4:]
+    meet, own = _pair(cx_ref.CxOracleModel)
+    weights = {'conv2_2': 1.3, 'conv3_1': 0.8}
+    assert 'conv2_2' in CL and 'conv3_1' in SL
+    assert [cx_ref.grid(TH // s, TW // s, CX_POINTS)[0] for s in (2, 4)] == [2, 1]
+    own.cx_banks, own.cx_weights, own.cx_points, own.cx_eta = _cx_banks(feats, weights), weights, CX_POINTS, eta
+    assert own.cx_banks['conv3_1'].shape[1] == 256
+    for l, rows in own.cx_banks.items():
+        meet.add_extra(l, 'cx', weights[l], terms_meet_ref.cx_term(rows, CX_POINTS, eta))
+    _same(_run(meet), _run(own))
+
+
+def test_the_contextual_term_enters_the_loss_whole():
+    """``cx_term`` hands back E where every other adapter hands back E / 2: with nothing else armed the loss is
+    lw w E of cx_ref.terms on the pass's own blob."""
+    feats = _scene()[4]
+    meet = _model(terms_meet_ref.MeetOracleModel)
+    rows = _cx_banks(feats, ['conv2_2'])['conv2_2']
+    meet.add_extra('conv2_2', 'cx', 1.3, terms_meet_ref.cx_term(rows, CX_POINTS, 0.5))
+    none = {b: 0.0 for b in meet.blob_names}
+    tile = _scene()[5]
+    loss, _ = meet.sc_grad_tile(tile, START, [], [], {'conv2_2': 0.9}, none, none)
+    mu, B = cx_ref.bank(rows)
+    E = cx_ref.terms(meet.net.blobs['conv2_2'].data[0], B, mu, CX_POINTS, 0.5).E
+    assert E > 0 and loss == 0.9 * 1.3 * E
+
+
 def test_masked_content():
     meet, own = _pair(content_mask_ref.MaskedContentOracleModel)
     mask = _smooth_mask(FRAME, 1)
@@ -160,7 +219,8 @@ def test_masked_style():
 
 
 def test_term_gradients_add_up_and_loss64_is_the_loss():
-    """Everything armed: the single terms' gradients add up to the full gradient.  Each is a float32 array and the
+    """Everything armed -- both newer kinds (shifted Gram, contextual) beside every older one: the single terms'
+    gradients add up to the full gradient.  Each is a float32 array and the
     full pass adds the same diffs in float32 before the same linear backward pass: the two differ by the rounding of
     n_terms float32 sums, at most n_terms 2^-23 of the sum of the terms' maxima.  loss64 agrees with the float32 loss
     to the oracle's own sdot error (1e-5 at this size) and its family shares add up to it."""
@@ -174,6 +234,11 @@ def test_term_gradients_add_up_and_loss64_is_the_loss():
     V = swd_directions(3, 'conv2_1', 128, 8)
     meet.add_extra('conv2_1', 'swd', 0.9, terms_meet_ref.swd_term(V, swd_ref.target(feats[0]['conv2_1'], V, 20)))
     meet.add_extra('conv2_2', 'selfsim', 1.3, terms_meet_ref.selfsim_term(meet, 'conv2_2', 16))
+    # (added out of the library's order: terms_of sorts them)
+    rows = _cx_banks(feats, ['conv2_1'])['conv2_1']
+    meet.add_extra('conv2_1', 'cx', 0.6, terms_meet_ref.cx_term(rows, CX_POINTS, 0.5))
+    meet.add_extra('conv2_1', 'shift', 1.1, terms_meet_ref.shift_term(*_shift_targets(feats, ['conv2_1'])['conv2_1']))
+    meet.add_extra('conv2_2', 'shift', 0.4, terms_meet_ref.shift_term(*_shift_targets(feats, ['conv2_2'])['conv2_2']))
     tile = _scene()[5]
     args = (CL, SL, LW, CW, SW)
     meet.roll_contents(ROLL)
@@ -187,9 +252,12 @@ def test_term_gradients_add_up_and_loss64_is_the_loss():
     names = meet.term_names(CL, SL, DL)
     assert [n for n, _ in names] == list(parts) == list(terms)
     assert {f for _, f in names} == set(terms_meet_ref.FAMILIES)
-    # the library's order on conv2_1: styles, statistics, swd
+    # the library's order on conv2_1: styles, statistics, swd, shift, cx
     on = [n for n, _ in names if n.endswith(':conv2_1')]
-    assert on == ['style0:conv2_1', 'style1:conv2_1', 'statistics:conv2_1', 'swd:conv2_1']
+    assert on == ['style0:conv2_1', 'style1:conv2_1', 'statistics:conv2_1', 'swd:conv2_1', 'shift:conv2_1',
+                  'cx:conv2_1']
+    assert terms_meet_ref.FAMILIES[-3:] == ['shift', 'cx', 'dream'] and len(terms_meet_ref.FAMILIES) == 9
+    assert terms_meet_ref.EXTRA_ORDER == ['statistics', 'nnfm', 'swd', 'selfsim', 'shift', 'cx']
     bound = len(parts) * 2.0 ** -23 * sum(float(np.abs(g).max()) for g in parts.values())
     err = float(np.abs(np.float64(grad) - sum(np.float64(g) for g in parts.values())).max())
     print('sum of %d term gradients off by %.3e (bound %.3e); loss %.9g, loss64 %.9g' % (len(parts), err, bound, loss, total))
@@ -197,3 +265,33 @@ def test_term_gradients_add_up_and_loss64_is_the_loss():
     assert err <= bound
     assert total == pytest.approx(sum(families.values()), rel=1e-12) and families['dream'] < 0
     assert loss == pytest.approx(total, rel=1e-5)
+
+
+# ------------------------------------------------------- the inputs of the GPU scenes with a contextual term
+def _cx_cases():
+    from tests import terms_meet as tm
+    return [(name, graph) + tile for name, spec in tm.SPECS.items() if spec['cx'] for graph in tm.GRAPH_OF[name]
+            for tile in (tm.VGG_TILES if graph == 'vgg19' else tm.ODD_TILES)]
+
+
+def test_the_scenes_with_a_contextual_target():
+    assert sorted({c[0] for c in _cx_cases()}) == ['full house', 'fused new pair', 'mixed cx']
+
+
+@pytest.mark.parametrize('name,graph,th,tw,start,roll', _cx_cases())
+def test_the_gpu_scenes_meet_the_undecided_decisions_cap(name, graph, th, tw, start, roll):
+    """Per contextual target of the scene, on the oracle's blobs of the tile: the undecided k* and i* (cx_ref.undecided)
+    number at most cx_ref.undecided_cap(N, M).  A cap on the inputs, from the reference alone: where it holds, a
+    float32 implementation can differ from the reference in at most that many discrete decisions."""
+    from tests import terms_meet as tm
+    sc = tm.scene(name, graph)
+    tile = tm.cut_tile(sc.full, th, tw, start, roll)
+    acts = tm.reference(sc, tile, start, roll)[2]           # the blobs of the oracle's own pass
+    for l in sc.spec['cx']:
+        mu, B = cx_ref.bank(sc.cx[l])
+        rows, cols = cx_ref.undecided(acts[l], B, mu, sc.spec['cx_points'], sc.spec['cx_eta'])
+        g, N, _ = cx_ref.grid(*acts[l].shape[1:], sc.spec['cx_points'])
+        print('%s %s %dx%d %s: g %d N %d M %d, undecided rows %d columns %d (cap %.1f)'
+              % (name, graph, th, tw, l, g, N, len(B), rows.sum(), cols.sum(), cx_ref.undecided_cap(N, len(B))))
+        assert N == len(rows) and len(B) == len(cols) and len(B) % 64
+        assert rows.sum() + cols.sum() <= cx_ref.undecided_cap(N, len(B))
