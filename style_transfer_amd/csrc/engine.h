@@ -392,15 +392,28 @@ inline void clear_targets(std::vector<T> &targets) {
     for (T &t : targets) t.release();
     targets.clear();
 }
+// THE list of the per-layer kinds: the targets that hang on one layer each and make it part of every evaluation,
+// in planning order (plan_terms).  `visit` sees every kind's vector; whoever must know the kinds goes through here.
+template <class State, class Visit>
+inline void for_each_layer_kind(State &sh, Visit visit) {
+    visit(sh.stats);
+    visit(sh.nnfms);
+    visit(sh.swds);
+    visit(sh.selfsims);
+    visit(sh.shifts);
+    visit(sh.cxs);
+}
+// The element of `targets` that hangs on `blob`, or null.
+template <class T>
+inline const T *target_at(const std::vector<T> &targets, int blob) {
+    for (const T &t : targets)
+        if (t.blob == blob) return &t;
+    return nullptr;
+}
 inline void clear_dependent_targets(SharedState &sh) {   // what is set behind the contents and styles, and goes with them
     clear_targets(sh.masks);
-    clear_targets(sh.stats);
     clear_targets(sh.cmasks);
-    clear_targets(sh.nnfms);
-    clear_targets(sh.swds);
-    clear_targets(sh.selfsims);
-    clear_targets(sh.shifts);
-    clear_targets(sh.cxs);
+    for_each_layer_kind(sh, [](auto &targets) { clear_targets(targets); });
 }
 inline void clear_all_targets(SharedState &sh) {
     clear_targets(sh.contents);
@@ -462,7 +475,7 @@ struct TilePlan {
     std::vector<Tap> order;         // taps, deepest first
     std::vector<char> needed;       // blobs on the path
     std::vector<int> tap_of;        // blob -> index into order, or -1
-    std::deque<stx_tap> extra;      // taps of the layers that only a statistics, NNFM, SWD, self-similarity, shifted-Gram or contextual target names (lw = 1);
+    std::deque<stx_tap> extra;      // taps of the layers that only a per-layer target (for_each_layer_kind) names (lw = 1);
                                     // `order` points into it: a deque's elements stay where they are
     // The final sums of the loss terms are collected and run as ONE launch behind the forward pass
     // (STX_SUMS_LATE=0: each where it arises, as rounds 1-4 did); what they add up must outlive the term's
@@ -470,7 +483,7 @@ struct TilePlan {
     bool sums_late;
     bool interleave;                // (STX_TERMS_LATE=1: all loss terms after the forward pass, for A/B measurements)
     // The terms in queueing order -- shallowest tap first; per tap the content targets in sh->contents order,
-    // the style targets in sh->styles order, the statistics term, the NNFM term, the SWD term, the self-similarity term, the shifted-Gram term, the contextual term, Deep-Dream -- which is the order of
+    // the style targets in sh->styles order, the per-layer kinds' terms in for_each_layer_kind's order, Deep-Dream -- which is the order of
     // PendingLoss::terms: the host adds the loss up in it.
     std::vector<PlannedTerm> terms;
     std::vector<size_t> first_term;     // per tap: its first record

@@ -1,8 +1,9 @@
 // libstx host side: the targets of an engine group (stx_set_*).
 //
 // The engines of one GPU share their targets (SharedState): the content maps and style Grams, and behind them
-// the style masks, the content mask, the statistics targets, the NNFM banks, the sliced Wasserstein and the self-similarity targets, which go when new contents
-// and styles arrive.  Every setter is one swap (swap_targets) around a body that validates and copies.
+// the style masks, the content mask and the targets of every per-layer kind (engine.h: for_each_layer_kind), which
+// go when new contents and styles arrive.  Every setter is one swap (swap_targets) around a body that validates and
+// copies.
 
 #include <cmath>
 
@@ -56,6 +57,25 @@ struct MaskSource {
     }
 };
 
+// The opening of every per-layer setter's loop: target i of `kind` names `layer`, whose blob goes to *blob.  Refused:
+// an unknown layer, the input, a layer that `have` holds already and -- under the same message, which ends in
+// `or_no` -- a target without its data.  channels (or null: the kind has none) must be the blob's.
+template <class T>
+static int open_target(const stx_engine *e, const std::vector<T> &have, const char *kind, int i, const char *layer,
+                       bool has_data, const char *or_no, const int *channels, int *blob) {
+    *blob = e->find_blob(layer);
+    if (*blob <= 0 || !has_data || target_at(have, *blob)) {
+        set_error("%s target %d: bad layer '%s' (unknown, the input, or given twice)%s", kind, i,
+                  layer ? layer : "(null)", or_no);
+        return STX_ERR_ARG;
+    }
+    if (channels && *channels != e->blobs[*blob].channels) {
+        set_error("%s target %d: layer %s has %d channels, not %d", kind, i, layer, e->blobs[*blob].channels, *channels);
+        return STX_ERR_ARG;
+    }
+    return STX_OK;
+}
+
 // The banks of the four NNFM setters: a plain bank is a patch target with patch 1, both match k = 1 row, and all
 // three have no coverage part (cover 0).
 static int set_nnfm_banks(stx_engine *e, const stx_nnfm_cover_target *targets, int n, const char *who) {
@@ -84,19 +104,8 @@ static int set_nnfm_banks(stx_engine *e, const stx_nnfm_cover_target *targets, i
         clear_targets(nnfms);
         for (int i = 0; i < n; ++i) {
             const stx_nnfm_cover_target &nt = targets[i];
-            const int blob = e->find_blob(nt.layer);
-            bool twice = false;
-            for (const NnfmTarget &t : nnfms) twice |= t.blob == blob;
-            if (blob <= 0 || !nt.bank || nt.rows <= 0 || twice) {
-                set_error("NNFM target %d: bad layer '%s' (unknown, the input, or given twice) or no bank", i,
-                          nt.layer ? nt.layer : "(null)");
-                return STX_ERR_ARG;
-            }
-            if (nt.channels != e->blobs[blob].channels) {
-                set_error("NNFM target %d: layer %s has %d channels, not %d", i, nt.layer, e->blobs[blob].channels,
-                          nt.channels);
-                return STX_ERR_ARG;
-            }
+            int blob;
+            STX_TRY(open_target(e, nnfms, "NNFM", i, nt.layer, nt.bank && nt.rows > 0, " or no bank", &nt.channels, &blob));
             const int width = nt.patch * nt.patch * nt.channels;
             if (nt.channels % 64 != 0 || nt.rows >= (1ll << 31) / width) {
                 set_error("NNFM target %d: %d rows of %d channels (a multiple of 64 and rows x channels below 2^31 "
@@ -243,19 +252,8 @@ int stx_set_stat_targets(stx_engine *e, const stx_stat_target *targets, int n) {
         clear_targets(stats);
         for (int i = 0; i < n; ++i) {
             const stx_stat_target &st = targets[i];
-            const int blob = e->find_blob(st.layer);
-            bool twice = false;
-            for (const StatTarget &t : stats) twice |= t.blob == blob;
-            if (blob <= 0 || !st.mean || !st.sd || twice) {
-                set_error("statistics target %d: bad layer '%s' (unknown, the input, or given twice) or no data", i,
-                          st.layer ? st.layer : "(null)");
-                return STX_ERR_ARG;
-            }
-            if (st.channels != e->blobs[blob].channels) {
-                set_error("statistics target %d: layer %s has %d channels, not %d", i, st.layer,
-                          e->blobs[blob].channels, st.channels);
-                return STX_ERR_ARG;
-            }
+            int blob;
+            STX_TRY(open_target(e, stats, "statistics", i, st.layer, st.mean && st.sd, " or no data", &st.channels, &blob));
             stats.push_back(StatTarget{blob, st.channels, st.weight, std::unique_ptr<DevBuf>(new DevBuf)});
             StatTarget &t = stats.back();
             const size_t bytes = (size_t)t.C * sizeof(float);
@@ -274,19 +272,9 @@ int stx_set_swd_targets(stx_engine *e, const struct stx_swd_target *targets, int
         clear_targets(swds);
         for (int i = 0; i < n; ++i) {
             const struct stx_swd_target &wt = targets[i];
-            const int blob = e->find_blob(wt.layer);
-            bool twice = false;
-            for (const SwdTarget &t : swds) twice |= t.blob == blob;
-            if (blob <= 0 || !wt.V || !wt.Tq || twice) {
-                set_error("sliced Wasserstein target %d: bad layer '%s' (unknown, the input, or given twice) or no data",
-                          i, wt.layer ? wt.layer : "(null)");
-                return STX_ERR_ARG;
-            }
-            if (wt.channels != e->blobs[blob].channels) {
-                set_error("sliced Wasserstein target %d: layer %s has %d channels, not %d", i, wt.layer,
-                          e->blobs[blob].channels, wt.channels);
-                return STX_ERR_ARG;
-            }
+            int blob;
+            STX_TRY(open_target(e, swds, "sliced Wasserstein", i, wt.layer, wt.V && wt.Tq, " or no data", &wt.channels,
+                                &blob));
             STX_TRY(swd_check("stx_set_swd_targets", wt.channels, 1, wt.dirs, wt.quantiles));
             swds.push_back(SwdTarget{blob, wt.channels, wt.dirs, wt.quantiles, wt.weight,
                                      std::unique_ptr<DevBuf>(new DevBuf)});
@@ -307,14 +295,9 @@ int stx_set_selfsim_targets(stx_engine *e, const struct stx_selfsim_target *targ
         clear_targets(selfsims);
         for (int i = 0; i < n; ++i) {
             const struct stx_selfsim_target &ft = targets[i];
-            const int blob = e->find_blob(ft.layer);
-            bool twice = false, has_map = false;
-            for (const SelfsimTarget &t : selfsims) twice |= t.blob == blob;
-            if (blob <= 0 || twice) {
-                set_error("self-similarity target %d: bad layer '%s' (unknown, the input, or given twice)", i,
-                          ft.layer ? ft.layer : "(null)");
-                return STX_ERR_ARG;
-            }
+            int blob;
+            STX_TRY(open_target(e, selfsims, "self-similarity", i, ft.layer, true, "", nullptr, &blob));
+            bool has_map = false;
             for (const ContentTarget &ct : e->sh->contents) has_map |= ct.blob == blob && ct.index == 0;
             if (!has_map) {
                 set_error("self-similarity target %d: layer %s holds no content map of content_index 0", i, ft.layer);
@@ -334,19 +317,9 @@ int stx_set_shift_targets(stx_engine *e, const struct stx_shift_target *targets,
         clear_targets(shifts);
         for (int i = 0; i < n; ++i) {
             const struct stx_shift_target &ht = targets[i];
-            const int blob = e->find_blob(ht.layer);
-            bool twice = false;
-            for (const ShiftTarget &t : shifts) twice |= t.blob == blob;
-            if (blob <= 0 || !ht.grams || !ht.offsets || twice) {
-                set_error("shifted-Gram target %d: bad layer '%s' (unknown, the input, or given twice) or no data", i,
-                          ht.layer ? ht.layer : "(null)");
-                return STX_ERR_ARG;
-            }
-            if (ht.channels != e->blobs[blob].channels) {
-                set_error("shifted-Gram target %d: layer %s has %d channels, not %d", i, ht.layer,
-                          e->blobs[blob].channels, ht.channels);
-                return STX_ERR_ARG;
-            }
+            int blob;
+            STX_TRY(open_target(e, shifts, "shifted-Gram", i, ht.layer, ht.grams && ht.offsets, " or no data",
+                                &ht.channels, &blob));
             ShiftOffsets off;
             STX_TRY(shift_check_offsets("stx_set_shift_targets", ht.channels, ht.offsets, ht.n_offsets, &off));
             shifts.push_back(ShiftTarget{blob, ht.channels, off, ht.weight, std::unique_ptr<DevBuf>(new DevBuf)});
@@ -367,19 +340,9 @@ int stx_set_cx_targets(stx_engine *e, const struct stx_cx_target *targets, int n
         clear_targets(cxs);
         for (int i = 0; i < n; ++i) {
             const struct stx_cx_target &xt = targets[i];
-            const int blob = e->find_blob(xt.layer);
-            bool twice = false;
-            for (const CxTarget &t : cxs) twice |= t.blob == blob;
-            if (blob <= 0 || !xt.raw_rows || twice) {
-                set_error("contextual target %d: bad layer '%s' (unknown, the input, or given twice) or no rows", i,
-                          xt.layer ? xt.layer : "(null)");
-                return STX_ERR_ARG;
-            }
-            if (xt.channels != e->blobs[blob].channels) {
-                set_error("contextual target %d: layer %s has %d channels, not %d", i, xt.layer,
-                          e->blobs[blob].channels, xt.channels);
-                return STX_ERR_ARG;
-            }
+            int blob;
+            STX_TRY(open_target(e, cxs, "contextual", i, xt.layer, xt.raw_rows != nullptr, " or no rows", &xt.channels,
+                                &blob));
             STX_TRY(cx_check("stx_set_cx_targets", xt.channels, xt.points, xt.rows, (double)(float)xt.h));
             cxs.push_back(CxTarget{blob, xt.channels, xt.rows, xt.points, (float)xt.h, xt.weight,
                                    std::unique_ptr<DevBuf>(new DevBuf)});

@@ -433,14 +433,10 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
     const auto tapped = [&](int blob) {
         return std::any_of(order.begin(), order.end(), [=](const Tap &o) { return o.blob == blob; });
     };
-    const auto has_statistics = [&](int blob) {     // ... or an NNFM bank: a target that makes the layer part of the call
-        return std::any_of(e->sh->stats.begin(), e->sh->stats.end(), [=](const StatTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->nnfms.begin(), e->sh->nnfms.end(), [=](const NnfmTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->swds.begin(), e->sh->swds.end(), [=](const SwdTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->selfsims.begin(), e->sh->selfsims.end(),
-                           [=](const SelfsimTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->shifts.begin(), e->sh->shifts.end(), [=](const ShiftTarget &t) { return t.blob == blob; }) ||
-               std::any_of(e->sh->cxs.begin(), e->sh->cxs.end(), [=](const CxTarget &t) { return t.blob == blob; });
+    const auto has_layer_target = [&](int blob) {   // a per-layer target makes the layer part of the call
+        bool any = false;
+        for_each_layer_kind(*e->sh, [&](const auto &targets) { any |= target_at(targets, blob) != nullptr; });
+        return any;
     };
     for (int i = 0; i < n_taps; ++i) {
         const int blob = e->find_blob(taps[i].layer);
@@ -453,52 +449,19 @@ static int sc_grad_prepare(stx_engine *e, const TileCall &c, TilePlan &plan) {
             set_error("stx_sc_grad_tile: layer '%s' is tapped twice", taps[i].layer);
             return STX_ERR_ARG;
         }
-        if (!taps[i].is_content && !taps[i].is_style && !taps[i].is_dd && !has_statistics(blob)) continue;
+        if (!taps[i].is_content && !taps[i].is_style && !taps[i].is_dd && !has_layer_target(blob)) continue;
         order.push_back(Tap{blob, &taps[i]});
     }
-    // a layer with a statistics target is part of every evaluation, tapped or not
-    for (const StatTarget &st : e->sh->stats) {
-        if (tapped(st.blob)) continue;
-        stx_tap t{};
-        t.layer_weight = 1.0;
-        plan.extra.push_back(t);
-        order.push_back(Tap{st.blob, &plan.extra.back()});
-    }
-    for (const NnfmTarget &nt : e->sh->nnfms) {     // ... and a layer with an NNFM bank
-        if (tapped(nt.blob)) continue;
-        stx_tap t{};
-        t.layer_weight = 1.0;
-        plan.extra.push_back(t);
-        order.push_back(Tap{nt.blob, &plan.extra.back()});
-    }
-    for (const SwdTarget &wt : e->sh->swds) {       // ... and a layer with a sliced Wasserstein target
-        if (tapped(wt.blob)) continue;
-        stx_tap t{};
-        t.layer_weight = 1.0;
-        plan.extra.push_back(t);
-        order.push_back(Tap{wt.blob, &plan.extra.back()});
-    }
-    for (const SelfsimTarget &ft : e->sh->selfsims) {   // ... and a layer with a self-similarity target
-        if (tapped(ft.blob)) continue;
-        stx_tap t{};
-        t.layer_weight = 1.0;
-        plan.extra.push_back(t);
-        order.push_back(Tap{ft.blob, &plan.extra.back()});
-    }
-    for (const ShiftTarget &ht : e->sh->shifts) {       // ... and a layer with a shifted-Gram target
-        if (tapped(ht.blob)) continue;
-        stx_tap t{};
-        t.layer_weight = 1.0;
-        plan.extra.push_back(t);
-        order.push_back(Tap{ht.blob, &plan.extra.back()});
-    }
-    for (const CxTarget &xt : e->sh->cxs) {             // ... and a layer with a contextual target
-        if (tapped(xt.blob)) continue;
-        stx_tap t{};
-        t.layer_weight = 1.0;
-        plan.extra.push_back(t);
-        order.push_back(Tap{xt.blob, &plan.extra.back()});
-    }
+    // a layer with a per-layer target of any kind is part of every evaluation, tapped or not
+    for_each_layer_kind(*e->sh, [&](const auto &targets) {
+        for (const auto &target : targets) {
+            if (tapped(target.blob)) continue;
+            stx_tap t{};
+            t.layer_weight = 1.0;
+            plan.extra.push_back(t);
+            order.push_back(Tap{target.blob, &plan.extra.back()});
+        }
+    });
     if (order.empty()) {
         set_error("stx_sc_grad_tile: no content, style or Deep-Dream layer");
         return STX_ERR_ARG;

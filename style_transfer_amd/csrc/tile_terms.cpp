@@ -16,6 +16,20 @@ static size_t style_term_scratch_floats(int C, int HW) {
     return 2 * (size_t)ceil_div(C * C, 64) + (size_t)symm_num_workgroups(C, HW) + 64;
 }
 
+// The tail of every launch_*_terms: the final sums of a term's partials, launched now on `stream` or, with `defer`,
+// left as jobs of the caller's ONE launch behind the forward pass (sum_jobs_launch) -- two sums, or one.
+static int finish_sums(hipStream_t stream, std::vector<SumJob> *defer, const SumJob &a, const SumJob &b) {
+    if (!defer) return sum_partials2_launch(stream, a.src, a.n, a.dst, b.src, b.n, b.dst);
+    defer->push_back(a);
+    defer->push_back(b);
+    return STX_OK;
+}
+static int finish_sums(hipStream_t stream, std::vector<SumJob> *defer, const SumJob &a) {
+    if (!defer) return sum_partials_launch(stream, a.src, a.n, a.dst);
+    defer->push_back(a);
+    return STX_OK;
+}
+
 // Style terms of one tapped blob, the launches of style_transfer.py:584-593 in order: Gram of
 // `feat` -> D = G - target (fp32 + bf16 pieces) -> S = sym(D) feat into `sgrad`;
 // sc[0] = sum of squares of tril(D), sc[1] = sum |S| (one small launch for both).
@@ -69,10 +83,7 @@ int launch_style_terms(stx_engine *e, hipStream_t stream, const float *feat, int
     const float *block_sumsq = defer ? term_scratch : (fused ? partials : e->gram_partials.f()) + plan.partial_floats;
     // the two final sums: now, or as two jobs of the caller's one launch
     auto finish = [&](float *symm_partials, int n_wg) -> int {
-        if (!defer) return sum_partials2_launch(stream, block_sumsq, fin_blocks, sc, symm_partials, n_wg, sc + 1);
-        defer->push_back(SumJob{block_sumsq, fin_blocks, sc});
-        defer->push_back(SumJob{symm_partials, n_wg, sc + 1});
-        return STX_OK;
+        return finish_sums(stream, defer, SumJob{block_sumsq, fin_blocks, sc}, SumJob{symm_partials, n_wg, sc + 1});
     };
     if (symm_h2 || bf3) {
         const int n_wg = symm_num_workgroups(C, HW);
@@ -131,9 +142,7 @@ int launch_masked_style_terms(stx_engine *e, hipStream_t stream, const float *fe
     ProfScope scope(e, "smask " + name, 0.0, stream);
     int n_ms = 0;
     STX_TRY(mask_sgrad_launch(stream, sgrad, mask_map, win, sc + 3, ms_partials, &n_ms));
-    if (!defer) return sum_partials_launch(stream, ms_partials, n_ms, sc + 2);
-    defer->push_back(SumJob{ms_partials, n_ms, sc + 2});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{ms_partials, n_ms, sc + 2});
 }
 
 // The mean / std term of one tapped blob (stat.hip): the slices' partials, their merge against the targets
@@ -150,9 +159,7 @@ int launch_stat_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
     STX_TRY(stat_finish_launch(stream, partials, C, HW, MU, SD, table, sc, nullptr, nullptr));
     int n_parts = 0;
     STX_TRY(stat_grad_launch(stream, feat, C, HW, table, sgrad, abs_partials, &n_parts));
-    if (!defer) return sum_partials_launch(stream, abs_partials, n_parts, sc + 1);
-    defer->push_back(SumJob{abs_partials, n_parts, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{abs_partials, n_parts, sc + 1});
 }
 
 // The nearest-neighbour term of one tapped blob (nnfm.hip): 1 / |f_i| and the pieces of the unit columns, the
@@ -186,13 +193,13 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
         STX_TRY(nnfm_search_launch(stream, x, h, w, patch, pieces, rows, C, idx, k));
     }
     int n_parts = 0;
+    {
+        ProfScope scope(e, tag + "grad " + name, 0.0, stream);
+        STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts, k));
+    }
     if (covered) {
         int *const winner = winner_out ? winner_out : x.cov.winner;
         int n_e = 0, n_abs = 0;
-        {
-            ProfScope scope(e, tag + "grad " + name, 0.0, stream);
-            STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts, k));
-        }
         {
             ProfScope scope(e, "nnfm cover search " + name + " x" + std::to_string(nnfm_plan(rows, n).slices),
                             6.0 * n * (double)rows * C, stream);
@@ -207,17 +214,9 @@ int launch_nnfm_terms(stx_engine *e, hipStream_t stream, const float *feat, int 
             STX_TRY(nnfm_cover_grad_launch(stream, feat, C, n, x, bank, rows, cover, sgrad, &n_e, &n_abs));
         }
         if (e_cov_out) STX_TRY(sum_partials_launch(stream, x.cov.e_cov_parts, ceil_div(rows, 64), e_cov_out));
-        if (!defer) return sum_partials2_launch(stream, x.cov.e_parts, n_e, sc, x.cov.abs_parts, n_abs, sc + 1);
-        defer->push_back(SumJob{x.cov.e_parts, n_e, sc});
-        defer->push_back(SumJob{x.cov.abs_parts, n_abs, sc + 1});
-        return STX_OK;
+        return finish_sums(stream, defer, SumJob{x.cov.e_parts, n_e, sc}, SumJob{x.cov.abs_parts, n_abs, sc + 1});
     }
-    ProfScope scope(e, tag + "grad " + name, 0.0, stream);
-    STX_TRY(nnfm_grad_launch(stream, feat, C, h, w, patch, x, bank, rows, idx, sgrad, &n_parts, k));
-    if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
-    defer->push_back(SumJob{x.partials, n_parts, sc});
-    defer->push_back(SumJob{x.partials + n_parts, n_parts, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{x.partials, n_parts, sc}, SumJob{x.partials + n_parts, n_parts, sc + 1});
 }
 
 // The guided nearest-neighbour term of one tapped blob (nnfm.hip; patch 1): as above, with the mask windows and a
@@ -249,10 +248,7 @@ int launch_nnfm_guided_terms(stx_engine *e, hipStream_t stream, const float *fea
     int n_parts = 0;
     STX_TRY(nnfm_guided_grad_launch(stream, feat, C, n, x, bank, segs, idx, scale_by_a ? sc + 2 : nullptr, sgrad,
                                     &n_parts, k));
-    if (!defer) return sum_partials2_launch(stream, x.partials, n_parts, sc, x.partials + n_parts, n_parts, sc + 1);
-    defer->push_back(SumJob{x.partials, n_parts, sc});
-    defer->push_back(SumJob{x.partials + n_parts, n_parts, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{x.partials, n_parts, sc}, SumJob{x.partials + n_parts, n_parts, sc + 1});
 }
 
 // The sliced Wasserstein term of one tapped blob (swd.hip): the projections as sort records, the segmented sort
@@ -283,10 +279,7 @@ int launch_swd_terms(stx_engine *e, hipStream_t stream, const float *feat, int C
     ProfScope scope(e, "swd grad " + name, 2.0 * D * (double)C * n, stream);
     int n_abs = 0;
     STX_TRY(swd_grad_launch(stream, V, G, C, n, D, sgrad, abs_parts, &n_abs));
-    if (!defer) return sum_partials2_launch(stream, e_parts, n_e, sc, abs_parts, n_abs, sc + 1);
-    defer->push_back(SumJob{e_parts, n_e, sc});
-    defer->push_back(SumJob{abs_parts, n_abs, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{e_parts, n_e, sc}, SumJob{abs_parts, n_abs, sc + 1});
 }
 
 // The self-similarity content term of one tapped blob (selfsim.hip): both sides' unit columns on the sample grid,
@@ -314,10 +307,7 @@ int launch_selfsim_terms(stx_engine *e, hipStream_t stream, const float *feat, c
     }
     ProfScope scope(e, "selfsim grad " + name, product, stream);
     STX_TRY(selfsim_grad_launch(stream, C, h, w, gr, x, sgrad, &n_abs));
-    if (!defer) return sum_partials2_launch(stream, x.e_parts, n_e, sc, x.abs_parts, n_abs, sc + 1);
-    defer->push_back(SumJob{x.e_parts, n_e, sc});
-    defer->push_back(SumJob{x.abs_parts, n_abs, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{x.e_parts, n_e, sc}, SumJob{x.abs_parts, n_abs, sc + 1});
 }
 
 // The shifted-Gram term of one tapped blob (shiftgram.hip): the slices' partials of every offset's cross-Gram, their
@@ -339,10 +329,7 @@ int launch_shift_terms(stx_engine *e, hipStream_t stream, const float *feat, int
     }
     ProfScope scope(e, "shift grad " + name, 2.0 * product, stream);
     STX_TRY(shift_grad_launch(stream, feat, C, h, w, off, x, sgrad, &n_abs));
-    if (!defer) return sum_partials2_launch(stream, x.e_parts, n_e, sc, x.abs_parts, n_abs, sc + 1);
-    defer->push_back(SumJob{x.e_parts, n_e, sc});
-    defer->push_back(SumJob{x.abs_parts, n_abs, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{x.e_parts, n_e, sc}, SumJob{x.abs_parts, n_abs, sc + 1});
 }
 
 // The contextual term of one tapped blob (cx.hip): the unit columns of F - mu on the sample grid, the scores with
@@ -374,10 +361,7 @@ int launch_cx_terms(stx_engine *e, hipStream_t stream, const float *feat, int C,
     int n_abs = 0;
     ProfScope scope(e, "cx grad " + name, product, stream);
     STX_TRY(cx_grad_launch(stream, C, h, w, gr, rows, bank, x, sgrad, &n_abs));
-    if (!defer) return sum_partials2_launch(stream, x.e_part, 1, sc, x.abs_parts, n_abs, sc + 1);
-    defer->push_back(SumJob{x.e_part, 1, sc});
-    defer->push_back(SumJob{x.abs_parts, n_abs, sc + 1});
-    return STX_OK;
+    return finish_sums(stream, defer, SumJob{x.e_part, 1, sc}, SumJob{x.abs_parts, n_abs, sc + 1});
 }
 
 // A content term through a weight map (content_mask.hip): the window's mean weight, then the pass that writes
@@ -389,59 +373,7 @@ int launch_masked_content_terms(stx_engine *e, hipStream_t stream, const float *
     STX_TRY(content_mask_mean_launch(stream, mask_map, win, sc + 2));
     int n = 0;
     STX_TRY(content_mask_term_launch(stream, feat, content, mask_map, win, sc + 2, sgrad, partials, &n));
-    if (!defer) return sum_partials2_launch(stream, partials, n, sc, partials + n, n, sc + 1);
-    defer->push_back(SumJob{partials, n, sc});
-    defer->push_back(SumJob{partials + n, n, sc + 1});
-    return STX_OK;
-}
-
-// The mean / std target of `blob` (stx_set_stat_targets), or null.
-static const StatTarget *stat_target_of(const stx_engine *e, int blob) {
-    for (const StatTarget &t : e->sh->stats)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// The NNFM bank of `blob` (stx_set_nnfm_targets), or null.
-static const NnfmTarget *nnfm_target_of(const stx_engine *e, int blob) {
-    for (const NnfmTarget &t : e->sh->nnfms)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// The sliced Wasserstein target of `blob` (stx_set_swd_targets), or null.
-static const SwdTarget *swd_target_of(const stx_engine *e, int blob) {
-    for (const SwdTarget &t : e->sh->swds)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// The self-similarity target of `blob` (stx_set_selfsim_targets), or null.
-static const SelfsimTarget *selfsim_target_of(const stx_engine *e, int blob) {
-    for (const SelfsimTarget &t : e->sh->selfsims)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// The shifted-Gram target of `blob` (stx_set_shift_targets), or null.
-static const ShiftTarget *shift_target_of(const stx_engine *e, int blob) {
-    for (const ShiftTarget &t : e->sh->shifts)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// The contextual target of `blob` (stx_set_cx_targets), or null.
-static const CxTarget *cx_target_of(const stx_engine *e, int blob) {
-    for (const CxTarget &t : e->sh->cxs)
-        if (t.blob == blob) return &t;
-    return nullptr;
-}
-
-// The content mask map at `blob` (stx_set_content_mask), or null.
-static const ContentMask *content_mask_of(const stx_engine *e, int blob) {
-    for (const ContentMask &m : e->sh->cmasks)
-        if (m.blob == blob) return &m;
-    return nullptr;
+    return finish_sums(stream, defer, SumJob{partials, n, sc}, SumJob{partials + n, n, sc + 1});
 }
 
 // The mask map of style `index` at `blob` (stx_set_style_masks), or null.
@@ -493,8 +425,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
         const double lw = tp.t->layer_weight;
         plan.first_term[k] = plan.terms.size();
         // The tap's gradient buffer: the style slots, then (each group from a 256-byte boundary) the masked
-        // content slots, the statistics slot, the NNFM slot, the SWD slot, the self-similarity slot, the
-        // shifted-Gram slot and the contextual slot.
+        // content slots and one slot per per-layer kind that is present, in planning order (take_slot).
         size_t styles_here = 0;
         for (const StyleTarget &st : sh.styles) styles_here += tp.t->is_style && st.blob == tp.blob;
         size_t style_slot = 0, content_slot = align(styles_here * b.count());
@@ -507,7 +438,7 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
             if (slot != kNoSlot) plan.sgrad_floats[k] = std::max(plan.sgrad_floats[k], slot + b.count());
         };
         if (tp.t->is_content) {
-            const ContentMask *mk = content_mask_of(e, tp.blob);
+            const ContentMask *mk = target_at(sh.cmasks, tp.blob);
             bool any = false;
             for (const ContentTarget &ct : sh.contents) {
                 if (ct.blob != tp.blob) continue;
@@ -555,33 +486,39 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
                 style_slot += b.count();
             }
         }
-        size_t nnfm_slot = align(content_slot);
-        if (const StatTarget *st = stat_target_of(e, tp.blob)) {
+        // The per-layer kinds (for_each_layer_kind), each behind whatever came before it: ONE cursor, which a kind
+        // that is present moves on by its slot -- no kind asks which of the others are there.
+        size_t cursor = align(content_slot);
+        const auto take_slot = [&]() {
+            const size_t slot = cursor;
+            cursor = align(cursor + b.count());
+            return slot;
+        };
+        if (const StatTarget *st = target_at(sh.stats, tp.blob)) {
             add(TermKind::Stat, st->ms->f(), nullptr, ContentWindow{}, lw * st->weight, 2,
-                stat_scratch_floats(b.channels, b.h * b.w), align(content_slot));
-            nnfm_slot = align(nnfm_slot + b.count());
+                stat_scratch_floats(b.channels, b.h * b.w), take_slot());
         }
-        if (const NnfmTarget *nt = nnfm_target_of(e, tp.blob)) {
+        if (const NnfmTarget *nt = target_at(sh.nnfms, tp.blob)) {
             if (nt->segs.count) {       // guided: the tile's window of the mask maps, taken as a content map's is
                 const ContentWindow win = content_window(b, nt->mh, nt->mw, c.start, c.rx, c.ry);
                 STX_TRY(check_window(win, "NNFM mask", b));
                 add(TermKind::NnfmGuided, nt->bank->f(), nt->maps->f(), win, lw * nt->weight, 3,
-                    nnfm_guided_scratch_floats(b.channels, b.h * b.w, nt->segs, nt->k), nnfm_slot);
+                    nnfm_guided_scratch_floats(b.channels, b.h * b.w, nt->segs, nt->k), take_slot());
             } else {
                 add(TermKind::Nnfm, nt->bank->f(), nullptr, ContentWindow{}, lw * nt->weight, 2,
-                    nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k, nt->cover != 0.f), nnfm_slot);
+                    nnfm_scratch_floats(b.channels, b.h * b.w, nt->rows, nt->patch, nt->k, nt->cover != 0.f),
+                    take_slot());
             }
             plan.terms.back().nnfm = nt;
         }
-        if (const SwdTarget *wt = swd_target_of(e, tp.blob)) {      // (its slot: behind the NNFM slot, if there is one)
+        if (const SwdTarget *wt = target_at(sh.swds, tp.blob)) {
             STX_TRY(swd_check(("sliced Wasserstein target of layer " + b.name).c_str(), b.channels,
                               (long long)b.h * b.w, wt->D, wt->Q));
-            const size_t swd_slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
             add(TermKind::Swd, wt->Tq(), nullptr, ContentWindow{}, lw * wt->weight, 2,
-                swd_scratch_floats(b.channels, b.h * b.w, wt->D), swd_slot);
+                swd_scratch_floats(b.channels, b.h * b.w, wt->D), take_slot());
             plan.terms.back().swd = wt;
         }
-        if (const SelfsimTarget *ft = selfsim_target_of(e, tp.blob)) {  // (its slot: behind the SWD slot, if there is one)
+        if (const SelfsimTarget *ft = target_at(sh.selfsims, tp.blob)) {
             STX_TRY(selfsim_check(("self-similarity target of layer " + b.name).c_str(), b.channels, ft->points));
             const ContentTarget *map = nullptr;     // the layer's content map of content_index 0, whatever the tap says
             for (const ContentTarget &ct : sh.contents)
@@ -592,29 +529,20 @@ int plan_terms(stx_engine *e, const TileCall &c, TilePlan &plan) {
             }
             const ContentWindow win = content_window(b, map->h, map->w, c.start, c.rx, c.ry);
             STX_TRY(check_window(win, "content", b));
-            size_t slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
-            if (swd_target_of(e, tp.blob)) slot = align(slot + b.count());
             add(TermKind::Selfsim, map->feat->f(), nullptr, win, lw * ft->weight, 2,
-                selfsim_scratch_floats(b.channels, selfsim_grid(b.h, b.w, ft->points).N), slot);
+                selfsim_scratch_floats(b.channels, selfsim_grid(b.h, b.w, ft->points).N), take_slot());
             plan.terms.back().points = ft->points;
         }
-        if (const ShiftTarget *ht = shift_target_of(e, tp.blob)) {      // (its slot: behind the self-similarity slot, if there is one)
+        if (const ShiftTarget *ht = target_at(sh.shifts, tp.blob)) {
             STX_TRY(shift_check_map(("shifted-Gram target of layer " + b.name).c_str(), b.channels, b.h, b.w, ht->off));
-            size_t slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
-            if (swd_target_of(e, tp.blob)) slot = align(slot + b.count());
-            if (selfsim_target_of(e, tp.blob)) slot = align(slot + b.count());
             add(TermKind::Shift, ht->grams->f(), nullptr, ContentWindow{}, lw * ht->weight, 2,
-                shift_scratch_floats(b.channels, b.h * b.w, ht->off.n), slot);
+                shift_scratch_floats(b.channels, b.h * b.w, ht->off.n), take_slot());
             plan.terms.back().shift = ht;
         }
-        if (const CxTarget *xt = cx_target_of(e, tp.blob)) {            // (its slot: behind the shifted-Gram slot, if there is one)
+        if (const CxTarget *xt = target_at(sh.cxs, tp.blob)) {
             STX_TRY(cx_check(("contextual target of layer " + b.name).c_str(), b.channels, xt->points, xt->rows, xt->eta));
-            size_t slot = nnfm_target_of(e, tp.blob) ? align(nnfm_slot + b.count()) : nnfm_slot;
-            if (swd_target_of(e, tp.blob)) slot = align(slot + b.count());
-            if (selfsim_target_of(e, tp.blob)) slot = align(slot + b.count());
-            if (shift_target_of(e, tp.blob)) slot = align(slot + b.count());
             add(TermKind::Cx, xt->bank(), nullptr, ContentWindow{}, lw * xt->weight, 2,
-                cx_scratch_floats(b.channels, selfsim_grid(b.h, b.w, xt->points).N, xt->rows), slot);
+                cx_scratch_floats(b.channels, selfsim_grid(b.h, b.w, xt->points).N, xt->rows), take_slot());
             plan.terms.back().cx = xt;
         }
         // Deep-Dream (style_transfer.py:602-604): the content term against a zero map with a negative
